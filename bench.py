@@ -4,7 +4,7 @@ draw) on BASELINE.json's headline workload: 32^4 phi^4 lattice, 8 RQ-spline coup
 (knots_len 16, ConvAct hidden [8,8], kernel 3, tanh), batch 1024 per GPU, fp32, synthetic
 inputs already resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU (RCCL for the timing barriers only); the batch shards over ranks with no data-path
@@ -19,6 +19,11 @@ runs the full per-GPU batch); extra keys:
   selfcheck            : the two arithmetics compared on a slab of the timed input before timing (the kernels did the work)
   roofline             : the dominant kernel of the timed region, HIP-event timed in here; roofline_kernels: the others
   cpu_baseline         : the CPU oracle (oracle/nf_oracle.py, kind "port") on a bounded sample, fp32 and fp64 legs
+
+--dump-outputs DIR writes y and log|det J| of the last timed step as .npy files (dump_outputs below); weights and inputs are
+seeded, so two builds run with the same arguments can be compared output for output.  Compare with a tolerance: on the
+full 32^4 batch about 2% of the samples differ from one pass to the next, even within one process (log|det J| by ~2e-6
+relative, y by up to ~0.3 at a few sites).
 """
 import argparse
 import hashlib
@@ -57,7 +62,14 @@ def parse(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the CPU baseline sample")
     ap.add_argument("--kernel-reps", type=int, default=10)
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of a self-launched run (0 = pick a free one)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's shard) as float32 .npy files "
+                         "under DIR: logJ.npy in full, y.npy in full or, past %d values, at a fixed seeded sample of flat "
+                         "positions" % DUMP_Y_VALUES)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ------------------------------------------------------------------------------------------ self-launch
@@ -416,6 +428,26 @@ def other_configs(dev):
     return out
 
 
+# ------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_Y_VALUES = 1 << 22      # y values kept by --dump-outputs: 16 MB of float32
+DUMP_SEED = 20241015
+
+
+def dump_outputs(out_dir, y, logJ, max_values=DUMP_Y_VALUES):
+    """Write one step's outputs as float32 .npy files: DIR/logJ.npy (one value per sample) and DIR/y.npy -- y itself when it
+    has at most `max_values` values, otherwise y.reshape(-1) at `max_values` flat positions drawn (sorted, with repeats) by a
+    CPU generator seeded with DUMP_SEED, so that runs with the same arguments dump the same positions."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    if y.numel() > max_values:
+        g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+        idx = torch.randint(0, y.numel(), (max_values,), generator=g).sort().values
+        y = y.reshape(-1)[idx.to(y.device)]
+    np.save(os.path.join(out_dir, "y.npy"), y.detach().to("cpu", torch.float32).numpy())
+    np.save(os.path.join(out_dir, "logJ.npy"), logJ.detach().to("cpu", torch.float32).numpy())
+
+
 # ------------------------------------------------------------------------------------------ main
 def main():
     a = parse()
@@ -455,8 +487,9 @@ def main():
     g = torch.Generator(device=dev).manual_seed(1234 + rank)
     x = torch.randn((a.batch,) + lattice, device=dev, dtype=torch.float32, generator=g)
 
-    def timed(xb, steps, warmup):
-        """W untimed + exactly K timed passes over xb, barrier + synchronize on both sides, MAX over ranks."""
+    def timed(xb, steps, warmup, dump=False):
+        """W untimed + exactly K timed passes over xb, barrier + synchronize on both sides, MAX over ranks.  dump: rank 0 writes
+        the last timed pass's outputs to --dump-outputs (after the clock has stopped)."""
         y = logJ = None
         with torch.no_grad():
             for _ in range(warmup):
@@ -476,6 +509,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         assert bool(torch.isfinite(logJ).all()) and bool(torch.isfinite(y).all())
+        if dump and a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, y, logJ)
         return elapsed
 
     # ---- before timing: the timed arithmetic against exact fp32 products on a slab of the timed input
@@ -509,8 +544,9 @@ def main():
         del keep
 
     legs = {}
+    main_leg = "strong" if a.scaling == "strong" else "weak"
     if a.scaling in ("weak", "both") or world == 1:
-        el = timed(x, a.steps, a.warmup)
+        el = timed(x, a.steps, a.warmup, dump=main_leg == "weak" or world == 1)   # at N = 1 the strong leg is this one
         legs["weak"] = {"value": a.batch * world * a.steps / el, "ms_per_step": 1e3 * el / a.steps, "global_batch": a.batch * world,
                         "batch_per_gpu": a.batch}
     if a.scaling in ("strong", "both"):
@@ -518,10 +554,9 @@ def main():
             legs["strong"] = dict(legs["weak"])
         else:
             per = a.batch // world           # divisibility was checked before the process group came up
-            el = timed(x[:per], a.steps, a.warmup)
+            el = timed(x[:per], a.steps, a.warmup, dump=main_leg == "strong")
             legs["strong"] = {"value": a.batch * a.steps / el, "ms_per_step": 1e3 * el / a.steps, "global_batch": a.batch,
                               "batch_per_gpu": per}
-    main_leg = "strong" if a.scaling == "strong" else "weak"
     inloop = inloop_kernel_ms(net_, x if main_leg == "weak" else x[:a.batch // world]) if rank == 0 else None
     fp32_leg = None
     if not a.no_fp32_products:

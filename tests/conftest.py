@@ -14,6 +14,23 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
+@pytest.fixture(autouse=True)
+def _cpu_default_device_outside_gpu_tests(request):
+    """`import normflow__amd` makes cuda torch's default device where a GPU is present (the reference's import side effect,
+    normflow__amd/device/__init__.py).  A test not marked gpu runs as it does on a host without a GPU: with the CPU as the
+    default device."""
+    if request.node.get_closest_marker("gpu") is not None:
+        yield
+        return
+    import torch
+    prev = torch.get_default_device()
+    torch.set_default_device("cpu")
+    try:
+        yield
+    finally:
+        torch.set_default_device(prev)
+
+
 @pytest.fixture(scope="session")
 def golden():
     import numpy as np

@@ -514,3 +514,25 @@ def test_hidden_slabs_respect_the_budget_and_the_32_bit_site_index():
         assert cpl._hidden_slabs(torch.empty((4096, V), device="meta"), 8)[0] == (0, 256)
     finally:
         couplings_.set_slab_bytes(*old)
+
+
+def test_bench_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs (bench.py --dump-outputs): y and logJ as float32 .npy files, y in full up to the value budget and past
+    it a sample of its flat positions that is the same in every run; the headline workload's dump stays within 64 MB."""
+    monkeypatch.setattr(os, "environ", os.environ.copy())      # bench.py sets its defaults in os.environ at import
+    import bench
+    g = torch.Generator().manual_seed(0)
+    y = torch.randn((3, 4, 6), generator=g, dtype=torch.float32)
+    lj = torch.randn(3, generator=g, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "full"), y, lj)
+    yf, lf = np.load(tmp_path / "full" / "y.npy"), np.load(tmp_path / "full" / "logJ.npy")
+    assert yf.dtype == np.float32 and yf.shape == (3, 4, 6) and np.array_equal(yf, y.numpy())
+    assert lf.dtype == np.float32 and np.array_equal(lf, lj.float().numpy())
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), y, lj, max_values=10)
+    ya, yb = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert ya.dtype == np.float32 and ya.shape == (10,) and np.array_equal(ya, yb)
+    idx = torch.randint(0, y.numel(), (10,), generator=torch.Generator().manual_seed(bench.DUMP_SEED)).sort().values
+    assert np.array_equal(ya, y.reshape(-1)[idx].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "logJ.npy"), lf)
+    assert 4 * (bench.DUMP_Y_VALUES + 1024) <= 64 << 20

@@ -12,10 +12,19 @@ import os
 import socket
 import tempfile
 
+import pytest
 import torch
 
 import normflow__amd as nf
 from test_abi_and_host import make_cpu_model
+
+
+@pytest.fixture(autouse=True)
+def _ranks_without_gpu(monkeypatch):
+    """The spawned ranks are CPU processes on any host: with a GPU visible they would take RCCL and cuda:<rank> (one process
+    per GPU, device/_core.py) instead of gloo on the CPU.  The children inherit this environment; the parent's GPU runtime
+    was initialised before, at import."""
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "-1")
 
 
 def _free_port():

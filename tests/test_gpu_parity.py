@@ -1289,6 +1289,45 @@ def test_bench_self_launch_two_ranks_rehearsal():
     assert "cpu_baseline" not in line          # rank 0 at N = 1 only
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`python bench.py --steps 3 --dump-outputs DIR` on a small lattice: the line reports 3 timed steps and ms_per_step, and
+    DIR/y.npy, DIR/logJ.npy (float32, in full at this size) are bench.build_net's network on bench's seeded input, recomputed
+    here with bench's torch defaults (float32, CPU-initialised weights)."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lattice, B, layers = (4, 4, 4, 32), 8, 2
+    out = tmp_path / "dump"
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", str(B), "--lattice", ",".join(map(str, lattice)), "--layers", str(layers), "--kernel-reps", "3",
+                        "--no-cpu-baseline", "--no-other-configs", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    yd, ld = np.load(out / "y.npy"), np.load(out / "logJ.npy")
+    assert yd.dtype == np.float32 and yd.shape == (B,) + lattice and ld.dtype == np.float32 and ld.shape == (B,)
+    dtype, device = torch.get_default_dtype(), torch.get_default_device()
+    torch.set_default_dtype(torch.float32)
+    torch.set_default_device("cpu")
+    try:
+        net_, _ = bench.build_net(lattice, layers, 16, DEV, seed=2024)
+    finally:
+        torch.set_default_dtype(dtype)
+        torch.set_default_device(device)
+    g = torch.Generator(device=DEV).manual_seed(1234)
+    x = torch.randn((B,) + lattice, device=DEV, dtype=torch.float32, generator=g)
+    with torch.no_grad():
+        y, lj = net_(x)
+    assert rel(torch.from_numpy(yd), y) <= 1e-6 and rel(torch.from_numpy(ld), lj) <= 1e-6, (rel(torch.from_numpy(yd), y),
+                                                                                            rel(torch.from_numpy(ld), lj))
+
+
 # -------------------------------------------------- SURVEY 8(f) 3: the prior as one Philox kernel
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 @pytest.mark.parametrize("B,shape,affine", [(3, (4, 4, 2, 6), False), (5, (7,), True), (2, (6, 5), True), (1, (1,), False),

@@ -46,6 +46,25 @@ def atom_cases():
     return [str(c) for c in z["_cases"]]
 
 
+def on_knots(tag, x, out, amask, opts):
+    """make_golden.py puts every third input of the rqs_lin cases exactly on a knot (the tie rule of the bin search).  The
+    knots are softmax / cumsum results whose last bits follow the CPU's vector code path: on another CPU the stored input
+    sits an ulp or two beside the oracle's knot, and the gradient there takes the other one-sided derivative.  Those
+    inputs are checked to be the knots of the stored case and put back on the oracle's knots, bit for bit."""
+    if not tag.startswith("rqs_lin"):
+        return x
+    kx, ky, kd = O.knots_from_logits(out, opts["xlim"], opts["ylim"])
+    kx = O.augment_knots(kx, ky, kd, axis=1, **opts["extrap"])[0]
+    B, n = x.shape[0], kx.shape[1]
+    flat, kflat, active = x.clone().reshape(B, -1), kx.reshape(B, n, -1), amask.reshape(-1)
+    for j in range(0, flat.shape[1], 3):
+        if active[j]:
+            k = kflat[:, (j // 3) % n, j]
+            assert float((flat[:, j] - k).abs().max()) <= 1e-12, (tag, j)
+            flat[:, j] = k
+    return flat.reshape(x.shape)
+
+
 @pytest.mark.parametrize("tag", atom_cases())
 def test_atom_forward_inverse_grads(golden, tag):
     z = golden("atoms")
@@ -56,7 +75,7 @@ def test_atom_forward_inverse_grads(golden, tag):
         opts["knots_x"] = g("knots_x")
     shape, parity = tuple(int(v) for v in z[f"{tag}/shape"]), int(z[f"{tag}/parity"])
     amask = O.channel_mask(shape, parity)
-    x = g("x_active").clone().requires_grad_(True)
+    x = on_knots(tag, g("x_active"), g("out"), amask, opts).requires_grad_(True)
     out = g("out").clone().requires_grad_(True)
     y, logJ = fn(x, out, amask, log0=g("log0"), **opts)
     close(y, g("y"))
