@@ -344,9 +344,12 @@ int nf_conv_weight_layout(const int32_t *lattice, const int32_t *ksize, int cin,
 /* A hidden 8 -> 8 layer whose input AND output are the fp16 (hi, lo) pair tensor above (nf_conv_g.hip: two-site columns,
  * one v_mfma_f32_16x16x32_f16 slice per kernel row, three fp16 products per fp32 product; persistent workgroups marching
  * 2 x 2 columns of lattice rows through an LDS ring filled by LDS-DMA).  in16 and out16 must not overlap.
- *   in16, out16: (B, V, 16) halfs; wsplit: [kernel row (27)][hi|lo][64 lanes][8] halfs -- lane 16*g + n holds, for column
- *   n = 8*shift + co, the 8 input channels of tap (g - shift) of that kernel row (zero outside 0..2), scaled by 2^10
- *   and split as in NF_WLAYOUT_SPLIT16; bias (8) fp32 or NULL; act must keep |out| <= 1 (tanh, logistic).
+ *   in16, out16: (B, V, 16) halfs; wsplit: 72 fragments of [64 lanes][8] halfs, scaled by 2^10 and split as in
+ *   NF_WLAYOUT_SPLIT16.  First 18 STACKED fragments [set (2)][j2 (3)][j3 (3)]: lane 16*g + n holds, for row n = 8*part + co
+ *   (part 0: hi, 1: lo), the 8 input channels of kernel row (j0, j1, j2) with 3 j0 + j1 = 4*set + g, tap j3.  Then the
+ *   two-site fragments [kernel row (27)][hi|lo]: lane 16*g + n holds, for column n = 8*shift + co, the 8 input channels of
+ *   tap (g - shift) of that kernel row (zero outside 0..2).  normflow__amd._hip.pack_conv_weight_split16_stacked packs it.
+ *   bias (8) fp32 or NULL; act must keep |out| <= 1 (tanh, logistic).
  *   nf_conv_split16_supported: 3^4 kernel, 8 -> 8 channels, a fastest axis of 32 + 16 n sites, even other extents. */
 int nf_conv_split16_supported(const int32_t *lattice, const int32_t *ksize, int cin, int cout, int act);
 /* The LAST layer of an AffineCoupling_'s net (8 -> 2 channels: t, s) fused with the coupling (src/nn/scalar/couplings_.py:123-139),

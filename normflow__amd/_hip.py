@@ -661,6 +661,22 @@ def pack_conv_weight_split16_two_site(w):
     return out.contiguous()
 
 
+def pack_conv_weight_split16_stacked(w):
+    """(8, 8, 3, 3, 3, 3) fp32 weights of a hidden layer -> the A fragments of conv_g2_kernel (include/normflow_hip.h,
+    nf_conv_fwd_split16): 18 STACKED fragments [set (2)][j2 (3)][dx (3)][lane (64)][8], then the two-site fragments of
+    `pack_conv_weight_split16_two_site` (27 x [hi|lo]); 72 fragments of 64 lanes x 8 halfs.  Stacked: lane 16*g + n holds, for
+    row n = 8*part + co (part 0: hi, 1: lo of the split), the 8 input channels of kernel row (j0, j1, j2) with 3 j0 + j1 =
+    4*set + g, fastest-axis tap j3 = dx."""
+    assert tuple(w.shape) == (8, 8, 3, 3, 3, 3)
+    wr = w.reshape(8, 8, 9, 3, 3).float() * SPLIT16_WEIGHT_SCALE       # co, ch, combo (j0, j1), j2, j3
+    hi = wr.half()
+    lo = (wr - hi.float()).half()
+    parts = torch.stack((hi, lo))[:, :, :, :8]                          # part, co, ch, combo (0..7), j2, j3
+    v = parts.reshape(2, 8, 8, 2, 4, 3, 3).permute(3, 5, 6, 4, 0, 1, 2)  # set, j2, j3, g, part, co, ch
+    stacked = v.reshape(18, 64, 8)
+    return torch.cat((stacked, pack_conv_weight_split16_two_site(w).reshape(54, 64, 8))).contiguous()
+
+
 def pack_conv_weight_split16_first(w):
     """(8, 1, 3, 3, 3, 3) fp32 weights of a first ConvAct layer -> the B fragments of conv_c2_kernel (include/normflow_hip.h,
     nf_conv_first_split16): [K slice (4)][hi|lo][lane (64)][8]; K index = 4 r + t with r the kernel row (j0, j1, j2) row-major
@@ -743,7 +759,7 @@ def conv_layer_split16(h16, weight, bias, act, lattice):
     lib = load()
     B = h16.shape[0]
     lat4 = (C.c_int32 * 4)(*lattice)
-    wsp = _cached_pack(weight, 'two_site16', pack_conv_weight_split16_two_site)
+    wsp = _cached_pack(weight, 'stacked16', pack_conv_weight_split16_stacked)
     bias = None if bias is None else bias.detach().float().contiguous()
     out = torch.empty_like(h16)
     for b0 in range(0, B, MAX_B):
@@ -1012,7 +1028,7 @@ def conv_input_grad_split16(gz, wt, bits=None, compact_parity=-1, lattice=None, 
     wpad = wt.new_zeros((8, 8 * G, 3, 3, 3, 3), dtype=torch.float32)
     wpad[:cin, :Cc] = wt.float()
     for g in range(G):
-        wsp = pack_conv_weight_split16_two_site(wpad[:, 8 * g:8 * g + 8].contiguous())
+        wsp = pack_conv_weight_split16_stacked(wpad[:, 8 * g:8 * g + 8].contiguous())
         _check(lib.nf_conv_dgrad_split16(_ptr(g16[g]), _ptr(wsp), None, _ptr(gx), B, lat4, _ptr(bits), int(g > 0), 0,
                                          _stream()), "nf_conv_dgrad_split16")
     return gx if cin == 8 else gx[:, :cin].contiguous()
@@ -1034,7 +1050,7 @@ def conv_hidden_planes_split16(x, weight, bias, act):
     x16 = torch.empty((1, B, V, 16), dtype=torch.float16, device=x.device)
     bits = absmax_bits(x)                        # (any input range: the pair tensor is scaled like a cotangent's)
     _check(lib.nf_planes_to_split16(_ptr(x), _ptr(x16), _ptr(bits), B, 8, lat4, -1, _stream()), "nf_planes_to_split16")
-    wsp = pack_conv_weight_split16_two_site(weight.detach().float())
+    wsp = pack_conv_weight_split16_stacked(weight.detach().float())
     out = torch.empty_like(x)
     b = None if bias is None else bias.detach().float().contiguous()
     _check(lib.nf_conv_dgrad_split16(_ptr(x16[0]), _ptr(wsp), _ptr(b), _ptr(out), B, lat4, _ptr(bits), 0, int(act), _stream()),
@@ -1072,7 +1088,7 @@ def conv_last_logits_split16(x, weight, bias, parity):
 def pack_wide_split16(w1, b1, w2, b2, w3, b3):
     """Weights of a stack 1 -> h -> h -> C with 8 < h <= 16 (3^4 kernels) for `conv_wide_logits_split16`: the hidden channels
     zero-padded to 16 and cut into two groups of 8 -- [first-layer fragments x 2, biases x 2], [two-site fragments of the four
-    8 x 8 blocks of the hidden layer, biases x 2], [last-layer fragments x 2, bias]."""
+    8 x 8 blocks of the hidden layer (stacked + two-site), biases x 2], [last-layer fragments x 2, bias]."""
     h, cout = w1.shape[0], w3.shape[0]
     f = lambda t: t.detach().float()
     w1p = f(w1).new_zeros((16, 1, 3, 3, 3, 3)); w1p[:h] = f(w1)
@@ -1082,7 +1098,7 @@ def pack_wide_split16(w1, b1, w2, b2, w3, b3):
     b1p, b2p = padb(b1, 16), padb(b2, 16)
     cut = lambda b, g: None if b is None else b[8 * g:8 * g + 8].contiguous()
     first = [(pack_conv_weight_split16_first(w1p[8 * g:8 * g + 8].contiguous()), cut(b1p, g)) for g in (0, 1)]
-    hidden = [[pack_conv_weight_split16_two_site(w2p[8 * go:8 * go + 8, 8 * gi:8 * gi + 8].contiguous()) for gi in (0, 1)] for go in (0, 1)]
+    hidden = [[pack_conv_weight_split16_stacked(w2p[8 * go:8 * go + 8, 8 * gi:8 * gi + 8].contiguous()) for gi in (0, 1)] for go in (0, 1)]
     last = [pack_conv_weight_split16(w3p[:, 8 * gi:8 * gi + 8].contiguous()) for gi in (0, 1)]
     return first, (hidden, [cut(b2p, 0), cut(b2p, 1)]), (last, None if b3 is None else f(b3).contiguous()), cout
 
@@ -1291,8 +1307,8 @@ def conv_affine_split16(h16, weight, bias, x_active, log0, parity, inverse, latt
     def pack_affine(w):
         w8 = w.new_zeros((8, 8, 3, 3, 3, 3), dtype=torch.float32)
         w8[:2] = w.float()
-        return pack_conv_weight_split16_two_site(w8)
-    wsp = _cached_pack(weight, 'affine16', pack_affine)
+        return pack_conv_weight_split16_stacked(w8)
+    wsp = _cached_pack(weight, 'affine16s', pack_affine)
     b8 = torch.zeros(8, dtype=torch.float32, device=x_active.device)
     if bias is not None:
         b8[:2] = bias.detach().float()

@@ -5,7 +5,13 @@
 // Arithmetic as in nf_conv_h.hip: every fp32 product = three fp16 matrix-core products (a_hi w_hi + a_hi w_lo + a_lo w_hi,
 // fp32 accumulation, v_mfma_f32_16x16x32_f16).  Two-site columns (column n = 8*shift + co = channel co at site 2p + shift)
 // make the four fastest-axis taps -1..+2 of a site pair the four k-groups of one MFMA: a kernel row (j0, j1, j2) is exactly
-// one K = 32 slice, 27 slices per output tile (a tile = the 16 site pairs of one lattice row).
+// one K = 32 slice, 27 slices per output tile (a tile = the 16 site pairs of one lattice row).  But a site uses only three
+// of the four taps: a quarter of a two-site MFMA multiplies zeros.  So only w_hi a_lo keeps that form (27 MFMAs per tile).
+// The two products of a_hi are STACKED instead: rows m = 8 part + co (part = w_hi, w_lo) fill the 16 rows, a column is ONE
+// site (the even sites of the tile's pairs, or the odd ones), and k-group g is combo (j0, j1) = 4 set + g: per set of four
+// combos, tap j2 and fastest-axis offset dx, one MFMA per parity -- 2 x 3 x 3 x 2 = 36 dense MFMAs per tile; combo 8 keeps
+// the two-site form for them (6).  69 MFMAs per tile instead of 81; a permlane32 swap turns the stacked sums into the pair
+// layout of the two-site ones.
 //
 // Shape of the computation (what changed against the one-box-per-item kernel it replaces, and why):
 //   * MARCHING COLUMNS.  A persistent workgroup owns a 2 x 2 cross-section (axes 0, 1) and marches along axis 2, two
@@ -15,8 +21,9 @@
 //     global_load_lds_dwordx4 wave-instruction (1 KiB, fully coalesced): no staging registers, no ds_write, and the copy
 //     of the planes for step s+2 flies while steps s and s+1 multiply (counted vmcnt, LDS-only barriers).
 //   * TWO WAVES PER SIMD, K SPLIT BETWEEN THEM.  The freed registers let 8 waves fit (<= 256 VGPRs each).  Waves w ("A") and
-//     w+4 ("B") share a SIMD and the two output tiles of position (z0, z1) of the cross-section; A multiplies slices 0..13,
-//     B slices 14..26, for BOTH tiles.  The partial sums cross through a 2 KiB LDS exchange (A gets tile 0's, B tile 1's),
+//     w+4 ("B") share a SIMD and the two output tiles of position (z0, z1) of the cross-section; A multiplies the stacked
+//     products of combos 0..3, combo 8 and w_hi a_lo of combos 0..2 (72 MFMAs per step), B the stacked products of combos
+//     4..7 and w_hi a_lo of combos 3..7 (66), for BOTH tiles.  The partial sums cross through a 2 KiB LDS exchange (A gets tile 0's, B tile 1's),
 //     double-buffered, and each wave runs the epilogue of ITS tile of step s (add, bias, activation, split into (hi, lo),
 //     store -- straight from the accumulators: the weights are the MFMA's A operand, so a lane holds 4 channels of one site) at the start of step s+1 -- beside its partner's MFMAs.  While one wave of a SIMD waits or does vector
 //     work, the other's MFMAs keep the matrix pipe busy; the one-wave-per-SIMD form spent 42 % of an item outside its MFMAs.
@@ -56,7 +63,6 @@ struct Geo {
 #ifndef NF_G2_PRIO
 #define NF_G2_PRIO 1
 #endif
-constexpr int NSA = 14;                       // slices of the A waves (0..13); B waves: 14..26
 constexpr float kInvWScale = 1.0f / 1024.0f;  // the weights are packed scaled by 2^10 (normflow__amd/_hip.py: SPLIT16_WEIGHT_SCALE)
 }  // namespace g2
 
@@ -86,7 +92,7 @@ __global__ __launch_bounds__(512, 2) void conv_g2_kernel(ConvArgs A) {
   extern __shared__ __align__(16) unsigned char smem_g2[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const bool isB = wave >= 4;                 // A waves: slices 0..13, epilogue of tile 0; B waves: slices 14..26, tile 1
+  const bool isB = wave >= 4;                 // A waves: combo sets / slices of their own (below), epilogue of tile 0; B: tile 1
   const int q = wave & 3;                     // wave pair = position (z0, z1) = (q >> 1, q & 1) in the cross-section
   const int g = lane >> 4, p = lane & 15;
   const unsigned lds0 = unsigned(reinterpret_cast<size_t>((__attribute__((address_space(3))) unsigned char *)smem_g2));
@@ -131,17 +137,20 @@ __global__ __launch_bounds__(512, 2) void conv_g2_kernel(ConvArgs A) {
     i1 = (c % nt1) * td1 + t1;
   };
 
-  // ---- weights: my slices, hi and lo (A: 0..13; B: 14..26 -- its 14th register pair is never used)
-  const int sl0 = isB ? NSA : 0;
-  f16x8 bh[NSA], bl[NSA];
+  // ---- weights (layout: pack_conv_weight_split16_stacked): the 9 stacked fragments [j2][dx] of my combo set (A: combos
+  // 0..3, B: 4..7), and 15 two-site fragments, three taps each -- A: w_hi of combos 0, 1, 2, 8, w_lo of combo 8; B: w_hi of
+  // combos 5, 6, 7, 3, 4 (the same register for the same role in the two waves' schedules below)
+  f16x8 wp[9], bt[15];
   {
     const f16x8 *__restrict__ wsp = static_cast<const f16x8 *>(A.wfrag) + lane;
 #pragma unroll
-    for (int r = 0; r < NSA; ++r) {
-      const int rr = sl0 + r;
-      const int rc = rr < 27 ? rr : 26;
-      bh[r] = wsp[(2 * rc) * 64];
-      bl[r] = wsp[(2 * rc + 1) * 64];
+    for (int r = 0; r < 9; ++r) wp[r] = wsp[((isB ? 9 : 0) + r) * 64];
+#pragma unroll
+    for (int r = 0; r < 15; ++r) {
+      constexpr int kSP = 18;                  // the two-site fragments follow the stacked ones: [slice][hi|lo]
+      const int fa = r < 12 ? 2 * (3 * (r < 9 ? r / 3 : 8) + r % 3) : 2 * (24 + r - 12) + 1;
+      const int fb = 2 * (3 * (r < 9 ? 5 + r / 3 : 3 + (r - 9) / 3) + r % 3);
+      bt[r] = wsp[(kSP + (isB ? fb : fa)) * 64];
     }
   }
   float bv4[4], kc0[4];                        // bias of the four channels this lane ends up with: 4 (g & 1) + r
@@ -174,6 +183,19 @@ __global__ __launch_bounds__(512, 2) void conv_g2_kernel(ConvArgs A) {
   constexpr bool HALF = SEGM && EPI != 3 && HK;
   const int psh = p >> 3, pm = p & 7;
   const int lane_am_delta = int(rowsel + unsigned(para * 256 + (pm + (g >> 1)) * 16)) - int(lane_a);      // (local slot <= 8: the main piece)
+  // STACKED products (w_hi, w_lo in the rows, a_hi of ONE site per column): k-group g carries combo cP = 4 set + g, so lane
+  // (p, g) reads ITS combo's halo row at the four positions xp = 0..3 (sites 2q - 1 .. 2q + 2 -- the addresses lane_a has for
+  // g = xp); the even sites of the pairs take xp = dx + 1, the odd ones xp = dx + 2 (dx = -1, 0, +1)
+  unsigned lane_p[4];
+  {
+    const int cP = (isB ? 4 : 0) + g;
+    const unsigned coffP = unsigned(((cP / 3) * 4 + cP % 3) * RBL);
+#pragma unroll
+    for (int xp = 0; xp < 4; ++xp) {
+      const int jx = (HALF ? pm : p) + (xp >> 1), parx = (xp + 1) & 1;
+      lane_p[xp] = rowsel + coffP + unsigned((SEGM && jx == 16) ? 1024 + parx * 16 : parx * 256 + (jx & 15) * 16);
+    }
+  }
   // ---- DMA: wave w copies halo rows 2w and 2w + 1 of every plane; lane l brings slot (16 hs + (l & 15)) mod HP of block l >> 4
   // ([hi | lo][even | odd]) of the row; lanes 0..3 of a second piece bring the 17th slot of the four blocks
   const int hz0 = wave >> 1, hz1a = 2 * (wave & 1);
@@ -382,6 +404,7 @@ __global__ __launch_bounds__(512, 2) void conv_g2_kernel(ConvArgs A) {
       ndma += issue_entry() ? 2 * PPP : 0;
       ndma += issue_entry() ? 2 * PPP : 0;
     }
+    const int ndma_head = ndma;                 // (entries 4, 5 of a column: its SECOND step reads them)
     const bool refill = !(NF_G2_ABL & 1) && free_next >= 2;
     auto dma_slot = [&](int i) {               // slot i of 4: piece i & 1 of the entry under the cursor
       if (refill && issue_piece(i & 1)) ndma += PPP;
@@ -392,12 +415,14 @@ __global__ __launch_bounds__(512, 2) void conv_g2_kernel(ConvArgs A) {
     // of the step (with both epilogues up front the matrix pipe idled for ~1000 cycles of a ~4500-cycle step)
     if (isB && have_prev && !(NF_G2_ABL & 2)) epilogue((k - 1) & 1);
     NF_G2TICK(1)      // epilogue (B)
-    // (3) my share of the 27 slices, for both tiles
+    // (3) my share of the products, for both tiles.  A: the stacked products of combos 0..3, combo 8's three two-site
+    // products, w_hi a_lo of combos 0, 1, 2 (72 MFMAs); B: the stacked products of combos 4..7, w_hi a_lo of combos 3..7 (66)
 #if NF_G2_PRIO
     __builtin_amdgcn_s_setprio(2);             // the wave that multiplies goes first at the SIMD's issue port
 #endif
     f32x4 am[2], ac[2];                        // per tile: hi*hi sums, and the two correction products
-    am[0] = am[1] = ac[0] = ac[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 pe[2], po[2];                        // per tile: stacked products of the even / odd sites ([w_hi | w_lo] rows)
+    if (NF_G2_ABL & 4) pe[0] = pe[1] = po[0] = po[1] = f32x4{0.f, 0.f, 0.f, 0.f};      // (else: the first product sets them)
     unsigned rowa[4], rowl[4];                 // LDS offset of this lane's fragment (hi, lo) in ring plane (rbase + i), combo (0, 0)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -405,108 +430,137 @@ __global__ __launch_bounds__(512, 2) void conv_g2_kernel(ConvArgs A) {
       rowa[i] = po + lane_a;
       rowl[i] = po + lane_al;
     }
-    // rows I0 .. I1 of combo offset coff (tap j2 of tile t reads row t + j2); half column: taps H0 .. H1 of the merged tile
-    auto fetch = [&](f16x8 (&fh)[4], f16x8 (&fl)[4], int coff, int I0, int I1, int H0, int H1) {
+    // two-site fragments of combo offset coff, hi or lo half: rows 0..3 (tap j2 of tile t reads row t + j2); half column:
+    // taps 0..2 of the merged tile
+    auto fetch = [&](f16x8 (&f)[4], int coff, bool lo) {
       if constexpr (HALF) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          if (i < H0 || i > H1) continue;
           // this lane's fragment of tap i: plane i (+ 1 for the upper half of the lanes) of the ring window, its own slot
           // (arithmetic on the lane's plane index, not a select between rowa[i] and rowa[i + 1]: the compiler turned that
           //  select into a scratch array indexed per lane)
           const unsigned rm = unsigned(((rbase + i + psh) & (NSLOT - 1)) * PLANE) + unsigned(int(lane_a) + lane_am_delta);
-          fh[i] = *reinterpret_cast<const f16x8 *>(smem_g2 + rm + coff);
-          fl[i] = *reinterpret_cast<const f16x8 *>(smem_g2 + rm + 512 + coff);
+          f[i] = *reinterpret_cast<const f16x8 *>(smem_g2 + rm + (lo ? 512 : 0) + coff);
         }
         return;
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if (i < I0 || i > I1) continue;
         if (NF_G2_ABL & 8) {
-          fh[i] = bh[i]; fl[i] = bl[i];
-          asm volatile("" : "+v"(fh[i]), "+v"(fl[i]));
+          f[i] = bt[i];
+          asm volatile("" : "+v"(f[i]));
         } else {
-          fh[i] = *reinterpret_cast<const f16x8 *>(smem_g2 + rowa[i] + coff);
-          fl[i] = *reinterpret_cast<const f16x8 *>(smem_g2 + rowl[i] + coff);
+          f[i] = *reinterpret_cast<const f16x8 *>(smem_g2 + (lo ? rowl[i] : rowa[i]) + coff);
         }
       }
     };
-    // taps J0 .. J1 of a combo whose tap 0 is my local slice `base` (compile-time at every call site).  The WEIGHTS are the
-    // MFMA's A operand (rows m = column (shift, co) of the layer), the site pairs its B operand: D[m][pair] leaves the four
-    // channels 4 (g & 1) .. + 3 of ONE site (2p + (g >> 1)) in each lane -- what a store needs, no transpose
-    auto mult = [&](const f16x8 (&fh)[4], const f16x8 (&fl)[4], int base, int J0, int J1) {
-      if (NF_G2_ABL & 4) {
+    // stacked fragments: the four positions xp of ring plane i (half column: of tap i of the merged tile) at my k-group's combo
+    auto fetch_p = [&](f16x8 (&f)[4], int i) {
+      if (HALF && i > 2) return;
+      const unsigned pl = unsigned(((rbase + i + (HALF ? psh : 0)) & (NSLOT - 1)) * PLANE);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(fh[i]), "v"(fl[i]));
-        return;
+      for (int xp = 0; xp < 4; ++xp) {
+        if (NF_G2_ABL & 8) {
+          f[xp] = bt[xp];
+          asm volatile("" : "+v"(f[xp]));
+        } else {
+          f[xp] = *reinterpret_cast<const f16x8 *>(smem_g2 + pl + lane_p[xp]);
+        }
       }
-      if constexpr (HALF) {                    // one merged tile: tap j2 multiplies fragment j2
+    };
+    auto consume = [](const f16x8 (&f)[4]) {   // (ablation 4: no MFMAs, the fragments are still read)
 #pragma unroll
-        for (int j2 = 0; j2 < 3; ++j2)
-          if (j2 >= J0 && j2 <= J1) am[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[base + j2], fh[j2], am[0], 0, 0, 0);
+      for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(f[i]));
+    };
+    // The WEIGHTS are the MFMA's A operand, the sites its B operand: D[m][column] leaves rows 4 g .. 4 g + 3 in lane (p, g).
+    // Stacked: ring plane i serves tap j2 = i - t of tile t; weight fragment (j2, dx) meets position dx + 1 (even sites) and
+    // dx + 2 (odd sites).  Rows m = 8 part + co: lanes 0..31 hold w_hi a_hi, lanes 32..63 w_lo a_hi of the column's site.
+    auto mult_p = [&](const f16x8 (&f)[4], int i) {
+      if (NF_G2_ABL & 4) return consume(f);
 #pragma unroll
-        for (int j2 = 0; j2 < 3; ++j2)
-          if (j2 >= J0 && j2 <= J1) ac[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[base + j2], fh[j2], ac[0], 0, 0, 0);
+      for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-        for (int j2 = 0; j2 < 3; ++j2)
-          if (j2 >= J0 && j2 <= J1) ac[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[base + j2], fl[j2], ac[0], 0, 0, 0);
-        return;
-      }
+        for (int t = 0; t < 2; ++t) {
+          const int j2 = i - t;
+          if (j2 < 0 || j2 > 2 || (HALF && t > 0)) continue;
+          const bool first = j2 == 0 && dx == 0;           // (a zero accumulator operand: no zeroed registers)
+          pe[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wp[3 * j2 + dx], f[dx], first ? f32x4{0.f, 0.f, 0.f, 0.f} : pe[t], 0, 0, 0);
+          po[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wp[3 * j2 + dx], f[dx + 1], first ? f32x4{0.f, 0.f, 0.f, 0.f} : po[t], 0, 0, 0);
+        }
+    };
+    // Two-site: D[m][pair] leaves the four channels 4 (g & 1) .. + 3 of ONE site (2p + (g >> 1)) in each lane.  mult_q:
+    // the correction products of the fragments fl with the weights bt[hb ..] (w_hi a_lo, or w_lo a_hi for combo 8's)
+    constexpr int NT = HALF ? 1 : 2;           // (half column: one merged tile, tap j2 multiplies fragment j2)
+    auto mult_q = [&](const f16x8 (&fl)[4], int hb) {
+      if (NF_G2_ABL & 4) return consume(fl);
 #pragma unroll
       for (int j2 = 0; j2 < 3; ++j2)
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-          if (j2 >= J0 && j2 <= J1) am[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[base + j2], fh[t + j2], am[t], 0, 0, 0);
+        for (int t = 0; t < NT; ++t) ac[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bt[hb + j2], fl[t + j2], ac[t], 0, 0, 0);
+    };
+    auto mult_hh = [&](const f16x8 (&fh)[4], int hb) {      // w_hi a_hi of combo 8 (A waves)
+      if (NF_G2_ABL & 4) return;
 #pragma unroll
       for (int j2 = 0; j2 < 3; ++j2)
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-          if (j2 >= J0 && j2 <= J1) ac[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[base + j2], fh[t + j2], ac[t], 0, 0, 0);
+        for (int t = 0; t < NT; ++t) am[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bt[hb + j2], fh[t + j2], am[t], 0, 0, 0);
+    };
+    // The stacked sums become the pair layout of am / ac: one half exchange per register turns (P_even, P_odd) =
+    // ([hi | lo] of the even sites, [hi | lo] of the odd sites) into [hi even | hi odd] (hi*hi) and [lo even | lo odd] (a
+    // correction).  Done before the two-site products: am / ac start from these, and pe / po die here.
+    auto combine = [&]() {
 #pragma unroll
-      for (int j2 = 0; j2 < 3; ++j2)
+      for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-          if (j2 >= J0 && j2 <= J1) ac[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[base + j2], fl[t + j2], ac[t], 0, 0, 0);
+        for (int r = 0; r < 4; ++r) {
+          // (__float_as_uint, not __builtin_bit_cast: on a vector element the latter read element 0 for every r)
+          const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(pe[t][r]), __float_as_uint(po[t][r]), false, false);
+          am[t][r] = __uint_as_float(sw[0]);
+          ac[t][r] = __uint_as_float(sw[1]);
+        }
     };
     auto combo_off = [](int jj) { return ((jj / 3) * 4 + jj % 3) * RBL; };      // halo row (j0, j1) relative to the pair's own
-    f16x8 fh0[4], fl0[4], fh1[4], fl1[4];
+    f16x8 u0[4], u1[4], v0[4], v1[4];
     // (sched_barrier: left alone the compiler sinks every fragment read next to its first use and exposes the LDS latency
-    //  at each MFMA group; the reads of the next combo must issue BEFORE the current combo's MFMAs)
+    //  at each MFMA group; the reads of the next group must issue BEFORE the current group's MFMAs)
 #define NF_SB __builtin_amdgcn_sched_barrier(0)
-    if (!isB) {                                // slices 0..13: combos 0..3 and taps 0, 1 of combo 4
-      fetch(fh0, fl0, combo_off(0), 0, 3, 0, 2);
-      fetch(fh1, fl1, combo_off(1), 0, 3, 0, 2);
-      NF_SB; mult(fh0, fl0, 0, 0, 2); NF_SB;
-      dma_slot(0);
-      fetch(fh0, fl0, combo_off(2), 0, 3, 0, 2);
-      NF_SB; mult(fh1, fl1, 3, 0, 2); NF_SB;
-      dma_slot(1);
-      fetch(fh1, fl1, combo_off(3), 0, 3, 0, 2);
-      NF_SB; mult(fh0, fl0, 6, 0, 2); NF_SB;
-      dma_slot(2);
-      fetch(fh0, fl0, combo_off(4), 0, 2, 0, 1);
-      NF_SB; mult(fh1, fl1, 9, 0, 2); NF_SB;
-      dma_slot(3);
-      mult(fh0, fl0, 12, 0, 1);
-      NF_SB;
-    } else {                                   // slices 14..26: tap 2 of combo 4 and combos 5..8 (local index = global - 14)
-      fetch(fh0, fl0, combo_off(4), 2, 3, 2, 2);
-      fetch(fh1, fl1, combo_off(5), 0, 3, 0, 2);
-      NF_SB; mult(fh0, fl0, 12 - NSA, 2, 2); NF_SB;
-      fetch(fh0, fl0, combo_off(6), 0, 3, 0, 2);
-      NF_SB; mult(fh1, fl1, 15 - NSA, 0, 2); NF_SB;
-      dma_slot(0);
-      fetch(fh1, fl1, combo_off(7), 0, 3, 0, 2);
-      NF_SB; mult(fh0, fl0, 18 - NSA, 0, 2); NF_SB;
-      dma_slot(1);
-      fetch(fh0, fl0, combo_off(8), 0, 3, 0, 2);
-      NF_SB; mult(fh1, fl1, 21 - NSA, 0, 2); NF_SB;
-      dma_slot(2);
-      mult(fh0, fl0, 24 - NSA, 0, 2);
-      NF_SB;
-      dma_slot(3);
+    // A: stacked 0..3, then combo 8 (u0 = a_lo, u1 = a_hi) and w_hi a_lo of combos 0, 1, 2 (v0, v1, u0); B: stacked 4..7,
+    // then w_hi a_lo of combos 3, 4 (u0, u1) and 5, 6, 7 (v0, v1, u0).  The two schedules differ in the fetch addresses and
+    // in A's six w_hi a_hi products only: two diverging ones made the register allocator spill.
+    fetch_p(u0, 0);
+    fetch_p(u1, 1);
+    fetch_p(v0, 2);
+    fetch_p(v1, 3);
+    NF_SB; mult_p(u0, 0); mult_p(u1, 1); NF_SB;
+    dma_slot(0);
+    if (!isB) {
+      fetch(u0, combo_off(8), true);
+      fetch(u1, combo_off(8), false);
+    } else {
+      fetch(u0, combo_off(3), true);
+      fetch(u1, combo_off(4), true);
     }
+    NF_SB; mult_p(v0, 2); mult_p(v1, 3); NF_SB;
+    dma_slot(1);
+    if (!isB) {
+      fetch(v0, combo_off(0), true);
+      fetch(v1, combo_off(1), true);
+    } else {
+      fetch(v0, combo_off(5), true);
+      fetch(v1, combo_off(6), true);
+    }
+    combine();
+    NF_SB; mult_q(u0, 9); mult_q(u1, 12); NF_SB;
+    if (!isB) {
+      mult_hh(u1, 9);
+      NF_SB;
+    }
+    dma_slot(2);
+    fetch(u0, combo_off(isB ? 7 : 2), true);
+    NF_SB; mult_q(v0, 0); mult_q(v1, 3); NF_SB;
+    dma_slot(3);
+    mult_q(u0, 6);
+    NF_SB;
 #undef NF_SB
 #if NF_G2_PRIO
     __builtin_amdgcn_s_setprio(0);
@@ -532,11 +586,13 @@ __global__ __launch_bounds__(512, 2) void conv_g2_kernel(ConvArgs A) {
       pslot = col_slot;
     }
     have_prev = true;
-    // (5) the planes of the NEXT step were issued a full step ago or earlier: everything but this step's own DMAs (the
-    // youngest operations: the epilogue's stores precede them) must have landed before the barrier.  A column's first step
-    // reads four planes, the last two of which were issued during THIS step when this is a column's last step: then they
-    // must land as well.
-    const int allow = s + 1 == nstep ? 0 : ndma;
+    // (5) the planes of the NEXT step were issued a full step ago or earlier, except in two cases: everything but this
+    // step's own refill pieces (the youngest operations: the epilogue's stores precede them) must have landed before the
+    // barrier.  A column's first step reads four planes, the last two of which were issued during THIS step when this is a
+    // column's last step: then they must land as well.  And a column's second step reads entries 4 and 5 of the column,
+    // which its first step issued at its head: those must land too.  (Counting them as this step's own let the second
+    // step of a column read a plane still in flight when the first step was short: the half columns' steps are.)
+    const int allow = s + 1 == nstep ? 0 : ndma - ndma_head;
     if (allow >= 16) wait_vm<16>();
     else if (allow >= 12) wait_vm<12>();
     else if (allow >= 8) wait_vm<8>();
