@@ -770,13 +770,22 @@ def conv_layer_split16(h16, weight, bias, act, lattice):
 
 
 _UNIT_OK = {}
+_WEIGHT_EPOCH = [0]
 
 
 def invalidate_weight_checks():
     """Forget every cached verdict of `_weights_fit_fp16` and every cached fragment packing (call after editing weights
-    through `.data`, which does not bump a tensor's version counter)."""
+    through `.data`, which does not bump a tensor's version counter), and start a new `weight_epoch()`: the per-module
+    caches (ConvAct's widened / padded / packed weights) and GraphedFlow's capture key on it."""
     _UNIT_OK.clear()
     _PACKED.clear()
+    _WEIGHT_EPOCH[0] += 1
+
+
+def weight_epoch():
+    """Counts the `invalidate_weight_checks()` calls: a cache keyed on (tensor version, data_ptr) must also key on this, since
+    a write through `.data` changes neither."""
+    return _WEIGHT_EPOCH[0]
 
 
 _PACKED = {}
@@ -846,25 +855,57 @@ def conv_supported(x, weight):
 _GATHER_MAPS = {}
 
 
-def _pack_by_gather(weight, build, key):
-    """build(weight) -- a pure re-arrangement of the weights with zero padding (two-site expansion, fragment order, row
-    packing: a dozen small torch kernels) -- as ONE gather: the source index of every output element is found once per layer
-    shape by running `build` on a tensor of element numbers, then every packing is one nf_gather_pad launch.  (A training step
-    re-packs every layer's weights twice, forward and flipped / transposed for the input gradient: on small lattices those
-    launches were a quarter of the step.)"""
-    key = (tuple(weight.shape), weight.device) + key
+def _gather_map(shape, device, build, key):
+    """(source index of every element, shape) of build(w) for weights w of this shape -- a pure re-arrangement of the weights
+    with zero padding (two-site expansion, fragment order, row packing: a dozen small torch kernels) -- found once per `key` by
+    running `build` on a tensor of element numbers.  `key` must name everything `build` depends on besides the shape."""
+    key = (tuple(shape), device) + key
     ent = _GATHER_MAPS.get(key)
     if ent is None:
-        probe = torch.arange(1, weight.numel() + 1, dtype=torch.float64, device=weight.device).reshape(weight.shape)
+        n = 1
+        for s in shape:
+            n *= s
+        probe = torch.arange(1, n + 1, dtype=torch.float64, device=device).reshape(shape)
         packed = build(probe)
         idx = (packed.reshape(-1).round().to(torch.int64) - 1).to(torch.int32).contiguous()      # -1: a zero of the padding
         ent = (idx, tuple(packed.shape))
         _GATHER_MAPS[key] = ent
-    idx, shape = ent
+    return ent
+
+
+def _pack_by_gather(weight, gather_map):
+    """The packing a `_gather_map` describes, as ONE nf_gather_pad launch.  (A training step re-packs every layer's weights
+    twice, forward and flipped / transposed for the input gradient: on small lattices those launches were a quarter of the
+    step.)"""
+    idx, shape = gather_map
     w = weight.contiguous()
     out = torch.empty(shape, dtype=w.dtype, device=w.device)
     _check(load().nf_gather_pad(_ptr(w), _ptr(idx), _ptr(out), idx.numel(), w.numel(), w.element_size(), _stream()), "nf_gather_pad")
     return out
+
+
+def _conv_weight_map(shape, device, lat4, k4, cin, cout, compact, two_site, transposed, dtype_code):
+    """The `_gather_map` that packs (cout, cin, *k) weights (transposed: the input gradient's flipped / transposed weights of a
+    (cin, cout, *k) tensor) in the layout nf_conv_fwd reads for this layer.  That layout depends on the library's options
+    (NF_OPT_PIPE: row-packed for the persistent kernel, fragment order without it), so the layout code is part of the key."""
+    layout = load().nf_conv_weight_layout(lat4, k4, cin, cout, int(compact), 0, dtype_code)
+    ksize = list(shape[2:])
+
+    def build(w):
+        """the layer's weights (or its flipped / transposed weights: the input gradient's) in the library's fragment layout"""
+        if transposed:
+            w = w.flip(list(range(2, w.dim()))).transpose(0, 1)
+        if two_site:
+            # 16 columns: [0, cout) = the layer at site 2p (taps 0..k3-1), [8, 8+cout) = the same
+            # channels at site 2p+1 (taps 1..k3): one extra tap along the fastest axis
+            w2 = w.new_zeros((16, cin) + tuple(ksize[:-1]) + (ksize[-1] + 1,))
+            w2[:cout, ..., :ksize[-1]] = w
+            w2[8:8 + cout, ..., 1:] = w
+            w = w2
+        return conv_weight_for_layer(w, lat4, k4, cin, cout, compact, False, dtype_code)
+
+    return _gather_map(shape, device, build, (transposed, two_site, tuple(lat4), tuple(k4), cin, cout, int(compact), dtype_code,
+                                              layout))
 
 
 def _conv_launch(x, weight, bias, act, compact, parity, weight_src=None, transposed=False):
@@ -887,21 +928,8 @@ def _conv_launch(x, weight, bias, act, compact, parity, weight_src=None, transpo
         raise NormflowHipError("split-fp16 output needs an fp32 two-site layer with 8 output channels")
     two_site = bool(lib.nf_conv_two_site(cout, 0 if split16 else int(compact), lat[-1], ksize[-1]))
     eff_compact = False if (two_site and split16) else compact
-
-    def build(w):
-        """the layer's weights (or its flipped / transposed weights: the input gradient's) in the library's fragment layout"""
-        if transposed:
-            w = w.flip(list(range(2, w.dim()))).transpose(0, 1)
-        if two_site:
-            # 16 columns: [0, cout) = the layer at site 2p (taps 0..k3-1), [8, 8+cout) = the same
-            # channels at site 2p+1 (taps 1..k3): one extra tap along the fastest axis
-            w2 = w.new_zeros((16, cin) + tuple(ksize[:-1]) + (ksize[-1] + 1,))
-            w2[:cout, ..., :ksize[-1]] = w
-            w2[8:8 + cout, ..., 1:] = w
-            w = w2
-        return conv_weight_for_layer(w, lat4, k4, cin, cout, eff_compact, False, _dtype_code(x))
-
-    wfrag = _pack_by_gather(weight, build, (transposed, two_site, tuple(lat4), tuple(k4), cin, cout, int(eff_compact), _dtype_code(x)))
+    wfrag = _pack_by_gather(weight, _conv_weight_map(weight.shape, weight.device, lat4, k4, cin, cout, eff_compact, two_site,
+                                                     transposed, _dtype_code(x)))
     V = 1
     for n in lat:
         V *= n

@@ -24,7 +24,9 @@ class GraphedFlow:
         self._capture()
 
     def _param_state(self):
-        return tuple((p.data_ptr(), p._version) for p in self._net.parameters())
+        # (a write through .data bumps no version: invalidate_weight_checks() after it starts a new weight epoch)
+        from . import _hip
+        return tuple((p.data_ptr(), p._version) for p in self._net.parameters()) + (_hip.weight_epoch(),)
 
     def _capture(self):
         fn = self._net.backward if self._inverse else self._net.forward

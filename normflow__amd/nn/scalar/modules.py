@@ -84,7 +84,7 @@ class ConvAct(torch.nn.Sequential):
             return w, b
         cache = self.__dict__.setdefault('_w32', {})
         key = id(conv)
-        ver = (w._version, w.data_ptr(), None if b is None else b._version)
+        ver = (w._version, w.data_ptr(), None if b is None else b._version, _hip.weight_epoch())
         hit = cache.get(key)
         if hit is None or hit[0] != ver:
             hit = (ver, w.detach().float(), None if b is None else b.detach().float())
@@ -140,7 +140,7 @@ class ConvAct(torch.nn.Sequential):
             return w, b
         cache = self.__dict__.setdefault('_w8', {})
         key = (id(conv), pad_out, pad_in)
-        ver = (w._version, w.data_ptr(), None if b is None else b._version)
+        ver = (w._version, w.data_ptr(), None if b is None else b._version, _hip.weight_epoch())
         hit = cache.get(key)
         if hit is None or hit[0] != ver:
             w8 = w.new_zeros((no, ni) + tuple(w.shape[2:]))
@@ -238,7 +238,7 @@ class ConvAct(torch.nn.Sequential):
             return None
         if not all(_hip._weights_fit_fp16(w) for w, _ in wbs):
             return None
-        ver = tuple((w._version, w.data_ptr(), None if b is None else (b._version, b.data_ptr())) for w, b in wbs)
+        ver = tuple((w._version, w.data_ptr(), None if b is None else (b._version, b.data_ptr())) for w, b in wbs) + (_hip.weight_epoch(),)
         hit = self.__dict__.get('_small3d')
         if hit is None or hit[0] != ver:
             with torch.no_grad():
@@ -349,7 +349,7 @@ class ConvAct(torch.nn.Sequential):
             return None
         if not all(_hip._weights_fit_fp16(w) for w, _ in wbs):
             return None
-        ver = tuple((w._version, w.data_ptr(), None if b is None else (b._version, b.data_ptr())) for w, b in wbs)
+        ver = tuple((w._version, w.data_ptr(), None if b is None else (b._version, b.data_ptr())) for w, b in wbs) + (_hip.weight_epoch(),)
         hit = self.__dict__.get('_wide16')
         if hit is None or hit[0] != ver:
             with torch.no_grad():

@@ -536,3 +536,65 @@ def test_bench_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path, monkeypa
     assert np.array_equal(ya, y.reshape(-1)[idx].numpy())
     assert np.array_equal(np.load(tmp_path / "a" / "logJ.npy"), lf)
     assert 4 * (bench.DUMP_Y_VALUES + 1024) <= 64 << 20
+
+
+@pytest.mark.parametrize("cout,transposed", [(46, False), (8, False), (8, True)])
+def test_conv_gather_map_follows_the_pipe_option(cout, transposed):
+    """The index map `_conv_launch` packs a layer's weights with is cached per layer shape; the layout it must produce also
+    depends on NF_OPT_PIPE (row-packed for the persistent kernel, fragment order without it).  Warm under pipe on, then
+    pipe off, then on: each map reproduces, element for element, the packing `conv_weight_for_layer` makes under the option
+    in force -- a map cached under the other option would hand the kernel a blob of the wrong shape."""
+    lib = _hip.load()
+    lat4, k4 = (ctypes.c_int32 * 4)(4, 4, 4, 32), (ctypes.c_int32 * 4)(3, 3, 3, 3)
+    cin = 8
+    two_site = bool(lib.nf_conv_two_site(cout, 0, 32, 3))
+    g = torch.Generator().manual_seed(cout)
+    shape = (cin, cout, 3, 3, 3, 3) if transposed else (cout, cin, 3, 3, 3, 3)
+    w = torch.randn(shape, generator=g, dtype=torch.float64)
+
+    def direct():
+        v = w.flip([2, 3, 4, 5]).transpose(0, 1) if transposed else w
+        if two_site:
+            v2 = v.new_zeros((16, cin, 3, 3, 3, 4))
+            v2[:cout, ..., :3] = v
+            v2[8:8 + cout, ..., 1:] = v
+            v = v2
+        return _hip.conv_weight_for_layer(v, lat4, k4, cin, cout, False, False, _hip.NF_F32)
+
+    def via_map():
+        idx, out_shape = _hip._conv_weight_map(w.shape, w.device, lat4, k4, cin, cout, False, two_site, transposed, _hip.NF_F32)
+        flat = torch.cat((w.reshape(-1), w.new_zeros(1)))        # index -1: a zero of the padding
+        return flat[idx.long()].reshape(out_shape)
+
+    layouts = []
+    for pipe in (True, False, True):
+        with _hip.options(pipe=pipe):
+            layouts.append(lib.nf_conv_weight_layout(lat4, k4, cin, cout, 0, 0, _hip.NF_F32))
+            want, got = direct(), via_map()
+        assert got.shape == want.shape and torch.equal(got, want), (pipe, tuple(got.shape), tuple(want.shape))
+    assert layouts == [1, 0, 1]
+
+
+def test_data_edit_invalidation_reaches_every_weight_cache():
+    """A write through `.data` bumps no version counter, so the caches keyed on (version, data_ptr) -- ConvAct's fp32 copies of
+    half weights (_wb) and zero-padded narrow weights (_pad8), GraphedFlow's capture -- cannot see it by themselves; the
+    documented `_hip.invalidate_weight_checks()` after the edit must make each of them serve the edited values."""
+    from types import SimpleNamespace
+    from normflow__amd.graphs import GraphedFlow
+    torch.manual_seed(3)
+    net = ConvAct(1, 46, 3, conv_dim=4, hidden_sizes=[4, 4], acts=['tanh', 'tanh', None]).to(CPU, torch.float32)
+    conv = [m for m in net if hasattr(m, 'weight')][1]
+    w8, _ = net._pad8(conv, conv.weight, conv.bias, pad_out=True, pad_in=True)
+    state = GraphedFlow._param_state(SimpleNamespace(_net=net))
+    conv.weight.data.mul_(0.5)
+    _hip.invalidate_weight_checks()
+    w8b, _ = net._pad8(conv, conv.weight, conv.bias, pad_out=True, pad_in=True)
+    assert torch.equal(w8b[:4, :4], conv.weight.detach()) and not torch.equal(w8b, w8)
+    assert GraphedFlow._param_state(SimpleNamespace(_net=net)) != state
+    half = ConvAct(1, 2, 3, conv_dim=2, hidden_sizes=[4], acts=['tanh', None]).to(CPU, torch.float16)
+    hconv = [m for m in half if hasattr(m, 'weight')][0]
+    w32, _ = half._wb(hconv)
+    hconv.weight.data.mul_(0.5)
+    _hip.invalidate_weight_checks()
+    w32b, _ = half._wb(hconv)
+    assert torch.equal(w32b, hconv.weight.detach().float()) and not torch.equal(w32b, w32)

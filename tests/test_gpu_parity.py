@@ -1324,8 +1324,10 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
     x = torch.randn((B,) + lattice, device=DEV, dtype=torch.float32, generator=g)
     with torch.no_grad():
         y, lj = net_(x)
-    assert rel(torch.from_numpy(yd), y) <= 1e-6 and rel(torch.from_numpy(ld), lj) <= 1e-6, (rel(torch.from_numpy(yd), y),
-                                                                                            rel(torch.from_numpy(ld), lj))
+    # the timed pass has no float atomics and static item schedules: the dump is these outputs bit for bit
+    # (tests/test_kernel_state.py holds every kernel of the chain to that)
+    assert np.array_equal(yd.view(np.int32), y.cpu().numpy().view(np.int32)), rel(torch.from_numpy(yd), y)
+    assert np.array_equal(ld.view(np.int32), lj.cpu().numpy().view(np.int32)), rel(torch.from_numpy(ld), lj)
 
 
 # -------------------------------------------------- the prior as one Philox kernel
