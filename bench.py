@@ -4,7 +4,7 @@ draw) on BASELINE.json's headline workload: 32^4 phi^4 lattice, 8 RQ-spline coup
 (knots_len 16, ConvAct hidden [8,8], kernel 3, tanh), batch 1024 per GPU, fp32, synthetic
 inputs already resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU (RCCL for the timing barriers only); the batch shards over ranks with no data-path
@@ -12,12 +12,15 @@ collective (forward / sampling needs none).  With `--gpus N` and no torchrun env
 N ranks itself (plain child processes, before it makes any GPU call) and relays rank 0's line.
 
 Rank 0 prints ONE JSON line (contract in the task statement).  `value` is the WEAK-scaling aggregate (every rank
-runs the full per-GPU batch); extra keys:
+runs the full per-GPU batch).  A plain run does only what `value` and `ms_per_step` need: set-up, two untimed
+allocator-priming passes, W warm-up and K timed steps, the dump, the line.  --full also measures and checks the rest,
+each in work of its own, and adds these keys (the --no-* options drop single ones):
   strong               : the same network on a FIXED global batch (--batch, 1024) cut into N shards (BASELINE config 4)
   value_fp32_products  : the same timed loop with exact fp32 MFMA products everywhere (nf_set_option(NF_OPT_SPLIT16, 0));
                          `value` itself forms the conv products of tanh-fed layers from three fp16 MFMA products
   selfcheck            : the two arithmetics compared on a slab of the timed input before timing (the kernels did the work)
   roofline             : the dominant kernel of the timed region, HIP-event timed in here; roofline_kernels: the others
+  other_configs        : short timings of BASELINE configs 2, 3 and 5
   cpu_baseline         : the CPU oracle (oracle/nf_oracle.py, kind "port") on a bounded sample, fp32 and fp64 legs
 
 --dump-outputs DIR writes y and log|det J| of the last timed step as .npy files (dump_outputs below); weights and inputs are
@@ -53,14 +56,18 @@ def parse(argv=None):
     ap.add_argument("--lattice", type=str, default="32,32,32,32")
     ap.add_argument("--layers", type=int, default=8)
     ap.add_argument("--knots", type=int, default=16)
-    ap.add_argument("--scaling", choices=["weak", "strong", "both"], default="both",
-                    help="which leg(s) to time at N > 1; `value`/`scaling` of the line are the weak leg unless 'strong'")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-products", action="store_true", help="skip the exact-fp32-product leg")
-    ap.add_argument("--no-selfcheck", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short timings of BASELINE configs 2, 3 and 5")
+    ap.add_argument("--scaling", choices=["weak", "strong", "both"], default=None,
+                    help="which leg(s) to time at N > 1 (default 'weak', with --full 'both'); `value`/`scaling` of the line are "
+                         "the weak leg unless 'strong'")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the other scaling leg, the exact-fp32-product leg, "
+                         "the self-check, the per-kernel roofline timings, BASELINE configs 2, 3 and 5 and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fp32-products", action="store_true", help="with --full: skip the exact-fp32-product leg")
+    ap.add_argument("--no-selfcheck", action="store_true", help="with --full: skip the self-check")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short timings of BASELINE configs 2, 3 and 5")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--kernel-reps", type=int, default=10)
+    ap.add_argument("--kernel-reps", type=int, default=10, help="launches per roofline kernel timing (--full)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of a self-launched run (0 = pick a free one)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (rank 0's shard) as float32 .npy files "
@@ -69,6 +76,8 @@ def parse(argv=None):
     a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.scaling is None:
+        a.scaling = "both" if a.full else "weak"
     return a
 
 
@@ -319,6 +328,79 @@ def profiled_traffic(kernel_key, slab, lattice, knots):
     return None, reason
 
 
+# ------------------------------------------------------------------------------------------ roofline figures (--full)
+def roofline_figures(cpl, lattice, dev, a, inloop):
+    """The kernels of the timed pipeline, each timed by HIP events in launches of its own (and, where `inloop` has them,
+    inside one more pass of the timed loop) against the bound of its kind: the line's roofline keys."""
+    import torch
+    # Which kernels the timed pipeline runs: with this package's ConvAct on a plain even-odd
+    # mask the last conv layer and the spline are ONE kernel (nf_conv_rqs); otherwise the
+    # stand-alone coupling kernel consumes a materialised logit tensor.
+    with torch.no_grad():
+        probe = torch.zeros((1,) + lattice, device=dev, dtype=torch.float32)
+        fused = cpl._fused_atom(False, probe, probe, 0, cpl.nets[0], 0) is not None
+        pipeline_pair = cpl._params(cpl.nets[0], probe, parity=0)[1] == 1
+    kt = time_rqs_kernel(cpl, lattice, a.knots, dev, a.kernel_reps, pipeline_pair)
+    traffic, traffic_src = profiled_traffic("rqs_kernel", kt["slab"], lattice, a.knots)
+    hbm_obj = {"kernel": "nf::rqs_kernel<float,16,fwd>" + ("<pair>" if pipeline_pair else "<full>") +
+                         " (stand-alone RQ-spline coupling kernel)",
+               "bound": "hbm", "achieved": kt["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+               "frac": kt["gbs"] / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+               "launch_ms": 1e3 * kt["seconds"], "slab_batch": kt["slab"],
+               "algorithmic_bytes_per_launch": kt["algo_bytes"],
+               "in_timed_pipeline": not fused}
+    others = []
+    if fused:
+        reps = max(2, a.kernel_reps // 3)
+        ft = time_fused_last_layer(cpl, lattice, a.knots, dev, reps, a.batch)
+        split16 = ft["path"] == 3
+        if split16:
+            # K5h: every fp32 product = three fp16 MFMA products (fp32 accumulate).  `achieved` stays the ALGORITHMIC
+            # (fp32-equivalent) rate; the peak that bounds it is the fp16 matrix peak / 3.  Executed fp16 flops per
+            # algorithmic flop: 3 products x 84/81 (K slices padded to 4 kernel rows) x 48/46 (columns padded to 3 tiles).
+            peak = MFMA_F16_PEAK_TFLOPS / 3.0
+            h_traffic, h_src = profiled_traffic("conv_h_kernel", ft["slab"], lattice, a.knots)
+            il = inloop.get("nf_conv_rqs") if inloop else None
+            if il is not None:                       # the duration inside the timed loop; the burst figure stays beside it
+                ft = dict(ft, burst_seconds=ft["seconds"], seconds=1e-3 * il["ms"], tflops=ft["flops"] / (1e-3 * il["ms"]) / 1e12,
+                          launches=il["launches"])
+            executed = ft["tflops"] * 3.0 * (84.0 / 81.0) * (48.0 / 46.0)
+            roof = {"kernel": "nf::conv_h_kernel<fwd> (last conv layer 8->46 at the active sites + RQ-spline coupling epilogue, "
+                              "fp32 products as 3 x v_mfma_f32_16x16x32_f16; dominant kernel of the timed region)",
+                    "bound": "mfma", "achieved": ft["tflops"], "peak": peak, "unit": "TFLOP/s",
+                    "frac": ft["tflops"] / peak, "traffic": h_traffic, "traffic_source": h_src,
+                    "launch_ms": 1e3 * ft["seconds"], "slab_batch": ft["slab"],
+                    "algorithmic_flops_per_launch": ft["flops"],
+                    "peak_note": "dense fp16 MFMA peak 2500 TFLOP/s / 3 fp16 products per fp32 product",
+                    "executed_fp16_tflops": executed, "executed_frac_of_fp16_peak": executed / MFMA_F16_PEAK_TFLOPS,
+                    "vs_fp32_mfma_peak": ft["tflops"] / MFMA_F32_PEAK_TFLOPS}
+            if "burst_seconds" in ft:
+                roof["launch_ms_source"] = (f"HIP events around each of the {ft['launches']} launches of one more pass of the timed loop, "
+                                            "right after the timed steps")
+                roof["launch_ms_burst"] = 1e3 * ft["burst_seconds"]
+        else:
+            p_traffic, p_src = profiled_traffic("conv_pipe_kernel_fused", ft["slab"], lattice, a.knots)
+            roof = {"kernel": "nf::conv_pipe_kernel<2,3,3,compact,fused-rqs-fwd,wide,unrolled> (last conv layer 8->46 at the active sites "
+                              "+ RQ-spline coupling epilogue; dominant kernel of the timed region)",
+                    "bound": "mfma", "achieved": ft["tflops"], "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": ft["tflops"] / MFMA_F32_PEAK_TFLOPS, "traffic": p_traffic, "traffic_source": p_src,
+                    "launch_ms": 1e3 * ft["seconds"], "slab_batch": ft["slab"],
+                    "algorithmic_flops_per_launch": ft["flops"]}
+        others = time_hidden_layers(cpl, lattice, dev, reps, a.batch)
+        for o, key, entry in zip(others, ("conv_c2_kernel", "conv_g2_kernel"), ("nf_conv_first_split16", "nf_conv_fwd_split16")):
+            o["traffic"], o["traffic_source"] = profiled_traffic(key, o["slab_batch"], lattice, a.knots)
+            il = inloop.get(entry) if (inloop and split16) else None
+            if il is not None:
+                o["launch_ms_burst"] = o["launch_ms"]
+                o["achieved"] *= o["launch_ms"] / il["ms"]
+                o["frac"] = o["achieved"] / o["peak"]
+                o["launch_ms"] = il["ms"]
+                o["launch_ms_source"] = f"HIP events around each of the {il['launches']} launches of one more pass of the timed loop"
+    else:
+        roof = hbm_obj
+    return {"roofline": roof, "roofline_kernels": others, "roofline_hbm_kernel": hbm_obj}
+
+
 # ------------------------------------------------------------------------------------------ CPU baseline
 def cpu_model_string():
     try:
@@ -515,7 +597,7 @@ def main():
 
     # ---- before timing: the timed arithmetic against exact fp32 products on a slab of the timed input
     selfcheck = None
-    if not a.no_selfcheck:
+    if a.full and not a.no_selfcheck:
         nb = min(4, a.batch)
         with torch.no_grad():
             y1, l1 = net_(x[:nb])
@@ -557,9 +639,9 @@ def main():
             el = timed(x[:per], a.steps, a.warmup, dump=main_leg == "strong")
             legs["strong"] = {"value": a.batch * a.steps / el, "ms_per_step": 1e3 * el / a.steps, "global_batch": a.batch,
                               "batch_per_gpu": per}
-    inloop = inloop_kernel_ms(net_, x if main_leg == "weak" else x[:a.batch // world]) if rank == 0 else None
+    inloop = inloop_kernel_ms(net_, x if main_leg == "weak" else x[:a.batch // world]) if rank == 0 and a.full else None
     fp32_leg = None
-    if not a.no_fp32_products:
+    if a.full and not a.no_fp32_products:
         k2 = max(1, min(a.steps, 2))
         xb = x if main_leg == "weak" else x[:a.batch // world]
         with _hip.options(split16=False):
@@ -567,71 +649,6 @@ def main():
         fp32_leg = {"value": xb.shape[0] * world * k2 / el, "ms_per_step": 1e3 * el / k2, "steps": k2, "warmup": 1}
 
     if rank == 0:
-        # Which kernels the timed pipeline runs: with this package's ConvAct on a plain even-odd
-        # mask the last conv layer and the spline are ONE kernel (nf_conv_rqs); otherwise the
-        # stand-alone coupling kernel consumes a materialised logit tensor.
-        with torch.no_grad():
-            probe = torch.zeros((1,) + lattice, device=dev, dtype=torch.float32)
-            fused = cpl._fused_atom(False, probe, probe, 0, cpl.nets[0], 0) is not None
-            pipeline_pair = cpl._params(cpl.nets[0], probe, parity=0)[1] == 1
-        kt = time_rqs_kernel(cpl, lattice, a.knots, dev, a.kernel_reps, pipeline_pair)
-        traffic, traffic_src = profiled_traffic("rqs_kernel", kt["slab"], lattice, a.knots)
-        hbm_obj = {"kernel": "nf::rqs_kernel<float,16,fwd>" + ("<pair>" if pipeline_pair else "<full>") +
-                             " (stand-alone RQ-spline coupling kernel)",
-                   "bound": "hbm", "achieved": kt["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                   "frac": kt["gbs"] / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                   "launch_ms": 1e3 * kt["seconds"], "slab_batch": kt["slab"],
-                   "algorithmic_bytes_per_launch": kt["algo_bytes"],
-                   "in_timed_pipeline": not fused}
-        others = []
-        if fused:
-            reps = max(2, a.kernel_reps // 3)
-            ft = time_fused_last_layer(cpl, lattice, a.knots, dev, reps, a.batch)
-            split16 = ft["path"] == 3
-            if split16:
-                # K5h: every fp32 product = three fp16 MFMA products (fp32 accumulate).  `achieved` stays the ALGORITHMIC
-                # (fp32-equivalent) rate; the peak that bounds it is the fp16 matrix peak / 3.  Executed fp16 flops per
-                # algorithmic flop: 3 products x 84/81 (K slices padded to 4 kernel rows) x 48/46 (columns padded to 3 tiles).
-                peak = MFMA_F16_PEAK_TFLOPS / 3.0
-                h_traffic, h_src = profiled_traffic("conv_h_kernel", ft["slab"], lattice, a.knots)
-                il = inloop.get("nf_conv_rqs") if inloop else None
-                if il is not None:                       # the duration inside the timed loop; the burst figure stays beside it
-                    ft = dict(ft, burst_seconds=ft["seconds"], seconds=1e-3 * il["ms"], tflops=ft["flops"] / (1e-3 * il["ms"]) / 1e12,
-                              launches=il["launches"])
-                executed = ft["tflops"] * 3.0 * (84.0 / 81.0) * (48.0 / 46.0)
-                roof = {"kernel": "nf::conv_h_kernel<fwd> (last conv layer 8->46 at the active sites + RQ-spline coupling epilogue, "
-                                  "fp32 products as 3 x v_mfma_f32_16x16x32_f16; dominant kernel of the timed region)",
-                        "bound": "mfma", "achieved": ft["tflops"], "peak": peak, "unit": "TFLOP/s",
-                        "frac": ft["tflops"] / peak, "traffic": h_traffic, "traffic_source": h_src,
-                        "launch_ms": 1e3 * ft["seconds"], "slab_batch": ft["slab"],
-                        "algorithmic_flops_per_launch": ft["flops"],
-                        "peak_note": "dense fp16 MFMA peak 2500 TFLOP/s / 3 fp16 products per fp32 product",
-                        "executed_fp16_tflops": executed, "executed_frac_of_fp16_peak": executed / MFMA_F16_PEAK_TFLOPS,
-                        "vs_fp32_mfma_peak": ft["tflops"] / MFMA_F32_PEAK_TFLOPS}
-                if "burst_seconds" in ft:
-                    roof["launch_ms_source"] = (f"HIP events around each of the {ft['launches']} launches of one more pass of the timed loop, "
-                                                "right after the timed steps")
-                    roof["launch_ms_burst"] = 1e3 * ft["burst_seconds"]
-            else:
-                p_traffic, p_src = profiled_traffic("conv_pipe_kernel_fused", ft["slab"], lattice, a.knots)
-                roof = {"kernel": "nf::conv_pipe_kernel<2,3,3,compact,fused-rqs-fwd,wide,unrolled> (last conv layer 8->46 at the active sites "
-                                  "+ RQ-spline coupling epilogue; dominant kernel of the timed region)",
-                        "bound": "mfma", "achieved": ft["tflops"], "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": ft["tflops"] / MFMA_F32_PEAK_TFLOPS, "traffic": p_traffic, "traffic_source": p_src,
-                        "launch_ms": 1e3 * ft["seconds"], "slab_batch": ft["slab"],
-                        "algorithmic_flops_per_launch": ft["flops"]}
-            others = time_hidden_layers(cpl, lattice, dev, reps, a.batch)
-            for o, key, entry in zip(others, ("conv_c2_kernel", "conv_g2_kernel"), ("nf_conv_first_split16", "nf_conv_fwd_split16")):
-                o["traffic"], o["traffic_source"] = profiled_traffic(key, o["slab_batch"], lattice, a.knots)
-                il = inloop.get(entry) if (inloop and split16) else None
-                if il is not None:
-                    o["launch_ms_burst"] = o["launch_ms"]
-                    o["achieved"] *= o["launch_ms"] / il["ms"]
-                    o["frac"] = o["achieved"] / o["peak"]
-                    o["launch_ms"] = il["ms"]
-                    o["launch_ms_source"] = f"HIP events around each of the {il['launches']} launches of one more pass of the timed loop"
-        else:
-            roof = hbm_obj
         lead = legs[main_leg]
         line = {
             "metric": "lattice configs/sec (forward+logdet)", "value": lead["value"], "unit": "configs/s",
@@ -643,11 +660,10 @@ def main():
                                    f"layers (knots_len {a.knots}, ConvAct 1-8-8-{3*a.knots-2}, k=3, tanh), "
                                    f"batch {lead['batch_per_gpu']} per GPU, forward + log|det J|, no_grad",
                        "global_batch": lead["global_batch"], "parallelism": f"dp{world}"},
-            "roofline": roof,
-            "roofline_kernels": others,
-            "roofline_hbm_kernel": hbm_obj,
             "kernel_src_sha": kernel_src_sha(),
         }
+        if a.full:
+            line.update(roofline_figures(cpl, lattice, dev, a, inloop))
         if ranks_info is not None:
             line.update(ranks_info)
         for name, leg in legs.items():
@@ -658,9 +674,9 @@ def main():
             line["fp32_products"] = dict(fp32_leg, arithmetic="exact fp32 MFMA products everywhere (nf_set_option(NF_OPT_SPLIT16, 0)); same network, same input")
         if selfcheck is not None:
             line["selfcheck"] = selfcheck
-        if not a.no_other_configs and world == 1:
+        if a.full and not a.no_other_configs and world == 1:
             line["other_configs"] = other_configs(dev)
-        if not a.no_cpu_baseline and world == 1:     # CPU baseline: rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1:     # CPU baseline: rank 0 at N=1 only
             line["cpu_baseline"] = cpu_baseline(cpl, lattice, a.knots, a.cpu_seconds)
         print(json.dumps(line), flush=True)
     if world > 1:

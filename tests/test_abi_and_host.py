@@ -538,6 +538,18 @@ def test_bench_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path, monkeypa
     assert 4 * (bench.DUMP_Y_VALUES + 1024) <= 64 << 20
 
 
+def test_bench_full_is_off_by_default(monkeypatch):
+    """A plain bench.py run times the headline leg alone; --full adds the other scaling leg (and the rest), an explicit
+    --scaling holds either way."""
+    monkeypatch.setattr(os, "environ", os.environ.copy())      # bench.py sets its defaults in os.environ at import
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and a.scaling == "weak"
+    assert bench.parse(["--full"]).scaling == "both"
+    assert bench.parse(["--scaling", "strong"]).scaling == "strong"
+    assert bench.parse(["--full", "--scaling", "weak"]).scaling == "weak"
+
+
 @pytest.mark.parametrize("cout,transposed", [(46, False), (8, False), (8, True)])
 def test_conv_gather_map_follows_the_pipe_option(cout, transposed):
     """The index map `_conv_launch` packs a layer's weights with is cached per layer shape; the layout it must produce also

@@ -1267,8 +1267,8 @@ def test_headline_network_full_size_vs_fp64_oracle(parity_report):
 
 
 def test_bench_self_launch_two_ranks_rehearsal():
-    """`python bench.py --gpus 2` with no launcher: the parent starts two ranks itself (before any GPU call of its own) and
-    rank 0 prints ONE line with n_gpus 2, a weak and a strong leg.  NF_BENCH_REHEARSAL=1: both ranks share cuda:0 and meet
+    """`python bench.py --gpus 2 --full` with no launcher: the parent starts two ranks itself (before any GPU call of its own)
+    and rank 0 prints ONE line with n_gpus 2, a weak and a strong leg.  NF_BENCH_REHEARSAL=1: both ranks share cuda:0 and meet
     over gloo -- the code path of the 8-GPU run (RCCL there), on the one-GPU box."""
     import json
     import subprocess
@@ -1277,7 +1277,7 @@ def test_bench_self_launch_two_ranks_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["NF_BENCH_REHEARSAL"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8",
-                        "--lattice", "4,4,4,32", "--layers", "2", "--kernel-reps", "3"],
+                        "--lattice", "4,4,4,32", "--layers", "2", "--kernel-reps", "3", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1290,9 +1290,10 @@ def test_bench_self_launch_two_ranks_rehearsal():
 
 
 def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
-    """`python bench.py --steps 3 --dump-outputs DIR` on a small lattice: the line reports 3 timed steps and ms_per_step, and
-    DIR/y.npy, DIR/logJ.npy (float32, in full at this size) are bench.build_net's network on bench's seeded input, recomputed
-    here with bench's torch defaults (float32, CPU-initialised weights)."""
+    """`python bench.py --steps 3 --dump-outputs DIR` on a small lattice: the line reports 3 timed steps and ms_per_step and,
+    without --full, nothing else that takes work of its own; DIR/y.npy, DIR/logJ.npy (float32, in full at this size) are
+    bench.build_net's network on bench's seeded input, recomputed here with bench's torch defaults (float32, CPU-initialised
+    weights)."""
     import json
     import subprocess
     import sys
@@ -1302,14 +1303,17 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
     out = tmp_path / "dump"
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--batch", str(B), "--lattice", ",".join(map(str, lattice)), "--layers", str(layers), "--kernel-reps", "3",
-                        "--no-cpu-baseline", "--no-other-configs", "--dump-outputs", str(out)],
+                        "--batch", str(B), "--lattice", ",".join(map(str, lattice)), "--layers", str(layers),
+                        "--dump-outputs", str(out)],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
     line = json.loads(lines[0])
     assert line["steps"] == 3 and line["ms_per_step"] > 0
+    full_only = {"strong", "value_fp32_products", "fp32_products", "selfcheck", "roofline", "roofline_kernels",
+                 "roofline_hbm_kernel", "other_configs", "cpu_baseline"}
+    assert not full_only & set(line), sorted(full_only & set(line))
     yd, ld = np.load(out / "y.npy"), np.load(out / "logJ.npy")
     assert yd.dtype == np.float32 and yd.shape == (B,) + lattice and ld.dtype == np.float32 and ld.shape == (B,)
     dtype, device = torch.get_default_dtype(), torch.get_default_device()
