@@ -447,6 +447,32 @@ int nf_normal_logprob_vjp(const void *x, const void *loc, const void *scale, con
 int nf_normal_sample(void *x, void *logr, const void *loc, const void *scale, int64_t B, int64_t V, uint64_t seed,
                      uint64_t offset, void *workspace, size_t workspace_bytes, int dtype, void *stream);
 
+/* ---- blocked Metropolis on the device (BlockedMCMCSampler, src/mcmc/mcmc.py:132-220; block updater
+ * src/prior/prior.py:106-112, 161-178) for C independent chains.  x is the chains' prior-side field (C, V); block k is the
+ * sites [k block_len, (k+1) block_len) of every chain.  Neither entry allocates, copies or synchronises: both can be
+ * captured into a HIP graph.  fp32 and fp64.
+ *
+ * nf_block_propose: backup[c, j] = x[c, k block_len + j], then x[c, k block_len + j] = loc[s] + scale[s] z[c, j] with
+ * s = k block_len + j: the block's OWN sites' loc / scale ((V) or NULL: 0 / 1).  Sites outside the block are not touched.
+ * z is exactly what nf_normal_sample draws for a (B = C, V = block_len) field with the same seed and offset (its layout
+ * above: group q = j / 4 (fp32) or j / 2 (fp64), g = c ceil(block_len / per) + q, counter = (lo32 g, hi32 g, lo32 offset,
+ * hi32 offset), key = (lo32 seed, hi32 seed ^ NF_PHILOX_KEY_DOMAIN)), i.e. the block is
+ * oracle/nf_oracle.py::normal_prior_sample(seed, offset, C, block_len, loc_blk, scale_blk).
+ *
+ * nf_block_accept: per chain c one uniform from counter = (lo32 c, hi32 c, lo32 offset, hi32 offset) and key =
+ * (lo32 seed, hi32 seed ^ NF_PHILOX_ACCEPT_DOMAIN) -- a key domain of its own, so the uniforms never share a stream with
+ * the normals -- u = ((r0 << 21 ^ r1 >> 11) + 1) 2^-53 in (0, 1]; in double:
+ *   accept = force_accept || log u < logqp_ref[c] - (logq[c] - logp[c]).
+ * Accepted: logqp_ref[c] = logq[c] - logp[c].  Rejected: the block of x[c] is copied back from backup[c], bitwise.
+ * accept_out[c] = accept (uint8).  logq / logp (C) are of the field dtype, logqp_ref (C) is double for either.
+ * The caller owns the stream positions, as for nf_normal_sample: a fresh offset per launch. */
+#define NF_PHILOX_ACCEPT_DOMAIN 0x6e666163u   /* 'nfac' */
+int nf_block_propose(void *x, void *backup, const void *loc, const void *scale, int64_t C, int64_t V, int64_t block_len,
+                     int64_t block_ind, uint64_t seed, uint64_t offset, int dtype, void *stream);
+int nf_block_accept(void *x, const void *backup, const void *logq, const void *logp, double *logqp_ref,
+                    uint8_t *accept_out, int64_t C, int64_t V, int64_t block_len, int64_t block_ind, int force_accept,
+                    uint64_t seed, uint64_t offset, int dtype, void *stream);
+
 /* ---- VJP of the conv layer (K5) ---------------------------------------------------------------
  * grad_input is nf_conv_fwd itself applied to the pre-activation cotangent with the weights
  * flipped along every kernel axis and in/out channels swapped.  The two entry points below are

@@ -71,6 +71,8 @@ PROTOTYPES = {
     "nf_normal_logprob": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _SZ, _I, _P]),
     "nf_normal_logprob_vjp": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I, _P]),
     "nf_normal_sample": (_I, [_P, _P, _P, _P, _I64, _I64, C.c_uint64, C.c_uint64, _P, _SZ, _I, _P]),
+    "nf_block_propose": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, C.c_uint64, C.c_uint64, _I, _P]),
+    "nf_block_accept": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_act_vjp": (_I, [_P, _P, _P, _I64, _I, _I, _P]),
     "nf_conv_wgrad_cols": (_I, [_I, _I]),
     "nf_conv_wgrad": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, _P]),
@@ -1567,3 +1569,51 @@ def normal_sample(loc, scale, batch_size, shape, dtype, device, generator=None):
                                        C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64((offset // 4) + ((b0 // MAX_B) << 40)),
                                        _ptr(ws), ws.numel(), _dtype_code(x), _stream()), "nf_normal_sample")
     return x, logr
+
+
+# ========================================================================= blocked Metropolis (nf_mcmc.hip)
+def _philox_position(device, generator=None):
+    """(seed, kernel offset) for one launch of a Philox kernel, taken from torch's CUDA generator of `device` (or
+    `generator`) and advanced by one call's worth, as `normal_sample` does: torch.manual_seed governs these kernels too."""
+    gen = generator if generator is not None else torch.cuda.default_generators[device.index if device.index is not None
+                                                                                  else torch.cuda.current_device()]
+    seed, offset = gen.initial_seed(), gen.get_offset()
+    gen.set_offset(offset + 4)            # torch keeps offsets in multiples of 4
+    return C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(offset // 4)
+
+
+def _block_args(x, backup, block_len, block_ind):
+    _require_device(x, backup)
+    if not x.is_contiguous() or not backup.is_contiguous():
+        raise NormflowHipError("blocked Metropolis kernels need contiguous x and backup")
+    Cn = x.shape[0]
+    V = x[0].numel() if Cn else x.numel()
+    if backup.dtype != x.dtype or backup.numel() != Cn * block_len:
+        raise NormflowHipError(f"backup must hold ({Cn}, {block_len}) values of {x.dtype}")
+    return Cn, V
+
+
+def block_propose(x, backup, loc, scale, block_len, block_ind, generator=None):
+    """nf_block_propose: block `block_ind` of every chain of x (C, *L) is saved into backup (C, block_len) and redrawn
+    from the normal prior (loc / scale (V) or None), in place."""
+    Cn, V = _block_args(x, backup, block_len, block_ind)
+    for t in (loc, scale):
+        if t is not None and (t.dtype != x.dtype or t.device != x.device or t.numel() != V or not t.is_contiguous()):
+            raise NormflowHipError("loc / scale must be contiguous (V) tensors of the field's dtype and device")
+    seed, offset = _philox_position(x.device, generator)
+    _check(load().nf_block_propose(_ptr(x), _ptr(backup), _ptr(loc), _ptr(scale), Cn, V, int(block_len), int(block_ind),
+                                   seed, offset, _dtype_code(x), _stream()), "nf_block_propose")
+
+
+def block_accept(x, backup, logq, logp, logqp_ref, accept_out, block_len, block_ind, force_accept=False, generator=None):
+    """nf_block_accept: the Metropolis decision of every chain on the device; logqp_ref (C) float64 is updated where
+    accepted, the block of x is restored from backup where rejected, accept_out (C) uint8 gets the flags."""
+    Cn, V = _block_args(x, backup, block_len, block_ind)
+    _require_device(logq, logp, logqp_ref, accept_out)
+    for t, dt in ((logq, x.dtype), (logp, x.dtype), (logqp_ref, torch.float64), (accept_out, torch.uint8)):
+        if t.dtype != dt or t.numel() != Cn or not t.is_contiguous():
+            raise NormflowHipError(f"block_accept: expected a contiguous ({Cn},) {dt} tensor, got {tuple(t.shape)} {t.dtype}")
+    seed, offset = _philox_position(x.device, generator)
+    _check(load().nf_block_accept(_ptr(x), _ptr(backup), _ptr(logq), _ptr(logp), _ptr(logqp_ref), _ptr(accept_out), Cn, V,
+                                  int(block_len), int(block_ind), int(bool(force_accept)), seed, offset, _dtype_code(x),
+                                  _stream()), "nf_block_accept")

@@ -1,1 +1,1 @@
-from .mcmc import MCMCSampler, MCMCHistory, Metropolis
+from .mcmc import MCMCSampler, BlockedMCMCSampler, MCMCHistory, Metropolis, ModifiedMetropolis

@@ -1,11 +1,15 @@
-"""Independence-Metropolis sampling on top of the flow (reference: src/mcmc/mcmc.py).
-Host-side and serial by nature (accept/reject is a chain); the proposals come from
-`posterior.sample__`, i.e. from the HIP path."""
+"""Metropolis sampling on top of the flow (reference: src/mcmc/mcmc.py).
+
+`MCMCSampler` (independence Metropolis) is host-side and serial by nature (accept/reject is a chain); the proposals come
+from `posterior.sample__`, i.e. from the HIP path.  `BlockedMCMCSampler` redraws one block of the prior-side field at a
+time; on a HIP device it runs C independent chains batched through the flow, with proposal, accept/reject and restore
+on the GPU (nf_mcmc.hip)."""
 import copy
 
 import numpy as np
 import torch
 
+from .. import _hip
 from ..lib.stats import Resampler, estimate_logz, fmt_val_err
 
 seize = lambda t: t.detach().cpu().numpy()
@@ -42,6 +46,36 @@ class Metropolis:
     def calc_accept_count(accept_seq):
         pos = np.where(accept_seq)[0]
         return pos[1:] - pos[:-1]
+
+    @staticmethod
+    def calc_tau_rejections_prob(accept_seq, max_tau=100):
+        """p[tau] = fraction of positions i with tau + 1 rejections in a row from i on (mcmc.py:338-351)."""
+        rej = ~np.asarray(accept_seq, dtype=bool)
+        p_tau = np.zeros(max_tau)
+        run = rej
+        p_tau[0] = np.mean(run)
+        for tau in range(1, max_tau):
+            run = run[:-1] & rej[tau:]
+            p_tau[tau] = np.mean(run)
+        return p_tau
+
+
+class ModifiedMetropolis(Metropolis):
+    """Metropolis with an extra Gaussian penalty tau (logqp_ref - logqp)^2 on the log acceptance (mcmc.py:354-375)."""
+
+    @staticmethod
+    @torch.no_grad()
+    def calc_accept_status(logqp, logqp_ref=None, tau=0):
+        logqp = np.asarray(logqp)
+        ref = logqp[0] if logqp_ref is None else logqp_ref
+        logu = np.log(np.random.rand(logqp.shape[0]))
+        status = np.empty(len(logqp), dtype=bool)
+        for i, cur in enumerate(logqp):
+            d = ref - cur
+            status[i] = logu[i] < -(tau * d ** 2 + (-d if d < 0 else 0))
+            if status[i]:
+                ref = cur
+        return status
 
 
 class MCMCHistory:
@@ -150,3 +184,196 @@ class MCMCSampler:
 
     def log_prob(self, y, action_logz=0):
         return -self._model.action(y) - action_logz
+
+
+class BlockedMCMCSampler(MCMCSampler):
+    """Metropolis with block updates of the prior-side field x (mcmc.py:132-220): a sweep redraws the blocks of x one at a
+    time from the prior, pushes x through the flow and accepts or rejects the new block by log u < logqp_ref - (logq - logp).
+
+    With n_chains=1 it is the reference's sampler: the same start, `_ref` update, history keys and return shapes.
+    MI355X-side extension (no counterpart in the reference), like `Posterior.graphed`: `n_chains=C` runs C independent
+    chains at once; output row r is sweep r // C of chain r % C, and `_ref` keeps every chain's last configuration and
+    logqp, so the next call continues all C chains.  On a HIP device with the kernel prior (NormalPrior with
+    torch_rng=False) a block step is nf_block_propose, the flow and the action at batch C, and nf_block_accept: no host
+    synchronisation per block, the accept flags collect on the device and are read once per `sample__`.  Its random
+    streams are those kernels' (include/normflow_hip.h), keyed by torch's CUDA generator.  On CPU tensors, or with
+    torch_rng=True, the reference's loop runs as written (torch's sampler, `np.random` uniforms)."""
+
+    @torch.no_grad()
+    def sample(self, batch_size=1, **kwargs):
+        return self.sample__(batch_size=batch_size, **kwargs)[0]
+
+    @torch.no_grad()
+    def sample_(self, batch_size=1, **kwargs):
+        return self.sample__(batch_size=batch_size, **kwargs)[:2]
+
+    @torch.no_grad()
+    def sample__(self, batch_size=1, n_blocks=1, bookkeeping=False, n_chains=1):
+        """(cfgs, logq, logp) of batch_size samples: batch_size // n_chains sweeps of every chain."""
+        prior = self._model.prior
+        n_chains = int(n_chains)
+        if n_chains < 1 or batch_size % n_chains != 0:
+            raise ValueError(f"batch_size ({batch_size}) must be a positive multiple of n_chains ({n_chains})")
+        block_len, n_blocks = self._block_len(n_blocks)
+        x, logqp_ref = self._start(n_chains)
+        prior.setup_blockupdater(block_len)
+
+        n_sweeps = batch_size // n_chains
+        cfgs = torch.empty((batch_size, *prior.shape), dtype=x.dtype, device=x.device)
+        logq = torch.empty((batch_size,), dtype=x.dtype, device=x.device)
+        logp = torch.empty((batch_size,), dtype=x.dtype, device=x.device)
+        device = self._on_device(x)
+        if device:
+            ref_t = self._ref_tensor(logqp_ref, n_chains, x.device)
+            flags = torch.empty((n_sweeps, n_blocks, n_chains), dtype=torch.uint8, device=x.device)
+        else:
+            accept_seq = np.empty((batch_size, n_blocks), dtype=bool)
+
+        for s in range(n_sweeps):
+            rows = slice(s * n_chains, (s + 1) * n_chains)
+            if device:
+                self._sweep_device(x, n_blocks, ref_t, flags[s], fresh=(logqp_ref is None and s == 0))
+            else:
+                acc, logqp_ref = self._sweep_host(x, n_blocks, logqp_ref)
+                accept_seq[rows] = acc.reshape(n_chains, n_blocks)
+            y, lq, lp = self._evaluate(x)
+            cfgs[rows], logq[rows], logp[rows] = y, lq, lp
+        if device:     # the one read of the flags per call
+            accept_seq = flags.permute(0, 2, 1).reshape(batch_size, n_blocks).cpu().numpy().astype(bool)
+
+        # update the '_ref' dictionary for the next round
+        if n_chains == 1:
+            self._ref['sample'] = y[-1]
+            self._ref['logq'] = logq[-1].item()
+            self._ref['logp'] = logp[-1].item()
+            self._ref['logqp'] = (logq[-1] - logp[-1]).item()
+        else:
+            self._ref.update(sample=y, logq=lq, logp=lp, logqp=(lq - lp).to(torch.float64))
+
+        self.history.bookkeeping(accept_rate=np.mean(accept_seq))  # always save
+        if bookkeeping:
+            self.history.bookkeeping(logq=logq, logp=logp)
+            self.history.bookkeeping(accept_seq=accept_seq.ravel() if n_chains == 1 else accept_seq)
+        return cfgs, logq, logp
+
+    @torch.no_grad()
+    def sweep(self, x, n_blocks=1, logqp_ref=None):
+        """In-place sweeper over the n_blocks blocks of x (C, *shape): returns (accept_seq, logqp_ref), accept_seq of shape
+        (n_blocks,) for one chain and (C, n_blocks) for C; logqp_ref None starts fresh chains (first block accepted)."""
+        block_len, n_blocks = self._block_len(n_blocks)
+        prior = self._model.prior
+        bu = getattr(prior, 'blockupdater', None)
+        if bu is None or bu.block_len != block_len:
+            prior.setup_blockupdater(block_len)
+        self._check_field(x)
+        if not self._on_device(x):
+            return self._sweep_host(x, n_blocks, logqp_ref)
+        n = x.shape[0]
+        ref_t = self._ref_tensor(logqp_ref, n, x.device)
+        flags = torch.empty((n_blocks, n), dtype=torch.uint8, device=x.device)
+        self._sweep_device(x, n_blocks, ref_t, flags, fresh=logqp_ref is None)
+        acc = flags.t().cpu().numpy().astype(bool)
+        if n == 1:
+            return acc[0], ref_t.item()
+        return acc, ref_t
+
+    @torch.no_grad()
+    def step(self, x, block_ind, logqp_ref, accept_out, force_accept=False):
+        """One block step of C chains on the device, in place: nf_block_propose, the flow and the action at batch C, then
+        nf_block_accept, which updates logqp_ref (C) float64 and writes the flags into accept_out (C) uint8."""
+        prior, model = self._model.prior, self._model
+        bu = prior.blockupdater
+        bu(x, block_ind)
+        y, logJ = model.net_(x)
+        logq = (prior.log_prob(x) - logJ).to(x.dtype)
+        logp = (-model.action(y)).to(x.dtype)
+        _hip.block_accept(x, bu.backup_block, logq.contiguous(), logp.contiguous(), logqp_ref, accept_out, bu.block_len,
+                          block_ind, force_accept=force_accept)
+
+    # ---- internals
+    def _block_len(self, n_blocks):
+        nvar = self._model.prior.nvar
+        if isinstance(n_blocks, int):
+            block_len = nvar // n_blocks
+            if n_blocks < 1 or block_len * n_blocks != nvar:
+                raise AssertionError(f"n_blocks ({n_blocks}) must divide the number of sites ({nvar})")
+            return block_len, n_blocks
+        return nvar, 1
+
+    @staticmethod
+    def _check_field(x):
+        if x.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"BlockedMCMCSampler supports float32 and float64 fields, got {x.dtype}")
+
+    def _on_device(self, x):
+        return x.is_cuda and not getattr(self._model.prior, 'torch_rng', True)
+
+    def _start(self, n_chains):
+        """Chains to continue (inverse flow of `_ref['sample']`) or fresh prior draws with logqp_ref None."""
+        model, prior = self._model, self._model.prior
+        s = self._ref['sample']
+        want = tuple(prior.shape) if n_chains == 1 else (n_chains, *prior.shape)
+        if s is not None and tuple(s.shape) == want:
+            x = model.net_.backward(s.unsqueeze(0) if n_chains == 1 else s)[0]
+            logqp_ref = self._ref['logqp']
+        else:
+            print("Starting from scratch & setting logqp_ref to None")
+            x = prior.sample(n_chains)
+            logqp_ref = None
+        x = x.contiguous()
+        self._check_field(x)
+        return x, logqp_ref
+
+    @staticmethod
+    def _ref_tensor(logqp_ref, n, device):
+        """logqp_ref as the (n) float64 device buffer nf_block_accept updates (a copy: `_ref` is left as it is)."""
+        if logqp_ref is None:
+            return torch.zeros(n, dtype=torch.float64, device=device)
+        t = torch.as_tensor(logqp_ref, dtype=torch.float64).to(device).reshape(-1)
+        return (t.expand(n) if t.numel() == 1 else t).clone()
+
+    def _evaluate(self, x):
+        model = self._model
+        y, logJ = model.net_(x)
+        return y, model.prior.log_prob(x) - logJ, -model.action(y)
+
+    def _sweep_device(self, x, n_blocks, ref_t, flags, fresh):
+        for k in range(n_blocks):
+            self.step(x, k, ref_t, flags[k], force_accept=(fresh and k == 0))
+
+    def _sweep_host(self, x, n_blocks, logqp_ref):
+        """The reference's sweep (mcmc.py:199-220); with C > 1 chains every chain takes its own uniform and decision."""
+        prior, net_, action = self._model.prior, self._model.net_, self._model.action
+        n = x.shape[0]
+        if n == 1:
+            accept_seq = np.empty(n_blocks, dtype=bool)
+            lrand_arr = np.log(np.random.rand(n_blocks))
+        else:
+            accept_seq = np.empty((n, n_blocks), dtype=bool)
+            lrand_arr = np.log(np.random.rand(n_blocks, n))
+            if logqp_ref is not None:
+                logqp_ref = seize(torch.as_tensor(logqp_ref, dtype=torch.float64)).reshape(-1)
+        for ind in range(n_blocks):
+            prior.blockupdater(x, ind)  # in-place updater
+            y, logJ = net_(x)
+            logq = prior.log_prob(x) - logJ
+            logp = -action(y)
+            if n == 1:
+                if ind == 0 and logqp_ref is None:
+                    accept_seq[ind] = True
+                else:
+                    accept_seq[ind] = lrand_arr[ind] < logqp_ref - (logq - logp)[0]
+                if accept_seq[ind]:
+                    logqp_ref = (logq - logp).item()
+                else:
+                    prior.blockupdater.restore(x, ind)
+                continue
+            d = seize(logq - logp).astype(np.float64)
+            ok = np.ones(n, dtype=bool) if (ind == 0 and logqp_ref is None) else lrand_arr[ind] < logqp_ref - d
+            accept_seq[:, ind] = ok
+            logqp_ref = d if logqp_ref is None else np.where(ok, d, logqp_ref)
+            if not ok.all():
+                prior.blockupdater.restore(x, ind, torch.as_tensor(~ok, device=x.device))
+        if n > 1:
+            logqp_ref = torch.as_tensor(logqp_ref, dtype=torch.float64)
+        return accept_seq, logqp_ref

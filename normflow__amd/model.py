@@ -7,7 +7,7 @@ import torch
 
 from .device import ModelDeviceHandler
 from .fitter import Fitter
-from .mcmc import MCMCSampler
+from .mcmc import MCMCSampler, BlockedMCMCSampler
 
 
 class Posterior:
@@ -64,13 +64,15 @@ class Posterior:
 
 class Model:
     """Model(prior=..., net_=..., action=...): `.fit(...)` trains, `.posterior.sample(n)` draws,
-    `.mcmc.sample(n)` draws with Metropolis correction, `.device_handler` places / parallelises."""
+    `.mcmc.sample(n)` draws with Metropolis correction, `.blocked_mcmc.sample(n, n_blocks=k)` with block-update Metropolis,
+    `.device_handler` places / parallelises."""
 
     def __init__(self, *, prior, net_, action, name=None):
         self.prior, self.net_, self.action, self.name = prior, net_, action, name
         self.fit = Fitter(self)
         self.posterior = self.raw_dist = Posterior(self)
         self.mcmc = MCMCSampler(self)
+        self.blocked_mcmc = BlockedMCMCSampler(self)
         self.device_handler = ModelDeviceHandler(self)
 
     def transform(self, x):

@@ -111,6 +111,10 @@ class NormalPrior(Prior):
     loc = property(lambda self: self._p[0])
     scale = property(lambda self: self._p[1])
 
+    def setup_blockupdater(self, block_len):
+        """`self.blockupdater`: the in-place block updater of the blocked Metropolis sampler (prior.py:106-112)."""
+        self.blockupdater = BlockUpdater(self, block_len)
+
     @property
     def dist(self):
         """The equivalent torch.distributions object (reference attribute)."""
@@ -131,6 +135,56 @@ class NormalPrior(Prior):
         if fused:
             return _hip.NormalLogProbFn.apply(x, self.loc.contiguous(), self.scale.contiguous())
         return super().log_prob(x)
+
+
+class BlockUpdater:
+    """Redraws block k = the flattened sites [k block_len, (k+1) block_len) of every sample of x from the prior, in place,
+    and keeps the old block for `restore` (prior.py:161-178).  On a HIP device with the kernel prior (torch_rng=False) a call
+    is ONE launch of nf_block_propose (the stream of nf_normal_sample on a (C, block_len) field); on CPU tensors, or with
+    torch_rng=True, it is the reference's: a copy of the block, then one `Normal(loc_blk, scale_blk).sample((C,))`.
+    Departure from the reference: every block is drawn from its OWN sites' loc / scale.  The reference draws every block
+    from the first block's (prior.py:109-110), which is wrong for a non-uniform prior, because the Metropolis ratio uses
+    the full prior.log_prob; the two agree for the unit prior."""
+
+    def __init__(self, prior, block_len):
+        self.prior = prior
+        self.block_len = int(block_len)
+        self.backup_block = None
+
+    def _kernel(self, x):
+        return (not self.prior.torch_rng and x.is_cuda and x.dtype in (torch.float32, torch.float64)
+                and self.prior.loc.device == x.device)
+
+    def _params(self, x):
+        """loc / scale flattened to (V) in x's dtype (None for the unit prior), cached per dtype."""
+        key = (x.dtype, x.device, self.prior.loc.data_ptr(), self.prior.scale.data_ptr())
+        if getattr(self, '_pkey', None) != key:
+            unit = self.prior._unit
+            flat = lambda t: t.detach().to(device=x.device, dtype=x.dtype).reshape(-1).contiguous()
+            self._pcache = (None, None) if unit else (flat(self.prior.loc), flat(self.prior.scale))
+            self._pkey = key
+        return self._pcache
+
+    def __call__(self, x, block_ind):
+        """In-place updater."""
+        n, bl = x.shape[0], self.block_len
+        if self._kernel(x):
+            bk = self.backup_block
+            if bk is None or bk.shape != (n, bl) or bk.dtype != x.dtype or bk.device != x.device:
+                bk = self.backup_block = torch.empty((n, bl), dtype=x.dtype, device=x.device)
+            _hip.block_propose(x, bk, *self._params(x), bl, block_ind)
+            return
+        view = x.view(n, -1, bl)
+        self.backup_block = view[:, block_ind].clone()
+        lo, hi = block_ind * bl, (block_ind + 1) * bl
+        loc = self.prior.loc.reshape(-1)[lo:hi].to(x.device)
+        scale = self.prior.scale.reshape(-1)[lo:hi].to(x.device)
+        with torch.no_grad():      # Normal(loc_blk, scale_blk).sample((n,))
+            view[:, block_ind] = torch.normal(loc.expand(n, bl), scale.expand(n, bl))
+
+    def restore(self, x, block_ind, restore_ind=slice(None)):
+        view = x.view(x.shape[0], -1, self.block_len)
+        view[restore_ind, block_ind] = self.backup_block[restore_ind]
 
 
 class UniformPrior(Prior):
