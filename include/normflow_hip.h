@@ -283,6 +283,41 @@ int nf_distconv_vjp(const void *v, const void *knots, int K, const void *grad_ou
                     int64_t V, int stages, int inverse, void *workspace,
                     size_t workspace_bytes, int dtype, void *stream);
 
+/* ---- Pade11_ / Pade22_: learnable monotone maps of [0, 1] with per-channel parameters --
+ * Replaces src/nn/scalar/modules_.py:117-222 (forward and backward of both modules: ~15
+ * eager element-wise ops plus Module_.sum_density, src/nn/_core.py:38-42) with ONE pass:
+ *   NF_PADE11  y = x / (x + d (1 - x))                                     (d = d0; d1 unused)
+ *   NF_PADE22  y = x (x + d0 (1 - x)) / (1 + (d0 + d1 - 2) x (1 - x))
+ * inverse = 1 applies the inverse map (Pade11: x / (x + (1 - x) / d); Pade22: the root
+ * 2y / (-b + sqrt(b^2 - 4 a y)), b = (d0 + d1 - 2) y - d0, a = -1 - b, with no a == 0
+ * branch) and adds log|dx/dy| (Pade22: -log f'(x) at the recovered x).  No clamping.
+ *
+ *   x, y      the field as (outer, C, inner), dense; B samples of outer*C*inner / B elements
+ *             each (a sample is whole rows of `inner`: B divides outer*C, and the rows per
+ *             sample are a multiple of C, or 1 when the channel axis is the batch axis)
+ *   d0, d1    C values of dtype each: the per-channel parameters, already softplus(beta=ln2)
+ *             mapped (modules_.py:156-163, 210-220); channel of element (o, c, i) = c
+ *   per_site  0: log0 / logj are (B): logj = log0 + the per-sample sum of log|f'|;
+ *             1: log0 / logj have the shape of x: logj = log0 + log|f'| at every element
+ *             (Module_.propagate_density, src/nn/_core.py:19,38-42)
+ *   log0      NULL = 0
+ * Scratch: nf_pade_workspace_bytes(B, outer, C, inner) bytes (none for per_site map calls).
+ */
+enum nf_pade_kind { NF_PADE11 = 11, NF_PADE22 = 22 };
+size_t nf_pade_workspace_bytes(int64_t B, int64_t outer, int64_t C, int64_t inner);
+int nf_pade(const void *x, const void *d0, const void *d1, const void *log0, void *y, void *logj, int64_t B,
+            int64_t outer, int64_t C, int64_t inner, int kind, int inverse, int per_site, void *workspace,
+            size_t workspace_bytes, int dtype, void *stream);
+/* VJP of nf_pade: x is the forward map's INPUT (inverse = 0) or the inverse map's OUTPUT
+ * (inverse = 1), so no root is recomputed.  grad_y has the shape of x; grad_logj is (B)
+ * (per_site = 0) or has the shape of x (per_site = 1).  Writes grad_x (shape of x) and
+ * grad_d: 2C doubles, the cotangents of d0 (first C) and d1 (next C; 0 for NF_PADE11) summed
+ * over batch and sites per workgroup, then per channel in a fixed order (no atomics: the
+ * same inputs give the same bits). */
+int nf_pade_vjp(const void *x, const void *d0, const void *d1, const void *grad_y, const void *grad_logj,
+                void *grad_x, double *grad_d, int64_t B, int64_t outer, int64_t C, int64_t inner, int kind,
+                int inverse, int per_site, void *workspace, size_t workspace_bytes, int dtype, void *stream);
+
 /* ---- K5: circular 'same' convolution + bias + activation on the f32 matrix cores ----
  * Replaces one Conv{1,2,3}d(padding='same', padding_mode='circular') / Conv4d layer of
  * ConvAct together with the activation that follows it (src/nn/scalar/modules.py:120-145,

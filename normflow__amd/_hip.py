@@ -62,6 +62,9 @@ PROTOTYPES = {
     "nf_affine_vjp": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, _I, _I, _I, _P]),
     "nf_distconv": (_I, [_P, _P, _I, _P, _P, _P, _I64, _I64, _I, _I, _P, _SZ, _I, _P]),
     "nf_distconv_vjp": (_I, [_P, _P, _I, _P, _P, _P, _P, _I64, _I64, _I, _I, _P, _SZ, _I, _P]),
+    "nf_pade_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "nf_pade": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _I, _P, _SZ, _I, _P]),
+    "nf_pade_vjp": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _I, _P, _SZ, _I, _P]),
     "nf_conv_two_site": (_I, [_I, _I, _I, _I]),
     "nf_conv_cin_pad": (_I, [_I]),
     "nf_conv_ntiles": (_I, [_I]),
@@ -573,6 +576,53 @@ class DistConvFn(torch.autograd.Function):
             gk += part
         gk = gk.to(knots.dtype) if knots is not None else None
         return gin, gk, (glogj if ctx.has_log0 else None), None, None
+
+
+# ============================================================================== pade
+PADE11, PADE22 = 11, 22      # nf_pade_kind
+
+
+def _pade_workspace(layout, device):
+    need = load().nf_pade_workspace_bytes(*layout)
+    return torch.empty(max(int(need), 256), dtype=torch.uint8, device=device)
+
+
+class PadeFn(torch.autograd.Function):
+    """Pade11_ / Pade22_ (nf_pade) forward or inverse, differentiable in the field and in the per-channel parameters.
+
+    v: the field (any shape, contiguous); d0, d1: (C,) parameters after softplus_ln2 (d1 None for Pade11_);
+    layout: (B, outer, C, inner) of nf_pade; log0: None, (B,) or (per_site) the shape of v."""
+
+    @staticmethod
+    def forward(ctx, v, d0, d1, log0, kind, inverse, per_site, layout):
+        _require_device(v, d0, d1, log0)
+        if v.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"Pade11_ / Pade22_ run on float32 / float64 fields, got {v.dtype}")
+        v = v.contiguous()
+        out = torch.empty_like(v)
+        logj = torch.empty_like(v) if per_site else torch.empty(layout[0], dtype=v.dtype, device=v.device)
+        ws = None if per_site else _pade_workspace(layout, v.device)
+        _check(load().nf_pade(_ptr(v), _ptr(d0), _ptr(d1), _ptr(log0), _ptr(out), _ptr(logj), *layout, kind,
+                              int(bool(inverse)), int(bool(per_site)), _ptr(ws), ws.numel() if ws is not None else 0,
+                              _dtype_code(v), _stream()), "nf_pade")
+        ctx.save_for_backward(out if inverse else v, d0, d1)
+        ctx.kind, ctx.inverse, ctx.per_site, ctx.layout = kind, inverse, per_site, layout
+        ctx.has_log0 = log0 is not None
+        return out, logj
+
+    @staticmethod
+    def backward(ctx, gout, glogj):
+        x, d0, d1 = ctx.saved_tensors
+        gout, glogj = gout.contiguous(), glogj.contiguous()
+        gin = torch.empty_like(x)
+        gd = torch.empty(2, d0.numel(), dtype=torch.float64, device=x.device)
+        ws = _pade_workspace(ctx.layout, x.device)
+        _check(load().nf_pade_vjp(_ptr(x), _ptr(d0), _ptr(d1), _ptr(gout), _ptr(glogj), _ptr(gin), _ptr(gd),
+                                  *ctx.layout, ctx.kind, int(bool(ctx.inverse)), int(bool(ctx.per_site)), _ptr(ws),
+                                  ws.numel(), _dtype_code(x), _stream()), "nf_pade_vjp")
+        gd = gd.to(x.dtype)
+        return (gin, gd[0], gd[1] if d1 is not None else None, glogj if ctx.has_log0 else None,
+                None, None, None, None)
 
 
 # ============================================================================== conv

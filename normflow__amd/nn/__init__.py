@@ -5,6 +5,7 @@ from .scalar.convNd import ConvNd, Conv4d
 from .scalar.modules_ import DistConvertor_, Identity_, Clone_
 from .scalar.modules_ import UnityDistConvertor_, PhaseDistConvertor_
 from .scalar.modules_ import Expit_, Logit_, SplineNet_, ScaleNet_, SgnBiasNet_
+from .scalar.modules_ import Pade11_, Pade22_
 
 from .scalar.couplings_ import Coupling_, ShiftCoupling_, AffineCoupling_
 from .scalar.couplings_ import RQSplineCoupling_, MultiRQSplineCoupling_

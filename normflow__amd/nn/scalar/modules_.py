@@ -4,7 +4,8 @@ Expit_, SplineNet_, Logit_ and their composition DistConvertor_ run on the fused
 kernel (`nf_distconv`): one pass over the field for any subset of the three stages,
 the shared spline's knots staged in LDS.  DistConvertor_ keeps the reference's list
 structure (so `1.weights_x`-style state_dict keys and `.spline_layer_` still work) but
-executes the whole Expit_ -> SplineNet_ -> Logit_ triple as ONE launch.
+executes the whole Expit_ -> SplineNet_ -> Logit_ triple as ONE launch.  Pade11_ and
+Pade22_ run on `nf_pade`: one pass per direction, per-site densities included.
 """
 import math
 
@@ -94,6 +95,78 @@ class Logit_(Module_):
 
     def backward(self, x, log0=0):
         return _run_stages(self, x, log0, _hip.STAGE_EXPIT, False)
+
+
+def _pade(module, x, log0, kind, inverse, d0, d1):
+    """One nf_pade pass over x: the field is described to the kernel as (outer, C, inner) around the channel axis, with
+    no copy; the per-channel parameters go in already softplus-mapped (autograd takes the chain through softplus_ln2)."""
+    _hip._require_device(x)
+    C = module.n_channels
+    if C == 1:
+        B = x.shape[0] if x.dim() > 0 else 1
+        layout = (B, B, 1, x.numel() // B if B else 0)
+    else:
+        axis = module.channels_axis % x.dim()
+        if x.shape[axis] != C:
+            raise ValueError(f"{type(module).__name__}: axis {module.channels_axis} of a {tuple(x.shape)} field has "
+                             f"{x.shape[axis]} entries, not n_channels={C}")
+        layout = (x.shape[0], math.prod(x.shape[:axis]), C, math.prod(x.shape[axis + 1:]))
+    d0 = d0.to(x.dtype)
+    d1 = d1.to(x.dtype) if d1 is not None else None
+    per_site = module.propagate_density
+    if per_site:
+        l0 = (log0.to(x.dtype).expand(x.shape).contiguous() if torch.is_tensor(log0)
+              else None if log0 == 0 else torch.full_like(x, float(log0)))
+    else:
+        l0 = _hip._log0_tensor(log0, x, layout[0])
+    return _hip.PadeFn.apply(x, d0, d1, l0, kind, inverse, per_site, layout)
+
+
+class Pade11_(Module_):
+    """y = x / (x + d (1 - x)) = expit(logit(x) - log d), d = softplus_ln2(w1) per channel: a monotone map of [0, 1]
+    onto itself; the inverse is the same map with 1/d (modules_.py:117-163).  One nf_pade pass per direction; with
+    propagate_density the per-site log-derivatives, in inference and in training."""
+
+    def __init__(self, n_channels=1, channels_axis=1, label='pade11'):
+        super().__init__(label=label)
+        self.w1 = torch.nn.Parameter(torch.zeros(n_channels))
+        self.n_channels = n_channels
+        self.channels_axis = channels_axis
+
+    def forward(self, x, log0=0):
+        return _pade(self, x, log0, _hip.PADE11, False, softplus_ln2(self.w1), None)
+
+    def backward(self, x, log0=0):
+        return _pade(self, x, log0, _hip.PADE11, True, softplus_ln2(self.w1), None)
+
+
+class Pade22_(Module_):
+    """y = x (x + d0 (1 - x)) / (1 + (d0 + d1 - 2) x (1 - x)): a one-bin rational-quadratic spline of [0, 1] with
+    end-point derivatives d0 = softplus_ln2(w0), d1 = softplus_ln2(w1) per channel; symmetric=True makes w1 the same
+    parameter as w0 (modules_.py:166-222).  One nf_pade pass per direction (the inverse by the cancellation-free root);
+    with propagate_density the per-site log-derivatives, in inference and in training."""
+
+    def __init__(self, n_channels=1, channels_axis=1, symmetric=False, label='pade22'):
+        super().__init__(label=label)
+        self.w0 = torch.nn.Parameter(torch.zeros(n_channels))
+        if not symmetric:
+            self.w1 = torch.nn.Parameter(torch.zeros(n_channels))
+        else:
+            self.w1 = self.w0
+        self.n_channels = n_channels
+        self.channels_axis = channels_axis
+        self.symmetric = symmetric
+
+    def _run(self, x, log0, inverse):
+        d0 = softplus_ln2(self.w0)
+        d1 = d0 if self.symmetric else softplus_ln2(self.w1)
+        return _pade(self, x, log0, _hip.PADE22, inverse, d0, d1)
+
+    def forward(self, x, log0=0):
+        return self._run(x, log0, False)
+
+    def backward(self, x, log0=0):
+        return self._run(x, log0, True)
 
 
 class SplineNet_(SplineNet, Module_):
