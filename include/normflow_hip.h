@@ -283,6 +283,30 @@ int nf_distconv_vjp(const void *v, const void *knots, int K, const void *grad_ou
                     int64_t V, int stages, int inverse, void *workspace,
                     size_t workspace_bytes, int dtype, void *stream);
 
+/* ---- K4 per site: Module_.propagate_density on Expit_ / SplineNet_ / Logit_ and their
+ * fused triple (src/nn/_core.py:19,38-42 with src/nn/scalar/modules_.py:93-114, 277-302),
+ * and InvisibilityMaskWrapperModule_ around one of them (src/nn/_core.py:196-231: split,
+ * net_ on the visible part, purify(channel=0), sum_density, cat) as ONE masked pass.
+ * Stages, knots and directions as nf_distconv.
+ *   mask    (V) uint8 activity bytes or NULL (all active).  Where 0: y = x, the site's
+ *           log-density is 0 and the site is not evaluated.
+ *   mode    NF_DC_SITES: site_out (B, V) = log0 + log|f'| per site; log0 (B, V) or NULL;
+ *                        logj unused.
+ *           NF_DC_SUM:   logj (B) = log0 + sum of log|f'| over the ACTIVE sites; log0 (B)
+ *                        or NULL; site_out unused.  Scratch: nf_workspace_bytes(B, V).
+ */
+enum nf_distconv_mode { NF_DC_SUM = 0, NF_DC_SITES = 1 };
+int nf_distconv_sites(const void *x, const void *knots, int K, const void *log0, const uint8_t *mask,
+                      void *y, void *site_out, void *logj, int64_t B, int64_t V, int stages, int inverse,
+                      int mode, void *workspace, size_t workspace_bytes, int dtype, void *stream);
+/* VJP of nf_distconv_sites, arguments as nf_distconv_vjp: grad_logj is (B, V) in
+ * NF_DC_SITES mode and (B) in NF_DC_SUM mode; inactive sites pass grad_out through and add
+ * nothing to grad_knots (3K doubles, per-workgroup partials then one reduction). */
+int nf_distconv_sites_vjp(const void *v, const void *knots, int K, const uint8_t *mask, const void *grad_out,
+                          const void *grad_logj, void *grad_in, double *grad_knots, int64_t B, int64_t V,
+                          int stages, int inverse, int mode, void *workspace, size_t workspace_bytes,
+                          int dtype, void *stream);
+
 /* ---- Pade11_ / Pade22_: learnable monotone maps of [0, 1] with per-channel parameters --
  * Replaces src/nn/scalar/modules_.py:117-222 (forward and backward of both modules: ~15
  * eager element-wise ops plus Module_.sum_density, src/nn/_core.py:38-42) with ONE pass:
@@ -461,6 +485,17 @@ int nf_phi4_action(const void *cfgs, void *action, int64_t B, const int32_t *lat
                    double w4, void *workspace, size_t workspace_bytes, int dtype, void *stream);
 int nf_phi4_action_vjp(const void *cfgs, const void *grad_action, void *grad_cfgs, int64_t B,
                        const int32_t *lattice, double w0, double w2, double w4, int dtype, void *stream);
+/* nf_phi4_action_density: the per-site action (ScalarPhi4Action.action_density,
+ * src/action/scalar_action.py:48-62; the reference's 1 + 2d passes), ONE stencil pass:
+ *   density[b, x] = wm phi^2 + w4 phi^4
+ *                   + (w0 / 4) sum_mu [(phi(x) - phi(x + mu))^2 + (phi(x) - phi(x - mu))^2]
+ * with wm = w2 - d w0 (= m^2 a^d / 2), periodic; an axis of extent 1 adds nothing.  Its sites
+ * sum to the action.  cfgs, density (B, V).  nf_phi4_action_density_vjp: grad_cfgs from the
+ * per-site cotangent grad_density (B, V), one pass. */
+int nf_phi4_action_density(const void *cfgs, void *density, int64_t B, const int32_t *lattice, double w0,
+                           double wm, double w4, int dtype, void *stream);
+int nf_phi4_action_density_vjp(const void *cfgs, const void *grad_density, void *grad_cfgs, int64_t B,
+                               const int32_t *lattice, double w0, double wm, double w4, int dtype, void *stream);
 int nf_normal_logprob(const void *x, const void *loc, const void *scale, void *logp, int64_t B, int64_t V,
                       void *workspace, size_t workspace_bytes, int dtype, void *stream);
 int nf_normal_logprob_vjp(const void *x, const void *loc, const void *scale, const void *grad_logp,

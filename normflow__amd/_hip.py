@@ -62,6 +62,8 @@ PROTOTYPES = {
     "nf_affine_vjp": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, _I, _I, _I, _P]),
     "nf_distconv": (_I, [_P, _P, _I, _P, _P, _P, _I64, _I64, _I, _I, _P, _SZ, _I, _P]),
     "nf_distconv_vjp": (_I, [_P, _P, _I, _P, _P, _P, _P, _I64, _I64, _I, _I, _P, _SZ, _I, _P]),
+    "nf_distconv_sites": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I64, _I64, _I, _I, _I, _P, _SZ, _I, _P]),
+    "nf_distconv_sites_vjp": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I64, _I64, _I, _I, _I, _P, _SZ, _I, _P]),
     "nf_pade_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
     "nf_pade": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _I, _P, _SZ, _I, _P]),
     "nf_pade_vjp": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _I, _P, _SZ, _I, _P]),
@@ -71,6 +73,8 @@ PROTOTYPES = {
     "nf_conv_packed_steps": (_I, [_I, _I]),
     "nf_phi4_action": (_I, [_P, _P, _I64, C.POINTER(C.c_int32), _D, _D, _D, _P, _SZ, _I, _P]),
     "nf_phi4_action_vjp": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _D, _D, _D, _I, _P]),
+    "nf_phi4_action_density": (_I, [_P, _P, _I64, C.POINTER(C.c_int32), _D, _D, _D, _I, _P]),
+    "nf_phi4_action_density_vjp": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _D, _D, _D, _I, _P]),
     "nf_normal_logprob": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _SZ, _I, _P]),
     "nf_normal_logprob_vjp": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I, _P]),
     "nf_normal_sample": (_I, [_P, _P, _P, _P, _I64, _I64, C.c_uint64, C.c_uint64, _P, _SZ, _I, _P]),
@@ -576,6 +580,65 @@ class DistConvFn(torch.autograd.Function):
             gk += part
         gk = gk.to(knots.dtype) if knots is not None else None
         return gin, gk, (glogj if ctx.has_log0 else None), None, None
+
+
+DC_SUM, DC_SITES = 0, 1      # nf_distconv_mode
+
+
+class DistConvSitesFn(torch.autograd.Function):
+    """nf_distconv_sites: the stages of DistConvFn with an optional (V,) uint8 activity mask (inactive sites: y = x,
+    density 0) and, with per_site, the per-site log-density log0 + log|f'| (B, V) instead of the per-sample sum over the
+    active sites (B).  log0: None, (B, V) (per_site) or (B,).  Differentiable in v, knots and log0."""
+
+    @staticmethod
+    def forward(ctx, v, knots, log0, mask, stages, inverse, per_site):
+        _require_device(v, knots, log0, mask)
+        if v.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"per-site densities are built for float32 / float64 fields, got {v.dtype}")
+        B, V = v.shape
+        v = v.contiguous()
+        if knots is not None:
+            knots = knots.to(v.dtype).contiguous()
+        if mask is not None and (mask.dtype != torch.uint8 or mask.numel() != V):
+            raise ValueError(f"the activity mask must be {V} uint8 bytes, got {mask.numel()} {mask.dtype}")
+        K = knots.shape[1] if knots is not None else 0
+        lib = load()
+        out = torch.empty_like(v)
+        dens = torch.empty_like(v) if per_site else torch.empty(B, dtype=v.dtype, device=v.device)
+        ws = None if per_site else _workspace(min(B, MAX_B), V, v.device)
+        mode = DC_SITES if per_site else DC_SUM
+        for b0 in range(0, B, MAX_B):
+            b1 = min(B, b0 + MAX_B)
+            l0 = log0[b0:b1] if log0 is not None else None
+            _check(lib.nf_distconv_sites(_ptr(v[b0:b1]), _ptr(knots), K, _ptr(l0), _ptr(mask), _ptr(out[b0:b1]),
+                                         _ptr(dens[b0:b1]) if per_site else None,
+                                         None if per_site else _ptr(dens[b0:b1]), b1 - b0, V, stages, int(inverse),
+                                         mode, _ptr(ws), ws.numel() if ws is not None else 0, _dtype_code(v),
+                                         _stream()), "nf_distconv_sites")
+        ctx.save_for_backward(out if inverse else v, knots, mask)
+        ctx.stages, ctx.inverse, ctx.mode, ctx.has_log0 = stages, inverse, mode, log0 is not None
+        return out, dens
+
+    @staticmethod
+    def backward(ctx, gout, gdens):
+        x, knots, mask = ctx.saved_tensors
+        B, V = x.shape
+        K = knots.shape[1] if knots is not None else 0
+        gout, gdens = gout.contiguous(), gdens.contiguous()
+        gin = torch.empty_like(x)
+        gk = torch.zeros(3, max(K, 1), dtype=torch.float64, device=x.device)
+        lib = load()
+        ws = _workspace(min(B, MAX_B), V, x.device)
+        for b0 in range(0, B, MAX_B):
+            b1 = min(B, b0 + MAX_B)
+            part = torch.zeros(3, max(K, 1), dtype=torch.float64, device=x.device)
+            _check(lib.nf_distconv_sites_vjp(_ptr(x[b0:b1]), _ptr(knots), K, _ptr(mask), _ptr(gout[b0:b1]),
+                                             _ptr(gdens[b0:b1]), _ptr(gin[b0:b1]), _ptr(part), b1 - b0, V, ctx.stages,
+                                             int(ctx.inverse), ctx.mode, _ptr(ws), ws.numel(), _dtype_code(x),
+                                             _stream()), "nf_distconv_sites_vjp")
+            gk += part
+        gk = gk.to(knots.dtype) if knots is not None else None
+        return gin, gk, (gdens if ctx.has_log0 else None), None, None, None, None
 
 
 # ============================================================================== pade
@@ -1561,6 +1624,38 @@ class Phi4ActionFn(torch.autograd.Function):
             b1 = min(B, b0 + MAX_B)
             _check(load().nf_phi4_action_vjp(_ptr(cfgs[b0:b1]), _ptr(g[b0:b1]), _ptr(gc[b0:b1]), b1 - b0, lat4,
                                              *ctx.w, _dtype_code(cfgs), _stream()), "nf_phi4_action_vjp")
+        return gc, None, None, None
+
+
+class Phi4ActionDensityFn(torch.autograd.Function):
+    """Per-site phi^4 action density of (B, *L) configurations, one stencil pass (nf_phi4_action_density); wm = w2 - d w0."""
+
+    @staticmethod
+    def forward(ctx, cfgs, w0, wm, w4):
+        cfgs = cfgs.contiguous()
+        B, lat = cfgs.shape[0], list(cfgs.shape[1:])
+        lat4 = (C.c_int32 * 4)(*([1] * (4 - len(lat)) + lat))
+        out = torch.empty_like(cfgs)
+        for b0 in range(0, B, MAX_B):
+            b1 = min(B, b0 + MAX_B)
+            _check(load().nf_phi4_action_density(_ptr(cfgs[b0:b1]), _ptr(out[b0:b1]), b1 - b0, lat4, w0, wm, w4,
+                                                 _dtype_code(cfgs), _stream()), "nf_phi4_action_density")
+        ctx.save_for_backward(cfgs)
+        ctx.w = (w0, wm, w4)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (cfgs,) = ctx.saved_tensors
+        B, lat = cfgs.shape[0], list(cfgs.shape[1:])
+        lat4 = (C.c_int32 * 4)(*([1] * (4 - len(lat)) + lat))
+        g = g.contiguous()
+        gc = torch.empty_like(cfgs)
+        for b0 in range(0, B, MAX_B):
+            b1 = min(B, b0 + MAX_B)
+            _check(load().nf_phi4_action_density_vjp(_ptr(cfgs[b0:b1]), _ptr(g[b0:b1]), _ptr(gc[b0:b1]), b1 - b0,
+                                                     lat4, *ctx.w, _dtype_code(cfgs), _stream()),
+                   "nf_phi4_action_density_vjp")
         return gc, None, None, None
 
 

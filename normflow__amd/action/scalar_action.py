@@ -2,7 +2,8 @@
 
     S[phi] = sum_x ( w2 phi^2 + w4 phi^4 ) - w0 sum_mu sum_x phi(x) phi(x - mu)        (periodic)
 with w0 = kappa a^(d-2), w2 = (m^2 a^d + 2 d kappa a^(d-2)) / 2, w4 = lambda a^d.
-On the device the whole thing is one pass of the `nf_phi4_action` kernel (with its VJP).
+On the device the whole thing is one pass of the `nf_phi4_action` kernel (with its VJP); the per-site
+`action_density` is one pass of `nf_phi4_action_density`.
 """
 import torch
 
@@ -35,6 +36,23 @@ class ScalarPhi4Action:
         return total
 
     __call__ = action
+
+    def action_density(self, cfgs):
+        """(B, *L) configurations -> (B, *L) per-site action (reference: scalar_action.py:48-62): the symmetric density
+        with a non-negative kinetic term,
+            s(x) = wm phi^2 + w4 phi^4 + (w0 / 4) sum_mu [(phi(x) - phi(x + mu))^2 + (phi(x) - phi(x - mu))^2],
+        wm = w2 - d w0 (= m^2 a^d / 2).  Its sites sum to `action`.  On the device one `nf_phi4_action_density` pass."""
+        d = cfgs.ndim - 1
+        w0, w2, w4 = self.get_coef(d)
+        wm = w2 - w0 * d
+        if d >= 1 and cfgs.numel() and _hip.endpoint_supported(cfgs):
+            return _hip.Phi4ActionDensityFn.apply(cfgs, float(w0), float(wm), float(w4))
+        # host tensors: the reference's formula, one roll per direction and sign
+        dens = wm * cfgs ** 2 + w4 * cfgs ** 4
+        for mu in range(1, d + 1):
+            dens = dens + (w0 / 4) * (cfgs - cfgs.roll(-1, dims=mu)) ** 2
+            dens = dens + (w0 / 4) * (cfgs - cfgs.roll(1, dims=mu)) ** 2
+        return dens
 
     def potential(self, x):
         return self.m_sq * x ** 2 + self.lambd * x ** 4

@@ -11,6 +11,13 @@
 // 2 log y)), :105-114 (Logit_: y = log(x/(1-x)), logJ = -sum log(x(1-x))), :277-302
 // (SplineNet_) and the list order of :333-358; the inverse chain is the reversed list
 // of inverted stages (src/nn/_core.py:69-72), which is again expit -> spline^-1 -> logit.
+//
+// nf_distconv_sites / nf_distconv_sites_vjp run the same per-site arithmetic with two
+// additions: an optional uint8 activity mask (inactive sites: y = x, density 0, never
+// evaluated) and a per-site log-density output.  They restate Module_.propagate_density
+// (src/nn/_core.py:19,38-42) on the three leaves, and the reference's
+// InvisibilityMaskWrapperModule_ around one of them (src/nn/_core.py:196-231: split ->
+// net_ on the visible part -> purify(channel=0) -> sum_density -> cat) as ONE masked pass.
 #include "nf_internal.h"
 
 namespace nf {
@@ -22,6 +29,9 @@ struct DcArgs {
   const void *v;
   const void *knots;        // 3*K values of T: x | y | d
   void *out;
+  const void *log0_sites;   // sites mode: (B, V) or NULL
+  void *site_out;           // sites mode: (B, V)
+  const uint8_t *mask;      // (V) activity bytes or NULL
   double *partial;
   const void *grad_out;
   const void *grad_logj;
@@ -55,7 +65,9 @@ template <typename T> __device__ __forceinline__ T neg_log1p_exp_neg(T e) {
   return e < Num<T>::tiny_log1p_cut() ? -e * (T(1) - T(0.5) * e) : -nf_log(T(1) + e);
 }
 
-template <typename T, bool INV>
+// SITES: write log0_sites + log|f'| per site instead of the per-sample partial sums.
+// MASKED: sites whose activity byte is 0 are copied (density 0) and not evaluated.
+template <typename T, bool INV, bool SITES = false, bool MASKED = false>
 __global__ __launch_bounds__(kBlock) void distconv_kernel(DcArgs A) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   __shared__ double red[kBlock / kWave];
@@ -72,6 +84,16 @@ __global__ __launch_bounds__(kBlock) void distconv_kernel(DcArgs A) {
     const int64_t i = base + int64_t(it) * kBlock;
     if (i >= A.V) break;
     T u = vin[i], lg = T(0);
+    if constexpr (MASKED) {
+      if (!A.mask[i]) {
+        out[i] = u;
+        if constexpr (SITES) {
+          const T *l0 = static_cast<const T *>(A.log0_sites);
+          static_cast<T *>(A.site_out)[int64_t(b) * A.V + i] = l0 ? l0[int64_t(b) * A.V + i] : T(0);
+        }
+        continue;
+      }
+    }
     if (A.pre_expit) {
       const T e = nf_exp(-Num<T>::abs(u));           // in (0,1]
       lg += -Num<T>::abs(u) + T(2) * neg_log1p_exp_neg(e);   // log(u(1-u)) = -x + 2 log expit(x)
@@ -108,15 +130,23 @@ __global__ __launch_bounds__(kBlock) void distconv_kernel(DcArgs A) {
       u = nf_log(u / (T(1) - u));
     }
     out[i] = u;
-    acc += double(lg);
+    if constexpr (SITES) {
+      const T *l0 = static_cast<const T *>(A.log0_sites);
+      static_cast<T *>(A.site_out)[int64_t(b) * A.V + i] = l0 ? l0[int64_t(b) * A.V + i] + lg : lg;
+    } else {
+      acc += double(lg);
+    }
   }
-  const double tot = block_sum(acc, red);
-  if (threadIdx.x == 0) A.partial[int64_t(b) * gridDim.x + blockIdx.x] = tot;
+  if constexpr (!SITES) {
+    const double tot = block_sum(acc, red);
+    if (threadIdx.x == 0) A.partial[int64_t(b) * gridDim.x + blockIdx.x] = tot;
+  }
 }
 
 // VJP.  `v` is the x-side end point of the chain (forward input / inverse output), so
 // the chain is always re-run in its forward direction; no root is recomputed.
-template <typename T, bool INV>
+// SITES: grad_logj is per site, (B, V).  MASKED: inactive sites pass grad_out through.
+template <typename T, bool INV, bool SITES = false, bool MASKED = false>
 __global__ __launch_bounds__(kBlock) void distconv_vjp_kernel(DcArgs A, int64_t B) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   double *gacc = reinterpret_cast<double *>(smem_raw);          // 3K doubles
@@ -131,7 +161,13 @@ __global__ __launch_bounds__(kBlock) void distconv_vjp_kernel(DcArgs A, int64_t 
     const int64_t b = i / A.V;
     const T p = static_cast<const T *>(A.v)[i];
     const T gout = static_cast<const T *>(A.grad_out)[i];
-    const T glog = static_cast<const T *>(A.grad_logj)[b];
+    if constexpr (MASKED) {
+      if (!A.mask[i - b * A.V]) {
+        static_cast<T *>(A.grad_in)[i] = gout;
+        continue;
+      }
+    }
+    const T glog = static_cast<const T *>(A.grad_logj)[SITES ? i : b];
     // stage 1: expit
     T u = p, du_dp = T(1), l1p = T(0);
     if (A.pre_expit) {
@@ -283,6 +319,107 @@ static int run_vjp(const void *v, const void *knots, int K, const void *grad_out
   return check_launch("knot reduce kernel");
 }
 
+// nf_distconv_sites: mode NF_DC_SITES writes log0_sites + log|f'| per site; NF_DC_SUM reduces the
+// active sites per sample as run_map does.  Instances are picked by (direction, mode, mask).
+template <typename T, bool INV, bool SITES>
+static void launch_sites(const dim3 &grid, size_t lds, hipStream_t stream, const DcArgs &A) {
+  if (A.mask) hipLaunchKernelGGL((distconv_kernel<T, INV, SITES, true>), grid, dim3(kBlock), lds, stream, A);
+  else hipLaunchKernelGGL((distconv_kernel<T, INV, SITES, false>), grid, dim3(kBlock), lds, stream, A);
+}
+
+template <typename T>
+static int run_sites(const void *v, const void *knots, int K, const void *log0, const uint8_t *mask, void *out,
+                     void *site_out, void *logj, int64_t B, int64_t V, int stages, int inverse, int mode, void *ws,
+                     size_t ws_bytes, hipStream_t stream) {
+  DcArgs A{};
+  int rc = fill(A, K, B, V, stages, inverse);
+  if (rc) return rc;
+  NF_REQUIRE(mode == NF_DC_SUM || mode == NF_DC_SITES, "nf_distconv_sites: mode %d is neither NF_DC_SUM nor NF_DC_SITES", mode);
+  const bool sites = mode == NF_DC_SITES;
+  NF_REQUIRE(v && out && (sites ? site_out != nullptr : logj != nullptr) && (knots || !A.spline),
+             "nf_distconv_sites: NULL tensor pointer");
+  if (B == 0) return NF_OK;
+  const Tiling t = make_tiling(V, B);
+  A.v = v; A.knots = knots; A.out = out; A.mask = mask; A.iters = t.iters;
+  if (sites) {
+    A.log0_sites = log0; A.site_out = site_out;
+  } else {
+    const size_t need = size_t(B) * size_t(t.blocks_x > 0 ? t.blocks_x : 1) * sizeof(double);
+    if (ws == nullptr || ws_bytes < need) {
+      set_error("nf_distconv_sites: workspace %zu B < %zu B needed", ws_bytes, need);
+      return NF_EWORKSPACE;
+    }
+    A.partial = static_cast<double *>(ws);
+  }
+  if (t.blocks_x > 0) {
+    const dim3 grid(unsigned(t.blocks_x), unsigned(B));
+    const size_t lds = size_t(3) * A.K * sizeof(T);
+    if (inverse) {
+      if (sites) launch_sites<T, true, true>(grid, lds, stream, A);
+      else launch_sites<T, true, false>(grid, lds, stream, A);
+    } else {
+      if (sites) launch_sites<T, false, true>(grid, lds, stream, A);
+      else launch_sites<T, false, false>(grid, lds, stream, A);
+    }
+    rc = check_launch("distconv sites kernel");
+    if (rc) return rc;
+  }
+  return sites ? NF_OK : launch_finalize<T>(A.partial, t.blocks_x, log0, logj, B, stream);
+}
+
+template <typename T, bool INV, bool SITES>
+static void launch_sites_vjp(int blocks, size_t lds, hipStream_t stream, const DcArgs &A, int64_t B) {
+  if (A.mask) hipLaunchKernelGGL((distconv_vjp_kernel<T, INV, SITES, true>), dim3(blocks), dim3(kBlock), lds, stream, A, B);
+  else hipLaunchKernelGGL((distconv_vjp_kernel<T, INV, SITES, false>), dim3(blocks), dim3(kBlock), lds, stream, A, B);
+}
+
+template <typename T>
+static int run_sites_vjp(const void *v, const void *knots, int K, const uint8_t *mask, const void *grad_out,
+                         const void *grad_logj, void *grad_in, double *grad_knots, int64_t B, int64_t V, int stages,
+                         int inverse, int mode, void *ws, size_t ws_bytes, hipStream_t stream) {
+  DcArgs A{};
+  int rc = fill(A, K, B, V, stages, inverse);
+  if (rc) return rc;
+  NF_REQUIRE(mode == NF_DC_SUM || mode == NF_DC_SITES, "nf_distconv_sites_vjp: mode %d is neither NF_DC_SUM nor NF_DC_SITES", mode);
+  NF_REQUIRE(v && grad_out && grad_logj && grad_in && (!A.spline || (knots && grad_knots)),
+             "nf_distconv_sites_vjp: NULL tensor pointer");
+  // the kernel re-runs the FORWARD chain at v, so it takes the forward direction's end stages (fill() gives the
+  // inverse chain's: the same for the symmetric sets 2, 5 and 7 that the modules use, swapped for 1, 3, 4 and 6)
+  if (inverse) {
+    A.pre_expit = (stages & 1) != 0;
+    A.post_logit = (stages & 4) != 0;
+  }
+  const int64_t n = B * V;
+  const int n3 = 3 * A.K;
+  int blocks = int((n + kBlock - 1) / kBlock);
+  if (blocks > kVjpBlocks) blocks = kVjpBlocks;
+  if (blocks == 0) {
+    if (n3) (void)hipMemsetAsync(grad_knots, 0, size_t(n3) * sizeof(double), stream);
+    return NF_OK;
+  }
+  const size_t need = size_t(blocks) * size_t(n3 > 0 ? n3 : 1) * sizeof(double);
+  if (ws == nullptr || ws_bytes < need) {
+    set_error("nf_distconv_sites_vjp: workspace %zu B < %zu B needed", ws_bytes, need);
+    return NF_EWORKSPACE;
+  }
+  A.v = v; A.knots = knots; A.mask = mask; A.grad_out = grad_out; A.grad_logj = grad_logj; A.grad_in = grad_in;
+  A.knot_partial = static_cast<double *>(ws);
+  const size_t lds = size_t(n3) * (sizeof(double) + sizeof(T));
+  const bool sites = mode == NF_DC_SITES;
+  if (inverse) {
+    if (sites) launch_sites_vjp<T, true, true>(blocks, lds, stream, A, B);
+    else launch_sites_vjp<T, true, false>(blocks, lds, stream, A, B);
+  } else {
+    if (sites) launch_sites_vjp<T, false, true>(blocks, lds, stream, A, B);
+    else launch_sites_vjp<T, false, false>(blocks, lds, stream, A, B);
+  }
+  rc = check_launch("distconv sites vjp kernel");
+  if (rc || n3 == 0) return rc;
+  hipLaunchKernelGGL(knot_reduce_kernel, dim3((n3 + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
+                     A.knot_partial, blocks, n3, grad_knots);
+  return check_launch("knot reduce kernel");
+}
+
 }  // namespace nf
 
 using namespace nf;
@@ -305,5 +442,26 @@ extern "C" int nf_distconv_vjp(const void *v, const void *knots, int K, const vo
   if (dtype == NF_F32) return run_vjp<float>(v, knots, K, grad_out, grad_logj, grad_in, grad_knots, B, V, stages, inverse, workspace, workspace_bytes, s);
   if (dtype == NF_F64) return run_vjp<double>(v, knots, K, grad_out, grad_logj, grad_in, grad_knots, B, V, stages, inverse, workspace, workspace_bytes, s);
   set_error("nf_distconv_vjp: unsupported dtype %d", dtype);
+  return NF_EINVAL;
+}
+
+extern "C" int nf_distconv_sites(const void *x, const void *knots, int K, const void *log0, const uint8_t *mask,
+                                 void *y, void *site_out, void *logj, int64_t B, int64_t V, int stages, int inverse,
+                                 int mode, void *workspace, size_t workspace_bytes, int dtype, void *stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == NF_F32) return run_sites<float>(x, knots, K, log0, mask, y, site_out, logj, B, V, stages, inverse, mode, workspace, workspace_bytes, s);
+  if (dtype == NF_F64) return run_sites<double>(x, knots, K, log0, mask, y, site_out, logj, B, V, stages, inverse, mode, workspace, workspace_bytes, s);
+  set_error("nf_distconv_sites: unsupported dtype %d", dtype);
+  return NF_EINVAL;
+}
+
+extern "C" int nf_distconv_sites_vjp(const void *v, const void *knots, int K, const uint8_t *mask, const void *grad_out,
+                                     const void *grad_logj, void *grad_in, double *grad_knots, int64_t B, int64_t V,
+                                     int stages, int inverse, int mode, void *workspace, size_t workspace_bytes,
+                                     int dtype, void *stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == NF_F32) return run_sites_vjp<float>(v, knots, K, mask, grad_out, grad_logj, grad_in, grad_knots, B, V, stages, inverse, mode, workspace, workspace_bytes, s);
+  if (dtype == NF_F64) return run_sites_vjp<double>(v, knots, K, mask, grad_out, grad_logj, grad_in, grad_knots, B, V, stages, inverse, mode, workspace, workspace_bytes, s);
+  set_error("nf_distconv_sites_vjp: unsupported dtype %d", dtype);
   return NF_EINVAL;
 }

@@ -7,6 +7,11 @@
 //   * Normal prior log-density  (reference: src/prior/prior.py:30-36 with
 //     torch.distributions.Normal.log_prob): sum_x [ -(x-loc)^2/(2 s^2) - log s - log sqrt(2 pi) ].
 // Both come with their VJPs (Fitter.step differentiates the action, src/_normflowcore.py:285-288).
+//   * ScalarPhi4Action.action_density (reference: src/action/scalar_action.py:48-62), the per-site
+//     counterpart of the action, symmetric and with a non-negative kinetic term:
+//       s[b, x] = wm phi^2 + w4 phi^4 + (w0 / 4) sum_mu [(phi(x) - phi(x + mu))^2 + (phi(x) - phi(x - mu))^2]
+//     with wm = w2 - d w0; its sites sum to S[b].  One stencil pass, and one for its VJP (which
+//     also reads the cotangent at the 2d neighbours).
 #include "nf_internal.h"
 
 namespace nf {
@@ -23,7 +28,8 @@ struct EpArgs {
   int iters;
 };
 
-template <typename T, bool GRAD>
+// DENSITY: write the per-site action density (w2 = wm) or, with GRAD, its VJP; no reduction.
+template <typename T, bool GRAD, bool DENSITY = false>
 __global__ __launch_bounds__(kBlock) void phi4_kernel(EpArgs A) {
   __shared__ double red[kBlock / kWave];
   const int b = blockIdx.y;
@@ -65,7 +71,36 @@ __global__ __launch_bounds__(kBlock) void phi4_kernel(EpArgs A) {
     const T n1 = A.L[1] > 1 ? phi[i + (x1 ? -s1 : s1 * (A.L[1] - 1))] : T(0);
     const T n2 = A.L[2] > 1 ? phi[i + (x2 ? -s2 : s2 * (A.L[2] - 1))] : T(0);
     const T n3 = A.L[3] > 1 ? phi[i + (x3 ? -s3 : s3 * (A.L[3] - 1))] : T(0);
-    if (!GRAD) {
+    if constexpr (DENSITY) {
+      const T f0 = A.L[0] > 1 ? phi[i + (x0 + 1 < A.L[0] ? s0 : -s0 * (A.L[0] - 1))] : p;
+      const T f1 = A.L[1] > 1 ? phi[i + (x1 + 1 < A.L[1] ? s1 : -s1 * (A.L[1] - 1))] : p;
+      const T f2 = A.L[2] > 1 ? phi[i + (x2 + 1 < A.L[2] ? s2 : -s2 * (A.L[2] - 1))] : p;
+      const T f3 = A.L[3] > 1 ? phi[i + (x3 + 1 < A.L[3] ? s3 : -s3 * (A.L[3] - 1))] : p;
+      // an axis of extent 1 has no neighbours: its differences are 0 (the reference's roll is the identity there)
+      const T m0 = A.L[0] > 1 ? n0 : p, m1 = A.L[1] > 1 ? n1 : p, m2 = A.L[2] > 1 ? n2 : p, m3 = A.L[3] > 1 ? n3 : p;
+      const T p2 = p * p;
+      T *__restrict__ dst = static_cast<T *>(A.out) + int64_t(b) * A.V;
+      if (!GRAD) {
+        const T kin = (p - f0) * (p - f0) + (p - m0) * (p - m0) + (p - f1) * (p - f1) + (p - m1) * (p - m1) +
+                      (p - f2) * (p - f2) + (p - m2) * (p - m2) + (p - f3) * (p - f3) + (p - m3) * (p - m3);
+        dst[i] = (w2 + w4 * p2) * p2 + T(0.25) * w0 * kin;
+      } else {
+        // d/dphi(x) of sum_y G(y) s(y): the site's own terms, and the one term of each neighbour that holds phi(x)
+        const T *__restrict__ G = static_cast<const T *>(A.gout) + int64_t(b) * A.V;
+        const T gx = G[i];
+        const T gf0 = A.L[0] > 1 ? G[i + (x0 + 1 < A.L[0] ? s0 : -s0 * (A.L[0] - 1))] : T(0);
+        const T gf1 = A.L[1] > 1 ? G[i + (x1 + 1 < A.L[1] ? s1 : -s1 * (A.L[1] - 1))] : T(0);
+        const T gf2 = A.L[2] > 1 ? G[i + (x2 + 1 < A.L[2] ? s2 : -s2 * (A.L[2] - 1))] : T(0);
+        const T gf3 = A.L[3] > 1 ? G[i + (x3 + 1 < A.L[3] ? s3 : -s3 * (A.L[3] - 1))] : T(0);
+        const T gn0 = A.L[0] > 1 ? G[i + (x0 ? -s0 : s0 * (A.L[0] - 1))] : T(0);
+        const T gn1 = A.L[1] > 1 ? G[i + (x1 ? -s1 : s1 * (A.L[1] - 1))] : T(0);
+        const T gn2 = A.L[2] > 1 ? G[i + (x2 ? -s2 : s2 * (A.L[2] - 1))] : T(0);
+        const T gn3 = A.L[3] > 1 ? G[i + (x3 ? -s3 : s3 * (A.L[3] - 1))] : T(0);
+        const T kin = (p - f0) * (gx + gf0) + (p - m0) * (gx + gn0) + (p - f1) * (gx + gf1) + (p - m1) * (gx + gn1) +
+                      (p - f2) * (gx + gf2) + (p - m2) * (gx + gn2) + (p - f3) * (gx + gf3) + (p - m3) * (gx + gn3);
+        dst[i] = gx * (T(2) * w2 * p + T(4) * w4 * p2 * p) + T(0.5) * w0 * kin;
+      }
+    } else if (!GRAD) {
       const T p2 = p * p;
       acc += double((w2 + w4 * p2) * p2 - w0 * p * (n0 + n1 + n2 + n3));
     } else {
@@ -78,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void phi4_kernel(EpArgs A) {
           g * (T(2) * w2 * p + T(4) * w4 * p * p * p - w0 * (n0 + n1 + n2 + n3 + f0 + f1 + f2 + f3));
     }
   }
-  if (!GRAD) {
+  if (!GRAD && !DENSITY) {
     const double tot = block_sum(acc, red);
     if (threadIdx.x == 0) A.partial[int64_t(b) * gridDim.x + blockIdx.x] = tot;
   }
@@ -130,6 +165,15 @@ static int run(EpArgs &A, void *out_b, int64_t B, void *ws, size_t ws_bytes, hip
   return GRAD ? NF_OK : launch_finalize<T>(A.partial, t.blocks_x, nullptr, out_b, B, stream);
 }
 
+template <typename T, bool GRAD>
+static int run_density(EpArgs &A, int64_t B, hipStream_t stream) {
+  if (B == 0) return NF_OK;
+  const Tiling t = make_tiling(A.V, B);
+  A.iters = t.iters;
+  if (t.blocks_x == 0) return NF_OK;
+  hipLaunchKernelGGL((phi4_kernel<T, GRAD, true>), dim3(unsigned(t.blocks_x), unsigned(B)), dim3(kBlock), 0, stream, A);
+  return check_launch("phi4 density kernel");
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // NormalPrior.sample_ (reference: src/prior/prior.py:26-29 + :30-36 = torch.distributions.Normal.sample, then a second
@@ -249,6 +293,35 @@ extern "C" int nf_phi4_action_vjp(const void *cfgs, const void *grad_action, voi
   if (dtype == NF_F32) return run<float, true, true>(A, nullptr, B, nullptr, 0, s);
   if (dtype == NF_F64) return run<double, true, true>(A, nullptr, B, nullptr, 0, s);
   set_error("nf_phi4_action_vjp: unsupported dtype %d", dtype);
+  return NF_EINVAL;
+}
+
+extern "C" int nf_phi4_action_density(const void *cfgs, void *density, int64_t B, const int32_t *lattice, double w0,
+                                      double wm, double w4, int dtype, void *stream) {
+  EpArgs A{};
+  int rc = fill_lattice(A, lattice);
+  if (rc) return rc;
+  NF_REQUIRE(cfgs && density && B >= 0 && B <= 65535, "nf_phi4_action_density: bad arguments");
+  A.x = cfgs; A.out = density; A.w0 = w0; A.w2 = wm; A.w4 = w4;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == NF_F32) return run_density<float, false>(A, B, s);
+  if (dtype == NF_F64) return run_density<double, false>(A, B, s);
+  set_error("nf_phi4_action_density: unsupported dtype %d", dtype);
+  return NF_EINVAL;
+}
+
+extern "C" int nf_phi4_action_density_vjp(const void *cfgs, const void *grad_density, void *grad_cfgs, int64_t B,
+                                          const int32_t *lattice, double w0, double wm, double w4, int dtype,
+                                          void *stream) {
+  EpArgs A{};
+  int rc = fill_lattice(A, lattice);
+  if (rc) return rc;
+  NF_REQUIRE(cfgs && grad_density && grad_cfgs && B >= 0 && B <= 65535, "nf_phi4_action_density_vjp: bad arguments");
+  A.x = cfgs; A.gout = grad_density; A.out = grad_cfgs; A.w0 = w0; A.w2 = wm; A.w4 = w4;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == NF_F32) return run_density<float, true>(A, B, s);
+  if (dtype == NF_F64) return run_density<double, true>(A, B, s);
+  set_error("nf_phi4_action_density_vjp: unsupported dtype %d", dtype);
   return NF_EINVAL;
 }
 

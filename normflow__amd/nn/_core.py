@@ -1,10 +1,13 @@
 """The flow-network protocol (API of the reference's src/nn/_core.py).
 
 A module whose name ends in an underscore maps `(x, log0) -> (y, log0 + log|det dy/dx|)` in
-`forward` and applies the inverse map in `backward`; `log0` may be the python number 0.  Only the
-two classes the scalar phi^4 path uses are provided: `Module_` (a leaf transformation) and
-`ModuleList_` (their composition).  The reference's multi-channel / invisibility wrappers serve its
-gauge-theory scaffolding and are out of scope.
+`forward` and applies the inverse map in `backward`; `log0` may be the python number 0.
+`Module_` is a leaf transformation and `ModuleList_` their composition.  Three wrappers compose
+site-local leaves as the reference does: `MultiChannelModule_` (one module per channel),
+`MultiOutChannelModule_` (every module on the whole input, outputs stacked as channels) and
+`InvisibilityMaskWrapperModule_` (a leaf on the sites of a mask's channel 0, the others passed
+through).  The last runs on `Module_.propagate_density`, the per-site log-density protocol; around
+Expit_, Logit_ or SplineNet_ it is one masked K4 pass (`nf_distconv_sites`).
 """
 import base64
 import copy
@@ -148,3 +151,96 @@ class ModuleList_(torch.nn.ModuleList):
         return self
 
     npar = property(count_parameters)
+
+
+class MultiChannelModule_(torch.nn.ModuleList):
+    """One module per channel (reference: src/nn/_core.py:137-178): channel j of the input, split off along
+    `channels_axis` (kept as an axis of extent 1 with keep_channels_axis, removed otherwise), goes through nets_[j]; the
+    outputs are put back together along the same axis and the log-Jacobians of the channels add up."""
+
+    def __init__(self, nets_, label=None, channels_axis=1, keep_channels_axis=True):
+        super().__init__(nets_)
+        self.channels_axis = channels_axis
+        self.keep_channels_axis = keep_channels_axis
+        self.label = label
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+    def forward(self, x, log0=0):
+        return self._map(x, [net_.forward for net_ in self], log0=log0)
+
+    def backward(self, x, log0=0):
+        return self._map(x, [net_.backward for net_ in self], log0=log0)
+
+    def _map(self, x, f_, log0=0):
+        if self.keep_channels_axis:
+            parts = x.split(1, dim=self.channels_axis)
+        else:
+            parts = x.unbind(dim=self.channels_axis)
+        if len(parts) != len(f_):
+            raise ValueError(f"{len(parts)} channels on axis {self.channels_axis} but {len(f_)} networks")
+        out = [fj_(xj) for fj_, xj in zip(f_, parts)]
+        join = torch.cat if self.keep_channels_axis else torch.stack
+        x = join([o[0] for o in out], dim=self.channels_axis)
+        return x, log0 + sum(o[1] for o in out)
+
+    npar = property(count_parameters)
+
+
+class MultiOutChannelModule_(MultiChannelModule_):
+    """Every module on the whole input; the outputs are concatenated along `channels_axis` and the log-Jacobians add up
+    (reference: src/nn/_core.py:182-191)."""
+
+    def _map(self, x, f_, log0=0):
+        out = [fj_(x) for fj_ in f_]
+        x = torch.cat([o[0] for o in out], dim=self.channels_axis)
+        return x, log0 + sum(o[1] for o in out)
+
+
+class InvisibilityMaskWrapperModule_(Module_):
+    """`net_` on the visible sites only: the sites of the mask's channel 0 are transformed and keep their log-densities,
+    the others pass through with log-density 0 (reference: src/nn/_core.py:195-231).  Sets net_.propagate_density, as
+    the reference does; the wrapper's own flag chooses per-sample sums or per-site densities.
+
+    Around Expit_, Logit_ or SplineNet_ (any K4 leaf) on a mask with `activity()` whose shape is the lattice, the whole
+    wrapper is ONE masked nf_distconv_sites pass over the visible sites: no split, purify, cat or per-site tensor.  Any
+    other leaf takes the reference's composition.  Departure: the reference evaluates net_ on the zeroed invisible sites
+    too, and for Logit_ its log(0) * 0 gives NaN in both y and log J; the masked pass copies those sites unchanged, so
+    its values are finite, and equal to the reference's wherever those are finite."""
+
+    def __init__(self, net_, *, mask):
+        super().__init__(label=f'wrapper:{net_.label}')
+        self.net_ = net_
+        self.mask = mask
+        self.net_.propagate_density = True  # does not sum the density
+
+    def _activity(self, x):
+        """The visible sites as (V,) uint8 bytes on x's device, or None where the masked pass does not apply."""
+        if not hasattr(self.net_, '_k4') or not hasattr(self.mask, 'activity') or not x.is_cuda or x.dim() < 2:
+            return None
+        act = self.mask.activity(0)
+        if tuple(act.shape) != tuple(x.shape[1:]):
+            return None
+        cache = self.__dict__.get('_act_cache')
+        if cache is None or cache[0] is not act or cache[1] != x.device:
+            cache = (act, x.device, act.to(device=x.device, dtype=torch.uint8).reshape(-1).contiguous())
+            self.__dict__['_act_cache'] = cache
+        return cache[2]
+
+    def _run(self, x, log0, inverse):
+        act = self._activity(x)
+        if act is not None:
+            from .scalar.modules_ import _run_stages
+            return _run_stages(bool(self.propagate_density), x, log0, *self.net_._k4(inverse), mask=act)
+        x_v, x_invisible = self.mask.split(x)  # x_v: x_visible
+        x_v, logJ_density = self.net_.backward(x_v) if inverse else self.net_.forward(x_v)
+        x_v = self.mask.purify(x_v, channel=0)
+        logJ = self.sum_density(self.mask.purify(logJ_density, channel=0))
+        return self.mask.cat(x_v, x_invisible), log0 + logJ
+
+    def forward(self, x, log0=0):
+        return self._run(x, log0, False)
+
+    def backward(self, x, log0=0):
+        return self._run(x, log0, True)

@@ -4,7 +4,9 @@ Expit_, SplineNet_, Logit_ and their composition DistConvertor_ run on the fused
 kernel (`nf_distconv`): one pass over the field for any subset of the three stages,
 the shared spline's knots staged in LDS.  DistConvertor_ keeps the reference's list
 structure (so `1.weights_x`-style state_dict keys and `.spline_layer_` still work) but
-executes the whole Expit_ -> SplineNet_ -> Logit_ triple as ONE launch.  Pade11_ and
+executes the whole Expit_ -> SplineNet_ -> Logit_ triple as ONE launch.  With
+propagate_density (on the instance or on the class) the same pass writes per-site
+log-densities (`nf_distconv_sites`), in inference and in training.  Pade11_ and
 Pade22_ run on `nf_pade`: one pass per direction, per-site densities included.
 """
 import math
@@ -21,13 +23,42 @@ def _as_rows(x):
     return x.reshape(x.shape[0], -1) if x.dim() > 1 else x.reshape(-1, 1)
 
 
-def _run_stages(module, x, log0, stages, inverse, knots=None):
-    if module is not None and module.propagate_density:
-        raise NotImplementedError("propagate_density=True is not provided by the fused kernels")
+def _site_log0(log0, x):
+    """A per-site log0 as a (B, V) tensor (None for the number 0), broadcast against the field as the reference's
+    `log0 + logJ` does."""
+    if torch.is_tensor(log0):
+        return log0.to(x.dtype).expand(x.shape).reshape(x.shape[0], -1).contiguous()
+    return None if log0 == 0 else torch.full((x.shape[0], x[0].numel()), float(log0), dtype=x.dtype, device=x.device)
+
+
+def _run_stages(per_site, x, log0, stages, inverse, knots=None, mask=None):
+    """One K4 pass.  per_site (Module_.propagate_density): log0 + log|f'| at every site, shaped like x (nf_distconv_sites);
+    otherwise the per-sample sum on the summed kernel (nf_distconv).  With an activity `mask` (V uint8 bytes: the
+    invisibility wrapper) the masked pass of nf_distconv_sites in either mode."""
     v = _as_rows(x)
+    if per_site:
+        val, dens = _hip.DistConvSitesFn.apply(v, knots, _site_log0(log0, x), mask, stages, inverse, True)
+        return val.reshape(x.shape), dens.reshape(x.shape)
     l0 = _hip._log0_tensor(log0, v, v.shape[0])
-    val, lj = _hip.DistConvFn.apply(v, knots, l0, stages, inverse)
+    if mask is not None:
+        val, lj = _hip.DistConvSitesFn.apply(v, knots, l0, mask, stages, inverse, False)
+    else:
+        val, lj = _hip.DistConvFn.apply(v, knots, l0, stages, inverse)
     return val.reshape(x.shape), lj
+
+
+class _K4Leaf:
+    """A leaf that runs on K4: `_k4(inverse)` gives its (stages, inverse, knots) for nf_distconv(_sites); the invisibility
+    wrapper reads it to run the whole wrapped module as one masked pass."""
+
+    def _k4(self, inverse):
+        raise NotImplementedError
+
+    def forward(self, x, log0=0):
+        return _run_stages(self.propagate_density, x, log0, *self._k4(False))
+
+    def backward(self, x, log0=0):
+        return _run_stages(self.propagate_density, x, log0, *self._k4(True))
 
 
 class Identity_(Module_):
@@ -77,24 +108,21 @@ class ScaleNet_(Module_):
         return x / self.weight, log0 - self._logj(x)
 
 
-class Expit_(Module_):
-    """y = 1/(1+e^-x); log|J| = sum(-x + 2 log y) (modules_.py:93-102)."""
+class Expit_(_K4Leaf, Module_):
+    """y = 1/(1+e^-x); log|J| = sum(-x + 2 log y) (modules_.py:93-102); with propagate_density the per-site terms.
+    Unlike the reference, whose backward builds a fresh Logit_ that ignores this instance's flag (modules_.py:101-102),
+    the flag holds in both directions."""
 
-    def forward(self, x, log0=0):
-        return _run_stages(self, x, log0, _hip.STAGE_EXPIT, False)
-
-    def backward(self, x, log0=0):
-        return _run_stages(self, x, log0, _hip.STAGE_LOGIT, False)
+    def _k4(self, inverse):
+        return (_hip.STAGE_LOGIT if inverse else _hip.STAGE_EXPIT), False, None
 
 
-class Logit_(Module_):
-    """y = log(x/(1-x)); log|J| = -sum log(x(1-x)) (modules_.py:105-114)."""
+class Logit_(_K4Leaf, Module_):
+    """y = log(x/(1-x)); log|J| = -sum log(x(1-x)) (modules_.py:105-114); with propagate_density the per-site terms.
+    The instance's flag holds in both directions (the reference's backward is a fresh Expit_, modules_.py:113-114)."""
 
-    def forward(self, x, log0=0):
-        return _run_stages(self, x, log0, _hip.STAGE_LOGIT, False)
-
-    def backward(self, x, log0=0):
-        return _run_stages(self, x, log0, _hip.STAGE_EXPIT, False)
+    def _k4(self, inverse):
+        return (_hip.STAGE_EXPIT if inverse else _hip.STAGE_LOGIT), False, None
 
 
 def _pade(module, x, log0, kind, inverse, d0, d1):
@@ -169,14 +197,11 @@ class Pade22_(Module_):
         return self._run(x, log0, True)
 
 
-class SplineNet_(SplineNet, Module_):
-    """SplineNet with the log-Jacobian (modules_.py:277-302)."""
+class SplineNet_(_K4Leaf, SplineNet, Module_):
+    """SplineNet with the log-Jacobian (modules_.py:277-302); with propagate_density the per-site log-derivatives."""
 
-    def forward(self, x, log0=0):
-        return _run_stages(self, x, log0, _hip.STAGE_SPLINE, False, self.knots())
-
-    def backward(self, x, log0=0):
-        return _run_stages(self, x, log0, _hip.STAGE_SPLINE, True, self.knots())
+    def _k4(self, inverse):
+        return _hip.STAGE_SPLINE, inverse, self.knots()
 
 
 class UnityDistConvertor_(SplineNet_):
@@ -243,12 +268,13 @@ class DistConvertor_(ModuleList_):
     sgnbias_layer_ = property(lambda self: self._by_label('sgnbias_'))
 
     def _steps(self):
-        """Group the children into ('fused', spline_) triples and ('single', module) steps."""
+        """Group the children into ('fused', spline_) triples and ('single', module) steps.  A triple fuses when its three
+        members carry the same propagate_density; with mixed flags they run one by one, as the reference composes them."""
         mods, steps, i = list(self), [], 0
         while i < len(mods):
             tri = mods[i:i + 3]
             if (len(tri) == 3 and type(tri[0]) is Expit_ and isinstance(tri[1], SplineNet_)
-                    and type(tri[2]) is Logit_ and not any(t.propagate_density for t in tri)):
+                    and type(tri[2]) is Logit_ and len({bool(t.propagate_density) for t in tri}) == 1):
                 steps.append(('fused', tri[1]))
                 i += 3
             else:
@@ -260,7 +286,7 @@ class DistConvertor_(ModuleList_):
         steps = self._steps()
         for kind, mod in (reversed(steps) if inverse else steps):
             if kind == 'fused':
-                x, log0 = _run_stages(None, x, log0, 7, inverse, mod.knots())
+                x, log0 = _run_stages(bool(mod.propagate_density), x, log0, 7, inverse, mod.knots())
             else:
                 x, log0 = mod.backward(x, log0) if inverse else mod.forward(x, log0)
         return x, log0
