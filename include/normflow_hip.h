@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NF_VERSION 300 /* 0.3.0 */
+#define NF_VERSION 301 /* 0.3.1 */
 
 /* NF_F16 (nf_rqs_fwd / nf_rqs_inv with knots_len 4/8/16, nf_affine_fwd / nf_affine_inv): x, params and y are IEEE half, the arithmetic is fp32 and
  * log0 / logj are fp32 ("fp16 params / fp32 log-det accumulate", BASELINE config 5). */
@@ -88,11 +88,9 @@ const char *nf_last_error_string(void);
  *                  (nf_conv_weight_layout / nf_conv_split16_supported answer accordingly);
  *   NF_OPT_PIPE    (default 1): eligible fp32 layers run the persistent, staging-overlapped kernels (nf_conv_pipe.hip);
  *                  0 = one box per workgroup (nf_conv.hip).
- *   NF_OPT_SMALL8  (default 1): the small-lattice fused layer (nf_small3d_rqs / nf_small_lattice_coupling) runs its
- *                  eight-wave form (two roles, two waves per SIMD); 0: the four-wave form (every wave holds all weights).
  * nf_set_option returns the previous value (>= 0) or NF_EINVAL; set options before launching, not concurrently with calls.
  */
-enum nf_option { NF_OPT_SPLIT16 = 0, NF_OPT_PIPE = 1, NF_OPT_SMALL8 = 2, NF_OPT_COUNT_ = 3 };
+enum nf_option { NF_OPT_SPLIT16 = 0, NF_OPT_PIPE = 1, NF_OPT_COUNT_ = 2 };
 int nf_set_option(int which, int value);
 int nf_get_option(int which);
 
@@ -210,8 +208,9 @@ int nf_conv_rqs_split16_vjp(const void *in, int in_split16, const void *wsplit, 
                             void *grad_x, int64_t B, const int32_t *lattice, int active_parity,
                             const void *absmax_bits, const nf_rqs_opts *opts, int inverse, void *stream);
 
-/* ---- K5s: a whole RQ-spline coupling layer of a SMALL 3-D lattice in one kernel ---------
- * Replaces, for lattices (L0, L1, 16) that fit a CU's LDS (16^3 = BASELINE config 3), the whole atom
+/* ---- K5s: a whole coupling layer of a SMALL lattice in one kernel ---------
+ * kind 0 = RQ-spline coupling (cout = 3m - 2, m = 2..16), ndim 3: replaces, for lattices (L0, L1, 16) that fit a CU's LDS
+ * (16^3 = BASELINE config 3), the whole atom
  * src/nn/scalar/couplings_.py:178-200: net(x_frozen) = ConvAct 1 -> 8 -> 8 -> cout (src/nn/scalar/modules.py:120-145,
  * 3^3 circular kernels, tanh / logistic hidden activations), make_spline (:211-262), the spline map and log g
  * (src/lib/spline/spline.py:154-287), purify and sum_density -- the hidden activations and the logits never leave the CU.
@@ -223,23 +222,17 @@ int nf_conv_rqs_split16_vjp(const void *in, int in_split16, const void *wsplit, 
  *      the fastest axis for output site s of a pair (zero outside 0..2);
  *   w3 [column tile (3)][K slice (7)][hi|lo][64][8]: B operand, lane 16 g + n holds the 8 input channels of tap 4 slice + g
  *      for logit channel 16 tile + n (zero for tap 27 and channels >= cout);
- * b1, b2 (8), b3 (cout): fp32 biases or NULL.  Hidden widths below 8: zero-padded by the host.  cout = 3m - 2, m = 2..16.
- * active_parity: the active site of pair (2h, 2h+1) in row (z, y) is 2h + ((active_parity + z + y) & 1).  fp32 only. */
-int nf_small3d_rqs_supported(const int32_t *lattice3, int cout, int m, int act1, int act2);
-/* The same kernel for the other small-lattice atoms: kind 0 = RQ-spline coupling (cout = 3m - 2), kind 1 = AFFINE coupling
- * (couplings_.py:123-139: the net ends in (t, s), cout = 2; y = t + x e^{-|s|}, logj = log0 - sum |s|; opts may be NULL);
- * ndim 3: lattice (L0, L1, 16); ndim 2: lattice (L1, 16) -- BASELINE config 2's 16 x 16 -- with the 3^2 kernels embedded as the
- * middle plane (j0 = 1) of 3^3 weight tensors, zero elsewhere, packed as for nf_small3d_rqs.  In 2-D the active site of
- * pair (2h, 2h+1) in row y is 2h + ((active_parity + y) & 1). */
+ * b1, b2 (8), b3 (cout): fp32 biases or NULL.  Hidden widths below 8: zero-padded by the host.
+ * active_parity: the active site of pair (2h, 2h+1) in row (z, y) is 2h + ((active_parity + z + y) & 1).  fp32 only.
+ * The same kernel serves the other small-lattice atoms: kind 1 = AFFINE coupling (couplings_.py:123-139: the net ends in
+ * (t, s), cout = 2; y = t + x e^{-|s|}, logj = log0 - sum |s|; opts may be NULL); ndim 2: lattice (L1, 16) -- BASELINE
+ * config 2's 16 x 16 -- with the 3^2 kernels embedded as the middle plane (j0 = 1) of 3^3 weight tensors, zero elsewhere,
+ * packed in the same fragments.  In 2-D the active site of pair (2h, 2h+1) in row y is 2h + ((active_parity + y) & 1). */
 int nf_small_lattice_supported(const int32_t *lattice, int ndim, int kind, int cout, int m, int act1, int act2);
 int nf_small_lattice_coupling(int kind, const void *x_frozen, const void *x_active, const void *w1, const void *b1,
                               const void *w2, const void *b2, const void *w3, const void *b3, const void *log0,
                               void *y, void *logj, int64_t B, const int32_t *lattice, int ndim, int active_parity,
                               int cout, int act1, int act2, const nf_rqs_opts *opts, int inverse, void *stream);
-int nf_small3d_rqs(const void *x_frozen, const void *x_active, const void *w1, const void *b1, const void *w2,
-                   const void *b2, const void *w3, const void *b3, const void *log0, void *y, void *logj,
-                   int64_t B, const int32_t *lattice3, int active_parity, int cout, int act1, int act2,
-                   const nf_rqs_opts *opts, int inverse, void *stream);
 
 /* ---- K1: affine / shift coupling --------------------------------------------
  * Replaces couplings_.py:123-139 (affine: chunk, 2 purify, abs, exp, fma, sum)

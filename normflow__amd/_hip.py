@@ -20,7 +20,7 @@ LAYOUT_FULL, LAYOUT_PAIR = 0, 1
 EXTRAP = {None: 0, 'none': 0, 'linear': 1, 'anti': 2, 'anti-periodic': 2}
 
 
-OPT_SPLIT16, OPT_PIPE, OPT_SMALL8 = 0, 1, 2
+OPT_SPLIT16, OPT_PIPE = 0, 1
 
 
 class NormflowHipError(RuntimeError):
@@ -96,12 +96,9 @@ PROTOTYPES = {
     "nf_conv_wgrad_split16_supported": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I]),
     "nf_conv_wgrad_split16_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
     "nf_conv_wgrad_split16": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _P, _I, _P, _SZ, _P]),
-    "nf_small3d_rqs_supported": (_I, [C.POINTER(C.c_int32), _I, _I, _I, _I]),
     "nf_small_lattice_supported": (_I, [C.POINTER(C.c_int32), _I, _I, _I, _I, _I, _I]),
     "nf_small_lattice_coupling": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _I, _I, _I, _I, _I,
                                        C.POINTER(RqsOpts), _I, _P]),
-    "nf_small3d_rqs": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _I, _I, _I, _I,
-                            C.POINTER(RqsOpts), _I, _P]),
     "nf_conv_rqs_split16_train": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _I, _P,
                                        C.POINTER(RqsOpts), _I, _P, _SZ, _P]),
     "nf_conv_rqs_split16_vjp": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _I, _P,
@@ -148,7 +145,7 @@ def load():
 class options:
     """Context manager / setter for the library's kernel-selection options (include/normflow_hip.h, nf_set_option):
     `with _hip.options(split16=False): ...` runs the block with exact fp32 MFMA products everywhere."""
-    _CODES = {"split16": OPT_SPLIT16, "pipe": OPT_PIPE, "small8": OPT_SMALL8}
+    _CODES = {"split16": OPT_SPLIT16, "pipe": OPT_PIPE}
 
     def __init__(self, **kw):
         self._new = {self._CODES[k]: int(bool(v)) for k, v in kw.items()}
@@ -222,6 +219,36 @@ def _log0_tensor(log0, like, B):
 MAX_B = 32768  # the batch is the grid's y extent; larger batches are cut into slabs
 
 
+def _slabs(B, step=MAX_B):
+    """(b0, b1) of the consecutive slabs of at most `step` samples that cover a batch of B (none when B == 0)."""
+    for b0 in range(0, B, step):
+        yield b0, min(B, b0 + step)
+
+
+def _slab(t, b0, b1):
+    """Rows b0 .. b1 of a tensor that may be None (log0, a bias)."""
+    return None if t is None else t[b0:b1]
+
+
+def _c_ints(vals):
+    return (C.c_int32 * len(vals))(*vals)
+
+
+def _lat4(lat, ksize=None):
+    """The lattice extents as the c_int32[4] the library takes, fewer than four axes padded with leading 1s; with `ksize`
+    the pair (lattice, kernel extents)."""
+    pad4 = lambda t: _c_ints([1] * (4 - len(t)) + list(t))
+    return pad4(lat) if ksize is None else (pad4(lat), pad4(ksize))
+
+
+def _sites(lat):
+    """Number of sites of a lattice (or of elements of any shape)."""
+    n = 1
+    for k in lat:
+        n *= k
+    return n
+
+
 # =============================================================================== RQS
 def make_rqs_opts(m, xlim, ylim, extrap, layout, knots_x=None, knots_y=None):
     """knots_x / knots_y: optional contiguous 1-D device tensors of m fixed knot coordinates (of
@@ -243,21 +270,23 @@ def make_rqs_opts(m, xlim, ylim, extrap, layout, knots_x=None, knots_y=None):
     return opts
 
 
-def _rqs_call(fn_name, v, params, mask, log0, opts, strides, B, V):
+def _rqs_call(fn_name, v, params, mask, log0, opts, strides, B, V, sites_mode=None, what=None):
+    """(value, logJ) of nf_rqs_fwd / nf_rqs_inv; with `sites_mode` (an nf_sites_mode) the *_sites entry points, which take
+    one more output: (value, logJ, per-site log-derivative or derivative)."""
     lib = load()
     out = torch.empty_like(v)
+    sites = None if sites_mode is None else torch.empty_like(v)
     logj = torch.empty(B, dtype=torch.float32 if v.dtype == torch.float16 else v.dtype, device=v.device)
     if log0 is not None and log0.dtype != logj.dtype:
         raise TypeError(f"log0 must be {logj.dtype} for a {v.dtype} field")
     ws = _workspace(min(B, MAX_B), V, v.device)
-    for b0 in range(0, B, MAX_B):
-        b1 = min(B, b0 + MAX_B)
-        l0 = log0[b0:b1] if log0 is not None else None
-        _check(getattr(lib, fn_name)(_ptr(v[b0:b1]), _ptr(params[b0:b1]), _ptr(mask), _ptr(l0),
-                                      _ptr(out[b0:b1]), _ptr(logj[b0:b1]), b1 - b0, V, C.byref(opts),
+    for b0, b1 in _slabs(B):
+        extra = () if sites is None else (_ptr(sites[b0:b1]), int(sites_mode))
+        _check(getattr(lib, fn_name)(_ptr(v[b0:b1]), _ptr(params[b0:b1]), _ptr(mask), _ptr(_slab(log0, b0, b1)),
+                                      _ptr(out[b0:b1]), _ptr(logj[b0:b1]), *extra, b1 - b0, V, C.byref(opts),
                                       C.byref(strides) if strides is not None else None, _ptr(ws),
-                                      ws.numel(), _dtype_code(v), _stream()), fn_name)
-    return out, logj
+                                      ws.numel(), _dtype_code(v), _stream()), what or fn_name)
+    return (out, logj) if sites is None else (out, logj, sites)
 
 
 SITES_LOG, SITES_DERIVATIVE = 1, 2       # nf_sites_mode
@@ -269,20 +298,15 @@ def rqs_sites(v, params, mask, log0, opts, inverse, mode=SITES_LOG):
     _require_device(v, params, mask, log0)
     if v.dtype not in (torch.float32, torch.float64) or params.dtype != v.dtype:
         raise TypeError(f"per-site derivatives are built for float32 / float64 fields; got {v.dtype} / {params.dtype}")
-    lib = load()
     B, V = v.shape
     v, params = v.detach().contiguous(), params.detach().contiguous()
-    out, sites = torch.empty_like(v), torch.empty_like(v)
-    logj = torch.empty(B, dtype=v.dtype, device=v.device)
-    ws = _workspace(min(B, MAX_B), V, v.device)
-    fn = lib.nf_rqs_inv_sites if inverse else lib.nf_rqs_fwd_sites
-    for b0 in range(0, B, MAX_B):
-        b1 = min(B, b0 + MAX_B)
-        l0 = log0[b0:b1] if log0 is not None else None
-        _check(fn(_ptr(v[b0:b1]), _ptr(params[b0:b1]), _ptr(mask), _ptr(l0), _ptr(out[b0:b1]), _ptr(logj[b0:b1]),
-                  _ptr(sites[b0:b1]), int(mode), b1 - b0, V, C.byref(opts), None, _ptr(ws), ws.numel(),
-                  _dtype_code(v), _stream()), "nf_rqs_sites")
-    return out, logj, sites
+    return _rqs_call("nf_rqs_inv_sites" if inverse else "nf_rqs_fwd_sites", v, params, mask, log0, opts, None, B, V,
+                     sites_mode=mode, what="nf_rqs_sites")
+
+
+def _channels(params, b0, b1, i, Cs):
+    """The logits of spline i of a multi-spline call: a view, whose first element the kernel addresses with batch strides."""
+    return params[b0:b1, i * Cs:(i + 1) * Cs]
 
 
 def multi_rqs_sites(v, params, mask, opts_list, inverse, mode=SITES_LOG):
@@ -302,14 +326,11 @@ def multi_rqs_sites(v, params, mask, opts_list, inverse, mode=SITES_LOG):
     logj = torch.empty(B, dtype=v.dtype, device=v.device)
     ws = _workspace(min(B, MAX_B), V, v.device)
     fn = lib.nf_rqs_inv_sites if inverse else lib.nf_rqs_fwd_sites
-    esz = v.element_size()
     st = Strides(ns * V, ns * V, Ctot * Vp)
     for i, opts in enumerate(opts_list):
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
-            _check(fn(C.c_void_p(v[b0:b1].data_ptr() + i * V * esz),
-                      C.c_void_p(params[b0:b1].data_ptr() + i * Cs * Vp * esz), _ptr(mask), None,
-                      C.c_void_p(out[b0:b1].data_ptr() + i * V * esz), _ptr(logj[b0:b1]), _ptr(sites[i, b0:b1]),
+        for b0, b1 in _slabs(B):
+            _check(fn(_ptr(v[b0:b1, i]), _ptr(_channels(params, b0, b1, i, Cs)), _ptr(mask), None,
+                      _ptr(out[b0:b1, i]), _ptr(logj[b0:b1]), _ptr(sites[i, b0:b1]),
                       int(mode), b1 - b0, V, C.byref(opts), C.byref(st), _ptr(ws), ws.numel(), _dtype_code(v),
                       _stream()), "nf_rqs_sites (multi)")
     return out, sites.movedim(0, 1)
@@ -338,8 +359,7 @@ def rqs_knots(params, opts):
     params = params.detach().contiguous()
     B, _, V = params.shape
     knots = torch.empty(B, 3 * opts.m, V, dtype=params.dtype, device=params.device)
-    for b0 in range(0, B, 65535):
-        b1 = min(B, b0 + 65535)
+    for b0, b1 in _slabs(B, 65535):
         _check(load().nf_rqs_knots(_ptr(params[b0:b1]), _ptr(knots[b0:b1]), b1 - b0, V, C.byref(opts),
                                    _dtype_code(params), _stream()), "nf_rqs_knots")
     return knots
@@ -349,8 +369,7 @@ def _rqs_vjp_call(fn_name, x, params, mask, gout, glogj, opts, strides, B, V):
     lib = load()
     gin = torch.empty_like(x)
     gpar = torch.empty_like(params)
-    for b0 in range(0, B, MAX_B):
-        b1 = min(B, b0 + MAX_B)
+    for b0, b1 in _slabs(B):
         _check(getattr(lib, fn_name)(_ptr(x[b0:b1]), _ptr(params[b0:b1]), _ptr(mask), _ptr(gout[b0:b1]),
                                       _ptr(glogj[b0:b1]), _ptr(gin[b0:b1]), _ptr(gpar[b0:b1]), b1 - b0, V,
                                       C.byref(opts), C.byref(strides) if strides is not None else None,
@@ -398,7 +417,7 @@ class MultiRQSCouplingFn(torch.autograd.Function):
         _require_device(v, params, mask, log0)
         B, ns, V = v.shape
         v, params = v.contiguous(), params.contiguous()
-        if params.dtype != v.dtype:        # the channels are addressed by byte offsets: a silent reinterpretation otherwise
+        if params.dtype != v.dtype:        # the kernel reads both with the field's dtype code: a silent reinterpretation otherwise
             raise TypeError(f"field is {v.dtype} but net output is {params.dtype}")
         if log0 is not None and log0.dtype != v.dtype:
             raise TypeError(f"log0 must be {v.dtype} for a {v.dtype} field")
@@ -408,17 +427,13 @@ class MultiRQSCouplingFn(torch.autograd.Function):
         lib = load()
         fn = lib.nf_rqs_inv if inverse else lib.nf_rqs_fwd
         ws = _workspace(min(B, MAX_B), V, v.device)
-        esz = v.element_size()
         st = Strides(ns * V, ns * V, Ctot * Vp)
         logj = log0
         for i, opts in enumerate(opts_list):
             nxt = torch.empty(B, dtype=v.dtype, device=v.device)
-            for b0 in range(0, B, MAX_B):       # the batch is the grid's y extent
-                b1 = min(B, b0 + MAX_B)
-                l0 = logj[b0:b1] if logj is not None else None
-                _check(fn(C.c_void_p(v[b0:b1].data_ptr() + i * V * esz),
-                          C.c_void_p(params[b0:b1].data_ptr() + i * Cs * Vp * esz), _ptr(mask), _ptr(l0),
-                          C.c_void_p(out[b0:b1].data_ptr() + i * V * esz), _ptr(nxt[b0:b1]), b1 - b0, V,
+            for b0, b1 in _slabs(B):       # the batch is the grid's y extent
+                _check(fn(_ptr(v[b0:b1, i]), _ptr(_channels(params, b0, b1, i, Cs)), _ptr(mask), _ptr(_slab(logj, b0, b1)),
+                          _ptr(out[b0:b1, i]), _ptr(nxt[b0:b1]), b1 - b0, V,
                           C.byref(opts), C.byref(st), _ptr(ws), ws.numel(), _dtype_code(v), _stream()),
                        "nf_rqs (multi)")
             logj = nxt
@@ -436,15 +451,12 @@ class MultiRQSCouplingFn(torch.autograd.Function):
         gin, gpar = torch.empty_like(x), torch.empty_like(params)
         lib = load()
         fn = lib.nf_rqs_inv_vjp if ctx.inverse else lib.nf_rqs_fwd_vjp
-        esz = x.element_size()
         st = Strides(ns * V, ns * V, Ctot * Vp)
         for i, opts in enumerate(ctx.opts_list):
-            xo, po = i * V * esz, i * Cs * Vp * esz
-            for b0 in range(0, B, MAX_B):
-                b1 = min(B, b0 + MAX_B)
-                _check(fn(C.c_void_p(x[b0:b1].data_ptr() + xo), C.c_void_p(params[b0:b1].data_ptr() + po), _ptr(mask),
-                          C.c_void_p(gout[b0:b1].data_ptr() + xo), _ptr(glogj[b0:b1]),
-                          C.c_void_p(gin[b0:b1].data_ptr() + xo), C.c_void_p(gpar[b0:b1].data_ptr() + po), b1 - b0, V,
+            for b0, b1 in _slabs(B):
+                _check(fn(_ptr(x[b0:b1, i]), _ptr(_channels(params, b0, b1, i, Cs)), _ptr(mask),
+                          _ptr(gout[b0:b1, i]), _ptr(glogj[b0:b1]),
+                          _ptr(gin[b0:b1, i]), _ptr(_channels(gpar, b0, b1, i, Cs)), b1 - b0, V,
                           C.byref(opts), C.byref(st), _dtype_code(x), _stream()), "nf_rqs_vjp (multi)")
         return gin, gpar, (glogj if ctx.has_log0 else None), None, None, None
 
@@ -460,10 +472,8 @@ def affine_sites(v, params, mask, log0, layout, inverse):
     out, sites = torch.empty_like(v), torch.empty_like(v)
     logj = torch.empty(B, dtype=v.dtype, device=v.device)
     ws = _workspace(min(B, MAX_B), V, v.device)
-    for b0 in range(0, B, MAX_B):
-        b1 = min(B, b0 + MAX_B)
-        l0 = log0[b0:b1] if log0 is not None else None
-        _check(load().nf_affine_sites(_ptr(v[b0:b1]), _ptr(params[b0:b1]), _ptr(mask), _ptr(l0), _ptr(out[b0:b1]),
+    for b0, b1 in _slabs(B):
+        _check(load().nf_affine_sites(_ptr(v[b0:b1]), _ptr(params[b0:b1]), _ptr(mask), _ptr(_slab(log0, b0, b1)), _ptr(out[b0:b1]),
                                       _ptr(logj[b0:b1]), _ptr(sites[b0:b1]), b1 - b0, V, params.shape[1], layout,
                                       int(bool(inverse)), _ptr(ws), ws.numel(), _dtype_code(v), _stream()),
                "nf_affine_sites")
@@ -500,10 +510,8 @@ class AffineCouplingFn(torch.autograd.Function):
         logj = torch.empty(B, dtype=ldt, device=v.device)
         ws = _workspace(min(B, MAX_B), V, v.device)
         fn = lib.nf_affine_inv if inverse else lib.nf_affine_fwd
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
-            l0 = log0[b0:b1] if log0 is not None else None
-            _check(fn(_ptr(v[b0:b1]), _ptr(params[b0:b1]), _ptr(mask), _ptr(l0), _ptr(out[b0:b1]),
+        for b0, b1 in _slabs(B):
+            _check(fn(_ptr(v[b0:b1]), _ptr(params[b0:b1]), _ptr(mask), _ptr(_slab(log0, b0, b1)), _ptr(out[b0:b1]),
                       _ptr(logj[b0:b1]), b1 - b0, V, n_ch, layout, _ptr(ws), ws.numel(), code,
                       _stream()), "nf_affine")
         ctx.save_for_backward(v, params, mask)
@@ -519,8 +527,7 @@ class AffineCouplingFn(torch.autograd.Function):
         gout, glogj = gout.contiguous(), glogj.contiguous()
         gin, gpar = torch.empty_like(v), torch.empty_like(params)
         lib = load()
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
+        for b0, b1 in _slabs(B):
             _check(lib.nf_affine_vjp(_ptr(v[b0:b1]), _ptr(params[b0:b1]), _ptr(mask), _ptr(gout[b0:b1]),
                                      _ptr(glogj[b0:b1]), _ptr(gin[b0:b1]), _ptr(gpar[b0:b1]), b1 - b0, V,
                                      params.shape[1], ctx.layout, int(ctx.inverse), _dtype_code(v),
@@ -550,10 +557,8 @@ class DistConvFn(torch.autograd.Function):
         out = torch.empty_like(v)
         logj = torch.empty(B, dtype=v.dtype, device=v.device)
         ws = _workspace(min(B, MAX_B), V, v.device)
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
-            l0 = log0[b0:b1] if log0 is not None else None
-            _check(lib.nf_distconv(_ptr(v[b0:b1]), _ptr(knots), K, _ptr(l0), _ptr(out[b0:b1]),
+        for b0, b1 in _slabs(B):
+            _check(lib.nf_distconv(_ptr(v[b0:b1]), _ptr(knots), K, _ptr(_slab(log0, b0, b1)), _ptr(out[b0:b1]),
                                    _ptr(logj[b0:b1]), b1 - b0, V, stages, int(inverse), _ptr(ws),
                                    ws.numel(), _dtype_code(v), _stream()), "nf_distconv")
         ctx.save_for_backward(out if inverse else v, knots)
@@ -570,8 +575,7 @@ class DistConvFn(torch.autograd.Function):
         gk = torch.zeros(3, max(K, 1), dtype=torch.float64, device=x.device)
         lib = load()
         ws = _workspace(min(B, MAX_B), V, x.device)
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
+        for b0, b1 in _slabs(B):
             part = torch.zeros(3, max(K, 1), dtype=torch.float64, device=x.device)
             _check(lib.nf_distconv_vjp(_ptr(x[b0:b1]), _ptr(knots), K, _ptr(gout[b0:b1]), _ptr(glogj[b0:b1]),
                                        _ptr(gin[b0:b1]), _ptr(part), b1 - b0, V, ctx.stages,
@@ -607,10 +611,8 @@ class DistConvSitesFn(torch.autograd.Function):
         dens = torch.empty_like(v) if per_site else torch.empty(B, dtype=v.dtype, device=v.device)
         ws = None if per_site else _workspace(min(B, MAX_B), V, v.device)
         mode = DC_SITES if per_site else DC_SUM
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
-            l0 = log0[b0:b1] if log0 is not None else None
-            _check(lib.nf_distconv_sites(_ptr(v[b0:b1]), _ptr(knots), K, _ptr(l0), _ptr(mask), _ptr(out[b0:b1]),
+        for b0, b1 in _slabs(B):
+            _check(lib.nf_distconv_sites(_ptr(v[b0:b1]), _ptr(knots), K, _ptr(_slab(log0, b0, b1)), _ptr(mask), _ptr(out[b0:b1]),
                                          _ptr(dens[b0:b1]) if per_site else None,
                                          None if per_site else _ptr(dens[b0:b1]), b1 - b0, V, stages, int(inverse),
                                          mode, _ptr(ws), ws.numel() if ws is not None else 0, _dtype_code(v),
@@ -629,8 +631,7 @@ class DistConvSitesFn(torch.autograd.Function):
         gk = torch.zeros(3, max(K, 1), dtype=torch.float64, device=x.device)
         lib = load()
         ws = _workspace(min(B, MAX_B), V, x.device)
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
+        for b0, b1 in _slabs(B):
             part = torch.zeros(3, max(K, 1), dtype=torch.float64, device=x.device)
             _check(lib.nf_distconv_sites_vjp(_ptr(x[b0:b1]), _ptr(knots), K, _ptr(mask), _ptr(gout[b0:b1]),
                                              _ptr(gdens[b0:b1]), _ptr(gin[b0:b1]), _ptr(part), b1 - b0, V, ctx.stages,
@@ -698,9 +699,7 @@ _TORCH_ACT = {0: lambda t: t, 1: torch.tanh, 2: torch.relu,
 def pack_conv_weight(w):
     """(Cout, Cin, *k) -> MFMA fragment order [tap][cin/4][cout/16][4][16] (zero padded)."""
     cout, cin = w.shape[:2]
-    ntaps = 1
-    for k in w.shape[2:]:
-        ntaps *= k
+    ntaps = _sites(w.shape[2:])
     nt = (cout + 15) // 16
     ns = load().nf_conv_packed_steps(cin, ntaps)
     if ns:      # cin % 4 != 0: K = (tap, ci) flattened, 4 per step
@@ -817,17 +816,12 @@ def conv_first_split16(x, weight, bias, act, weight_src=None):
     tensor (B, V, 16); inference only."""
     lib = load()
     B = x.shape[0]
-    lat = list(x.shape[2:])
-    lat4 = (C.c_int32 * 4)(*lat)
-    V = 1
-    for n in lat:
-        V *= n
+    lat4 = _lat4(x.shape[2:])
+    V = _sites(x.shape[2:])
     wsp = _cached_pack(weight if weight_src is None else weight_src, 'first16', pack_conv_weight_split16_first)
     bias = None if bias is None else bias.detach().float().contiguous()
     out = torch.empty((B, V, 16), dtype=torch.float16, device=x.device)
-    step = max(1, min(MAX_B, ((1 << 31) - 1) // V))
-    for b0 in range(0, B, step):
-        b1 = min(B, b0 + step)
+    for b0, b1 in _slabs(B, max(1, min(MAX_B, ((1 << 31) - 1) // V))):
         _check(lib.nf_conv_first_split16(_ptr(x[b0:b1]), _ptr(wsp), _ptr(bias), _ptr(out[b0:b1]), b1 - b0, lat4,
                                          int(act), _stream()), "nf_conv_first_split16")
     return out
@@ -873,18 +867,36 @@ def conv_layer_split16(h16, weight, bias, act, lattice):
     """Hidden 8 -> 8 layer on fp16 (hi, lo) pairs in and out (nf_conv_fwd_split16); inference only."""
     lib = load()
     B = h16.shape[0]
-    lat4 = (C.c_int32 * 4)(*lattice)
+    lat4 = _lat4(lattice)
     wsp = _cached_pack(weight, 'stacked16', pack_conv_weight_split16_stacked)
     bias = None if bias is None else bias.detach().float().contiguous()
     out = torch.empty_like(h16)
-    for b0 in range(0, B, MAX_B):
-        b1 = min(B, b0 + MAX_B)
+    for b0, b1 in _slabs(B):
         _check(lib.nf_conv_fwd_split16(_ptr(h16[b0:b1]), _ptr(wsp), _ptr(bias), _ptr(out[b0:b1]), b1 - b0, lat4,
                                        int(act), _stream()), "nf_conv_fwd_split16")
     return out
 
 
-_UNIT_OK = {}
+class _PerTensorCache(dict):
+    """Values cached per live tensor OBJECT (the parameter a view like Conv4d.weight is based on), `kind` and `state` (the
+    caller's tuple of version, address, ...).  The tensor is held by weak reference: when it dies its entries go with it, so a
+    new tensor that reuses the freed address never inherits one, and a detached alias or a temporary (a flipped / transposed
+    copy made for one call) has no live base and is never found."""
+    MISS = object()
+
+    def lookup(self, w, kind, state):
+        base = w._base if w._base is not None else w
+        hit = self.get((id(base), kind))
+        return hit[2] if hit is not None and hit[0]() is base and hit[1] == state else self.MISS
+
+    def store(self, w, kind, state, value):
+        base = w._base if w._base is not None else w
+        key = (id(base), kind)
+        self[key] = (weakref.ref(base, lambda _, k=key: self.pop(k, None)), state, value)
+        return value
+
+
+_UNIT_OK = _PerTensorCache()
 _WEIGHT_EPOCH = [0]
 
 
@@ -903,7 +915,7 @@ def weight_epoch():
     return _WEIGHT_EPOCH[0]
 
 
-_PACKED = {}
+_PACKED = _PerTensorCache()
 _PACK_IN_CAPTURE = [False]
 
 
@@ -922,44 +934,34 @@ class pack_inside_capture:
 
 
 def _cached_pack(w, kind, fn):
-    """fn(w.detach()) -- a weight tensor repacked into a kernel's fragment layout -- cached per live tensor OBJECT (the
-    parameter a view like Conv4d.weight is based on, held by weak reference as in `_weights_fit_fp16`) and version, so that
-    an inference pass does not repack (a dozen small torch kernels per layer and launch) weights that have not changed.
-    A detached alias or a temporary has no live base: it is packed every time."""
+    """fn(w.detach()) -- a weight tensor repacked into a kernel's fragment layout -- cached per live tensor and version
+    (`_PerTensorCache`), so that an inference pass does not repack (a dozen small torch kernels per layer and launch) weights
+    that have not changed.  A detached alias or a temporary has no live base: it is packed every time."""
     if _PACK_IN_CAPTURE[0] and torch.cuda.is_current_stream_capturing():
         return fn(w.detach())          # a training graph: the packing is part of the graph, replayed on the current values
-    base = w._base if w._base is not None else w
-    key = (id(base), kind)
     state = (w._version, w.data_ptr(), tuple(w.shape), w.dtype)
-    hit = _PACKED.get(key)
-    if hit is not None and hit[0]() is base and hit[1] == state:
-        return hit[2]
-    out = fn(w.detach())
-    _PACKED[key] = (weakref.ref(base, lambda _, k=key: _PACKED.pop(k, None)), state, out)
+    out = _PACKED.lookup(w, kind, state)
+    if out is _PACKED.MISS:
+        out = _PACKED.store(w, kind, state, fn(w.detach()))
     return out
 
 
 def _weights_fit_fp16(w):
     """finite and inside the fp16 range (the split-fp16 kernel's precondition on the weights); cached per
     parameter version so that the device->host sync happens once per optimiser step, not per launch.
-    An entry belongs to one live tensor OBJECT (the parameter a view like Conv4d.weight is based on), held by weak
-    reference: when that tensor dies its entry goes with it, so a new tensor that reuses the freed address never inherits
-    a verdict, and temporaries (a flipped / transposed copy made for one call) are checked every time.
+    An entry belongs to one live tensor (`_PerTensorCache`): temporaries are checked every time.
     In-place ops under no_grad (optimizers, `p.copy_`) bump the version; writes through `p.data` do NOT -- after
     those call `invalidate_weight_checks()` (ModelDeviceHandler.broadcast_parameters does).  Under stream capture
     (GraphedFlow) the check cannot run: only an already cached verdict is accepted, so GraphedFlow validates the
     weights eagerly before it captures and must be re-captured after the weights change."""
-    base = w._base if w._base is not None else w
-    key = id(base)
     state = (w._version, w.data_ptr(), tuple(w.shape))
-    hit = _UNIT_OK.get(key)
-    if hit is not None and hit[0]() is base and hit[1] == state:
-        return hit[2]
+    ok = _UNIT_OK.lookup(w, None, state)
+    if ok is not _UNIT_OK.MISS:
+        return ok
     if torch.cuda.is_current_stream_capturing():
         return False            # cannot synchronise here; the fp32 kernels are always valid
     ok = bool(torch.isfinite(w.detach()).all()) and float(w.detach().abs().max()) * SPLIT16_WEIGHT_SCALE < 3.0e4
-    _UNIT_OK[key] = (weakref.ref(base, lambda _, k=key: _UNIT_OK.pop(k, None)), state, ok)
-    return ok
+    return _UNIT_OK.store(w, None, state, ok)
 
 
 def conv_supported(x, weight):
@@ -977,9 +979,7 @@ def _gather_map(shape, device, build, key):
     key = (tuple(shape), device) + key
     ent = _GATHER_MAPS.get(key)
     if ent is None:
-        n = 1
-        for s in shape:
-            n *= s
+        n = _sites(shape)
         probe = torch.arange(1, n + 1, dtype=torch.float64, device=device).reshape(shape)
         packed = build(probe)
         idx = (packed.reshape(-1).round().to(torch.int64) - 1).to(torch.int32).contiguous()      # -1: a zero of the padding
@@ -1032,8 +1032,7 @@ def _conv_launch(x, weight, bias, act, compact, parity, weight_src=None, transpo
     lat = list(x.shape[2:])
     cout, ksize = weight.shape[1 if transposed else 0], list(weight.shape[2:])
     d = len(lat)
-    lat4 = (C.c_int32 * 4)(*([1] * (4 - d) + lat))
-    k4 = (C.c_int32 * 4)(*([1] * (4 - d) + ksize))
+    lat4, k4 = _lat4(lat, ksize)
     split16 = compact == 2                 # NF_OUT_SPLIT16: the fp16 (hi, lo) pair tensor, (B, V, 16) halfs
     if (split16 and cin == 1 and cout == 8 and d == 4 and x.dtype == torch.float32
             and _weights_fit_fp16(weight if weight_src is None else weight_src)     # (the caller's tensor: its verdict is cached)
@@ -1045,15 +1044,12 @@ def _conv_launch(x, weight, bias, act, compact, parity, weight_src=None, transpo
     eff_compact = False if (two_site and split16) else compact
     wfrag = _pack_by_gather(weight, _conv_weight_map(weight.shape, weight.device, lat4, k4, cin, cout, eff_compact, two_site,
                                                      transposed, _dtype_code(x)))
-    V = 1
-    for n in lat:
-        V *= n
+    V = _sites(lat)
     if split16:
         out = torch.empty((B, V, 16), dtype=torch.float16, device=x.device)
     else:
         out = torch.empty((B, cout, V // 2) if compact else (B, cout) + tuple(lat), dtype=x.dtype, device=x.device)
-    for b0 in range(0, B, MAX_B):
-        b1 = min(B, b0 + MAX_B)
+    for b0, b1 in _slabs(B):
         _check(lib.nf_conv_fwd(_ptr(x[b0:b1]), _ptr(wfrag), _ptr(bias), _ptr(out[b0:b1]), b1 - b0, lat4, k4,
                                cin, cout, act, int(compact), int(parity), _dtype_code(x), _stream()), "nf_conv_fwd")
     return out
@@ -1066,15 +1062,9 @@ def _compact_to_full(t, lattice, parity):
     B, Cc, Vh = t.shape
     t = t.contiguous()
     full = torch.empty((B, Cc) + tuple(lattice), dtype=t.dtype, device=t.device)
-    lat4 = (C.c_int32 * 4)(*([1] * (4 - len(lattice)) + list(lattice)))
-    _check(load().nf_expand_pairs(_ptr(t), _ptr(full), B * Cc, lat4, int(parity), _dtype_code(t), _stream()),
+    _check(load().nf_expand_pairs(_ptr(t), _ptr(full), B * Cc, _lat4(lattice), int(parity), _dtype_code(t), _stream()),
            "nf_expand_pairs")
     return full
-
-
-def _lat4(lat, ksize):
-    d = len(lat)
-    return (C.c_int32 * 4)(*([1] * (4 - d) + list(lat))), (C.c_int32 * 4)(*([1] * (4 - d) + list(ksize)))
 
 
 def absmax_bits(t):
@@ -1094,9 +1084,7 @@ def conv_weight_grad(x, gz, ksize, bits=None, compact_parity=-1):
     lib = load()
     B, cin = x.shape[:2]
     cout = gz.shape[1]
-    ntaps = 1
-    for k in ksize:
-        ntaps *= k
+    ntaps = _sites(ksize)
     lat4, k4 = _lat4(x.shape[2:], ksize)
     ncols = lib.nf_conv_wgrad_cols(cin, ntaps)
     gws, gbs = [], []
@@ -1112,8 +1100,7 @@ def conv_weight_grad(x, gz, ksize, bits=None, compact_parity=-1):
             return None
         if compact_parity >= 0 and sites and x.shape[-1] % 2:
             return None
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
+        for b0, b1 in _slabs(B):
             if split:       # fp16 matrix cores, three products per fp32 product (nf_conv_w.hip)
                 need = lib.nf_conv_wgrad_split16_workspace(b1 - b0, lat4, cin)
                 ws = torch.empty(int(need), dtype=torch.uint8, device=x.device)
@@ -1158,9 +1145,7 @@ def conv_input_grad_split16(gz, wt, bits=None, compact_parity=-1, lattice=None, 
     if not _weights_fit_fp16(wt if weight is None else weight):      # (`weight`: the layer's parameter, whose verdict is cached)
         return None
     G = (Cc + 7) // 8
-    V = 1
-    for n in lattice:
-        V *= n
+    V = _sites(lattice)
     gz = gz.contiguous()
     g16 = torch.empty((G, B, V, 16), dtype=torch.float16, device=gz.device)
     if bits is None:
@@ -1211,18 +1196,13 @@ def conv_last_logits_split16(x, weight, bias, parity):
             or not lib.nf_get_option(OPT_SPLIT16) or not _weights_fit_fp16(weight)):
         return None
     B = x.shape[0]
-    lattice = tuple(x.shape[2:])
-    lat4 = (C.c_int32 * 4)(*lattice)
+    lat4 = _lat4(x.shape[2:])
     V = x[0, 0].numel()
     bits = absmax_bits(x)
     wsp = pack_conv_weight_split16(weight.detach().float())
     b = None if bias is None else bias.detach().float().contiguous()
     out = torch.empty((B, 46, V // 2), dtype=torch.float32, device=x.device)
-    src, is16 = x, 0
-    if lattice[-1] != 32:            # the kernel stages fp32 planes only for whole-row segments: hand it the pair tensor
-        src = torch.empty((1, B, V, 16), dtype=torch.float16, device=x.device)
-        _check(lib.nf_planes_to_split16(_ptr(x), _ptr(src), _ptr(bits), B, 8, lat4, -1, _stream()), "nf_planes_to_split16")
-        is16 = 1
+    src, is16 = FusedLastRqsFn._source(x, bits, lat4)
     _check(lib.nf_conv_last_logits_split16(_ptr(src), is16, _ptr(wsp), _ptr(b), _ptr(out), B, lat4, int(parity), _ptr(bits),
                                            _stream()), "nf_conv_last_logits_split16")
     return out
@@ -1256,7 +1236,7 @@ def conv_wide_logits_split16(x, packed, act1, parity):
     first, (hidden, hb), (last, b3), cout = packed
     B = x.shape[0]
     lattice = tuple(x.shape[2:])
-    lat4 = (C.c_int32 * 4)(*lattice)
+    lat4 = _lat4(lattice)
     V = x[0, 0].numel()
     x = x.contiguous()
     tanh = ACT_CODES['tanh']
@@ -1353,7 +1333,7 @@ def fused_last_rqs_trainable(h, weight):
             or tuple(weight.shape[2:]) != (3, 3, 3, 3) or weight.shape[0] > 46 or (weight.shape[0] + 2) % 3
             or not lib.nf_get_option(OPT_SPLIT16)):
         return False
-    lat4 = (C.c_int32 * 4)(*h.shape[2:])
+    lat4 = _lat4(h.shape[2:])
     return bool(lib.nf_conv_rqs_split16_supported(lat4, weight.shape[0], (weight.shape[0] + 2) // 3)) and _weights_fit_fp16(weight)
 
 
@@ -1379,8 +1359,7 @@ class FusedLastRqsFn(torch.autograd.Function):
         lib = load()
         h, x_active = h.contiguous(), x_active.contiguous()
         B, V = x_active.shape
-        lattice = tuple(h.shape[2:])
-        lat4 = (C.c_int32 * 4)(*lattice)
+        lat4 = _lat4(h.shape[2:])
         bits = absmax_bits(h)
         src, is16 = FusedLastRqsFn._source(h, bits, lat4)
         wsp = pack_conv_weight_split16(weight.detach().float())
@@ -1401,7 +1380,7 @@ class FusedLastRqsFn(torch.autograd.Function):
         lib = load()
         B, V = xpt.shape
         lattice = tuple(h.shape[2:])
-        lat4 = (C.c_int32 * 4)(*lattice)
+        lat4 = _lat4(lattice)
         cout = weight.shape[0]
         bits = absmax_bits(h)
         src, is16 = FusedLastRqsFn._source(h, bits, lat4)
@@ -1446,7 +1425,7 @@ def conv_affine_split16(h16, weight, bias, x_active, log0, parity, inverse, latt
     lib = load()
     B, V = x_active.shape
     x_active = x_active.contiguous()
-    lat4 = (C.c_int32 * 4)(*lattice)
+    lat4 = _lat4(lattice)
     def pack_affine(w):
         w8 = w.new_zeros((8, 8, 3, 3, 3, 3), dtype=torch.float32)
         w8[:2] = w.float()
@@ -1462,10 +1441,8 @@ def conv_affine_split16(h16, weight, bias, x_active, log0, parity, inverse, latt
     else:
         y, logj = out
     ws = _workspace(min(B, MAX_B), V, x_active.device)
-    for b0 in range(0, B, MAX_B):
-        b1 = min(B, b0 + MAX_B)
-        l0 = log0[b0:b1] if log0 is not None else None
-        _check(lib.nf_conv_affine_split16(_ptr(h16[b0:b1]), _ptr(wsp), _ptr(b8), _ptr(x_active[b0:b1]), _ptr(l0),
+    for b0, b1 in _slabs(B):
+        _check(lib.nf_conv_affine_split16(_ptr(h16[b0:b1]), _ptr(wsp), _ptr(b8), _ptr(x_active[b0:b1]), _ptr(_slab(log0, b0, b1)),
                                           _ptr(y[b0:b1]), _ptr(logj[b0:b1]), b1 - b0, lat4, int(parity), int(inverse),
                                           4 if field16 else 0, _ptr(ws), ws.numel(), _stream()), "nf_conv_affine_split16")
     return y, logj
@@ -1483,9 +1460,7 @@ def conv_rqs(h, weight, bias, x_active, log0, parity, opts, inverse, unit_input=
     B = h.shape[0]
     cin = weight.shape[1] if split_in else h.shape[1]
     lat = list(lattice) if split_in else list(h.shape[2:])
-    d = len(lat)
-    lat4 = (C.c_int32 * 4)(*([1] * (4 - d) + lat))
-    k4 = (C.c_int32 * 4)(*([1] * (4 - d) + list(weight.shape[2:])))
+    lat4, k4 = _lat4(lat, weight.shape[2:])
     V = x_active.shape[1]
     flags = 1 if (unit_input and _weights_fit_fp16(weight)) else 0          # NF_CONV_UNIT_INPUT: |h| <= 1 (tanh outputs)
     field16 = x_active.dtype == torch.float16                                # NF_CONV_FIELD_F16: fp16 field storage
@@ -1510,17 +1485,15 @@ def conv_rqs(h, weight, bias, x_active, log0, parity, opts, inverse, unit_input=
             raise NormflowHipError("conv_rqs: `out` must be contiguous (B, V) and (B,) tensors of the input's dtype (log|J| fp32 for a half field)")
         _require_device(y, logj)
     ws = _workspace(min(B, MAX_B), V, h.device)
-    for b0 in range(0, B, MAX_B):
-        b1 = min(B, b0 + MAX_B)
-        l0 = log0[b0:b1] if log0 is not None else None
-        _check(lib.nf_conv_rqs(_ptr(h[b0:b1]), _ptr(wfrag), _ptr(bias), _ptr(x_active[b0:b1]), _ptr(l0),
+    for b0, b1 in _slabs(B):
+        _check(lib.nf_conv_rqs(_ptr(h[b0:b1]), _ptr(wfrag), _ptr(bias), _ptr(x_active[b0:b1]), _ptr(_slab(log0, b0, b1)),
                                _ptr(y[b0:b1]), _ptr(logj[b0:b1]), b1 - b0, lat4, k4, cin, weight.shape[0],
                                int(parity), C.byref(opts), int(inverse), flags, _ptr(ws), ws.numel(), NF_F32,
                                _stream()), "nf_conv_rqs")
     return y, logj
 
 
-# ============================================================ small 3-D lattices: one kernel per layer
+# ============================================================ small lattices: one kernel per layer
 def _split_hi_lo(w):
     w = w.float() * SPLIT16_WEIGHT_SCALE
     hi = w.half()
@@ -1529,7 +1502,7 @@ def _split_hi_lo(w):
 
 def pack_small3d_weights(w1, w2, w3):
     """(8, 1, 3, 3, 3), (8, 8, 3, 3, 3), (cout <= 48, 8, 3, 3, 3) fp32 weights -> the three fragment tensors of
-    nf_small3d_rqs (include/normflow_hip.h): scaled by 2^10, split into fp16 (hi, lo)."""
+    nf_small_lattice_coupling (include/normflow_hip.h): scaled by 2^10, split into fp16 (hi, lo)."""
     dev = w1.device
     cout = w3.shape[0]
     assert tuple(w1.shape) == (8, 1, 3, 3, 3) and tuple(w2.shape) == (8, 8, 3, 3, 3) and tuple(w3.shape[1:]) == (8, 3, 3, 3) and cout <= 48
@@ -1550,33 +1523,14 @@ def pack_small3d_weights(w1, w2, w3):
     return p1.contiguous(), p2.contiguous(), p3.contiguous()        # (2,64,8), (9,2,64,8), (3,7,2,64,8)
 
 
-def small_lattice_coupling(kind, x_frozen, x_active, packed, biases, log0, parity, cout, acts, opts, inverse):
+def small_lattice_coupling(kind, x_frozen, x_active, packed, biases, log0, parity, cout, acts, opts, inverse, out=None):
     """One launch per coupling layer of a small lattice (nf_small_lattice_coupling): kind 0 RQ-spline, 1 affine;
-    x_frozen, x_active: (B, L0, L1, 16) or (B, L1, 16) fp32; inference only."""
+    x_frozen, x_active: (B, L0, L1, 16) or (B, L1, 16) fp32; packed = pack_small3d_weights(...); biases = (b1, b2, b3) fp32 or
+    None each; `out` = (y, logJ) tensors to fill instead of new ones.  Inference only."""
     _require_device(x_frozen, x_active, log0, *packed)
     lib = load()
     B = x_active.shape[0]
     lat = tuple(x_active.shape[1:])
-    latc = (C.c_int32 * len(lat))(*lat)
-    x_frozen, x_active = x_frozen.contiguous(), x_active.contiguous()
-    y = torch.empty_like(x_active)
-    logj = torch.empty(B, dtype=torch.float32, device=x_active.device)
-    b1, b2, b3 = (None if b is None else b.detach().float().contiguous() for b in biases)
-    _check(lib.nf_small_lattice_coupling(int(kind), _ptr(x_frozen), _ptr(x_active), _ptr(packed[0]), _ptr(b1), _ptr(packed[1]),
-                                         _ptr(b2), _ptr(packed[2]), _ptr(b3), _ptr(log0), _ptr(y), _ptr(logj), B, latc, len(lat),
-                                         int(parity), int(cout), int(acts[0]), int(acts[1]),
-                                         C.byref(opts) if opts is not None else None, int(bool(inverse)), _stream()),
-           "nf_small_lattice_coupling")
-    return y, logj
-
-
-def small3d_rqs(x_frozen, x_active, packed, biases, log0, parity, cout, acts, opts, inverse, out=None):
-    """One launch per RQ-spline coupling layer of a small 3-D lattice (nf_small3d_rqs); inference only.
-    x_frozen, x_active: (B, L0, L1, 16) fp32; packed = pack_small3d_weights(...); biases = (b1, b2, b3) fp32 or None each."""
-    _require_device(x_frozen, x_active, log0, *packed)
-    lib = load()
-    B = x_active.shape[0]
-    lat3 = (C.c_int32 * 3)(*x_active.shape[1:])
     x_frozen, x_active = x_frozen.contiguous(), x_active.contiguous()
     if out is None:
         y = torch.empty_like(x_active)
@@ -1584,9 +1538,11 @@ def small3d_rqs(x_frozen, x_active, packed, biases, log0, parity, cout, acts, op
     else:
         y, logj = out
     b1, b2, b3 = (None if b is None else b.detach().float().contiguous() for b in biases)
-    _check(lib.nf_small3d_rqs(_ptr(x_frozen), _ptr(x_active), _ptr(packed[0]), _ptr(b1), _ptr(packed[1]), _ptr(b2),
-                              _ptr(packed[2]), _ptr(b3), _ptr(log0), _ptr(y), _ptr(logj), B, lat3, int(parity), int(cout),
-                              int(acts[0]), int(acts[1]), C.byref(opts), int(bool(inverse)), _stream()), "nf_small3d_rqs")
+    _check(lib.nf_small_lattice_coupling(int(kind), _ptr(x_frozen), _ptr(x_active), _ptr(packed[0]), _ptr(b1), _ptr(packed[1]),
+                                         _ptr(b2), _ptr(packed[2]), _ptr(b3), _ptr(log0), _ptr(y), _ptr(logj), B, _c_ints(lat), len(lat),
+                                         int(parity), int(cout), int(acts[0]), int(acts[1]),
+                                         C.byref(opts) if opts is not None else None, int(bool(inverse)), _stream()),
+           "nf_small_lattice_coupling")
     return y, logj
 
 
@@ -1601,12 +1557,10 @@ class Phi4ActionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfgs, w0, w2, w4):
         cfgs = cfgs.contiguous()
-        B, lat = cfgs.shape[0], list(cfgs.shape[1:])
-        lat4 = (C.c_int32 * 4)(*([1] * (4 - len(lat)) + lat))
+        B, lat4 = cfgs.shape[0], _lat4(cfgs.shape[1:])
         out = torch.empty(B, dtype=cfgs.dtype, device=cfgs.device)
         ws = _workspace(min(B, MAX_B), cfgs[0].numel(), cfgs.device)
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
+        for b0, b1 in _slabs(B):
             _check(load().nf_phi4_action(_ptr(cfgs[b0:b1]), _ptr(out[b0:b1]), b1 - b0, lat4, w0, w2, w4, _ptr(ws),
                                          ws.numel(), _dtype_code(cfgs), _stream()), "nf_phi4_action")
         ctx.save_for_backward(cfgs)
@@ -1616,12 +1570,10 @@ class Phi4ActionFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (cfgs,) = ctx.saved_tensors
-        B, lat = cfgs.shape[0], list(cfgs.shape[1:])
-        lat4 = (C.c_int32 * 4)(*([1] * (4 - len(lat)) + lat))
+        B, lat4 = cfgs.shape[0], _lat4(cfgs.shape[1:])
         g = g.contiguous()
         gc = torch.empty_like(cfgs)
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
+        for b0, b1 in _slabs(B):
             _check(load().nf_phi4_action_vjp(_ptr(cfgs[b0:b1]), _ptr(g[b0:b1]), _ptr(gc[b0:b1]), b1 - b0, lat4,
                                              *ctx.w, _dtype_code(cfgs), _stream()), "nf_phi4_action_vjp")
         return gc, None, None, None
@@ -1633,11 +1585,9 @@ class Phi4ActionDensityFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfgs, w0, wm, w4):
         cfgs = cfgs.contiguous()
-        B, lat = cfgs.shape[0], list(cfgs.shape[1:])
-        lat4 = (C.c_int32 * 4)(*([1] * (4 - len(lat)) + lat))
+        B, lat4 = cfgs.shape[0], _lat4(cfgs.shape[1:])
         out = torch.empty_like(cfgs)
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
+        for b0, b1 in _slabs(B):
             _check(load().nf_phi4_action_density(_ptr(cfgs[b0:b1]), _ptr(out[b0:b1]), b1 - b0, lat4, w0, wm, w4,
                                                  _dtype_code(cfgs), _stream()), "nf_phi4_action_density")
         ctx.save_for_backward(cfgs)
@@ -1647,12 +1597,10 @@ class Phi4ActionDensityFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (cfgs,) = ctx.saved_tensors
-        B, lat = cfgs.shape[0], list(cfgs.shape[1:])
-        lat4 = (C.c_int32 * 4)(*([1] * (4 - len(lat)) + lat))
+        B, lat4 = cfgs.shape[0], _lat4(cfgs.shape[1:])
         g = g.contiguous()
         gc = torch.empty_like(cfgs)
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
+        for b0, b1 in _slabs(B):
             _check(load().nf_phi4_action_density_vjp(_ptr(cfgs[b0:b1]), _ptr(g[b0:b1]), _ptr(gc[b0:b1]), b1 - b0,
                                                      lat4, *ctx.w, _dtype_code(cfgs), _stream()),
                    "nf_phi4_action_density_vjp")
@@ -1669,8 +1617,7 @@ class NormalLogProbFn(torch.autograd.Function):
         V = x[0].numel() if B else 0
         out = torch.empty(B, dtype=x.dtype, device=x.device)
         ws = _workspace(min(B, MAX_B), V, x.device)
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
+        for b0, b1 in _slabs(B):
             _check(load().nf_normal_logprob(_ptr(x[b0:b1]), _ptr(loc), _ptr(scale), _ptr(out[b0:b1]), b1 - b0, V,
                                             _ptr(ws), ws.numel(), _dtype_code(x), _stream()), "nf_normal_logprob")
         ctx.save_for_backward(x, loc, scale)
@@ -1683,50 +1630,42 @@ class NormalLogProbFn(torch.autograd.Function):
         V = x[0].numel() if B else 0
         g = g.contiguous()
         gx = torch.empty_like(x)
-        for b0 in range(0, B, MAX_B):
-            b1 = min(B, b0 + MAX_B)
+        for b0, b1 in _slabs(B):
             _check(load().nf_normal_logprob_vjp(_ptr(x[b0:b1]), _ptr(loc), _ptr(scale), _ptr(g[b0:b1]),
                                                 _ptr(gx[b0:b1]), b1 - b0, V, _dtype_code(x), _stream()),
                    "nf_normal_logprob_vjp")
         return gx, None, None
 
 
-def normal_sample(loc, scale, batch_size, shape, dtype, device, generator=None):
-    """(x (B, *shape), logr (B)) of a NormalPrior in one launch (nf_normal_sample).  Seed and stream offset come from
-    torch's CUDA generator of `device` (or `generator`), which is advanced by one Philox call's worth per launch -- so
-    torch.manual_seed(s) makes this kernel reproducible exactly as it does torch's own samplers."""
+def _philox_position(device, generator=None):
+    """(seed, kernel offset) for one call of a Philox kernel, taken from torch's CUDA generator of `device` (or
+    `generator`), which is advanced by one call's worth: torch.manual_seed governs these kernels as it does torch's own."""
     gen = generator if generator is not None else torch.cuda.default_generators[device.index if device.index is not None
                                                                                   else torch.cuda.current_device()]
     seed, offset = gen.initial_seed(), gen.get_offset()
     gen.set_offset(offset + 4)            # torch keeps offsets in multiples of 4
-    V = 1
-    for n in shape:
-        V *= n
+    return seed & (2 ** 64 - 1), offset // 4
+
+
+def normal_sample(loc, scale, batch_size, shape, dtype, device, generator=None):
+    """(x (B, *shape), logr (B)) of a NormalPrior in one launch (nf_normal_sample), at the `_philox_position` of torch's
+    generator: torch.manual_seed(s) makes this kernel reproducible exactly as it does torch's own samplers."""
+    seed, offset = _philox_position(device, generator)
+    V = _sites(shape)
     x = torch.empty((batch_size,) + tuple(shape), dtype=dtype, device=device)
     logr = torch.empty(batch_size, dtype=dtype, device=device)
     ws = _workspace(min(batch_size, MAX_B), V, device)
     loc = None if loc is None else loc.to(device=device, dtype=dtype).contiguous()
     scale = None if scale is None else scale.to(device=device, dtype=dtype).contiguous()
-    for b0 in range(0, batch_size, MAX_B):
-        b1 = min(batch_size, b0 + MAX_B)
+    for b0, b1 in _slabs(batch_size):
         # slabs of one call use disjoint counter ranges through the high word of the offset
         _check(load().nf_normal_sample(_ptr(x[b0:b1]), _ptr(logr[b0:b1]), _ptr(loc), _ptr(scale), b1 - b0, V,
-                                       C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64((offset // 4) + ((b0 // MAX_B) << 40)),
-                                       _ptr(ws), ws.numel(), _dtype_code(x), _stream()), "nf_normal_sample")
+                                       seed, offset + ((b0 // MAX_B) << 40), _ptr(ws), ws.numel(), _dtype_code(x),
+                                       _stream()), "nf_normal_sample")
     return x, logr
 
 
 # ========================================================================= blocked Metropolis (nf_mcmc.hip)
-def _philox_position(device, generator=None):
-    """(seed, kernel offset) for one launch of a Philox kernel, taken from torch's CUDA generator of `device` (or
-    `generator`) and advanced by one call's worth, as `normal_sample` does: torch.manual_seed governs these kernels too."""
-    gen = generator if generator is not None else torch.cuda.default_generators[device.index if device.index is not None
-                                                                                  else torch.cuda.current_device()]
-    seed, offset = gen.initial_seed(), gen.get_offset()
-    gen.set_offset(offset + 4)            # torch keeps offsets in multiples of 4
-    return C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(offset // 4)
-
-
 def _block_args(x, backup, block_len, block_ind):
     _require_device(x, backup)
     if not x.is_contiguous() or not backup.is_contiguous():

@@ -67,6 +67,30 @@ def _activity_bytes(mask, channel, lattice_shape, device):
     return act.to(device=device, dtype=torch.uint8).reshape(-1).contiguous()
 
 
+def _needs_grad(x_active, x_frozen, net):
+    """Will autograd record this atom (gradients enabled and wanted by the field or by the net's parameters)?"""
+    return torch.is_grad_enabled() and (x_active.requires_grad or x_frozen.requires_grad
+                                        or any(p.requires_grad for p in net.parameters()))
+
+
+def _fixed_knots(knots, like):
+    """A fixed 1-D knot vector as a contiguous device tensor of the field's dtype."""
+    if knots is None:
+        return None
+    k = torch.as_tensor(knots)
+    if k.dim() != 1:
+        raise NotImplementedError("only 1-D fixed knots_x / knots_y are supported")
+    return k.detach().to(device=like.device, dtype=like.dtype).contiguous()
+
+
+def _knots_len(n_channels, kx, ky):
+    """(m, number of fixed knot vectors) of a spline that gets `n_channels` logits: 3m-2 (free), 2m-1 (x or y fixed), m (both
+    fixed) (couplings_.py:236-256, :383-401); m is None when the count fits no m."""
+    n_fixed = (kx is not None) + (ky is not None)
+    m, rest = divmod(n_channels + 2 - n_fixed, 3 - n_fixed)
+    return (None if rest else m), n_fixed
+
+
 class Coupling_(Module_, ABC):
     """A stack of coupling layers acting alternately on the two partitions of a mask
     (couplings_.py:22-103).
@@ -140,14 +164,20 @@ class Coupling_(Module_, ABC):
             self._act_cache = {key: hit, **{k: v for k, v in self._act_cache.items() if k[0] != parity}}
         return hit
 
+    def _pair_parity(self, parity):
+        """The parity of the coordinate sum of partition `parity`'s sites when the mask is a checkerboard whose sites pair up
+        along the fastest axis (what the pair-compact and fused kernels need), else None."""
+        if not getattr(self.mask, 'pairable', False) or not hasattr(self.mask, 'checkerboard_parity'):
+            return None
+        return self.mask.checkerboard_parity(parity)
+
     def _check_density(self):
         if self.propagate_density:
             raise NotImplementedError("propagate_density=True (per-site densities) is not provided by "
                                       "this coupling's kernels, which reduce log|J| per sample")
 
     def _no_grad_only(self, x_active, x_frozen, net):
-        if torch.is_grad_enabled() and (x_active.requires_grad or x_frozen.requires_grad
-                                        or any(p.requires_grad for p in net.parameters())):
+        if _needs_grad(x_active, x_frozen, net):
             raise NotImplementedError("propagate_density=True is an inference path here (per-site densities have no VJP "
                                       "kernel); wrap the call in torch.no_grad()")
 
@@ -181,9 +211,8 @@ class Coupling_(Module_, ABC):
         fp16 fields (BASELINE config 5): the net computes in fp32 on the widened frozen half."""
         if x_frozen.dtype == torch.float16:
             x_frozen = x_frozen.float()
-        if (parity is not None and self.channels_axis == 1 and hasattr(net, 'forward_active')
-                and getattr(self.mask, 'pairable', False) and hasattr(self.mask, 'checkerboard_parity')):
-            a = self.mask.checkerboard_parity(parity)
+        if parity is not None and self.channels_axis == 1 and hasattr(net, 'forward_active'):
+            a = self._pair_parity(parity)
             if a is not None:
                 out = net.forward_active(self.preprocess_fz(x_frozen), a)
                 if out is not None:
@@ -197,24 +226,19 @@ class Coupling_(Module_, ABC):
         """Small lattices (L0, L1 <= 16, 16) or (L1 <= 16, 16) that fit a CU's LDS -- BASELINE configs 3 (16^3) and 2 (16^2) --:
         the WHOLE atom (parameter net 1 -> h -> h -> C and the coupling, kind 0 RQ-spline / 1 affine) is ONE launch of
         nf_small_lattice_coupling; nothing but x and y touches HBM.  None when it does not apply."""
-        if (torch.is_grad_enabled() and (x_active.requires_grad or x_frozen.requires_grad
-                                         or any(p.requires_grad for p in net.parameters()))):
-            return None
         if (self.propagate_density or self.channels_axis != 1 or x_active.dim() not in (3, 4) or x_active.dtype != torch.float32
-                or not hasattr(net, 'small3d_plan') or not getattr(self.mask, 'pairable', False)
-                or not hasattr(self.mask, 'checkerboard_parity')):
+                or not hasattr(net, 'small3d_plan') or _needs_grad(x_active, x_frozen, net)):
             return None
-        a = self.mask.checkerboard_parity(parity)
+        a = self._pair_parity(parity)
         if a is None:
             return None
         plan = net.small3d_plan()
         if plan is None:
             return None
-        import ctypes as C
         packed, biases, acts, cout = plan
         lat = tuple(x_active.shape[1:])
         m = opts.m if opts is not None else 0
-        if not _hip.load().nf_small_lattice_supported((C.c_int32 * len(lat))(*lat), len(lat), kind, cout, m, acts[0], acts[1]):
+        if not _hip.load().nf_small_lattice_supported(_hip._c_ints(lat), len(lat), kind, cout, m, acts[0], acts[1]):
             return None
         B = x_active.shape[0]
         l0 = _hip._log0_tensor(log0, x_active, B)
@@ -284,14 +308,12 @@ class AffineCoupling_(Coupling_):
         """Inference fast path on the split-fp16 chain: first layer -> pair tensor, hidden layers, and the net's last layer
         (8 -> 2) fused with the affine map (nf_conv_affine_split16); the (t, s) tensor never reaches HBM.  None when it does
         not apply (then: conv stack + nf_affine)."""
-        if (torch.is_grad_enabled() and (x_active.requires_grad or x_frozen.requires_grad
-                                         or any(p.requires_grad for p in net.parameters()))):
+        if _needs_grad(x_active, x_frozen, net):
             return None
         if (self.propagate_density or self.channels_axis != 1 or not hasattr(net, 'hidden_and_last')
-                or not getattr(self.mask, 'pairable', False) or x_active.dtype not in (torch.float32, torch.float16)
-                or not hasattr(self.mask, 'checkerboard_parity') or x_active.dim() != 5):
+                or x_active.dtype not in (torch.float32, torch.float16) or x_active.dim() != 5):
             return None
-        a = self.mask.checkerboard_parity(parity)
+        a = self._pair_parity(parity)
         if a is None or net.conv_kwargs['out_channels'] != 2:
             return None
         B = x_active.shape[0]
@@ -346,24 +368,13 @@ class RQSplineCoupling_(Coupling_):
         self.knots_y = knots_y
         self.extrap = extrap
 
-    def _fixed(self, knots, like):
-        """A fixed 1-D knot vector as a contiguous device tensor of the field's dtype."""
-        if knots is None:
-            return None
-        k = torch.as_tensor(knots)
-        if k.dim() != 1:
-            raise NotImplementedError("only 1-D fixed knots_x / knots_y are supported")
-        return k.detach().to(device=like.device, dtype=like.dtype).contiguous()
-
     def _opts(self, n_channels, layout, like):
         """knots_len m from the channel count: 3m-2 (free), 2m-1 (x or y fixed), m (both fixed)
         (couplings_.py:236-256)."""
-        kx, ky = self._fixed(self.knots_x, like), self._fixed(self.knots_y, like)
-        n_fixed = (kx is not None) + (ky is not None)
-        div = 3 - n_fixed
-        if (n_channels + 2 - n_fixed) % div:
-            raise Exception(f"net output has {n_channels} channels; {div}m-{2 - n_fixed} are needed for m knots")
-        m = (n_channels + 2 - n_fixed) // div
+        kx, ky = _fixed_knots(self.knots_x, like), _fixed_knots(self.knots_y, like)
+        m, n_fixed = _knots_len(n_channels, kx, ky)
+        if m is None:
+            raise Exception(f"net output has {n_channels} channels; {3 - n_fixed}m-{2 - n_fixed} are needed for m knots")
         for k in (kx, ky):
             if k is not None and k.numel() != m:
                 raise Exception(f"fixed knots have {k.numel()} entries but the net output implies m={m}")
@@ -372,22 +383,19 @@ class RQSplineCoupling_(Coupling_):
     def _fused_atom(self, inverse, x_active, x_frozen, parity, net, log0):
         """Inference fast path: ConvAct's last layer and the spline in ONE kernel (nf_conv_rqs);
         the logits never reach HBM.  Returns None when it does not apply."""
-        if (torch.is_grad_enabled() and (x_active.requires_grad or x_frozen.requires_grad
-                                         or any(p.requires_grad for p in net.parameters()))):
+        if _needs_grad(x_active, x_frozen, net):
             return None
         if (self.propagate_density or self.channels_axis != 1 or self.knots_x is not None
                 or self.knots_y is not None or not hasattr(net, 'hidden_and_last')
-                or not getattr(self.mask, 'pairable', False) or x_active.dtype not in (torch.float32, torch.float16)
-                or not hasattr(self.mask, 'checkerboard_parity')):
+                or x_active.dtype not in (torch.float32, torch.float16)):
             return None
-        a = self.mask.checkerboard_parity(parity)
+        a = self._pair_parity(parity)
         n_out = net.conv_kwargs['out_channels']
         if a is None or (n_out + 2) % 3:
             return None
-        small = self._small3d_atom(inverse, x_active, x_frozen, a, net, log0, n_out)
-        if small is None and x_active.dim() == 3:           # 2-D lattices (L1, 16): the same kernel, one plane
-            small = self._small_lattice_atom(0, inverse, x_active, x_frozen, parity, net, log0,
-                                             _hip.make_rqs_opts((n_out + 2) // 3, self.xlim, self.ylim, self.extrap, _hip.LAYOUT_PAIR))
+        opts = _hip.make_rqs_opts((n_out + 2) // 3, self.xlim, self.ylim, self.extrap, _hip.LAYOUT_PAIR)
+        # small lattices (L0, L1, 16) and (L1, 16): the whole atom in one launch
+        small = self._small_lattice_atom(0, inverse, x_active, x_frozen, parity, net, log0, opts)
         if small is not None:
             return small
         # hidden widths 9 .. 16: the stack runs the split-fp16 kernels in groups of 8 channels and hands the logits to the coupling
@@ -416,30 +424,10 @@ class RQSplineCoupling_(Coupling_):
             if got is None:
                 return None
             h, last, unit, split = got
-            opts = _hip.make_rqs_opts((n_out + 2) // 3, self.xlim, self.ylim, self.extrap, _hip.LAYOUT_PAIR)
             _hip.conv_rqs(h, last.weight, last.bias, v[b0:b1], None if l0 is None else l0[b0:b1], a,
                           opts, inverse, unit_input=unit, lattice=tuple(x_frozen.shape[1:]) if split else None,
                           out=(val[b0:b1], lj[b0:b1]))
         return val.reshape(x_active.shape), lj
-
-    def _small3d_atom(self, inverse, x_active, x_frozen, a, net, log0, n_out):
-        """Small 3-D lattices (L0, L1, 16) that fit a CU's LDS -- BASELINE config 3's 16^3 --: the WHOLE atom (parameter net
-        1 -> h -> h -> C and the spline coupling) is one launch of nf_small3d_rqs per slab; nothing but x and y touches HBM."""
-        if x_active.dim() != 4 or x_active.dtype != torch.float32 or not hasattr(net, 'small3d_plan'):
-            return None
-        import ctypes as C
-        lat = tuple(x_active.shape[1:])
-        plan = net.small3d_plan()
-        if plan is None:
-            return None
-        packed, biases, acts, cout = plan
-        m = (n_out + 2) // 3
-        if cout != n_out or not _hip.load().nf_small3d_rqs_supported((C.c_int32 * 3)(*lat), cout, m, acts[0], acts[1]):
-            return None
-        B = x_active.shape[0]
-        l0 = _hip._log0_tensor(log0, x_active, B)
-        opts = _hip.make_rqs_opts(m, self.xlim, self.ylim, self.extrap, _hip.LAYOUT_PAIR)
-        return _hip.small3d_rqs(x_frozen, x_active, packed, biases, l0, a, cout, acts, opts, inverse)
 
     def make_spline(self, out):
         """The spline the net output `out` (B, C, *L) stands for (couplings_.py:211-262): an `RQSpline` whose knots and
@@ -473,23 +461,19 @@ class RQSplineCoupling_(Coupling_):
         one differentiable node on the split-fp16 kernel (`_hip.FusedLastRqsFn`): the (B, 3m-2, *L) logits are never
         materialised, forward or backward (Fitter.step, _normflowcore.py:275-294).  None when it does not apply (then: conv
         stack with materialised logits + nf_rqs_fwd / _vjp)."""
-        if not torch.is_grad_enabled() or not (x_active.requires_grad or x_frozen.requires_grad
-                                               or any(p.requires_grad for p in net.parameters())):
+        if not _needs_grad(x_active, x_frozen, net):
             return None
         if (self.channels_axis != 1 or self.knots_x is not None or self.knots_y is not None
-                or not hasattr(net, 'hidden_differentiable') or not getattr(self.mask, 'pairable', False)
-                or x_active.dtype != torch.float32 or x_active.dim() != 5 or not hasattr(self.mask, 'checkerboard_parity')):
+                or not hasattr(net, 'hidden_differentiable') or x_active.dtype != torch.float32 or x_active.dim() != 5):
             return None
-        a = self.mask.checkerboard_parity(parity)
+        a = self._pair_parity(parity)
         n_out = net.conv_kwargs['out_channels']
         hidden = net.conv_kwargs['hidden_sizes'] or []
         if a is None or (n_out + 2) % 3 or not hidden or hidden[-1] != 8:
             return None
         if x_active.shape[0] * n_out * (x_active[0].numel() // 2) * 4 < TRAIN_FUSED_MIN_LOGIT_BYTES:
             return None                        # small atom: the materialising path is faster (no recomputation)
-        import ctypes as C
-        lat4 = (C.c_int32 * 4)(*x_active.shape[1:])
-        if not _hip.load().nf_conv_rqs_split16_supported(lat4, n_out, (n_out + 2) // 3):
+        if not _hip.load().nf_conv_rqs_split16_supported(_hip._lat4(x_active.shape[1:]), n_out, (n_out + 2) // 3):
             return None
         got = net.hidden_differentiable(self.preprocess_fz(x_frozen))
         if got is None:
@@ -552,17 +536,10 @@ class MultiRQSplineCoupling_(Coupling_):
         2m-1 with knots_x[i] or knots_y[i] fixed, m with both."""
         opts = []
         for i in range(self.num_splines):
-            fix = lambda k: None if k is None else torch.as_tensor(k).detach().to(
-                device=like.device, dtype=like.dtype).contiguous()
-            kx, ky = fix(self.knots_x[i]), fix(self.knots_y[i])
-            for k in (kx, ky):
-                if k is not None and k.dim() != 1:
-                    raise NotImplementedError("only 1-D fixed knots_x / knots_y are supported")
-            n_fixed = (kx is not None) + (ky is not None)
-            div = 3 - n_fixed
-            if (Cs + 2 - n_fixed) % div:
-                raise Exception(f"spline {i} gets {Cs} channels; {div}m-{2 - n_fixed} are needed for m knots")
-            m = (Cs + 2 - n_fixed) // div
+            kx, ky = _fixed_knots(self.knots_x[i], like), _fixed_knots(self.knots_y[i], like)
+            m, n_fixed = _knots_len(Cs, kx, ky)
+            if m is None:
+                raise Exception(f"spline {i} gets {Cs} channels; {3 - n_fixed}m-{2 - n_fixed} are needed for m knots")
             for k in (kx, ky):
                 if k is not None and k.numel() != m:
                     raise Exception(f"fixed knots of spline {i} have {k.numel()} entries but its channels imply m={m}")

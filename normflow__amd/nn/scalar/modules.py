@@ -45,6 +45,12 @@ class PlusBias(torch.nn.Module):
         return x + self.bias
 
 
+def _param_key(*wbs):
+    """What a per-module cache of something made from (weight, bias) pairs keys on: versions and addresses, and
+    `_hip.weight_epoch()` (a write through `.data` changes neither of the former)."""
+    return tuple((w._version, w.data_ptr(), None if b is None else (b._version, b.data_ptr())) for w, b in wbs) + (_hip.weight_epoch(),)
+
+
 class ConvAct(torch.nn.Sequential):
     """A stack of circular 'same' convolutions with activations, lattice dimension 1-4
     (modules.py:68-154).  `acts` has len(hidden_sizes)+1 entries (None = no activation).
@@ -84,7 +90,7 @@ class ConvAct(torch.nn.Sequential):
             return w, b
         cache = self.__dict__.setdefault('_w32', {})
         key = id(conv)
-        ver = (w._version, w.data_ptr(), None if b is None else b._version, _hip.weight_epoch())
+        ver = _param_key((w, b))
         hit = cache.get(key)
         if hit is None or hit[0] != ver:
             hit = (ver, w.detach().float(), None if b is None else b.detach().float())
@@ -140,7 +146,7 @@ class ConvAct(torch.nn.Sequential):
             return w, b
         cache = self.__dict__.setdefault('_w8', {})
         key = (id(conv), pad_out, pad_in)
-        ver = (w._version, w.data_ptr(), None if b is None else b._version, _hip.weight_epoch())
+        ver = _param_key((w, b))
         hit = cache.get(key)
         if hit is None or hit[0] != ver:
             w8 = w.new_zeros((no, ni) + tuple(w.shape[2:]))
@@ -219,8 +225,8 @@ class ConvAct(torch.nn.Sequential):
         return x, plan[-1][0], unit, split
 
     def small3d_plan(self):
-        """The fragment-packed weights of this stack for the small-lattice fused kernel (nf_small3d_rqs /
-        nf_small_lattice_coupling: ONE launch per coupling layer, the sample resident in LDS), or None when the stack is not
+        """The fragment-packed weights of this stack for the small-lattice fused kernel (nf_small_lattice_coupling:
+        ONE launch per coupling layer, the sample resident in LDS), or None when the stack is not
         1 -> h -> h -> C with 3^3 (or, on 2-D lattices, 3^2) circular kernels, h <= 8, tanh / logistic hidden activations and
         fp16-range weights.  Cached per parameter version."""
         cd = self.conv_kwargs['conv_dim']
@@ -238,7 +244,7 @@ class ConvAct(torch.nn.Sequential):
             return None
         if not all(_hip._weights_fit_fp16(w) for w, _ in wbs):
             return None
-        ver = tuple((w._version, w.data_ptr(), None if b is None else (b._version, b.data_ptr())) for w, b in wbs) + (_hip.weight_epoch(),)
+        ver = _param_key(*wbs)
         hit = self.__dict__.get('_small3d')
         if hit is None or hit[0] != ver:
             with torch.no_grad():
@@ -258,17 +264,16 @@ class ConvAct(torch.nn.Sequential):
 
     @staticmethod
     def _split16_chain(x, plan):
-        import ctypes as C
         lib = _hip.load()
         lat = list(x.shape[2:])
-        lat4 = (C.c_int32 * 4)(*lat)
+        lat4 = _hip._lat4(lat)
         first, fact = plan[0]
         if tuple(first.weight.shape[:2]) != (8, 1) or fact not in (_hip.ACT_CODES['tanh'], _hip.ACT_CODES['expit']):
             return False
         if not lib.nf_conv_two_site(8, 0, lat[-1], first.weight.shape[-1]):
             return False
         for conv, act in plan[1:-1]:
-            k4 = (C.c_int32 * 4)(*list(conv.weight.shape[2:]))
+            k4 = _hip._lat4(conv.weight.shape[2:])
             if conv.weight.dim() != 6 or not _hip._weights_fit_fp16(conv.weight):
                 return False
             if not lib.nf_conv_split16_supported(lat4, k4, conv.weight.shape[1], conv.weight.shape[0], act):
@@ -277,15 +282,13 @@ class ConvAct(torch.nn.Sequential):
 
     @staticmethod
     def _wants_split16(x, plan):
-        import ctypes as C
         last, prev = plan[-1][0], plan[-2][0]
         lat = list(x.shape[2:])
         d = len(lat)
         if x.dtype != torch.float32 or prev.weight.shape[0] != 8 or prev.weight.shape[1] % 4 or d != 4:
             return False
         lib = _hip.load()
-        lat4 = (C.c_int32 * 4)(*lat)
-        k4 = (C.c_int32 * 4)(*list(last.weight.shape[2:]))
+        lat4, k4 = _hip._lat4(lat, last.weight.shape[2:])
         if not _hip._weights_fit_fp16(last.weight):
             return False
         if lib.nf_conv_weight_layout(lat4, k4, last.weight.shape[1], last.weight.shape[0], 1, 7, _hip.NF_F32) != 2:      # fused | unit input | pair-tensor input
@@ -327,7 +330,6 @@ class ConvAct(torch.nn.Sequential):
         hidden activations (the first may be logistic) and fp16-range weights, on a lattice the split-fp16 kernels take, under
         no_grad: `_hip.conv_wide_logits_split16` composes it from those kernels in groups of 8 channels.  Cached per parameter
         version.  None otherwise (the fp32 MFMA kernels run the stack)."""
-        import ctypes as C
         if (torch.is_grad_enabled() or x.dim() != 6 or x.shape[1] != 1 or x.dtype != torch.float32 or not x.is_cuda
                 or self.conv_kwargs['conv_dim'] != 4):
             return None
@@ -342,14 +344,13 @@ class ConvAct(torch.nn.Sequential):
                 or w1.dtype != torch.float32 or any(tuple(w.shape[2:]) != (3, 3, 3, 3) for w, _ in wbs)):
             return None
         lib = _hip.load()
-        lat4 = (C.c_int32 * 4)(*x.shape[2:])
-        k4 = (C.c_int32 * 4)(3, 3, 3, 3)
+        lat4, k4 = _hip._lat4(x.shape[2:], (3, 3, 3, 3))
         if (not lib.nf_get_option(_hip.OPT_SPLIT16) or not lib.nf_conv_split16_supported(lat4, k4, 8, 8, T)
                 or not lib.nf_conv_first_split16_supported(lat4, k4, 8, plan[0][1]) or not lib.nf_conv_rqs_split16_supported(lat4, 46, 16)):
             return None
         if not all(_hip._weights_fit_fp16(w) for w, _ in wbs):
             return None
-        ver = tuple((w._version, w.data_ptr(), None if b is None else (b._version, b.data_ptr())) for w, b in wbs) + (_hip.weight_epoch(),)
+        ver = _param_key(*wbs)
         hit = self.__dict__.get('_wide16')
         if hit is None or hit[0] != ver:
             with torch.no_grad():

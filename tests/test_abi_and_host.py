@@ -34,7 +34,7 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in the header but not exported"
     assert set(_hip.PROTOTYPES) == declared
-    assert _hip.load().nf_version() == 300
+    assert _hip.load().nf_version() == 301
 
 
 def test_argument_validation_without_gpu():
@@ -372,7 +372,7 @@ def test_coupling_slab_budgets_are_module_settings():
 
 def test_round3_entry_points_validate_their_arguments_without_gpu():
     """The entry points added in round 3 refuse bad arguments with a status code and a message before any launch (no GPU
-    needed): nf_spline_eval, nf_small3d_rqs(+_supported), nf_conv_rqs_split16_supported, the training node's two calls."""
+    needed): nf_spline_eval, nf_small_lattice_coupling(+_supported), nf_conv_rqs_split16_supported, the training node's two calls."""
     lib = _hip.load()
     err = lambda: lib.nf_last_error_string().decode()
     assert lib.nf_spline_eval(None, None, None, None, None, None, 1, 8, 1, 0, 0, 0, 0, 0, None) == -1 and "2 knots" in err()
@@ -381,19 +381,19 @@ def test_round3_entry_points_validate_their_arguments_without_gpu():
     assert lib.nf_spline_eval(None, None, None, None, None, None, 1, 8, 4, 0, 0, 0, 0, 0, None) == -1 and "NULL" in err()
     lat3 = lambda *l: (ctypes.c_int32 * 3)(*l)
     T, S = _hip.ACT_CODES['tanh'], _hip.ACT_CODES['expit']
-    assert lib.nf_small3d_rqs_supported(lat3(16, 16, 16), 46, 16, T, T) == 1
-    assert lib.nf_small3d_rqs_supported(lat3(4, 6, 16), 22, 8, T, S) == 1
-    assert lib.nf_small3d_rqs_supported(lat3(16, 16, 32), 46, 16, T, T) == 0        # fastest axis must be 16
-    assert lib.nf_small3d_rqs_supported(lat3(16, 5, 16), 46, 16, T, T) == 0         # odd middle extent
-    assert lib.nf_small3d_rqs_supported(lat3(16, 16, 16), 46, 15, T, T) == 0        # cout != 3m - 2
-    assert lib.nf_small3d_rqs_supported(lat3(16, 16, 16), 46, 16, T, 2) == 0         # relu outputs are not fp16-safe
-    assert lib.nf_small3d_rqs_supported(lat3(64, 16, 16), 46, 16, T, T) == 0        # does not fit the LDS
+    assert lib.nf_small_lattice_supported(lat3(16, 16, 16), 3, 0, 46, 16, T, T) == 1
+    assert lib.nf_small_lattice_supported(lat3(4, 6, 16), 3, 0, 22, 8, T, S) == 1
+    assert lib.nf_small_lattice_supported(lat3(16, 16, 32), 3, 0, 46, 16, T, T) == 0        # fastest axis must be 16
+    assert lib.nf_small_lattice_supported(lat3(16, 5, 16), 3, 0, 46, 16, T, T) == 0         # odd middle extent
+    assert lib.nf_small_lattice_supported(lat3(16, 16, 16), 3, 0, 46, 15, T, T) == 0        # cout != 3m - 2
+    assert lib.nf_small_lattice_supported(lat3(16, 16, 16), 3, 0, 46, 16, T, 2) == 0         # relu outputs are not fp16-safe
+    assert lib.nf_small_lattice_supported(lat3(64, 16, 16), 3, 0, 46, 16, T, T) == 0        # does not fit the LDS
     opts = _hip.make_rqs_opts(16, (-5, 5), (-5, 5), {}, _hip.LAYOUT_PAIR)
-    rc = lib.nf_small3d_rqs(None, None, None, None, None, None, None, None, None, None, None, 2, lat3(16, 16, 32), 0, 46, T, T,
-                            ctypes.byref(opts), 0, None)
+    rc = lib.nf_small_lattice_coupling(0, None, None, None, None, None, None, None, None, None, None, None, 2, lat3(16, 16, 32), 3, 0, 46,
+                                       T, T, ctypes.byref(opts), 0, None)
     assert rc == -1 and "needs a lattice" in err()
-    rc = lib.nf_small3d_rqs(None, None, None, None, None, None, None, None, None, None, None, 0, lat3(16, 16, 16), 0, 46, T, T,
-                            ctypes.byref(opts), 0, None)
+    rc = lib.nf_small_lattice_coupling(0, None, None, None, None, None, None, None, None, None, None, None, 0, lat3(16, 16, 16), 3, 0, 46,
+                                       T, T, ctypes.byref(opts), 0, None)
     assert rc == 0
     lat2 = lambda *l: (ctypes.c_int32 * 2)(*l)
     assert lib.nf_small_lattice_supported(lat2(16, 16), 2, 1, 2, 0, T, T) == 1           # config 2: 16 x 16, affine
@@ -419,7 +419,7 @@ def test_round3_entry_points_validate_their_arguments_without_gpu():
 
 
 def test_small3d_weight_packers_match_the_documented_fragments():
-    """pack_small3d_weights against the fragment layouts include/normflow_hip.h documents for nf_small3d_rqs (hi + lo
+    """pack_small3d_weights against the fragment layouts include/normflow_hip.h documents for nf_small_lattice_coupling (hi + lo
     reassembled): lane 16 g + row, element i of every fragment."""
     torch.manual_seed(0)
     w1, w2, w3 = torch.randn(8, 1, 3, 3, 3), torch.randn(8, 8, 3, 3, 3), torch.randn(40, 8, 3, 3, 3)

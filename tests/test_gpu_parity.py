@@ -2146,7 +2146,6 @@ def test_small3d_fused_layer_vs_oracle(shape, B, m, hidden, acts, parity_report)
     in ONE launch with the sample resident in LDS: ConvAct 1 -> h -> h -> 3m-2 on split-fp16 products + the spline.  Forward
     and inverse against the fp64 oracle at north_star's 1e-5 (y, log|J|), against the fp32 kernels, batch order bitwise,
     more samples than workgroups; asserts that this kernel is the one that ran."""
-    import ctypes as C
     torch.manual_seed(7 * m + hidden)
     Cc = 3 * m - 2
     act_list = [acts[0], acts[1], None]
@@ -2159,7 +2158,8 @@ def test_small3d_fused_layer_vs_oracle(shape, B, m, hidden, acts, parity_report)
     cpl = RQSplineCoupling_([net, net], mask=mask, **lim).to(DEV)
     x = 1.5 * torch.randn((B,) + shape, device=DEV, dtype=torch.float32)
     assert net.small3d_plan() is not None
-    assert _hip.load().nf_small3d_rqs_supported((C.c_int32 * 3)(*shape), Cc, m, _hip.ACT_CODES[acts[0]], _hip.ACT_CODES[acts[1]])
+    assert _hip.load().nf_small_lattice_supported(_hip._c_ints(shape), 3, 0, Cc, m, _hip.ACT_CODES[acts[0]], _hip.ACT_CODES[acts[1]])
+    opts = _hip.make_rqs_opts(m, lim["xlim"], lim["ylim"], lim["extrap"], _hip.LAYOUT_PAIR)
     convs = [mod for mod in net if hasattr(mod, 'weight')]
     layers = [(c.weight.detach().double().cpu(), c.bias.detach().double().cpu()) for c in convs]
     nb = min(B, 6)
@@ -2167,8 +2167,7 @@ def test_small3d_fused_layer_vs_oracle(shape, B, m, hidden, acts, parity_report)
         xa, xf = mask.purify(x, parity), mask.purify(x, 1 - parity)
         l0 = torch.randn(B, device=DEV, dtype=torch.float32)
         with torch.no_grad():
-            a = mask.checkerboard_parity(parity)
-            got = cpl._small3d_atom(False, xa, xf, a, net, l0, Cc)
+            got = cpl._small_lattice_atom(0, False, xa, xf, parity, net, l0, opts)
             assert got is not None, "the small-lattice fused kernel did not take this layer"
             yf, lf = got
             yv, lv = cpl.atomic_forward(x_active=xa, x_frozen=xf, parity=parity, net=net, log0=l0)     # the API takes the same path
@@ -2177,10 +2176,10 @@ def test_small3d_fused_layer_vs_oracle(shape, B, m, hidden, acts, parity_report)
                 yu, lu = cpl.atomic_forward(x_active=xa, x_frozen=xf, parity=parity, net=net, log0=l0)
             assert rel(yf, yu) <= 1e-5 and rel(lf, lu) <= 1e-5, (rel(yf, yu), rel(lf, lu))
             perm = torch.randperm(B, device=DEV)
-            yp, lp = cpl._small3d_atom(False, xa[perm], xf[perm], a, net, l0[perm], Cc)
+            yp, lp = cpl._small_lattice_atom(0, False, xa[perm], xf[perm], parity, net, l0[perm], opts)
             assert torch.equal(yp, yf[perm]) and torch.equal(lp, lf[perm])
-            xb, lb = cpl._small3d_atom(True, yf, xf, a, net, lf, Cc)
-            y2, _ = cpl._small3d_atom(False, xb, xf, a, net, l0, Cc)
+            xb, lb = cpl._small_lattice_atom(0, True, yf, xf, parity, net, lf, opts)
+            y2, _ = cpl._small_lattice_atom(0, False, xb, xf, parity, net, l0, opts)
             assert rel(y2, yf) <= 2e-5, ("forward residual of the inverse", rel(y2, yf))
         am = O.channel_mask(shape, parity)
         assert float((yf.double().cpu() * (1 - am)).abs().max()) == 0.0            # frozen sites: exactly zero
@@ -2381,7 +2380,7 @@ def test_small_lattice_kernel_against_reference_goldens(golden, tag, parity_repo
 
 def test_small_lattice_kernel_edge_cases():
     """nf_small_lattice_coupling at its edges: empty batch, one sample, far more samples than workgroups (persistent loop),
-    non-contiguous inputs, both kernel forms (NF_OPT_SMALL8 on / off) bitwise equal per sample, unsupported shapes fall back
+    non-contiguous inputs, unsupported shapes fall back
     to the other kernels with the same results, CPU tensors refused."""
     torch.manual_seed(5)
     shape, m = (2, 4, 16), 16
@@ -2397,14 +2396,11 @@ def test_small_lattice_kernel_edge_cases():
         x0 = torch.empty((0,) + shape, device=DEV, dtype=torch.float32)
         y0, l0 = cpl(x0)
         assert y0.shape == x0.shape and l0.shape == (0,)
-        # one sample / many samples, and the two kernel forms
+        # one sample / many samples
         x = 1.2 * torch.randn((1500,) + shape, device=DEV, dtype=torch.float32)
         y, lj = cpl(x)
         y1, l1 = cpl(x[:1])
         assert torch.equal(y1, y[:1]) and torch.equal(l1, lj[:1])
-        with _hip.options(small8=False):
-            y4, l4 = cpl(x)
-        assert rel(y4, y) <= 2e-6 and rel(l4, lj) <= 2e-6           # same arithmetic per site, another summation order of log|J|
         # non-contiguous input (a strided view): same result as its contiguous copy
         xs = torch.randn((40,) + shape + (2,), device=DEV, dtype=torch.float32)[..., 0]
         assert not xs.is_contiguous()
@@ -2415,7 +2411,8 @@ def test_small_lattice_kernel_edge_cases():
         mask8 = EvenOddMask(shape=(2, 4, 8))
         cpl8 = RQSplineCoupling_([net, net], mask=mask8, **lim).to(DEV)
         x8 = torch.randn((3, 2, 4, 8), device=DEV, dtype=torch.float32)
-        assert cpl8._small3d_atom(False, mask8.purify(x8, 0), mask8.purify(x8, 1), mask8.checkerboard_parity(0), net, 0, 3 * m - 2) is None
+        assert cpl8._small_lattice_atom(0, False, mask8.purify(x8, 0), mask8.purify(x8, 1), 0, net, 0,
+                                        _hip.make_rqs_opts(m, lim["xlim"], lim["ylim"], lim["extrap"], _hip.LAYOUT_PAIR)) is None
         y8, l8 = cpl8(x8)
         xb8, lb8 = cpl8.backward(y8, l8)
         y8b, _ = cpl8(xb8)

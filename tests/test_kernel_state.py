@@ -289,7 +289,7 @@ def test_fused_affine_layer_state(shape, B):
 @pytest.mark.parametrize("shape,B,kind", [((16, 16, 16), 1024, 'rqs3d'), ((16, 16, 16), 1024, 'rqs'), ((16, 16, 16), 1024, 'affine'),
                                           ((16, 16), 4096, 'affine')])
 def test_k5s_small_lattice_state(shape, B, kind):
-    """small3d_rqs (out= given) and small_lattice_coupling (affine and rqs): a whole atom of a small lattice per launch."""
+    """small_lattice_coupling (rqs with out= given, affine and rqs): a whole atom of a small lattice per launch."""
     m = 16
     cout = 2 if kind == 'affine' else 3 * m - 2
     torch.manual_seed(9)
@@ -320,7 +320,7 @@ def test_k5s_small_lattice_state(shape, B, kind):
             if poison is not None:
                 _bits(y).view(torch.uint8).fill_(poison)
                 _bits(lj).view(torch.uint8).fill_(poison)
-            return _hip.small3d_rqs(xfi, xai, packed, biases, li, a, pcout, pacts, opts, False, out=(y, lj))
+            return _hip.small_lattice_coupling(0, xfi, xai, packed, biases, li, a, pcout, pacts, opts, False, out=(y, lj))
         call = lambda: _hip.small_lattice_coupling(1 if kind == 'affine' else 0, xfi, xai, packed, biases, li, a, pcout, pacts,
                                                    opts, False)
         return _alloc_run(call, xai.numel() * 4, poison)

@@ -81,7 +81,7 @@ def test_entry_points_exported_and_no_environment_read():
     und = subprocess.run(["nm", "-D", "--undefined-only", _hip.LIB_PATH], capture_output=True, text=True,
                          check=True).stdout
     assert "getenv" not in und
-    assert _hip.load().nf_version() == 300
+    assert _hip.load().nf_version() == 301
 
 
 def test_argument_checks_without_gpu():

@@ -103,4 +103,4 @@ def test_new_entry_points_are_exported_and_validate():
     assert lib.nf_phi4_action_density(x, x, 1, lat, 1.0, 1.0, 1.0, _hip.NF_F32, None) == -1
     lat = (ctypes.c_int32 * 4)(1, 1, 2, 4)
     assert lib.nf_phi4_action_density_vjp(x, x, x, 1, lat, 1.0, 1.0, 1.0, 7, None) == -1
-    assert lib.nf_version() == 300
+    assert lib.nf_version() == 301
