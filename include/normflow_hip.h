@@ -536,6 +536,39 @@ int nf_block_accept(void *x, const void *backup, const void *logq, const void *l
                     uint8_t *accept_out, int64_t C, int64_t V, int64_t block_len, int64_t block_ind, int force_accept,
                     uint64_t seed, uint64_t offset, int dtype, void *stream);
 
+/* ---- independence Metropolis on the device (MCMCSampler with n_chains = C; the reference does the accept/reject on the
+ * host: MCMCSampler._accept_reject_step, src/mcmc/mcmc.py:56-87, with Metropolis.calc_accept_status and
+ * calc_accept_indices, :304-328) for C independent chains over S steps.  The batch of B = S C proposals is laid out as the
+ * blocked sampler's: row r = s C + c is step s of chain c.  Neither entry allocates, copies or synchronises: both can be
+ * captured into a HIP graph.
+ *
+ * nf_metropolis_chains: every decision of the C chains over the S steps in ONE launch.  Per row r one uniform from
+ * counter = (lo32 r, hi32 r, lo32 offset, hi32 offset) and key = (lo32 seed, hi32 seed ^ NF_PHILOX_CHAIN_DOMAIN) -- a key
+ * domain of its own -- u = ((r0 << 21 ^ r1 >> 11) + 1) 2^-53 in (0, 1]; chain c walks s = 0 .. S-1 and decides in double:
+ *   accept[r] = (fresh && s == 0) || log u < logqp_ref[c] - (double(logq[r]) - double(logp[r])).
+ * Accepted: logqp_ref[c] = double(logq[r]) - double(logp[r]), ref_logq[c] = logq[r], ref_logp[c] = logp[r].
+ * keep[r] = the row that holds the configuration chain c has after step s: the last accepted row of the chain up to r,
+ * or row c while the chain still holds the state it came in with (then accept[c] == 0, and the configuration is the
+ * caller's stored sample of chain c, which nf_metropolis_select puts into row c); keep[r] <= r, keep[r] % C == c.
+ * logq_sel[r] / logp_sel[r] = the log q / log p of that configuration (bitwise logq[keep[r]], or the incoming
+ * ref_logq[c]), so the host needs no gather.  In: logq, logp (S C) of dtype fp32 or fp64.  In and out: logqp_ref (C)
+ * double, ref_logq, ref_logp (C) of dtype: the chains' stored state, on return the state after the last step.  With
+ * fresh != 0 the chains have no stored state: the three are not read and every chain accepts its step 0.  Out: accept
+ * (S C) uint8, keep (S C) int64, logq_sel, logp_sel (S C) of dtype; they may not overlap the inputs.
+ * One launch consumes one offset; the caller owns the stream position, as for nf_normal_sample.
+ *
+ * nf_metropolis_select: makes y (S C, V), the proposals, the chains' states IN PLACE from accept and keep.  A row with
+ * accept[r] != 0 is left as it is.  A rejected row r is overwritten, bitwise, with row keep[r] if accept[keep[r]] != 0,
+ * else with ref_sample[r % C] (C, V): the chain still holds its stored sample.  Only rejected rows move.  Rows are
+ * copied as bytes: elem_size (1, 2, 4 or 8) is the size of an element of y and ref_sample, any field dtype works.
+ * ref_sample may be NULL when no chain can need it (fresh chains: every step-0 row is accepted). */
+#define NF_PHILOX_CHAIN_DOMAIN 0x6e666368u   /* 'nfch' */
+int nf_metropolis_chains(const void *logq, const void *logp, double *logqp_ref, void *ref_logq, void *ref_logp,
+                         uint8_t *accept, int64_t *keep, void *logq_sel, void *logp_sel, int64_t S, int64_t C, int fresh,
+                         uint64_t seed, uint64_t offset, int dtype, void *stream);
+int nf_metropolis_select(void *y, const void *ref_sample, const uint8_t *accept, const int64_t *keep, int64_t S, int64_t C,
+                         int64_t V, int elem_size, void *stream);
+
 /* ---- VJP of the conv layer (K5) ---------------------------------------------------------------
  * grad_input is nf_conv_fwd itself applied to the pre-activation cotangent with the weights
  * flipped along every kernel axis and in/out channels swapped.  The two entry points below are

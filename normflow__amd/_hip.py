@@ -80,6 +80,8 @@ PROTOTYPES = {
     "nf_normal_sample": (_I, [_P, _P, _P, _P, _I64, _I64, C.c_uint64, C.c_uint64, _P, _SZ, _I, _P]),
     "nf_block_propose": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_block_accept": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, C.c_uint64, C.c_uint64, _I, _P]),
+    "nf_metropolis_chains": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, C.c_uint64, C.c_uint64, _I, _P]),
+    "nf_metropolis_select": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _P]),
     "nf_act_vjp": (_I, [_P, _P, _P, _I64, _I, _I, _P]),
     "nf_conv_wgrad_cols": (_I, [_I, _I]),
     "nf_conv_wgrad": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, _P]),
@@ -1701,3 +1703,51 @@ def block_accept(x, backup, logq, logp, logqp_ref, accept_out, block_len, block_
     _check(load().nf_block_accept(_ptr(x), _ptr(backup), _ptr(logq), _ptr(logp), _ptr(logqp_ref), _ptr(accept_out), Cn, V,
                                   int(block_len), int(block_ind), int(bool(force_accept)), seed, offset, _dtype_code(x),
                                   _stream()), "nf_block_accept")
+
+
+# ========================================================================= independence Metropolis, C chains (nf_mcmc.hip)
+def _expect(what, t, n, dtype):
+    if t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+        raise NormflowHipError(f"{what}: expected a contiguous tensor of {n} {dtype} values, got {tuple(t.shape)} {t.dtype}"
+                               f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+
+
+def metropolis_chains(logq, logp, logqp_ref, ref_logq, ref_logp, accept, keep, logq_sel, logp_sel, n_chains, fresh=False,
+                      generator=None):
+    """nf_metropolis_chains: the decisions of n_chains chains over S = len(logq) // n_chains steps in one launch (row
+    r = s C + c).  logqp_ref (C) float64, ref_logq, ref_logp (C) are the chains' stored state, updated in place (not read
+    when `fresh`); accept (S C) uint8, keep (S C) int64, logq_sel, logp_sel (S C) are written."""
+    Cn = int(n_chains)
+    B = logq.numel()
+    if logq.dtype not in (torch.float32, torch.float64):
+        raise NormflowHipError(f"metropolis_chains: log q must be float32 or float64, got {logq.dtype}")
+    if Cn < 1 or B % Cn != 0:
+        raise NormflowHipError(f"metropolis_chains: {B} rows are not a multiple of n_chains ({Cn})")
+    tensors = (logq, logp, logqp_ref, ref_logq, ref_logp, accept, keep, logq_sel, logp_sel)
+    _require_device(*tensors)
+    for t, n, dt in ((logq, B, logq.dtype), (logp, B, logq.dtype), (logqp_ref, Cn, torch.float64), (ref_logq, Cn, logq.dtype),
+                     (ref_logp, Cn, logq.dtype), (accept, B, torch.uint8), (keep, B, torch.int64), (logq_sel, B, logq.dtype),
+                     (logp_sel, B, logq.dtype)):
+        _expect("metropolis_chains", t, n, dt)
+    seed, offset = _philox_position(logq.device, generator)
+    _check(load().nf_metropolis_chains(*(_ptr(t) for t in tensors), B // Cn, Cn, int(bool(fresh)), seed, offset,
+                                       _dtype_code(logq), _stream()), "nf_metropolis_chains")
+
+
+def metropolis_select(y, ref_sample, accept, keep, n_chains):
+    """nf_metropolis_select: the rejected rows of y (S C, *L) are overwritten in place with the row keep[r], or with
+    ref_sample[r % C] (C, *L; None for fresh chains) while the chain holds its stored sample.  Any field dtype."""
+    Cn = int(n_chains)
+    B = y.shape[0]
+    if Cn < 1 or B % Cn != 0:
+        raise NormflowHipError(f"metropolis_select: {B} rows are not a multiple of n_chains ({Cn})")
+    _require_device(y, ref_sample, accept, keep)
+    if not y.is_contiguous():
+        raise NormflowHipError("metropolis_select needs a contiguous y")
+    V = y[0].numel() if B else 0
+    if ref_sample is not None:
+        _expect("metropolis_select (ref_sample)", ref_sample, Cn * V, y.dtype)
+    _expect("metropolis_select (accept)", accept, B, torch.uint8)
+    _expect("metropolis_select (keep)", keep, B, torch.int64)
+    _check(load().nf_metropolis_select(_ptr(y), _ptr(ref_sample), _ptr(accept), _ptr(keep), B // Cn, Cn, V,
+                                       y.element_size(), _stream()), "nf_metropolis_select")

@@ -1,7 +1,10 @@
 """Metropolis sampling on top of the flow (reference: src/mcmc/mcmc.py).
 
-`MCMCSampler` (independence Metropolis) is host-side and serial by nature (accept/reject is a chain); the proposals come
-from `posterior.sample__`, i.e. from the HIP path.  `BlockedMCMCSampler` redraws one block of the prior-side field at a
+`MCMCSampler` (independence Metropolis): the proposals come from `posterior.sample__`, i.e. from the HIP path.  By default
+the accept/reject is the reference's host code (one chain over the batch, `np.random` uniforms).  A chain is serial, but
+chains are independent: with `n_chains=C` on a HIP device the decisions of C chains are taken by one launch of
+nf_metropolis_chains and the rejected rows are overwritten in place by nf_metropolis_select (nf_mcmc.hip), with one read
+of the flags per call.  `BlockedMCMCSampler` redraws one block of the prior-side field at a
 time; on a HIP device it runs C independent chains batched through the flow, with proposal, accept/reject and restore
 on the GPU (nf_mcmc.hip)."""
 import copy
@@ -115,7 +118,16 @@ class MCMCHistory:
 
 
 class MCMCSampler:
-    """Draw proposals from the flow, keep/repeat them by Metropolis (mcmc.py:15-128)."""
+    """Draw proposals from the flow, keep/repeat them by Metropolis (mcmc.py:15-128).
+
+    MI355X-side extension (no counterpart in the reference), like `BlockedMCMCSampler(n_chains=)`: `n_chains=C` runs C
+    independent chains on one batch of proposals; proposal row r is step r // C of chain r % C, output row r the state of
+    chain r % C after step r // C, and `_ref` keeps every chain's last state, so the next call continues all C chains
+    (C = 1 keeps the reference's `_ref` shapes: calls with n_chains=None and n_chains=1 continue each other).  On a HIP
+    device with the kernel prior (NormalPrior with torch_rng=False) the accept/reject is nf_metropolis_chains and
+    nf_metropolis_select: no host loop, no gather, one device-to-host read (the flags) per call; its uniforms are that
+    kernel's stream (include/normflow_hip.h), keyed by torch's CUDA generator.  On CPU tensors, or with torch_rng=True,
+    the same rule runs on the host with `np.random` uniforms.  `n_chains=None` (the default) is the reference's code."""
 
     def __init__(self, model):
         self._model = model
@@ -131,11 +143,20 @@ class MCMCSampler:
         return self.sample__(batch_size=batch_size, **kwargs)[:2]
 
     @torch.no_grad()
-    def sample__(self, batch_size=1, bookkeeping=False):
+    def sample__(self, batch_size=1, bookkeeping=False, n_chains=None):
+        if n_chains is not None:
+            n_chains = int(n_chains)
+            if n_chains < 1 or batch_size < 1 or batch_size % n_chains != 0:
+                raise ValueError(f"batch_size ({batch_size}) must be a positive multiple of n_chains ({n_chains})")
+        else:
+            self._ref_for_host_chain()
         y, logq, logp = self._model.posterior.sample__(batch_size=batch_size)
         if bookkeeping:
             self.history.bookkeeping(raw_logq=logq, raw_logp=logp)
-        y, logq, logp = self._accept_reject_step(y, logq, logp, bookkeeping=bookkeeping)
+        if n_chains is None:
+            y, logq, logp = self._accept_reject_step(y, logq, logp, bookkeeping=bookkeeping)
+        else:
+            y, logq, logp = self._accept_reject_chains(y, logq, logp, n_chains, bookkeeping=bookkeeping)
         if bookkeeping:
             self.history.bookkeeping(logq=logq, logp=logp)
         return y, logq, logp
@@ -155,6 +176,114 @@ class MCMCSampler:
         if bookkeeping:
             self.history.bookkeeping(accept_seq=accept, accept_ind=keep)
         return y, logq, logp
+
+    # ---- n_chains=C: C independent chains on one batch of proposals
+    def _on_device(self, y, logq):
+        return (y.is_cuda and not getattr(self._model.prior, 'torch_rng', True)
+                and logq.dtype in (torch.float32, torch.float64))
+
+    def _stored_chains(self, n_chains):
+        """True if `_ref` holds the state of n_chains chains (else the chains start fresh, with the blocked sampler's message)."""
+        s = self._ref['sample']
+        shape = tuple(self._model.prior.shape)
+        want = shape if n_chains == 1 else (n_chains, *shape)
+        if s is not None and self._ref['logqp'] is not None and tuple(s.shape) == want:
+            return True
+        print("Starting from scratch & setting logqp_ref to None")
+        return False
+
+    def _ref_for_host_chain(self):
+        """Before the reference's single-chain code runs: a state left by a device call with n_chains=1 (0-dim device tensors)
+        becomes the floats that code keeps; the state of several chains cannot continue one chain and is dropped."""
+        ref = self._ref
+        if ref['sample'] is None:
+            return
+        if tuple(ref['sample'].shape) != tuple(self._model.prior.shape):
+            print("Starting from scratch & setting logqp_ref to None")
+            ref.update(sample=None, logq=None, logp=None, logqp=None)
+        elif torch.is_tensor(ref['logqp']):
+            ref.update(logq=ref['logq'].item(), logp=ref['logp'].item())
+            ref['logqp'] = ref['logq'] - ref['logp']
+
+    def _store_chains(self, n_chains, sample, logq, logp, logqp):
+        """`_ref` for the next call: (C, ...) tensors, or for one chain the reference's shapes (prior.shape and scalars)."""
+        if n_chains == 1:
+            sample, logq, logp, logqp = sample[0], logq[0], logp[0], logqp[0]
+        self._ref.update(sample=sample, logq=logq, logp=logp, logqp=logqp)
+
+    @torch.no_grad()
+    def _accept_reject_chains(self, y, logq, logp, n_chains, bookkeeping=False):
+        batch = y.shape[0]
+        if logp.dtype != logq.dtype:
+            logp = logp.to(logq.dtype)
+        cont = self._stored_chains(n_chains)
+        if self._on_device(y, logq):
+            y, logq, logp, flags, keep = self._chains_device(y, logq, logp, n_chains, cont)
+            accept = flags.cpu().numpy().astype(bool)             # the one device-to-host read of the call
+            keep = keep.cpu().numpy() if bookkeeping else None
+        else:
+            y, logq, logp, accept, keep = self._chains_host(y, logq, logp, n_chains, cont)
+        self.history.bookkeeping(accept_rate=np.mean(accept))
+        if bookkeeping:
+            shape = (batch,) if n_chains == 1 else (batch // n_chains, n_chains)
+            self.history.bookkeeping(accept_seq=accept.reshape(shape), accept_ind=keep.reshape(shape))
+        return y, logq, logp
+
+    def _chains_device(self, y, logq, logp, n_chains, cont):
+        """The two launches; nothing here copies to or from the host or synchronises when `_ref` holds device tensors."""
+        C, dev, dt = n_chains, y.device, logq.dtype
+        y, logq, logp = y.contiguous(), logq.contiguous(), logp.contiguous()
+        ref = self._ref
+        if cont:
+            state = lambda v, t: torch.as_tensor(v, dtype=t).to(dev).reshape(C).contiguous()
+            ref_s = ref['sample'].to(device=dev, dtype=y.dtype).contiguous()
+            ref_q, ref_p, ref_qp = state(ref['logq'], dt), state(ref['logp'], dt), state(ref['logqp'], torch.float64)
+        else:
+            ref_s = None
+            ref_q, ref_p = torch.empty(C, dtype=dt, device=dev), torch.empty(C, dtype=dt, device=dev)
+            ref_qp = torch.empty(C, dtype=torch.float64, device=dev)
+        flags = torch.empty(y.shape[0], dtype=torch.uint8, device=dev)
+        keep = torch.empty(y.shape[0], dtype=torch.int64, device=dev)
+        logq_sel, logp_sel = torch.empty_like(logq), torch.empty_like(logp)
+        _hip.metropolis_chains(logq, logp, ref_qp, ref_q, ref_p, flags, keep, logq_sel, logp_sel, C, fresh=not cont)
+        _hip.metropolis_select(y, ref_s, flags, keep, C)
+        self._store_chains(C, y[-C:].clone(), ref_q, ref_p, ref_qp)
+        return y, logq_sel, logp_sel, flags, keep
+
+    def _chains_host(self, y, logq, logp, n_chains, cont):
+        """The same rule on the host, vectorised over the chains: one np.random.rand(S, C), a loop over the S steps.  With
+        one chain it consumes np.random as the reference's code does and returns what that code returns."""
+        C, batch = n_chains, y.shape[0]
+        S = batch // C
+        d = seize(logq.double() - logp.double()).reshape(S, C)
+        logu = np.log(np.random.rand(S, C))
+        ref = self._ref
+        if cont:
+            cur = seize(torch.as_tensor(ref['logqp'], dtype=torch.float64)).reshape(C).copy()
+        accept = np.empty((S, C), dtype=bool)
+        keep = np.empty((S, C), dtype=np.int64)
+        last = np.arange(C)
+        for s in range(S):
+            ok = logu[s] < cur - d[s] if (cont or s > 0) else np.ones(C, dtype=bool)
+            cur = np.where(ok, d[s], cur) if (cont or s > 0) else d[s].copy()
+            last = np.where(ok, s * C + np.arange(C), last)
+            accept[s], keep[s] = ok, last
+        held = ~accept[0]                           # chains that reject their first proposal hold the stored state in row c
+        if held.any():
+            rows = torch.as_tensor(np.flatnonzero(held), device=y.device)
+            as_rows = lambda v, like: torch.as_tensor(v, dtype=like.dtype).to(like.device).reshape(C, *like.shape[1:])
+            y[rows] = as_rows(ref['sample'], y)[rows]
+            logq[rows] = as_rows(ref['logq'], logq)[rows]
+            logp[rows] = as_rows(ref['logp'], logp)[rows]
+        keep_t = torch.as_tensor(keep.ravel(), device=y.device)
+        y, logq, logp = (t.index_select(0, keep_t) for t in (y, logq, logp))
+        if C == 1:
+            lq, lp = logq[-1].item(), logp[-1].item()
+            self._ref.update(sample=y[-1].clone(), logq=lq, logp=lp, logqp=lq - lp)
+        else:
+            self._store_chains(C, y[-C:].clone(), logq[-C:].clone(), logp[-C:].clone(),
+                               torch.as_tensor(cur, dtype=torch.float64, device=y.device))
+        return y, logq, logp, accept.ravel(), keep.ravel()
 
     @torch.no_grad()
     def serial_sample_generator(self, n_samples, batch_size=16):
