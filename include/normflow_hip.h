@@ -335,6 +335,35 @@ int nf_pade_vjp(const void *x, const void *d0, const void *d1, const void *grad_
                 void *grad_x, double *grad_d, int64_t B, int64_t outer, int64_t C, int64_t inner, int kind,
                 int inverse, int per_site, void *workspace, size_t workspace_bytes, int dtype, void *stream);
 
+/* ---- the power-spectrum filter of FFTNet_ / PSDBlock_ in the separable real Hartley basis ----
+ * Replaces src/nn/scalar/fftflow_.py:98-176 (rfftn, multiply, irfftn) and, with the zero mode replaced, the mean-field
+ * split of src/nn/scalar/psd_.py:17-57 with ONE launch in which the sample never leaves LDS:
+ *   y_b = T D_b T x_b,   T = H_{N_1} x ... x H_{N_d},   H_N[k, n] = (cos(2 pi k n / N) + sin(2 pi k n / N)) / sqrt(N),
+ *   D_b(k) = w_half[k_1, .., min(k_d, N_d - k_d)], except D_b(0) -> the coefficient is SET to zero_new[b] when given.
+ * For a weight that is even in every k_mu separately (w = sigma(khat^2)^(-1/2) is) this equals
+ * irfftn(rfftn(x) w_half, s = lattice) for any axis lengths, odd ones included.
+ *   x, y       (B, V) fields, dense, of dtype (NF_F32 / NF_F64); y may be x
+ *   w_half     the weight on the rfftn grid, (N_1, .., N_d / 2 + 1), of dtype
+ *   zero_new   (B) or NULL;  zero_old (B) or NULL: receives (T x_b)(0) = sum(x_b) / sqrt(V)
+ *   lat, ndim  the ndim <= 4 axis lengths, each <= 64
+ * nf_spectral_supported(lat, ndim, dtype, for_vjp): 1 when the sample (for_vjp: the sample and its cotangent) and the
+ * Hartley matrices fit the 160 KiB of LDS -- every 1- to 4-D lattice up to 64 KiB per sample does --, else 0 with the
+ * reason in nf_last_error_string; launches nothing.
+ * nf_spectral_filter_vjp: T D T is symmetric, so gx_b = T D_b T g_b (mode 0 dropped when zero_replaced);
+ * gzero[b] = (T g_b)(0) ((B) or NULL); gw_half[k] = sum_b sum_{k' folding onto k} (T g_b)(k') (T x_b)(k') (entry 0 is 0
+ * when zero_replaced), summed per workgroup and then over the workgroups in a fixed order: no atomics, the same inputs
+ * give the same bits.  NOTE: entry by entry gw_half is not the gradient autograd derives through rfftn (the Hartley modes
+ * of a symmetry orbit (+-k_1, .., +-k_d) mix differently from the Fourier pairs); the sums over each orbit agree, so every
+ * parameter behind a weight that depends on k through khat^2 gets the same gradient.
+ * Scratch of the VJP: nf_spectral_workspace_bytes(lat, ndim, B, dtype) bytes. */
+int nf_spectral_supported(const int32_t *lat, int ndim, int dtype, int for_vjp);
+size_t nf_spectral_workspace_bytes(const int32_t *lat, int ndim, int64_t B, int dtype);
+int nf_spectral_filter(const void *x, const void *w_half, const void *zero_new, void *y, void *zero_old,
+                       const int32_t *lat, int ndim, int64_t B, int dtype, void *stream);
+int nf_spectral_filter_vjp(const void *x, const void *g, const void *w_half, int zero_replaced, void *gx, void *gw_half,
+                           void *gzero, void *workspace, size_t workspace_bytes, const int32_t *lat, int ndim, int64_t B,
+                           int dtype, void *stream);
+
 /* ---- K5: circular 'same' convolution + bias + activation on the f32 matrix cores ----
  * Replaces one Conv{1,2,3}d(padding='same', padding_mode='circular') / Conv4d layer of
  * ConvAct together with the activation that follows it (src/nn/scalar/modules.py:120-145,

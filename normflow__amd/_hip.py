@@ -67,6 +67,10 @@ PROTOTYPES = {
     "nf_pade_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
     "nf_pade": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _I, _P, _SZ, _I, _P]),
     "nf_pade_vjp": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _I, _P, _SZ, _I, _P]),
+    "nf_spectral_supported": (_I, [C.POINTER(C.c_int32), _I, _I, _I]),
+    "nf_spectral_workspace_bytes": (_SZ, [C.POINTER(C.c_int32), _I, _I64, _I]),
+    "nf_spectral_filter": (_I, [_P, _P, _P, _P, _P, C.POINTER(C.c_int32), _I, _I64, _I, _P]),
+    "nf_spectral_filter_vjp": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _SZ, C.POINTER(C.c_int32), _I, _I64, _I, _P]),
     "nf_conv_two_site": (_I, [_I, _I, _I, _I]),
     "nf_conv_cin_pad": (_I, [_I]),
     "nf_conv_ntiles": (_I, [_I]),
@@ -689,6 +693,87 @@ class PadeFn(torch.autograd.Function):
         gd = gd.to(x.dtype)
         return (gin, gd[0], gd[1] if d1 is not None else None, glogj if ctx.has_log0 else None,
                 None, None, None, None)
+
+
+# ========================================================================== spectral
+def spectral_supported(lat, dtype, for_vjp=False):
+    """nf_spectral_supported for a lattice and a torch dtype: (True, '') or (False, the library's reason)."""
+    code = {torch.float32: NF_F32, torch.float64: NF_F64}.get(dtype)
+    if code is None:
+        return False, f"the Hartley filter runs on float32 / float64 fields, got {dtype}"
+    lib = load()
+    if lib.nf_spectral_supported(_c_ints(list(lat)), len(lat), code, int(bool(for_vjp))):
+        return True, ""
+    return False, lib.nf_last_error_string().decode("utf-8", "replace")
+
+
+def spectral_require(x, lat, for_vjp=False):
+    """Raise NormflowHipError unless `x` is a field the Hartley filter takes: on the device, float32 / float64, trailing
+    axes == lat, and a lattice nf_spectral_supported accepts."""
+    _require_device(x)
+    if tuple(x.shape[-len(lat):]) != tuple(lat) or x.dim() < len(lat) + 1:
+        raise NormflowHipError(f"the Hartley filter of a {tuple(lat)} lattice got a field of shape {tuple(x.shape)}")
+    ok, why = spectral_supported(lat, x.dtype, for_vjp)
+    if not ok:
+        raise NormflowHipError(f"transform='hartley' cannot take this field: {why}")
+
+
+class SpectralFilterFn(torch.autograd.Function):
+    """y_b = T D_b T x_b in the separable Hartley basis T (nf_spectral_filter): irfftn(rfftn(x) * w_half, s=lattice) for a
+    weight that is even in every k_mu, in one launch with the sample resident in LDS.
+
+    x: (B, *lattice); w_half: the weight on the rfftn grid (*lattice[:-1], N/2 + 1); zero_new: None or (B,), the value
+    the zero-mode coefficient sum(x_b) / sqrt(V) is replaced by.  Differentiable in all three.  The cotangent of w_half
+    is the Hartley-basis one: summed over each symmetry orbit (+-k_1, .., +-k_d) it equals autograd's through rfftn, entry
+    by entry it does not (d >= 2) -- exact for every parameter behind a weight that depends on k through khat^2."""
+
+    @staticmethod
+    def forward(ctx, x, w_half, zero_new):
+        lat = tuple(x.shape[1:])
+        spectral_require(x, lat)
+        _require_device(w_half, zero_new)
+        B = x.shape[0]
+        if tuple(w_half.shape) != lat[:-1] + (lat[-1] // 2 + 1,):
+            raise ValueError(f"w_half must be on the rfftn grid of {lat}, got {tuple(w_half.shape)}")
+        if zero_new is not None and zero_new.numel() != B:
+            raise ValueError(f"zero_new must hold one value per sample ({B}), got {tuple(zero_new.shape)}")
+        x = x.contiguous()
+        w_half = w_half.to(x.dtype).contiguous()
+        zero_new = None if zero_new is None else zero_new.to(x.dtype).contiguous()
+        y = torch.empty_like(x)
+        _check(load().nf_spectral_filter(_ptr(x), _ptr(w_half), _ptr(zero_new), _ptr(y), None, _c_ints(list(lat)),
+                                         len(lat), B, _dtype_code(x), _stream()), "nf_spectral_filter")
+        ctx.save_for_backward(x, w_half)
+        ctx.replaced = zero_new is not None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w_half = ctx.saved_tensors
+        lat, B = tuple(x.shape[1:]), x.shape[0]
+        spectral_require(x, lat, for_vjp=True)
+        gy = gy.contiguous()
+        gx = torch.empty_like(x)
+        gw = torch.empty_like(w_half)
+        gzero = torch.empty(B, dtype=x.dtype, device=x.device) if ctx.replaced else None
+        lat_c = _c_ints(list(lat))
+        need = load().nf_spectral_workspace_bytes(lat_c, len(lat), B, _dtype_code(x))
+        ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=x.device)
+        _check(load().nf_spectral_filter_vjp(_ptr(x), _ptr(gy), _ptr(w_half), int(ctx.replaced), _ptr(gx), _ptr(gw),
+                                             _ptr(gzero), _ptr(ws), ws.numel(), lat_c, len(lat), B, _dtype_code(x),
+                                             _stream()), "nf_spectral_filter_vjp")
+        return gx, gw, gzero
+
+
+def spectral_filter(x, w_half, zero_new=None):
+    """SpectralFilterFn on a (..., *lattice) field (leading axes flattened into the batch), refusing up front a field
+    whose backward pass would not fit."""
+    lat = tuple(w_half.shape[:-1]) + (x.shape[-1],)
+    grads = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w_half, zero_new))
+    spectral_require(x, lat, for_vjp=grads)
+    y = SpectralFilterFn.apply(x.reshape((-1,) + lat), w_half.to(x.dtype), zero_new)
+    return y.reshape(x.shape)
 
 
 # ============================================================================== conv

@@ -10,7 +10,15 @@ Where the work runs: the FFTs are torch.fft (rocFFT) -- plumbing, as SURVEY sect
 and the learned curves are the package's own HIP paths: the inverse power spectrum is ONE shared
 rational-quadratic spline evaluated on the k^2 grid (SplineNet -> nf_distconv, spline stage only)
 and the mean-field map is a DistConvertor_ (fused expit-spline-logit kernel).  Both are O(V) or
-O(B); nothing here is on the timed hot path.
+O(B); at 32^4 nothing here is on the timed hot path.
+
+On the small lattices it is: there the coupling stack behind this block is launch-bound and the chain of stock ops above
+(mean, subtract, rfftn, multiply, irfftn, add) costs as much as the stack.  `transform='hartley'` (opt-in; 'fft' stays the
+default) runs the same filter in the separable real Hartley basis, T diag(w) T x, as ONE HIP kernel with the sample
+resident in LDS (nf_spectral.hip), and PSDBlock_ as that kernel with the zero-mode coefficient replaced by what the
+mean-field map returns.  The weight w is even in every k_mu, so both bases diagonalise the filter and the outputs agree;
+the cotangent of w agrees orbit by orbit (not entry by entry), which is all the parameters behind w can see
+(DESIGN.md, "Hartley path").
 """
 import copy
 import math
@@ -18,6 +26,7 @@ import math
 import torch
 
 from .._core import Module_
+from ... import _hip
 from .modules import SplineNet
 from .modules_ import DistConvertor_
 
@@ -54,8 +63,8 @@ class IPSD(SplineNet):
         y = torch.exp(self.logy)
         sigma = y[0] + y[1] * super().forward(x)
         if self.ignore_zeromode:          # the zero mode gets weight 1: no contribution to log J
-            hole = torch.zeros_like(sigma)
-            hole[(0,) * sigma.dim()] = 1
+            hole = torch.zeros(sigma.shape, dtype=sigma.dtype, device=sigma.device)
+            hole.view(-1)[:1].fill_(1)    # a fill kernel, not an indexed host-to-device copy: capturable into a HIP graph
             sigma = torch.where(hole.bool(), torch.ones_like(sigma), sigma)
         return sigma
 
@@ -79,8 +88,13 @@ class FFTNet_(Module_):
     """y = irfftn(rfftn(x) * w), w = sigma(k^2)^(-1/2); log J = sum over ALL modes of log w, i.e. twice the
     sum over the rfftn half minus its first and last columns (fftflow_.py:98-176)."""
 
-    def __init__(self, lat_shape, ipsd_net, ignore_zeromode=False, label='fftnet_'):
+    TRANSFORMS = ('fft', 'hartley')
+
+    def __init__(self, lat_shape, ipsd_net, ignore_zeromode=False, label='fftnet_', transform='fft'):
         super().__init__(label=label)
+        if transform not in self.TRANSFORMS:
+            raise ValueError(f"transform must be one of {self.TRANSFORMS}, got {transform!r}")
+        self.transform = transform          # how the filter is computed; not a parameter, not in state_dict
         self.lat_shape = tuple(lat_shape)
         self.lat_ndim = len(self.lat_shape)
         self.ipsd_net = ipsd_net
@@ -98,14 +112,24 @@ class FFTNet_(Module_):
         return torch.rsqrt(self.ipsd)
 
     def _filter(self, x, w):
+        if self.transform == 'hartley':
+            return _hip.spectral_filter(x, w)
         spec = torch.fft.rfftn(x, dim=self.rfft_dim)
         return torch.fft.irfftn(spec * w, s=self.lat_shape, dim=self.rfft_dim)
 
+    def _require(self, x):
+        """The Hartley path refuses what it cannot take (CPU tensors, fp16 fields, lattices beyond LDS) before any
+        work is done; there is no silent change of path."""
+        if self.transform == 'hartley':
+            _hip.spectral_require(x, self.lat_shape)
+
     def forward(self, x, log0=0):
+        self._require(x)
         w = self._weights()
         return self._filter(x, w), log0 + self.log_jacobian(w)
 
     def backward(self, x, log0=0):
+        self._require(x)
         w = self._weights()
         return self._filter(x, 1 / w), log0 - self.log_jacobian(w)
 
@@ -126,11 +150,11 @@ class FFTNet_(Module_):
     def transfer(self, scale_factor=1, shape=None, **extra):
         shape = self.lat_shape if shape is None else shape
         return self.__class__(shape, ipsd_net=self.ipsd_net.transfer(scale_factor=scale_factor, ndim=self.lat_ndim),
-                              ignore_zeromode=self.ignore_zeromode)
+                              ignore_zeromode=self.ignore_zeromode, transform=self.transform)
 
     @staticmethod
     def build(lat_shape, knots_len=10, eff_mass2=1, eff_kappa=1, a=1, ignore_zeromode=False, nozeromode=False,
-              **ipsd_kwargs):
+              transform='fft', **ipsd_kwargs):
         if nozeromode and not ignore_zeromode:
             raise NotImplementedError("the obsolete `nozeromode` variant is not provided; use ignore_zeromode=True")
         if knots_len < 2:                 # a 2-knot smooth spline is the identity: free-theory spectrum
@@ -139,7 +163,7 @@ class FFTNet_(Module_):
         k2max = float(lattice_k2(lat_shape).max())
         logy = _rescaled_logy(torch.tensor([math.log(eff_mass2), math.log(eff_kappa * k2max)]), a, len(lat_shape))
         return FFTNet_(lat_shape, IPSD(knots_len, logy=logy, ignore_zeromode=ignore_zeromode, **ipsd_kwargs),
-                       ignore_zeromode=ignore_zeromode)
+                       ignore_zeromode=ignore_zeromode, transform=transform)
 
 
 class MeanFieldNet_(Module_):
@@ -196,15 +220,44 @@ class PSDBlock_(Module_):
         ff = self.fftnet_.backward if inverse else self.fftnet_.forward
         return mean, mf(mean, rvol=rvol), ff(x - mean)
 
+    def _fused(self):
+        return getattr(self.fftnet_, 'transform', 'fft') == 'hartley' and isinstance(self.mfnet_, MeanFieldNet_)
+
+    def _hartley(self, x, inverse):
+        """The block as ONE filter launch: c0 = sum(x) / sqrt(V) is the zero-mode coefficient of T x, the mean-field map
+        acts on it (fused K4 kernel, its own autograd), and the filter sets the coefficient to the result instead of
+        multiplying it by w(0).  12 B/site: x is read for c0 and for the filter, y is written once.  Returns
+        (mean, y_mf, lj_mf, y, lj_fft) with the shapes of _parts."""
+        ff = self.fftnet_
+        ff._require(x)
+        dims = list(range(1, x.dim()))
+        rvol = math.prod(x.shape[1:]) ** 0.5
+        c0 = x.sum(dim=dims, keepdim=True) / rvol
+        dc_ = self.mfnet_.dc_
+        z, lj_mf = (dc_.backward if inverse else dc_.forward)(c0, 0)
+        w = ff._weights()
+        lj_fft = ff.log_jacobian(w)
+        y = _hip.spectral_filter(x, 1 / w if inverse else w, z.reshape(-1))
+        return c0 / rvol, z / rvol, lj_mf, y, (-lj_fft if inverse else lj_fft)
+
     def forward(self, x, log0=0):
+        if self._fused():
+            _, _, lj_mf, y, lj_fft = self._hartley(x, False)
+            return y, log0 + lj_mf + lj_fft
         _, (y_mf, lj_mf), (y_fft, lj_fft) = self._parts(x, False)
         return y_mf + y_fft, log0 + lj_mf + lj_fft
 
     def backward(self, x, log0=0):
+        if self._fused():
+            _, _, lj_mf, y, lj_fft = self._hartley(x, True)
+            return y, log0 + lj_mf + lj_fft
         _, (y_mf, lj_mf), (y_fft, lj_fft) = self._parts(x, True)
         return y_mf + y_fft, log0 + lj_mf + lj_fft
 
     def _hack(self, x, log0=0):
+        if self._fused():
+            mean, y_mf, lj_mf, y, lj_fft = self._hartley(x, False)
+            return [(mean, log0), (y_mf, lj_mf), (y - y_mf, lj_fft), (y, log0 + lj_mf + lj_fft)]
         mean, (y_mf, lj_mf), (y_fft, lj_fft) = self._parts(x, False)
         return [(mean, log0), (y_mf, lj_mf), (y_fft, lj_fft), (y_mf + y_fft, log0 + lj_mf + lj_fft)]
 
