@@ -3,8 +3,7 @@
 //   fwd  y = t + x e^{-|s|},  logJ -= sum|s|      inv  x = (y - t) e^{|s|},  logJ += sum|s|
 // with t, s read only at active sites (the reference's two `purify` passes) and the
 // per-sample sum (src/nn/_core.py:38-42) done by wave shuffles + one double per workgroup.
-#include <hip/hip_fp16.h>
-#include "nf_internal.h"
+#include "nf_rqs_core.h"   // Pair2
 
 namespace nf {
 
@@ -23,23 +22,19 @@ struct AffArgs {
   int n_ch, iters;
 };
 
-template <typename T> struct Pair2a;
-template <> struct Pair2a<float> { typedef float2 type; };
-template <> struct Pair2a<double> { typedef double2 type; };
-
 // Storage adaptors: T = arithmetic type; SX = storage of the field (x, y), SP = storage of the parameters.  SX = SP = T for
 // fp32 / fp64; SX = __half (and SP = __half or float) for BASELINE config 5's fp16 storage with fp32 arithmetic and log-det.
 template <typename T, typename S> struct Store {
   static __device__ __forceinline__ T ld(const S *p, int64_t i) { return T(p[i]); }
   static __device__ __forceinline__ void ld2(const S *p, int64_t u, T &a, T &b) {
-    const typename Pair2a<T>::type v = reinterpret_cast<const typename Pair2a<T>::type *>(p)[u];
+    const typename Pair2<T>::type v = reinterpret_cast<const typename Pair2<T>::type *>(p)[u];
     a = v.x; b = v.y;
   }
   static __device__ __forceinline__ void st(S *p, int64_t i, T v) { p[i] = S(v); }
   static __device__ __forceinline__ void st2(S *p, int64_t u, T a, T b) {
-    typename Pair2a<T>::type o;
+    typename Pair2<T>::type o;
     o.x = a; o.y = b;
-    reinterpret_cast<typename Pair2a<T>::type *>(p)[u] = o;
+    reinterpret_cast<typename Pair2<T>::type *>(p)[u] = o;
   }
 };
 template <> struct Store<float, __half> {
@@ -99,7 +94,7 @@ __global__ __launch_bounds__(kBlock) void affine_kernel(AffArgs A) {
 
 template <typename T, bool INV, bool PAIR>
 __global__ __launch_bounds__(kBlock) void affine_vjp_kernel(AffArgs A) {
-  typedef typename Pair2a<T>::type P2;
+  typedef typename Pair2<T>::type P2;
   const int b = blockIdx.y;
   const T *__restrict__ vin = static_cast<const T *>(A.v) + int64_t(b) * A.V;
   const T *__restrict__ par = static_cast<const T *>(A.params) + int64_t(b) * A.n_ch * A.Vp;

@@ -68,9 +68,6 @@ static_assert(lds_bytes<true>() <= 160 * 1024, "two item images and the logit sc
 #ifndef NF_H_DMA_EARLY
 #define NF_H_DMA_EARLY NROW
 #endif
-#ifndef NF_H_EPI
-#define NF_H_EPI 1          // 1: the mover's spline pass with the bin fetched by index (rqs_site_pt), 0: the generic rqs_site
-#endif
 #if !defined(NF_DIAG) || !defined(NF_H_ABL)
 #undef NF_H_ABL
 #define NF_H_ABL 0      // timing ablations of the compute waves (diagnostic builds only, make DIAG=1 with -DNF_H_ABL=..): 1 no fragment reads, 2 no reduction
@@ -87,24 +84,19 @@ __device__ __forceinline__ void static_for(F &&f) {
 }
 
 // The mover's spline pass: rqs_site (nf_rqs_core.h) for m = 16 free knots with the logits of the site in an LDS column
-// (`col[c * PTS]`, c = 0..45), restated so that the bin is FOUND by the scan and FETCHED by its index: the scan carries the
-// two running knots and a counter (2 FMA-able adds, 1 compare, 2 selects, 1 add per knot) instead of selecting seven values
-// per knot, and the bin's width / height numerators and the two derivative logits are read back from the column at
-// [j] -- 34 LDS reads and ~300 vector instructions per site where the generic form takes 46 and ~450.  Same operations
-// in the same order wherever a value is formed (running sums, widths as numerator x scale); two roundings differ from the
-// generic form: the softmax argument is one FMA, and quotients sharing a divisor share its reciprocal (both ~1e-7
-// relative; the parity tests hold the fused layer to the unfused one and to the oracle at the same bounds as before).
-// The mover's two passes per item are what it has to hide in an MFMA phase.
+// (`col[c * PTS]`, c = 0..45).  Frame and segment are the shared ones (with the shared-reciprocal rounding); its own are
+// the bin FOUND by the scan and FETCHED by its index -- the scan carries the two running knots and a counter instead of
+// selecting seven values per knot, and the bin's numerators and derivative logits are read back from the column at [j]:
+// 34 LDS reads and ~300 vector instructions per site where the generic form takes 46 and ~450 -- and the softmax
+// argument as ONE FMA (~1e-7 relative; the parity tests hold the fused layer to the unfused one and to the oracle at the
+// same bounds).  The mover's two passes per item are what it has to hide in an MFMA phase.
 template <bool INV>
 __device__ __forceinline__ void rqs_site_pt(const lds_f *col, const RqsParams &A, float v, float &val, float &logd) {
   using namespace h;
   constexpr int NB = M - 1, OX = 0, OY = NB, OD = 2 * NB;
-  const float xlo = float(A.xlo), W = float(A.xhi) - float(A.xlo), ylo = float(A.ylo), H = float(A.yhi) - float(A.ylo);
-  const float in_lo = INV ? ylo : xlo, in_hi = INV ? ylo + H : xlo + W;
-  const float out_lo = INV ? xlo : ylo, out_hi = INV ? xlo + W : ylo + H;
-  const bool refl_l = (A.el == NF_EXTRAP_ANTI) && (v < in_lo);
-  const bool refl_r = (A.er == NF_EXTRAP_ANTI) && (v > in_hi);
-  v = refl_l ? 2.f * in_lo - v : (refl_r ? 2.f * in_hi - v : v);
+  const RqFrame<float, INV> F(A, v);
+  v = F.reflected(v);
+  const float xlo = F.xlo, W = F.W, ylo = F.ylo, H = F.H;
   float a[2 * NB];
 #pragma unroll
   for (int c = 0; c < 2 * NB; ++c) a[c] = col[c * PTS];
@@ -141,45 +133,11 @@ __device__ __forceinline__ void rqs_site_pt(const lds_f *col, const RqsParams &A
     cx = cx + a[OX + k] * wx;
     cy = cy + a[OY + k] * wy;
   }
-  const float xe = cx, ye = cy;      // last knot as accumulated (the reference's cumsum end)
   const lds_f *cj = col + j * PTS;
   const float bw = Num<float>::exp2(__builtin_fmaf(cj[OX * PTS], Num<float>::kLog2e, am2)) * wx;
   const float bh = Num<float>::exp2(__builtin_fmaf(cj[OY * PTS], Num<float>::kLog2e, bm2)) * wy;
   const float c0 = cj[OD * PTS], c1 = cj[(OD + 1) * PTS];
-  const bool tail_l = (A.el == NF_EXTRAP_LINEAR) && !(in_lo < v);
-  const bool tail_r = (A.er == NF_EXTRAP_LINEAR) && ((INV ? ye : xe) < v);
-  const float d0 = softplus2(c0), d1 = softplus2(c1);
-  const float ibw = 1.f / bw;         // one correctly rounded reciprocal for the slope and for theta, one for the two
-  const float sl = bh * ibw;          // quotients by den (the generic form divides four times: ~10 instructions each)
-  const float curv = d0 + d1 - 2.f * sl;
-  float th, g;
-  if (!INV) {
-    th = (v - x0) * ibw;
-    const float t1 = th * (1.f - th);
-    const float den = sl + curv * t1, iden = 1.f / den;
-    val = y0 + bh * (sl * th * th + d0 * t1) * iden;
-    const float P = d1 * th * th + 2.f * sl * t1 + d0 * (1.f - th) * (1.f - th);
-    g = sl * sl * P * (iden * iden);
-    val = tail_l ? ylo + d0 * (v - xlo) : (tail_r ? ye + d1 * (v - xe) : val);
-    g = tail_l ? d0 : (tail_r ? d1 : g);
-    logd = nf_log(g);
-  } else {
-    const float eta = (v - y0) / bh;
-    const float a2 = -curv * eta + d0 - sl;
-    const float bb = a2 + sl;
-    const float a0 = sl * eta;
-    const float disc = Num<float>::sqrt(Num<float>::max(bb * bb - 4.f * a0 * a2, 0.f));
-    th = (bb >= 0.f) ? 2.f * a0 / (bb + disc) : (bb - disc) / (2.f * a2);
-    const float t1 = th * (1.f - th);
-    const float den = sl + curv * t1;
-    const float P = d1 * th * th + 2.f * sl * t1 + d0 * (1.f - th) * (1.f - th);
-    g = sl * sl * P / (den * den);
-    val = x0 + bw * th;
-    val = tail_l ? xlo + (v - ylo) / d0 : (tail_r ? xe + (v - ye) / d1 : val);
-    g = tail_l ? d0 : (tail_r ? d1 : g);
-    logd = -nf_log(g);
-  }
-  val = refl_l ? 2.f * out_lo - val : (refl_r ? 2.f * out_hi - val : val);
+  F.template eval<true>(A, Site<float>{x0, y0, bw, bh, c0, c1, cx, cy, j}, v, val, logd);   // (cx, cy): the last knot as accumulated
 }
 
 template <int FUSE, bool SEGM>
@@ -700,7 +658,6 @@ __global__ __launch_bounds__(256, 1) void conv_h_kernel(ConvArgs A) {
       const int64_t pair = pair_of(b, o, pass, pok);
       const float2 xv = xpre[pass];
       float val, logd;
-#if NF_H_EPI
       if (A.P.m == M) {
         rqs_site_pt<FUSE == 2>(ptl + u, A.P, offp ? xv.y : xv.x, val, logd);
       } else {
@@ -709,12 +666,6 @@ __global__ __launch_bounds__(256, 1) void conv_h_kernel(ConvArgs A) {
         LdsCol<float> colm{reinterpret_cast<float *>(const_cast<unsigned char *>(smem_h + 2 * ITEM)) + u, PTS};
         rqs_site<float, 0, FUSE == 2>(colm, A.P, offp ? xv.y : xv.x, val, logd);
       }
-#else
-      RegCol<float, C> a;
-#pragma unroll
-      for (int c = 0; c < C; ++c) a[c] = ptl[c * PTS + u];
-      rqs_site<float, M, FUSE == 2>(a, A.P, offp ? xv.y : xv.x, val, logd);
-#endif
       float2 ov;
       ov.x = offp ? 0.f : val;
       ov.y = offp ? val : 0.f;

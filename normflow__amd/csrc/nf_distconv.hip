@@ -4,8 +4,8 @@
 // The K (already boundary-augmented) knots are staged in LDS once per workgroup;
 // every lane binary-searches them (spline.py:154-172: left-bisect + clamp == number
 // of interior knots strictly below the value), evaluates / inverts the segment
-// (spline.py:185-220 / 222-287, stable root) and the per-sample log-det is reduced by
-// wave shuffles -> LDS -> one double per workgroup -> finalize kernel.
+// (rq_at_x / rq_at_y, rq_deriv, rq_y / rq_x of nf_rqs_core.h) and the per-sample log-det is
+// reduced by wave shuffles -> LDS -> one double per workgroup -> finalize kernel.
 //
 // Restates src/nn/scalar/modules_.py:93-102 (Expit_: y = 1/(1+e^-x), logJ = sum(-x +
 // 2 log y)), :105-114 (Logit_: y = log(x/(1-x)), logJ = -sum log(x(1-x))), :277-302
@@ -18,7 +18,7 @@
 // (src/nn/_core.py:19,38-42) on the three leaves, and the reference's
 // InvisibilityMaskWrapperModule_ around one of them (src/nn/_core.py:196-231: split ->
 // net_ on the visible part -> purify(channel=0) -> sum_density -> cat) as ONE masked pass.
-#include "nf_internal.h"
+#include "nf_rqs_core.h"
 
 namespace nf {
 
@@ -58,6 +58,9 @@ __device__ __forceinline__ Seg<T> find_segment(const T *__restrict__ key, const 
   s.d0 = kd[lo]; s.d1 = kd[lo + 1];
   return s;
 }
+template <typename T> __device__ __forceinline__ RqSeg<T> rq_seg(const Seg<T> &s) {   // knots -> left knot, width, height
+  return RqSeg<T>{s.x0, s.y0, s.x1 - s.x0, s.y1 - s.y0, s.d0, s.d1};
+}
 
 // -log(1 + e^-a) for a >= 0, accurate for large a
 template <typename T> __device__ __forceinline__ T neg_log1p_exp_neg(T e) {
@@ -83,7 +86,7 @@ __global__ __launch_bounds__(kBlock) void distconv_kernel(DcArgs A) {
   for (int it = 0; it < A.iters; ++it) {
     const int64_t i = base + int64_t(it) * kBlock;
     if (i >= A.V) break;
-    T u = vin[i], lg = T(0);
+    T lg = T(0), u = vin[i];
     if constexpr (MASKED) {
       if (!A.mask[i]) {
         out[i] = u;
@@ -101,27 +104,14 @@ __global__ __launch_bounds__(kBlock) void distconv_kernel(DcArgs A) {
       u = u > T(0) ? T(1) - p : p;
     }
     if (A.spline) {
-      const Seg<T> s = find_segment<T>(INV ? ky : kx, kx, ky, kd, A.K, u);
-      const T bw = s.x1 - s.x0, bh = s.y1 - s.y0;
-      const T sl = bh / bw, curv = s.d0 + s.d1 - T(2) * sl;
-      T th;
+      const RqSeg<T> s = rq_seg(find_segment<T>(INV ? ky : kx, kx, ky, kd, A.K, u));
+      const RqAt<T> a = INV ? rq_at_y<T, false>(s, u) : rq_at_x<T, false>(s, u);
+      const T lgs = nf_log(rq_deriv<T, false>(s, a));
       if (!INV) {
-        th = (u - s.x0) / bw;
-      } else {
-        const T eta = (u - s.y0) / bh;
-        const T a2 = -curv * eta + s.d0 - sl, bb = a2 + sl, a0 = sl * eta;
-        const T disc = Num<T>::sqrt(Num<T>::max(bb * bb - T(4) * a0 * a2, T(0)));
-        th = (bb >= T(0)) ? T(2) * a0 / (bb + disc) : (bb - disc) / (T(2) * a2);
-      }
-      const T om = T(1) - th, t1 = th * om;
-      const T den = sl + curv * t1;
-      const T P = s.d1 * th * th + T(2) * sl * t1 + s.d0 * om * om;
-      const T lgs = nf_log(sl * sl * P / (den * den));
-      if (!INV) {
-        u = s.y0 + bh * (sl * th * th + s.d0 * t1) / den;
+        u = rq_y<T, false>(s, a);
         lg += lgs;
       } else {
-        u = s.x0 + bw * th;
+        u = rq_x(s, a);
         lg -= lgs;
       }
     }
@@ -146,6 +136,9 @@ __global__ __launch_bounds__(kBlock) void distconv_kernel(DcArgs A) {
 // VJP.  `v` is the x-side end point of the chain (forward input / inverse output), so
 // the chain is always re-run in its forward direction; no root is recomputed.
 // SITES: grad_logj is per site, (B, V).  MASKED: inactive sites pass grad_out through.
+// The point and the cotangent block are stated here as in rq_point / rq_cotangents (nf_rqs_core.h), not through them: on
+// them the fp64 instances give the same bits, but the fp32 ones are packed differently into two-wide operations and
+// grad_in of the chains with a logit stage moves in its last bits.
 template <typename T, bool INV, bool SITES = false, bool MASKED = false>
 __global__ __launch_bounds__(kBlock) void distconv_vjp_kernel(DcArgs A, int64_t B) {
   extern __shared__ __align__(16) unsigned char smem_raw[];

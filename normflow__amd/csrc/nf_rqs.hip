@@ -188,8 +188,8 @@ __global__ __launch_bounds__(kBlock) void rqs_vjp_kernel(RqsArgs A) {
 
 // The knots a site's logits stand for -- the tensors `RQSplineCoupling_.make_spline` hands to `RQSpline`
 // (couplings_.py:211-262), before the boundary augmentation: out[b][0..m) = knots_x, [m..2m) = knots_y, [2m..3m) = knots_d,
-// each a plane of V sites.  Same arithmetic, in the same order, as scan_bins above: these ARE the knots the coupling
-// kernels evaluate.  An inspection path (three passes over the logits, no registers arrays): not tuned.
+// each a plane of V sites.  The terms come from scan_bins' own softmax_term and are accumulated in its order: these ARE the
+// knots the coupling kernels evaluate.  An inspection path (three passes over the logits, no registers arrays): not tuned.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void rqs_knots_kernel(RqsArgs A) {
   const int b = blockIdx.y;
@@ -212,12 +212,12 @@ __global__ __launch_bounds__(kBlock) void rqs_knots_kernel(RqsArgs A) {
     T amax = a[0];
     for (int k = 1; k < nb; ++k) amax = Num<T>::max(amax, a[int64_t(k) * A.V]);
     T sum = T(0);
-    for (int k = 0; k < nb; ++k) sum += Num<T>::exp2((a[int64_t(k) * A.V] - amax) * Num<T>::kLog2e);
+    for (int k = 0; k < nb; ++k) sum += softmax_term(a[int64_t(k) * A.V], amax);
     const T w = width / sum;
     T c = lo;
     o[0] = c;
     for (int k = 0; k < nb; ++k) {
-      c += Num<T>::exp2((a[int64_t(k) * A.V] - amax) * Num<T>::kLog2e) * w;
+      c += softmax_term(a[int64_t(k) * A.V], amax) * w;
       o[int64_t(k + 1) * A.V] = c;
     }
   }

@@ -1,14 +1,15 @@
 // nf_spline.hip -- a rational-quadratic spline given by EXPLICIT knot tensors, evaluated at every site:
 // the reference's generic spline object `RQSpline(knots_x, knots_y, knots_d)` = `Pade22Spline`
-// (src/lib/spline/spline.py:39-68 constructor, :87-123 forward / backward, :154-172 searchsorted + clamp,
-// :185-220 segment function, :222-287 inverse).  The coupling kernels (nf_rqs.hip) never materialise knots; this
-// kernel is for callers that hold them (a spline built by hand, or inspected and modified after make_spline).
+// (src/lib/spline/spline.py:39-68 constructor, :87-123 forward / backward, :154-172 searchsorted + clamp; the segment
+// and its inverse are those of nf_rqs_core.h, the ones the coupling kernels and K4 evaluate).  The coupling kernels
+// (nf_rqs.hip) never materialise knots; this kernel is for callers that hold them (a spline built by hand, or inspected
+// and modified after make_spline).
 //
 // One lane = one site.  Knot tensors are (B, K, V) planes (lane-coalesced reads along V) or shared 1-D vectors of K
 // entries (the reference's 1-D knots_x / knots_y case, spline.py:191-194).  The knots are taken as given -- already
 // augmented for extrapolation (the host mirrors AugmentKnots as a layout operation) -- and values outside the knot
 // range reuse the first / last segment, as the reference's clamp does (:171-172).  HBM-bound: 3K reads per site.
-#include "nf_internal.h"
+#include "nf_rqs_core.h"
 
 namespace nf {
 
@@ -39,27 +40,11 @@ template <typename T> __global__ __launch_bounds__(kBlock) void spline_eval_kern
     x0 = x1; y0 = y1; d0 = d1;
     x1 = kx[ox + (k + 1) * tx]; y1 = ky[oy + (k + 1) * ty]; d1 = kd[od + (k + 1) * td];
   }
-  const T bw = x1 - x0, bh = y1 - y0;
-  const T sl = bh / bw;
-  const T curv = d0 + d1 - T(2) * sl;
-  T th, res;
-  if (!A.inverse) {
-    th = (val - x0) / bw;
-    const T t1 = th * (T(1) - th);
-    res = y0 + bh * th * (sl * th + d0 * (T(1) - th)) / (sl + curv * t1);
-  } else {
-    const T eta = (val - y0) / bh;
-    const T a2 = -curv * eta + d0 - sl;
-    const T bb = a2 + sl;
-    const T a0 = sl * eta;
-    const T disc = Num<T>::sqrt(Num<T>::max(bb * bb - T(4) * a0 * a2, T(0)));
-    th = (bb >= T(0)) ? T(2) * a0 / (bb + disc) : (bb - disc) / (T(2) * a2);   // neither branch cancels
-    res = x0 + bw * th;
-  }
-  static_cast<T *>(A.out)[b * V + site] = res;
+  const RqSeg<T> s{x0, y0, x1 - x0, y1 - y0, d0, d1};
+  const RqAt<T> a = A.inverse ? rq_at_y<T, false>(s, val) : rq_at_x<T, false>(s, val);
+  static_cast<T *>(A.out)[b * V + site] = A.inverse ? rq_x(s, a) : rq_y<T, false>(s, a);
   if (A.deriv) {
-    const T den = sl + curv * th * (T(1) - th);
-    const T g = sl * sl * (d0 + T(2) * (sl - d0) * th + curv * th * th) / (den * den);
+    const T g = rq_deriv<T, false>(s, a);
     static_cast<T *>(A.deriv)[b * V + site] = A.inverse ? T(1) / g : g;
   }
 }

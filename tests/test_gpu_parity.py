@@ -1904,6 +1904,86 @@ def test_rqspline_from_explicit_knots_vs_oracle(layout, dtype):
         assert rel(sp.knots_d, want) <= tol
 
 
+_SEG_CASES = {}
+
+
+def _shared_segment_case(K):
+    """K shared knots on (0, 1) and (3, 257) points for each direction: drawn inside the knot range, with every interior
+    knot itself in front of each row (a value ON knot k belongs to bin k - 1: "strictly below").  Everything is rounded
+    through float32, so both precisions see the same numbers.  The fp64 oracle gives the expected values once per K, and is
+    used alone to check that no denominator of the segment or of its inverse root comes near zero at these points."""
+    if K in _SEG_CASES:
+        return _SEG_CASES[K]
+    g = torch.Generator(device='cpu').manual_seed(500 + K)
+    r32 = lambda t: t.float().double()
+    with torch.device("cpu"):
+        cum = lambda: torch.cat((torch.zeros(1, dtype=torch.float64),
+                                 torch.cumsum(0.5 + torch.rand(K - 1, generator=g, dtype=torch.float64), 0)))
+        cx, cy = cum(), cum()
+        kx, ky = r32(0.05 + 0.9 * cx / cx[-1]), r32(0.08 + 0.85 * cy / cy[-1])
+        kd = r32(0.5 + 1.5 * torch.rand(K, generator=g, dtype=torch.float64))
+        pts = {}
+        for name, kn in (("x", kx), ("y", ky)):
+            u = torch.rand((3, 257), generator=g, dtype=torch.float64)
+            p = r32(kn[0] + (kn[-1] - kn[0]) * (0.001 + 0.998 * u))
+            p[:, :K - 2] = kn[1:K - 1]
+            assert bool(((p > kn[0]) & (p < kn[-1])).all())
+            pts[name] = p
+        col = lambda t: t.reshape(-1, 1)
+        flat = lambda t: t.reshape(1, -1)
+        # denominators, from the oracle's own pieces: bin width and height, den on both sides, the root's divisor
+        for name, kn in (("x", kx), ("y", ky)):
+            v = flat(pts[name])
+            seg = O._segment_index(col(kn), v, 0)
+            x0, x1, y0, y1, d0, d1 = O._gather6(*(col(k).expand(K, v.shape[1]) for k in (kx, ky, kd)), seg, 0)
+            sl, curv = O._slope_terms(x0, x1, y0, y1, d0, d1)
+            assert float((x1 - x0).min()) > 1e-2 and float((y1 - y0).min()) > 1e-2
+            if name == "x":
+                th = (v - x0) / (x1 - x0)
+            else:
+                eta = (v - y0) / (y1 - y0)
+                a2, a0 = -curv * eta + d0 - sl, sl * eta
+                bb = a2 + sl
+                disc = torch.sqrt(bb * bb - 4 * a0 * a2)
+                div = torch.where(bb >= 0, bb + disc, 2 * a2)
+                assert float(div.abs().min()) > 0.1
+                th = torch.where(bb >= 0, 2 * a0 / div, (bb - disc) / div)
+            assert float(th.min()) >= 0.0 and float(th.max()) <= 1.0
+            assert float((sl + curv * th * (1 - th)).min()) > 0.1
+        fo, go = O.rqs_evaluate(col(kx), col(ky), col(kd), flat(pts["x"]), axis=0)
+        bo, igo = O.rqs_invert(col(kx), col(ky), col(kd), flat(pts["y"]), axis=0)
+        want = {False: (fo.reshape(3, 257), go.reshape(3, 257)), True: (bo.reshape(3, 257), igo.reshape(3, 257))}
+    _SEG_CASES[K] = (kx, ky, kd, pts, want)
+    return _SEG_CASES[K]
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("K", [2, 5, 16])
+def test_shared_segment_three_users_agree(K, dtype):
+    """One rational-quadratic segment in the device code (nf_rqs_core.h), three users of it on ONE spline of K shared
+    knots: RQSpline on nf_spline_eval (its own walk over global knots), DistConvFn with the spline stage alone (K4: binary
+    search in LDS) and nf_distconv_sites for the per-site log-derivative -- forward and inverse, at points inside the knot
+    range and ON every interior knot, each against the fp64 oracle's rqs_evaluate / rqs_invert.  The tolerances of
+    test_rqspline_from_explicit_knots_vs_oracle: values 1e-10 (fp64) / 1e-5 (fp32), derivatives and log-derivatives 10x."""
+    from normflow__amd.lib.spline import RQSpline
+    tol = 1e-10 if dtype == torch.float64 else 1e-5
+    kx, ky, kd, pts, want = _shared_segment_case(K)
+    to = lambda t: t.to(DEV, dtype)
+    sp = RQSpline(knots_x=to(kx), knots_y=to(ky), knots_d=to(kd), knots_axis=0)
+    knots = to(torch.stack((kx, ky, kd)))
+    for inverse in (False, True):
+        v = to(pts["y" if inverse else "x"])
+        val_o, der_o = want[inverse]                       # forward: g; inverse: 1 / g
+        val_s, der_s = sp.backward(v, grad=True) if inverse else sp(v, grad=True)
+        val_k, _ = _hip.DistConvFn.apply(v, knots, None, _hip.STAGE_SPLINE, inverse)
+        val_d, dens = _hip.DistConvSitesFn.apply(v, knots, None, None, _hip.STAGE_SPLINE, inverse, True)
+        errs = dict(spline=rel(val_s, val_o), k4=rel(val_k, val_o), sites=rel(val_d, val_o), deriv=rel(der_s, der_o),
+                    dens=rel(dens, der_o.log()), log_deriv_vs_dens=rel(der_s.log(), dens))
+        print(f"shared segment K={K} {dtype} inverse={inverse}: {errs}")
+        assert max(errs["spline"], errs["k4"], errs["sites"]) <= tol, errs
+        assert max(errs["deriv"], errs["dens"], errs["log_deriv_vs_dens"]) <= 10 * tol, errs
+
+
 def test_make_spline_accepts_the_anti_periodic_alias():
     """extrap 'anti-periodic' = 'anti' (spline.py:448-456): the spline object's stored knots are augmented either way."""
     shape, B, m = (4, 6), 2, 5
