@@ -308,6 +308,14 @@ int nf_distconv_sites_vjp(const void *v, const void *knots, int K, const uint8_t
  * inverse = 1 applies the inverse map (Pade11: x / (x + (1 - x) / d); Pade22: the root
  * 2y / (-b + sqrt(b^2 - 4 a y)), b = (d0 + d1 - 2) y - d0, a = -1 - b, with no a == 0
  * branch) and adds log|dx/dy| (Pade22: -log f'(x) at the recovered x).  No clamping.
+ * The same pass carries the site-local maps of the real line (modules_.py:72-90, 225-274):
+ *   NF_TANH    y = tanh x, log|f'| = -2 (|x| + log1p(e^{-2|x|}) - ln 2): finite for every finite
+ *              x, where the reference's log(cosh x) overflows.  No parameters: C = 1, d0 and d1
+ *              may be NULL.  inverse = 1: atanh, log = -(log1p(x) + log1p(-x))
+ *   NF_PADE32  y = x (a + x^2) / (1 + a x^2), a = d0 in (0, 3) per channel (the caller maps
+ *              3 expit(w0)); d1 unused.  inverse = 1: the one real root of
+ *              x^3 - a y x^2 + a x - y = 0 (scaled Cardano + two Newton steps; odd, 0 at 0,
+ *              finite for every finite y), log = -log f'(x) at that root
  *
  *   x, y      the field as (outer, C, inner), dense; B samples of outer*C*inner / B elements
  *             each (a sample is whole rows of `inner`: B divides outer*C, and the rows per
@@ -320,7 +328,7 @@ int nf_distconv_sites_vjp(const void *v, const void *knots, int K, const uint8_t
  *   log0      NULL = 0
  * Scratch: nf_pade_workspace_bytes(B, outer, C, inner) bytes (none for per_site map calls).
  */
-enum nf_pade_kind { NF_PADE11 = 11, NF_PADE22 = 22 };
+enum nf_pade_kind { NF_TANH = 1, NF_PADE11 = 11, NF_PADE22 = 22, NF_PADE32 = 32 };
 size_t nf_pade_workspace_bytes(int64_t B, int64_t outer, int64_t C, int64_t inner);
 int nf_pade(const void *x, const void *d0, const void *d1, const void *log0, void *y, void *logj, int64_t B,
             int64_t outer, int64_t C, int64_t inner, int kind, int inverse, int per_site, void *workspace,
@@ -328,7 +336,7 @@ int nf_pade(const void *x, const void *d0, const void *d1, const void *log0, voi
 /* VJP of nf_pade: x is the forward map's INPUT (inverse = 0) or the inverse map's OUTPUT
  * (inverse = 1), so no root is recomputed.  grad_y has the shape of x; grad_logj is (B)
  * (per_site = 0) or has the shape of x (per_site = 1).  Writes grad_x (shape of x) and
- * grad_d: 2C doubles, the cotangents of d0 (first C) and d1 (next C; 0 for NF_PADE11) summed
+ * grad_d: 2C doubles, the cotangents of d0 (first C; 0 for NF_TANH) and d1 (next C; 0 unless NF_PADE22) summed
  * over batch and sites per workgroup, then per channel in a fixed order (no atomics: the
  * same inputs give the same bits). */
 int nf_pade_vjp(const void *x, const void *d0, const void *d1, const void *grad_y, const void *grad_logj,

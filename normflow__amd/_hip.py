@@ -649,7 +649,7 @@ class DistConvSitesFn(torch.autograd.Function):
 
 
 # ============================================================================== pade
-PADE11, PADE22 = 11, 22      # nf_pade_kind
+TANH, PADE11, PADE22, PADE32 = 1, 11, 22, 32      # nf_pade_kind
 
 
 def _pade_workspace(layout, device):
@@ -658,16 +658,22 @@ def _pade_workspace(layout, device):
 
 
 class PadeFn(torch.autograd.Function):
-    """Pade11_ / Pade22_ (nf_pade) forward or inverse, differentiable in the field and in the per-channel parameters.
+    """Pade11_ / Pade22_ / Pade32_ / Tanh_ (nf_pade) forward or inverse, differentiable in the field and in the per-channel
+    parameters.
 
-    v: the field (any shape, contiguous); d0, d1: (C,) parameters after softplus_ln2 (d1 None for Pade11_);
+    v: the field (any shape, contiguous); d0, d1: (C,) parameters as the kernel takes them (softplus_ln2 of the Pade11_ /
+    Pade22_ weights, 3 expit(w0) for Pade32_; d1 only for Pade22_; both None for TANH, which has no parameter gradient);
     layout: (B, outer, C, inner) of nf_pade; log0: None, (B,) or (per_site) the shape of v."""
 
     @staticmethod
     def forward(ctx, v, d0, d1, log0, kind, inverse, per_site, layout):
         _require_device(v, d0, d1, log0)
         if v.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"Pade11_ / Pade22_ run on float32 / float64 fields, got {v.dtype}")
+            raise TypeError(f"the nf_pade maps run on float32 / float64 fields, got {v.dtype}")
+        if kind not in (TANH, PADE11, PADE22, PADE32):
+            raise ValueError(f"PadeFn: unknown kind {kind}")
+        if (d0 is None) != (kind == TANH) or (d1 is None) != (kind != PADE22):
+            raise ValueError(f"PadeFn: kind {kind} takes {'no parameters' if kind == TANH else 'd0 and d1' if kind == PADE22 else 'd0 only'}")
         v = v.contiguous()
         out = torch.empty_like(v)
         logj = torch.empty_like(v) if per_site else torch.empty(layout[0], dtype=v.dtype, device=v.device)
@@ -685,13 +691,13 @@ class PadeFn(torch.autograd.Function):
         x, d0, d1 = ctx.saved_tensors
         gout, glogj = gout.contiguous(), glogj.contiguous()
         gin = torch.empty_like(x)
-        gd = torch.empty(2, d0.numel(), dtype=torch.float64, device=x.device)
+        gd = torch.empty(2, d0.numel() if d0 is not None else 1, dtype=torch.float64, device=x.device)
         ws = _pade_workspace(ctx.layout, x.device)
         _check(load().nf_pade_vjp(_ptr(x), _ptr(d0), _ptr(d1), _ptr(gout), _ptr(glogj), _ptr(gin), _ptr(gd),
                                   *ctx.layout, ctx.kind, int(bool(ctx.inverse)), int(bool(ctx.per_site)), _ptr(ws),
                                   ws.numel(), _dtype_code(x), _stream()), "nf_pade_vjp")
         gd = gd.to(x.dtype)
-        return (gin, gd[0], gd[1] if d1 is not None else None, glogj if ctx.has_log0 else None,
+        return (gin, gd[0] if d0 is not None else None, gd[1] if d1 is not None else None, glogj if ctx.has_log0 else None,
                 None, None, None, None)
 
 

@@ -1,5 +1,6 @@
 // nf_pade.hip -- Pade11_ / Pade22_: learnable monotone maps of [0, 1] onto itself with per-channel parameters, forward,
-// inverse and their VJP, each one pass over the field.
+// inverse and their VJP, each one pass over the field; and on the same pass the site-local maps of the real line:
+// Tanh_ / ArcTanh_ (no parameters) and Pade32_ (one parameter per channel).
 //
 // Restates src/nn/scalar/modules_.py:117-222 (the reference's ~15 eager element-wise ops plus the reduction of
 // Module_.sum_density, src/nn/_core.py:38-42, per direction):
@@ -10,6 +11,13 @@
 //            inverse: the root x = 2y / (-b + sqrt(b^2 - 4 a y)), b = s y - d0, a = -1 - b: the reference's
 //            (-b - sqrt(..)) / (2a) without its a == 0 branch (:204), and log = -log g1(x) at that x.
 // No clamping: inputs outside [0, 1] give what the formulas give.
+//   Tanh_    y = tanh x, log f' = -2 log cosh x = -2 (|x| + log1p(e^{-2|x|}) - ln 2)   (modules_.py:72-90: the reference's
+//            log(cosh x) overflows to inf; this form is finite for every finite x and equal wherever that one is finite);
+//            inverse (ArcTanh_): atanh y, log = -log(1 - y^2) = -(log1p(y) + log1p(-y)).
+//   Pade32_  f(x) = x (a + x^2) / (1 + a x^2), 0 < a < 3 (modules_.py:225-274): odd, monotone, fixed points 0 and +-1;
+//            f' = (a (s - 1)^2 + (3 - a)(1 + a) s) / (1 + a s)^2, s = x^2: the reference's numerator a s^2 + (3 - a^2) s + a
+//            as a sum of two non-negative terms.  For |x| > 1 both are evaluated in u = 1/x, so nothing overflows.
+//            inverse: the one real root of x^3 - a y x^2 + a x - y = 0 (see pade32_root), log = -log f'(x) at that root.
 //
 // Layout.  The field is (outer, C, inner): rows of `inner` elements, row r has channel r % C, and a sample is RS =
 // outer C / B whole rows.  A work unit is (sample b, row group g, piece bx): group g holds the rows g, g + G, ... of the
@@ -101,10 +109,107 @@ struct PadeWalk {
   }
 };
 
-// The map at one element.  d is (d0, d1) for Pade22_ and (d, log d) for Pade11_.
+template <typename T> struct RealFn;
+template <> struct RealFn<float> {
+  static __device__ __forceinline__ float tanh(float x) { return ::tanhf(x); }
+  static __device__ __forceinline__ float atanh(float x) { return ::atanhf(x); }
+  static __device__ __forceinline__ float log1p(float x) { return ::log1pf(x); }
+  static __device__ __forceinline__ float exp(float x) { return ::expf(x); }
+  static __device__ __forceinline__ float cbrt(float x) { return ::cbrtf(x); }
+  static __device__ __forceinline__ float copysign(float x, float s) { return ::copysignf(x, s); }
+};
+template <> struct RealFn<double> {
+  static __device__ __forceinline__ double tanh(double x) { return ::tanh(x); }
+  static __device__ __forceinline__ double atanh(double x) { return ::atanh(x); }
+  static __device__ __forceinline__ double log1p(double x) { return ::log1p(x); }
+  static __device__ __forceinline__ double exp(double x) { return ::exp(x); }
+  static __device__ __forceinline__ double cbrt(double x) { return ::cbrt(x); }
+  static __device__ __forceinline__ double copysign(double x, double s) { return ::copysign(x, s); }
+};
+
+// Pade32_: f(x) and f'(x) > 0.  |x| <= 1 in s = x^2, |x| > 1 in r = 1 / x^2 (numerator and denominator divided by s or
+// s^2), so both stay finite up to the largest x.  ie = 1 / (1 + a s) in either form: f(x) - y = N ie with
+// N = x (a + s) - y (1 + a s).
+template <typename T> __device__ __forceinline__ void pade32_eval(T x, T a, T &f, T &g, T &ie) {
+  const T k = (T(3) - a) * (T(1) + a);
+  if (Num<T>::abs(x) <= T(1)) {
+    const T s = x * x, iden = T(1) / (T(1) + a * s), w = (x - T(1)) * (x + T(1));
+    f = x * (a + s) * iden;
+    g = (a * w * w + k * s) * (iden * iden);
+    ie = iden;
+  } else {
+    const T u = T(1) / x, r = u * u, iden = T(1) / (r + a), w = (T(1) - u) * (T(1) + u);
+    f = x * (a * r + T(1)) * iden;
+    g = (a * w * w + k * r) * (iden * iden);
+    ie = r * iden;
+  }
+}
+
+// One Newton step on f(x) - y.  The step cannot move x below the noise of the residual over f', and f' is as small as
+// (3 - a) / (1 + a) at |x| = 1; in fp32 the residual's numerator N is therefore formed in double (exact products of fp32
+// operands, five operations), which leaves the root within an ulp or so of the exact root of the fp32 inputs.
+template <typename T> __device__ __forceinline__ T pade32_newton(T x, T a, T y) {
+  T f, g, ie;
+  pade32_eval(x, a, f, g, ie);
+  if constexpr (sizeof(T) == sizeof(float)) {
+    const double xd = x, ad = a, s = xd * xd;
+    const double N = xd * (ad + s) - double(y) * (1.0 + ad * s);
+    return x - T(N * double(ie)) / g;
+  } else {
+    return x - (f - y) / g;
+  }
+}
+
+// The one real root of x^3 - a y x^2 + a x - y = 0 for 0 < a < 3: odd in y, 0 at 0.  |y| <= 1: the cubic in x; |y| > 1:
+// the cubic in z = x / y, z^3 - a z^2 + (a / y^2) z - 1 / y^2 = 0, whose coefficients are bounded.  Either is depressed
+// (shift h = -A2 / 3: t^3 + p t + q = 0) and solved by Cardano with the larger-magnitude cube root U of -q/2 +- sqrt(D)
+// and the other term as -p / (3U); D < 0 can only come from rounding near the almost-triple root (a -> 3, |y| = 1) and is
+// clamped.  Two Newton steps on f(x) - y remove the cancellation of U + V (x < 1) and of D; where y^2 < 1e-4 a^3 the root's
+// series y/a - (1 - a^2) (y/a)^3 / a (relative error < 1e-8) starts them instead, so tiny y keep their relative accuracy.
+template <typename T> __device__ __forceinline__ T pade32_root(T y, T a) {
+  const T ay = Num<T>::abs(y);
+  if (!(ay > T(0))) return y;                      // +-0 (and NaN) map to themselves
+  T A2, A1, A0, scale;
+  if (ay <= T(1)) {
+    A2 = -a * ay; A1 = a; A0 = -ay; scale = T(1);
+  } else {
+    const T c = (T(1) / ay) / ay;
+    A2 = -a; A1 = a * c; A0 = -c; scale = ay;
+  }
+  const T h = -A2 * T(1.0 / 3.0);
+  const T p = A1 - A2 * A2 * T(1.0 / 3.0);
+  const T q = A2 * (T(2.0 / 27.0) * A2 * A2 - A1 * T(1.0 / 3.0)) + A0;
+  const T hq = T(-0.5) * q, p3 = p * T(1.0 / 3.0);
+  const T D = Num<T>::max(hq * hq + p3 * p3 * p3, T(0));
+  const T U = RealFn<T>::cbrt(hq + RealFn<T>::copysign(Num<T>::sqrt(D), hq));
+  const T t = U != T(0) ? U - p3 / U : T(0);
+  T x = (t + h) * scale;
+  if (ay * ay < T(1e-4) * a * a * a) {             // x << sqrt(a): U + V would cancel to noise; the series of the root
+    const T z = ay / a;
+    x = z - (T(1) - a * a) * z * z * z / a;
+  }
+  x = pade32_newton(pade32_newton(x, a, ay), a, ay);
+  return RealFn<T>::copysign(x, y);
+}
+
+// The map at one element.  d is (d0, d1) for Pade22_, (d, log d) for Pade11_ and (a, -) for Pade32_; Tanh_ has none.
 template <typename T, int KIND, bool INV>
 __device__ __forceinline__ T pade_map(T v, T d0, T d1, T &lg) {
-  if constexpr (KIND == NF_PADE11) {
+  if constexpr (KIND == NF_TANH) {
+    if (INV) {
+      lg = -(RealFn<T>::log1p(v) + RealFn<T>::log1p(-v));
+      return RealFn<T>::atanh(v);
+    }
+    const T ax = Num<T>::abs(v);
+    lg = T(-2) * ((ax - Num<T>::kLn2) + RealFn<T>::log1p(RealFn<T>::exp(T(-2) * ax)));
+    return RealFn<T>::tanh(v);
+  } else if constexpr (KIND == NF_PADE32) {
+    const T x = INV ? pade32_root(v, d0) : v;
+    T f, g, ie;
+    pade32_eval(x, d0, f, g, ie);
+    lg = INV ? -nf_log(g) : nf_log(g);
+    return INV ? x : f;
+  } else if constexpr (KIND == NF_PADE11) {
     const T den = INV ? v + (T(1) - v) / d0 : v + d0 * (T(1) - v);
     lg = (INV ? -d1 : d1) - T(2) * nf_log(den);
     return v / den;
@@ -128,9 +233,10 @@ __global__ __launch_bounds__(kBlock) void pade_kernel(PadeArgs A) {
   const PadePlan &p = A.p;
   for (int64_t u = blockIdx.x; u < p.units; u += gridDim.x) {
     PadeUnit U(p, u);
-    T d0 = static_cast<const T *>(A.d0)[U.c], d1;
+    T d0 = T(0), d1 = T(0);
+    if constexpr (KIND != NF_TANH) d0 = static_cast<const T *>(A.d0)[U.c];
     if constexpr (KIND == NF_PADE11) d1 = nf_log(d0);
-    else d1 = static_cast<const T *>(A.d1)[U.c];
+    if constexpr (KIND == NF_PADE22) d1 = static_cast<const T *>(A.d1)[U.c];
     const int64_t base = U.row0 * p.inner;
     const T *__restrict__ xin = static_cast<const T *>(A.x) + base;
     const T *__restrict__ l0 = SITES && A.log0 ? static_cast<const T *>(A.log0) + base : nullptr;
@@ -174,8 +280,31 @@ __global__ __launch_bounds__(kBlock) void pade_kernel(PadeArgs A) {
 // directions (inverse: implicit differentiation, as nf_distconv_vjp), so no root is recomputed.
 template <typename T, int KIND, bool INV>
 __device__ __forceinline__ T pade_vjp(T x, T d0, T d1, T gy, T gl, double &gd0, double &gd1) {
-  T g, Lx, f0, L0, f1 = T(0), L1 = T(0);
-  if constexpr (KIND == NF_PADE11) {
+  T g, Lx, f0 = T(0), L0 = T(0), f1 = T(0), L1 = T(0);
+  if constexpr (KIND == NF_TANH) {
+    // e = e^{-2|x|}: sech^2 x = 4e / (1 + e)^2 does not cancel where tanh x rounds to +-1
+    const T e = RealFn<T>::exp(T(-2) * Num<T>::abs(x)), ie = T(1) / (T(1) + e);
+    g = T(4) * e * ie * ie;
+    Lx = T(-2) * RealFn<T>::tanh(x);
+  } else if constexpr (KIND == NF_PADE32) {
+    // in s = x^2 (|x| <= 1) or r = 1 / x^2 (|x| > 1), as pade32_eval: num = a s^2 + (3 - a^2) s + a, den = 1 + a s
+    const T a = d0, k = (T(3) - a) * (T(1) + a);
+    if (Num<T>::abs(x) <= T(1)) {
+      const T s = x * x, iden = T(1) / (T(1) + a * s), i2 = iden * iden, w = (x - T(1)) * (x + T(1));
+      const T num = a * w * w + k * s, inum = T(1) / num;
+      g = num * i2;
+      Lx = T(2) * x * ((T(2) * a * s + T(3) - a * a) * inum - T(2) * a * iden);
+      f0 = -x * w * (T(1) + s) * i2;
+      L0 = (s * s - T(2) * a * s + T(1)) * inum - T(2) * s * iden;
+    } else {
+      const T u = T(1) / x, r = u * u, iden = T(1) / (r + a), i2 = iden * iden, w = (T(1) - u) * (T(1) + u);
+      const T num = a * w * w + k * r, inum = T(1) / num;
+      g = num * i2;
+      Lx = T(2) * u * ((T(2) * a + (T(3) - a * a) * r) * inum - T(2) * a * iden);
+      f0 = -x * w * (T(1) + r) * i2;
+      L0 = (T(1) - T(2) * a * r + r * r) * inum - T(2) * iden;
+    }
+  } else if constexpr (KIND == NF_PADE11) {
     const T den = x + d0 * (T(1) - x), iden = T(1) / den, i2 = iden * iden;
     g = d0 * i2;
     Lx = -T(2) * (T(1) - d0) * iden;
@@ -201,7 +330,7 @@ __device__ __forceinline__ T pade_vjp(T x, T d0, T d1, T gy, T gl, double &gd0, 
     gin = (gy - gl * Lx) / g;
     gq = -gin; gL = -gl;
   }
-  gd0 += double(gq * f0 + gL * L0);
+  if (KIND != NF_TANH) gd0 += double(gq * f0 + gL * L0);
   if (KIND == NF_PADE22) gd1 += double(gq * f1 + gL * L1);
   return gin;
 }
@@ -212,7 +341,7 @@ __global__ __launch_bounds__(kBlock) void pade_vjp_kernel(PadeArgs A) {
   const PadePlan &p = A.p;
   for (int64_t u = blockIdx.x; u < p.units; u += gridDim.x) {
     PadeUnit U(p, u);
-    const T d0 = static_cast<const T *>(A.d0)[U.c];
+    const T d0 = KIND != NF_TANH ? static_cast<const T *>(A.d0)[U.c] : T(0);
     const T d1 = KIND == NF_PADE22 ? static_cast<const T *>(A.d1)[U.c] : T(0);
     const int64_t base = U.row0 * p.inner;
     const T *__restrict__ xin = static_cast<const T *>(A.x) + base;
@@ -298,22 +427,30 @@ static void launch_vjp(const PadeArgs &A, bool sites, hipStream_t s) {
   else hipLaunchKernelGGL((pade_vjp_kernel<T, KIND, INV, false>), dim3(pade_grid(A.p)), dim3(kBlock), 0, s, A);
 }
 
+template <typename T, int KIND>
+static void dispatch_kind(bool vjp, const PadeArgs &A, int inverse, bool st, hipStream_t s) {
+  if (vjp) inverse ? launch_vjp<T, KIND, true>(A, st, s) : launch_vjp<T, KIND, false>(A, st, s);
+  else inverse ? launch_map<T, KIND, true>(A, st, s) : launch_map<T, KIND, false>(A, st, s);
+}
+
 template <typename T>
 static void dispatch(bool vjp, const PadeArgs &A, int kind, int inverse, int per_site, hipStream_t s) {
   const bool st = per_site != 0;
-  if (kind == NF_PADE11) {
-    if (vjp) inverse ? launch_vjp<T, NF_PADE11, true>(A, st, s) : launch_vjp<T, NF_PADE11, false>(A, st, s);
-    else inverse ? launch_map<T, NF_PADE11, true>(A, st, s) : launch_map<T, NF_PADE11, false>(A, st, s);
-  } else {
-    if (vjp) inverse ? launch_vjp<T, NF_PADE22, true>(A, st, s) : launch_vjp<T, NF_PADE22, false>(A, st, s);
-    else inverse ? launch_map<T, NF_PADE22, true>(A, st, s) : launch_map<T, NF_PADE22, false>(A, st, s);
+  switch (kind) {
+    case NF_TANH: dispatch_kind<T, NF_TANH>(vjp, A, inverse, st, s); break;
+    case NF_PADE11: dispatch_kind<T, NF_PADE11>(vjp, A, inverse, st, s); break;
+    case NF_PADE22: dispatch_kind<T, NF_PADE22>(vjp, A, inverse, st, s); break;
+    default: dispatch_kind<T, NF_PADE32>(vjp, A, inverse, st, s); break;
   }
 }
 
-static int check_common(const char *who, int kind, int dtype, const void *x, const void *d0, const void *d1) {
-  NF_REQUIRE(kind == NF_PADE11 || kind == NF_PADE22, "%s: kind %d is neither NF_PADE11 nor NF_PADE22", who, kind);
+static int check_common(const char *who, int kind, int dtype, const void *x, const void *d0, const void *d1,
+                        int64_t C) {
+  NF_REQUIRE(kind == NF_TANH || kind == NF_PADE11 || kind == NF_PADE22 || kind == NF_PADE32,
+             "%s: kind %d is none of NF_TANH, NF_PADE11, NF_PADE22, NF_PADE32", who, kind);
   NF_REQUIRE(dtype == NF_F32 || dtype == NF_F64, "%s: unsupported dtype %d", who, dtype);
-  NF_REQUIRE(x && d0 && (d1 || kind == NF_PADE11), "%s: NULL tensor pointer", who);
+  NF_REQUIRE(x && (d0 || kind == NF_TANH) && (d1 || kind != NF_PADE22), "%s: NULL tensor pointer", who);
+  NF_REQUIRE(kind != NF_TANH || C == 1, "%s: NF_TANH has no channels (C=%lld, must be 1)", who, (long long)C);
   return NF_OK;
 }
 
@@ -330,7 +467,7 @@ extern "C" size_t nf_pade_workspace_bytes(int64_t B, int64_t outer, int64_t C, i
 extern "C" int nf_pade(const void *x, const void *d0, const void *d1, const void *log0, void *y, void *logj, int64_t B,
                        int64_t outer, int64_t C, int64_t inner, int kind, int inverse, int per_site, void *workspace,
                        size_t workspace_bytes, int dtype, void *stream) {
-  int rc = check_common("nf_pade", kind, dtype, x, d0, d1);
+  int rc = check_common("nf_pade", kind, dtype, x, d0, d1, C);
   if (rc) return rc;
   NF_REQUIRE(y && logj, "nf_pade: NULL tensor pointer");
   PadeArgs A{};
@@ -360,7 +497,7 @@ extern "C" int nf_pade(const void *x, const void *d0, const void *d1, const void
 extern "C" int nf_pade_vjp(const void *x, const void *d0, const void *d1, const void *grad_y, const void *grad_logj,
                            void *grad_x, double *grad_d, int64_t B, int64_t outer, int64_t C, int64_t inner, int kind,
                            int inverse, int per_site, void *workspace, size_t workspace_bytes, int dtype, void *stream) {
-  int rc = check_common("nf_pade_vjp", kind, dtype, x, d0, d1);
+  int rc = check_common("nf_pade_vjp", kind, dtype, x, d0, d1, C);
   if (rc) return rc;
   NF_REQUIRE(grad_y && grad_logj && grad_x && grad_d, "nf_pade_vjp: NULL tensor pointer");
   PadeArgs A{};

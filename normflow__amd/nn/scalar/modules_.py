@@ -6,8 +6,9 @@ the shared spline's knots staged in LDS.  DistConvertor_ keeps the reference's l
 structure (so `1.weights_x`-style state_dict keys and `.spline_layer_` still work) but
 executes the whole Expit_ -> SplineNet_ -> Logit_ triple as ONE launch.  With
 propagate_density (on the instance or on the class) the same pass writes per-site
-log-densities (`nf_distconv_sites`), in inference and in training.  Pade11_ and
-Pade22_ run on `nf_pade`: one pass per direction, per-site densities included.
+log-densities (`nf_distconv_sites`), in inference and in training.  Pade11_,
+Pade22_, Pade32_, Tanh_ and ArcTanh_ run on `nf_pade`: one pass per direction,
+per-site densities included.
 """
 import math
 
@@ -127,9 +128,10 @@ class Logit_(_K4Leaf, Module_):
 
 def _pade(module, x, log0, kind, inverse, d0, d1):
     """One nf_pade pass over x: the field is described to the kernel as (outer, C, inner) around the channel axis, with
-    no copy; the per-channel parameters go in already softplus-mapped (autograd takes the chain through softplus_ln2)."""
+    no copy; the per-channel parameters go in already mapped (autograd takes the chain through softplus_ln2 or expit).
+    A module without `n_channels` (Tanh_, ArcTanh_) has no parameters: d0 and d1 are None."""
     _hip._require_device(x)
-    C = module.n_channels
+    C = getattr(module, 'n_channels', 1)
     if C == 1:
         B = x.shape[0] if x.dim() > 0 else 1
         layout = (B, B, 1, x.numel() // B if B else 0)
@@ -139,7 +141,7 @@ def _pade(module, x, log0, kind, inverse, d0, d1):
             raise ValueError(f"{type(module).__name__}: axis {module.channels_axis} of a {tuple(x.shape)} field has "
                              f"{x.shape[axis]} entries, not n_channels={C}")
         layout = (x.shape[0], math.prod(x.shape[:axis]), C, math.prod(x.shape[axis + 1:]))
-    d0 = d0.to(x.dtype)
+    d0 = d0.to(x.dtype) if d0 is not None else None
     d1 = d1.to(x.dtype) if d1 is not None else None
     per_site = module.propagate_density
     if per_site:
@@ -195,6 +197,54 @@ class Pade22_(Module_):
 
     def backward(self, x, log0=0):
         return self._run(x, log0, True)
+
+
+class Pade32_(Module_):
+    """y = x (a + x^2) / (1 + a x^2), a = 3 expit(w0) in (0, 3) per channel: an odd monotone map of the real line with the
+    fixed points 0 and +-1, slope a at 0 and 1/a at infinity (modules_.py:225-274).  One nf_pade pass per direction; with
+    propagate_density the per-site log-derivatives, in inference and in training.
+
+    Departures from the reference: `w0` is a trainable Parameter (there `-torch.nn.Parameter(..)` leaves a plain tensor:
+    no parameters, an empty state_dict, a = 1 for ever), initialised to the reference's constant -log 2 (a = 1, the
+    identity); and `backward` works (there it raises UnboundLocalError): the one real root of
+    x^3 - a y x^2 + a x - y = 0, finite and odd for every finite y."""
+
+    def __init__(self, n_channels=1, channels_axis=1, label='pade32'):
+        super().__init__(label=label)
+        self.w0 = torch.nn.Parameter(torch.full((n_channels,), -math.log(2.0)))
+        self.n_channels = n_channels
+        self.channels_axis = channels_axis
+
+    def forward(self, x, log0=0):
+        return _pade(self, x, log0, _hip.PADE32, False, 3 * torch.special.expit(self.w0), None)
+
+    def backward(self, x, log0=0):
+        return _pade(self, x, log0, _hip.PADE32, True, 3 * torch.special.expit(self.w0), None)
+
+
+class Tanh_(Module_):
+    """y = tanh x; log|J| = -2 sum log cosh x (modules_.py:72-79); with propagate_density the per-site terms.  One nf_pade
+    pass.  log cosh x is evaluated as |x| + log1p(e^{-2|x|}) - ln 2, finite for every finite x: the reference's
+    log(cosh(x)) is inf once cosh overflows (|x| > 89 in fp32); the two agree wherever that one is finite.  The
+    instance's propagate_density holds in both directions (the reference's backward is a fresh ArcTanh_)."""
+
+    def forward(self, x, log0=0):
+        return _pade(self, x, log0, _hip.TANH, False, None, None)
+
+    def backward(self, x, log0=0):
+        return _pade(self, x, log0, _hip.TANH, True, None, None)
+
+
+class ArcTanh_(Module_):
+    """y = atanh x; log|J| = -sum log(1 - x^2) = 2 sum log cosh y (modules_.py:82-90), as log1p(x) + log1p(-x): finite
+    for every |x| < 1 (the reference's log(cosh(atanh x)) loses x -> +-1).  The inverse direction of Tanh_'s pass; the
+    instance's propagate_density holds in both directions."""
+
+    def forward(self, x, log0=0):
+        return _pade(self, x, log0, _hip.TANH, True, None, None)
+
+    def backward(self, x, log0=0):
+        return _pade(self, x, log0, _hip.TANH, False, None, None)
 
 
 class SplineNet_(_K4Leaf, SplineNet, Module_):
