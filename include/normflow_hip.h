@@ -97,6 +97,26 @@ int nf_get_option(int which);
 /* Bytes of scratch needed by any coupling / distconv call on a (B, V) problem. */
 size_t nf_workspace_bytes(int64_t B, int64_t V);
 
+/* ---- planning queries: how the element-wise kernels cut a (B, units) problem into workgroups.  Pure host code, no GPU
+ * work; they call the planners the launchers call, so a test can assert which regime a shape lands in.
+ *
+ * nf_plan_tiling: every workgroup of `block` lanes (256; 64 or 128 for the LDS-column spline kernel, see
+ * nf_rqs_plan_block) owns block * iters consecutive units of ONE sample, walks them in `iters` in {1, 2, 4, 8} strides of
+ * `block` and writes one double partial per (sample, workgroup); *blocks_x = workgroups per sample =
+ * ceil(units / (block * iters)).  iters doubles while (units / (2 block iters)) * B >= 8192.  `units` per entry point:
+ *   V            nf_rqs_* / nf_affine_* in NF_LAYOUT_FULL, nf_distconv, nf_distconv_sites, nf_phi4_action,
+ *                nf_normal_logprob
+ *   V / 2        nf_rqs_* / nf_affine_* in NF_LAYOUT_PAIR (one unit = one site pair)
+ *   ceil(V / 4)  nf_normal_sample in fp32 (one unit = one Philox call = four normals); ceil(V / 2) in fp64
+ * (nf_pade plans by itself; its plan can be read from nf_pade_workspace_bytes: one 16-byte partial per (sample, channel
+ * group, workgroup).)  Returns 0, or NF_EINVAL for a NULL output pointer, a negative size or a block other than 64, 128
+ * or 256.
+ * nf_rqs_plan_block: the workgroup size the spline kernels run this family with in `dtype` (256 for the register kernels
+ * of knots_len 4, 8, 16 without fixed knots; the LDS-column kernel halves it until a column of C logits per lane fits
+ * 64 KiB), or 0 -- with the reason in nf_last_error_string -- if the options are invalid or the spline does not fit. */
+int nf_plan_tiling(int64_t units, int64_t B, int block, int *iters, int64_t *blocks_x);
+int nf_rqs_plan_block(const nf_rqs_opts *opts, int dtype);
+
 /* ---- K2/K3: rational-quadratic spline coupling -----------------------------
  * Replaces, fused in one pass: knot construction (couplings_.py:211-262:
  * split, softmax, cumsum, scale/shift, softplus(beta=ln2)), boundary

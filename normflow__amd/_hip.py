@@ -48,6 +48,8 @@ PROTOTYPES = {
     "nf_set_option": (C.c_int, [C.c_int, C.c_int]),
     "nf_get_option": (C.c_int, [C.c_int]),
     "nf_workspace_bytes": (_SZ, [_I64, _I64]),
+    "nf_plan_tiling": (_I, [_I64, _I64, _I, C.POINTER(C.c_int), C.POINTER(_I64)]),
+    "nf_rqs_plan_block": (_I, [C.POINTER(RqsOpts), _I]),
     "nf_rqs_fwd": (_I, _MAP_ARGS),
     "nf_rqs_inv": (_I, _MAP_ARGS),
     "nf_rqs_fwd_sites": (_I, _SITES_ARGS),

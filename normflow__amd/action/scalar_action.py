@@ -26,7 +26,11 @@ class ScalarPhi4Action:
         d = cfgs.ndim - 1
         w0, w2, w4 = self.get_coef(d)
         if d >= 1 and cfgs.numel() and _hip.endpoint_supported(cfgs):
-            return _hip.Phi4ActionFn.apply(cfgs, float(w0), float(w2), float(w4))
+            # An axis of extent 1 is its own neighbour: roll is the identity there and the hopping term is -w0 phi(x)^2.
+            # The kernel takes extents of 1 as the padding of a lattice of fewer than four axes and reads no neighbour
+            # along them, so that term goes into the site-local coefficient.
+            own = sum(1 for n in cfgs.shape[1:] if n == 1)
+            return _hip.Phi4ActionFn.apply(cfgs, float(w0), float(w2 - own * w0), float(w4))
         # host tensors: site-local part, then one nearest-neighbour product per direction
         flat = lambda t: t.flatten(1).sum(dim=1) if d >= 1 else t
         sq = cfgs.square()

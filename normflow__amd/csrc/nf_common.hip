@@ -69,6 +69,16 @@ extern "C" int nf_set_option(int which, int value) {
 }
 extern "C" int nf_get_option(int which) { return nf::option(which); }
 extern "C" const char *nf_last_error_string(void) { return nf::g_err; }
+extern "C" int nf_plan_tiling(int64_t units, int64_t B, int block, int *iters, int64_t *blocks_x) {
+  NF_REQUIRE(iters != nullptr && blocks_x != nullptr, "nf_plan_tiling: NULL output pointer");
+  NF_REQUIRE(units >= 0 && B >= 0, "nf_plan_tiling: negative size");
+  NF_REQUIRE(block == nf::kWave || block == 2 * nf::kWave || block == nf::kBlock,
+             "nf_plan_tiling: workgroup size %d (the kernels run 64, 128 or 256 lanes)", block);
+  const nf::Tiling t = nf::make_tiling(units, B, block);
+  *iters = t.iters;
+  *blocks_x = t.blocks_x;
+  return NF_OK;
+}
 extern "C" size_t nf_workspace_bytes(int64_t B, int64_t V) {
   if (B < 0 || V < 0) return 0;
   // worst case of make_tiling: one double per 64-unit workgroup per sample (the LDS-column

@@ -446,6 +446,23 @@ extern "C" int nf_rqs_inv_sites(const void *y, const void *params, const uint8_t
   return rqs_sites(1, y, params, mask, log0, x, logj, site_out, site_mode, B, V, opts, strides, workspace, workspace_bytes, dtype, stream);
 }
 
+extern "C" int nf_rqs_plan_block(const nf_rqs_opts *opts, int dtype) {
+  static const uint8_t unused_mask = 1;
+  RqsArgs A{};
+  if (fill_args(A, 1, 2, opts, nullptr, &unused_mask)) return 0;
+  if (dtype != NF_F32 && dtype != NF_F64 && dtype != NF_F16) {
+    set_error("nf_rqs_plan_block: unsupported dtype %d", dtype);
+    return 0;
+  }
+  if (dtype == NF_F16 && !(has_static_kernel(A.P.m) && !A.P.fx && !A.P.fy)) {
+    set_error("nf_rqs: fp16 storage is built for knots_len 4, 8 and 16 without fixed knots");
+    return 0;
+  }
+  const int block = dtype == NF_F64 ? pick_block<double>(A) : pick_block<float>(A);   // fp16 storage: fp32 arithmetic
+  if (block == 0) set_error("nf_rqs: knots_len m=%d does not fit the 160 KiB of LDS of one CU", A.P.m);
+  return block;
+}
+
 extern "C" int nf_rqs_knots(const void *params, void *knots, int64_t B, int64_t V, const nf_rqs_opts *opts, int dtype,
                             void *stream) {
   NF_REQUIRE(opts != nullptr, "nf_rqs_knots: opts is NULL");

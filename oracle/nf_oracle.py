@@ -514,18 +514,23 @@ def philox4x32_10(counter, key):
     return np.stack([v.astype(np.uint32) for v in c], axis=-1)
 
 
-def normal_prior_sample(seed, offset, B, V, loc=None, scale=None, dtype=torch.float32):
+def normal_prior_sample(seed, offset, B, V, loc=None, scale=None, dtype=torch.float32, rows=None):
     """(x (B, V), logr (B)) exactly as nf_normal_sample lays its draws out (include/normflow_hip.h):
     group q = element index // 4 of sample b (float32: 4 normals per Philox call) or // 2 (float64: 2 per call);
     counter = (lo32(g), hi32(g), lo32(offset), hi32(offset)) with g = b * ngroups + q, key = (lo32(seed), hi32(seed) ^
     PHILOX_KEY_DOMAIN);
     Box-Muller: float32 u1 = (r + 1) 2^-32, u2 = r' 2^-32 from (r0, r1) -> (z0, z1) = rho (cos, sin)(2 pi u2) and (r2, r3) ->
     (z2, z3); float64 u1 = ((r0 << 21 ^ r1 >> 11) + 1) 2^-53, u2 likewise from (r2, r3) without the + 1.
-    x = loc + scale z;  logr = sum_x [-z^2/2 - log scale - log sqrt(2 pi)]."""
+    x = loc + scale z;  logr = sum_x [-z^2/2 - log scale - log sqrt(2 pi)].
+    rows: optional sample indices in [0, B): only those samples are generated, with the counters they have in the whole
+    batch, and returned in that order ((len(rows), V) and (len(rows)))."""
     import numpy as np
     per = 4 if dtype == torch.float32 else 2
     ngroups = (V + per - 1) // per
-    g = (np.arange(B, dtype=np.uint64)[:, None] * np.uint64(ngroups) + np.arange(ngroups, dtype=np.uint64)[None, :])
+    bs = np.arange(B, dtype=np.uint64) if rows is None else np.asarray(list(rows), dtype=np.uint64)
+    assert bs.size == 0 or int(bs.max()) < B, "rows must index the batch"
+    B = int(bs.size)
+    g = (bs[:, None] * np.uint64(ngroups) + np.arange(ngroups, dtype=np.uint64)[None, :])
     ctr = np.stack([(g & np.uint64(0xFFFFFFFF)), (g >> np.uint64(32)),
                     np.full_like(g, offset & 0xFFFFFFFF), np.full_like(g, (offset >> 32) & 0xFFFFFFFF)], axis=-1).astype(np.uint32)
     key = np.broadcast_to(np.array([seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ PHILOX_KEY_DOMAIN], dtype=np.uint32),

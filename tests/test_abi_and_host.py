@@ -49,6 +49,53 @@ def test_argument_validation_without_gpu():
         _hip.make_rqs_opts(4, (0, 1), (0, 1), {'left': 'periodic'}, 0)
 
 
+def test_tiling_plan_queries():
+    """nf_plan_tiling / nf_rqs_plan_block: pure host planning, the launchers' own make_tiling and pick_block.  A literal
+    table (iters doubles while (units // (2 block iters)) B >= 8192, blocks_x = ceil(units / (block iters))) and the
+    argument validation."""
+    lib = _hip.load()
+    err = lambda: lib.nf_last_error_string().decode()
+
+    def plan(units, B, block=256):
+        it, bx = ctypes.c_int(-7), ctypes.c_int64(-7)
+        assert lib.nf_plan_tiling(units, B, block, ctypes.byref(it), ctypes.byref(bx)) == 0
+        return it.value, bx.value
+
+    table = {(256, 5): (1, 1), (2310, 3): (1, 10), (1155, 4096): (2, 3), (1155, 8192): (4, 2), (2310, 8192): (8, 2),
+             (4096, 1024): (2, 8),                     # 16^3 at batch 1024: BASELINE config 3
+             (524288, 8): (2, 1024),                   # 32^4 in the pair layout at batch 8: config 4's slab
+             (1155, 4096, 64): (8, 3), (1155, 4096, 128): (4, 3), (1155, 3, 64): (1, 19),
+             (2 ** 22 + 3, 1): (2, 8193), (2 ** 22 - 1, 1): (1, 16384), (0, 4): (1, 0), (7, 0): (1, 1)}
+    for args, want in table.items():
+        assert plan(*args) == want, (args, plan(*args), want)
+    it, bx = ctypes.c_int(0), ctypes.c_int64(0)
+    assert lib.nf_plan_tiling(10, 1, 256, None, ctypes.byref(bx)) == -1 and "NULL" in err()
+    assert lib.nf_plan_tiling(10, 1, 256, ctypes.byref(it), None) == -1 and "NULL" in err()
+    assert lib.nf_plan_tiling(-1, 1, 256, ctypes.byref(it), ctypes.byref(bx)) == -1 and "negative" in err()
+    assert lib.nf_plan_tiling(10, -1, 256, ctypes.byref(it), ctypes.byref(bx)) == -1 and "negative" in err()
+    for block in (0, 32, 100, 512, -64):
+        assert lib.nf_plan_tiling(10, 1, block, ctypes.byref(it), ctypes.byref(bx)) == -1 and "workgroup size" in err()
+
+    lin = {'left': 'linear', 'right': 'linear'}
+    def block_of(m, dtype, layout=0, **kw):
+        return lib.nf_rqs_plan_block(ctypes.byref(_hip.make_rqs_opts(m, (-5, 5), (-5, 5), lin, layout, **kw)), dtype)
+    F32, F64, F16 = _hip.NF_F32, _hip.NF_F64, _hip.NF_F16
+    table = {(4, F32): 256, (8, F64): 256, (16, F32): 256, (16, F16): 256,       # register kernels
+             (3, F32): 256, (3, F64): 256, (10, F64): 256,                        # LDS columns that fit 64 KiB at 256 lanes
+             (24, F32): 128, (24, F64): 64, (24, F32, 1): 128, (48, F32): 64,     # shrunk workgroups
+             (200, F64): 0, (5, F16): 0}                                          # does not fit / no fp16 kernel
+    for args, want in table.items():
+        assert block_of(*args) == want, (args, block_of(*args), want)
+    assert "fp16 storage" in err()
+    assert block_of(200, F64) == 0 and "does not fit" in err()
+    kx = torch.linspace(-5, 5, 4)
+    assert block_of(4, F32, knots_x=kx) == 256        # fixed knots: the LDS-column kernel, C = 2m - 1 = 7 logits per lane
+    assert lib.nf_rqs_plan_block(None, F32) == 0 and "opts is NULL" in err()
+    assert block_of(1, F32) == 0 and "knots_len" in err()
+    assert block_of(4, 9) == 0 and "dtype" in err()
+    assert lib.nf_version() == 301
+
+
 def test_kernel_selection_options_in_process():
     """nf_set_option / nf_get_option: the in-process switch between the split-fp16 and the exact-fp32-product kernels (what
     bench.py's second value and the headline parity tests use; the library reads no environment variable)."""
