@@ -6,6 +6,7 @@ DistConvertor_), or a stack of RQ-spline couplings, assembled from the same name
     python examples/phi4_lattice.py --lat 8,8 --epochs 500
     python examples/phi4_lattice.py --lat 16,16,16 --kind rqs --layers 4 --epochs 100
     torchrun-free data parallel:  --nranks 8   (device_handler.spawnprocesses, one process per GPU)
+    python examples/phi4_lattice.py --lat 16,16 --hmc     after the fit: <phi^2> from model.mcmc next to model.hmc
 """
 import argparse
 import os
@@ -45,6 +46,22 @@ def fit(model, **kw):
     model.fit(**kw)
 
 
+def phi2(y, n_chains, drop):
+    """(mean, standard error across chains) of <phi^2> from sampler rows (row r = step r // C of chain r % C)."""
+    y = y.double().reshape(y.shape[0] // n_chains, n_chains, -1)[drop:]
+    per_chain = (y ** 2).mean(dim=(0, 2))
+    return per_chain.mean().item(), per_chain.std().item() / n_chains ** 0.5
+
+
+def compare_with_hmc(model, n_chains=64, rows=128):
+    """<phi^2> of the trained flow + Metropolis next to hybrid Monte Carlo on the action itself (exact up to its own
+    statistical error; the first quarter of every chain is dropped as thermalisation)."""
+    y = model.mcmc.sample(n_chains * rows, n_chains=n_chains)
+    print("<phi^2>  model.mcmc  %.5f +- %.5f   (accept rate %.3f)" % (*phi2(y, n_chains, rows // 4), model.mcmc.history.accept_rate[-1]))
+    y = model.hmc.sample(n_chains * rows, n_chains=n_chains, n_md=10, dt=0.1)
+    print("<phi^2>  model.hmc   %.5f +- %.5f   (accept rate %.3f)" % (*phi2(y, n_chains, rows // 4), model.hmc.history.accept_rate[-1]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lat", default="8,8")
@@ -59,6 +76,8 @@ def main():
     ap.add_argument("--lambd", type=float, default=0.5)
     ap.add_argument("--transform", choices=("fft", "hartley"), default="fft",
                     help="how the spectral block filters: torch.fft, or the LDS-resident Hartley kernel (lattices up to 64 KiB per sample)")
+    ap.add_argument("--hmc", action="store_true",
+                    help="after the fit, print <phi^2> from model.hmc (hybrid Monte Carlo on the action) next to model.mcmc")
     a = ap.parse_args()
     lat = tuple(int(n) for n in a.lat.split(","))
     model = nf.Model(net_=build_net(lat, a.kind, a.layers, a.knots, a.transform), prior=NormalPrior(shape=lat),
@@ -70,6 +89,8 @@ def main():
     else:
         model.fit(**kw)
         nf.backward_sanitychecker(model)
+        if a.hmc:
+            compare_with_hmc(model)
 
 
 if __name__ == "__main__":

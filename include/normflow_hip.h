@@ -626,6 +626,47 @@ int nf_metropolis_chains(const void *logq, const void *logp, double *logqp_ref, 
 int nf_metropolis_select(void *y, const void *ref_sample, const uint8_t *accept, const int64_t *keep, int64_t S, int64_t C,
                          int64_t V, int elem_size, void *stream);
 
+/* ---- hybrid Monte Carlo for the phi^4 action, the chain resident in a CU (MI355X-side extension; the action is
+ * src/action/scalar_action.py:24-46).  For C independent chains on lattice[4] (leading extents 1 for d < 4), per trajectory:
+ *   F(phi)(x) = 2 w2 phi(x) + 4 w4 phi(x)^3 - w0 sum_mu [phi(x + mu) + phi(x - mu)]                      (periodic)
+ *   pi ~ N(0, 1)^V;  H0 = sum pi^2 / 2 + S(phi)
+ *   pi -= (dt / 2) F(phi);  k = 1 .. n_md: phi += dt pi, pi -= (dt, or dt / 2 when k = n_md) F(phi)
+ *   H1 = sum pi^2 / 2 + S(phi);  dH = H1 - H0;  accept = force_accept || log u < -dH,  u in (0, 1]
+ * with S of nf_phi4_action.  The field arithmetic is in dtype; the energies are summed and compared in double for either
+ * dtype, in a fixed order: no atomics, a launch is bitwise reproducible and n_traj trajectories in one launch equal n_traj
+ * launches of one.  No neighbour is read along an axis of extent 1 (a caller that wants ScalarPhi4Action's treatment of a
+ * user axis of extent 1 folds -w0 phi^2 per such axis into w2, as for nf_phi4_action); on an axis of extent 2 the one
+ * neighbour counts twice; extents need not be even.  A rejected chain keeps its phi bit for bit.
+ * One workgroup per chain runs all n_traj trajectories with phi and pi in registers and one image of phi in LDS; the
+ * launch neither allocates nor synchronises and can be captured into a HIP graph.
+ *   phi        (C, V) of dtype, in and out: the chains' states
+ *   action_out (C) double: S of the final states
+ *   pi_in      (C, V) or NULL: replaces the drawn momenta (n_traj must be 1);  pi_out (C, V) or NULL: the momenta at the end
+ *              of the last trajectory (of the proposal, accepted or not)
+ *   dh_out     (n_traj, C) double;  accept_out (n_traj, C) uint8
+ *   record     (n_traj / record_every, C, V) of dtype or NULL: the chains' states after every record_every-th trajectory
+ * Random numbers: trajectory t draws its momenta as nf_normal_sample draws a unit (B = C, V) field at (seed, offset + 2 t)
+ * (group layout and key hi32 seed ^ NF_PHILOX_KEY_DOMAIN above) and its uniform as nf_block_accept does at
+ * (seed, offset + 2 t + 1): counter (lo32 c, hi32 c, lo32, hi32 of that offset), key hi32 seed ^ NF_PHILOX_ACCEPT_DOMAIN.
+ * A launch consumes the 2 n_traj offsets from `offset` on.
+ * nf_phi4_hmc_supported (pure host code, the launcher's own planner): 1 for NF_F32 / NF_F64 when a chain's image fits
+ * 64 KiB of LDS, V sizeof(dtype) <= 65536 (16^2, 64^2, 16^3, 8^4 in both, 24^3 and 128^2 in fp32), else 0 with the reason
+ * in nf_last_error_string.  The kernel runs ceil(V / ns) lanes (whole waves) per chain, ns = 1, 2, 4, 8 or 16 sites per lane.
+ * NF_EINVAL: a NULL phi / action_out / dh_out / accept_out / lattice, C outside 1 .. 65535, n_md, n_traj or record_every
+ * < 1, pi_in with n_traj > 1, an unsupported lattice or dtype, or
+ *   n_md n_traj max(V, 256) ceil(C / 1024) > NF_HMC_MAX_WORK
+ * (below 256 sites the two barriers of an MD step, not the sites, set its time; chains beyond the resident ones wait for
+ * a free CU, so the time of a launch grows with every further 1024 chains).  Measured on an MI355X at n_md = 10
+ * (tools/hmc_bench.py): 16^2 x 512 chains 0.7 us per MD step, 16^3 x 1024 chains 9 us per MD step; a launch at the cap
+ * (with up to 1024 chains 2^18 MD steps at 16^2, 2^14 at 16^3; with 65535 chains a 64th of that) then takes about 0.2 s.
+ * Longer runs are split into several launches by the caller. */
+#define NF_HMC_MAX_WORK 67108864 /* 2^26 */
+int nf_phi4_hmc_supported(const int32_t *lattice, int dtype);
+int nf_phi4_hmc(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out, uint8_t *accept_out,
+                void *record, int record_every, int64_t C, const int32_t *lattice, double w0, double w2, double w4,
+                int n_md, double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset, int dtype,
+                void *stream);
+
 /* ---- VJP of the conv layer (K5) ---------------------------------------------------------------
  * grad_input is nf_conv_fwd itself applied to the pre-activation cotangent with the weights
  * flipped along every kernel axis and in/out channels swapped.  The two entry points below are

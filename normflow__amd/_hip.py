@@ -88,6 +88,9 @@ PROTOTYPES = {
     "nf_block_accept": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_metropolis_chains": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_metropolis_select": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _P]),
+    "nf_phi4_hmc_supported": (_I, [C.POINTER(C.c_int32), _I]),
+    "nf_phi4_hmc": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, C.POINTER(C.c_int32), _D, _D, _D, _I, _D, _I, _I,
+                         C.c_uint64, C.c_uint64, _I, _P]),
     "nf_act_vjp": (_I, [_P, _P, _P, _I64, _I, _I, _P]),
     "nf_conv_wgrad_cols": (_I, [_I, _I]),
     "nf_conv_wgrad": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, _P]),
@@ -1742,6 +1745,16 @@ def _philox_position(device, generator=None):
     return seed & (2 ** 64 - 1), offset // 4
 
 
+def _philox_positions(device, n, generator=None):
+    """`_philox_position` for a launch that consumes n consecutive kernel offsets: (seed, first offset); the generator is
+    advanced past all n."""
+    gen = generator if generator is not None else torch.cuda.default_generators[device.index if device.index is not None
+                                                                                  else torch.cuda.current_device()]
+    seed, offset = gen.initial_seed(), gen.get_offset()
+    gen.set_offset(offset + 4 * int(n))
+    return seed & (2 ** 64 - 1), offset // 4
+
+
 def normal_sample(loc, scale, batch_size, shape, dtype, device, generator=None):
     """(x (B, *shape), logr (B)) of a NormalPrior in one launch (nf_normal_sample), at the `_philox_position` of torch's
     generator: torch.manual_seed(s) makes this kernel reproducible exactly as it does torch's own samplers."""
@@ -1844,3 +1857,45 @@ def metropolis_select(y, ref_sample, accept, keep, n_chains):
     _expect("metropolis_select (keep)", keep, B, torch.int64)
     _check(load().nf_metropolis_select(_ptr(y), _ptr(ref_sample), _ptr(accept), _ptr(keep), B // Cn, Cn, V,
                                        y.element_size(), _stream()), "nf_metropolis_select")
+
+
+# ========================================================================= hybrid Monte Carlo, phi^4 (nf_hmc.hip)
+HMC_MAX_WORK = 1 << 26        # NF_HMC_MAX_WORK: the cap on n_md * n_traj * max(V, 256) * ceil(C / 1024) of one launch
+
+
+def hmc_supported(lat, dtype):
+    """True if nf_phi4_hmc takes chains on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own planner,
+    pure host code."""
+    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
+        return False
+    return bool(load().nf_phi4_hmc_supported(_lat4(lat), NF_F32 if dtype == torch.float32 else NF_F64))
+
+
+def phi4_hmc(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in=None, want_pi=False, force_accept=False,
+             position=None, generator=None):
+    """nf_phi4_hmc: n_traj HMC trajectories of the C chains phi (C, *L), in place, in ONE launch.  (w0, w2, w4) are the
+    kernel's coefficients (a user axis of extent 1 already folded into w2).  Returns a dict with action (C) float64 of
+    the final states, dh (n_traj, C) float64, accept (n_traj, C) uint8, record (n_traj // record_every, C, *L) or None,
+    pi (C, *L) or None.  The launch takes 2 n_traj Philox positions from torch's CUDA generator, or starts at
+    `position` = (seed, offset) and leaves the generator alone."""
+    _require_device(phi, pi_in)
+    if not phi.is_contiguous() or (pi_in is not None and (not pi_in.is_contiguous() or pi_in.dtype != phi.dtype
+                                                            or pi_in.shape != phi.shape)):
+        raise NormflowHipError("phi4_hmc needs contiguous phi (C, *L) and pi_in of its shape and dtype")
+    Cn, lat, dev = phi.shape[0], tuple(phi.shape[1:]), phi.device
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"phi4_hmc: lattices of 1 to 4 axes, got {lat}")
+    n_traj = int(n_traj)
+    dh = torch.empty((max(n_traj, 0), Cn), dtype=torch.float64, device=dev)
+    accept = torch.empty((max(n_traj, 0), Cn), dtype=torch.uint8, device=dev)
+    action = torch.empty(Cn, dtype=torch.float64, device=dev)
+    record = None
+    if record_every is not None:
+        record = torch.empty((n_traj // int(record_every), Cn) + lat, dtype=phi.dtype, device=dev)
+    pi_out = torch.empty_like(phi) if want_pi else None
+    seed, offset = position if position is not None else _philox_positions(dev, 2 * max(n_traj, 1), generator)
+    _check(load().nf_phi4_hmc(_ptr(phi), _ptr(action), _ptr(pi_in), _ptr(pi_out), _ptr(dh), _ptr(accept), _ptr(record),
+                              1 if record_every is None else int(record_every), Cn, _lat4(lat), float(w0), float(w2),
+                              float(w4), int(n_md), float(dt), n_traj, int(bool(force_accept)), seed, offset,
+                              _dtype_code(phi), _stream()), "nf_phi4_hmc")
+    return dict(action=action, dh=dh, accept=accept, record=record, pi=pi_out)

@@ -1,0 +1,363 @@
+// nf_hmc.hip -- hybrid Monte Carlo for the lattice phi^4 action with the chain resident in a CU (MI355X-side extension, no
+// counterpart in the reference; the action is src/action/scalar_action.py:24-46).  For C independent chains:
+//   F(phi)(x) = 2 w2 phi(x) + 4 w4 phi(x)^3 - w0 sum_mu [phi(x + mu) + phi(x - mu)]                     (periodic)
+//   pi ~ N(0, 1)^V;  H0 = sum pi^2 / 2 + S(phi);  leapfrog of n_md steps of length dt (half kicks at both ends);
+//   H1 likewise;  accept iff log u < -(H1 - H0).
+// One workgroup per chain runs ALL n_traj trajectories of its chain in one launch.  Lane `tid` of the NT lanes owns the
+// sites tid + k NT (k < NS) and keeps their phi and pi in registers; one image of phi lives in LDS for the neighbour reads
+// (lanes of a wave read consecutive addresses along every axis: no bank conflicts away from the wrap).  An MD step is
+// "phi += dt pi | barrier | image <- phi | barrier | pi -= dt F(image)": two barriers.  The chain's phi in HBM is written
+// only when a trajectory is accepted and read back when one is rejected, so a rejected chain keeps its bits.
+// The energies are summed in double whatever the field dtype, in a fixed order (lane partial over k, wave shuffle tree,
+// waves in order): no atomics, the same inputs give the same bits, and a launch of n_traj trajectories equals n_traj
+// launches of one.  Random numbers: the streams of nf_normal_sample (momenta) and nf_block_accept (uniform), see the header.
+#include "nf_internal.h"
+
+namespace nf {
+
+constexpr int kHmcMaxLanes = 1024;
+constexpr size_t kHmcFieldBytes = 64 * 1024;       // the LDS image of one chain: V sizeof(T) <= 64 KiB
+constexpr size_t kHmcScratchBytes = 1024;          // reduction slots and the broadcast of the decision, in front of the image
+
+struct HmcPlan {
+  int64_t V;
+  int L[4];      // the extents above 1, in order, behind leading 1s: dropping an axis of extent 1 moves no site
+  int nd;        // how many there are (1 .. 4; a lattice of one site counts as one axis of extent 1)
+  int ns;        // sites per lane (1, 2, 4, 8, 16): the smallest power of two with ceil(V / ns) <= 1024
+  int nt;        // lanes per chain: ceil(V / ns) rounded up to whole waves
+  size_t lds;    // dynamic LDS of the launch
+};
+
+// The one planner: nf_phi4_hmc_supported answers from it and nf_phi4_hmc launches by it.
+static int hmc_plan(const char *what, const int32_t *lattice, int dtype, HmcPlan &p) {
+  NF_REQUIRE(lattice != nullptr, "%s: lattice is NULL", what);
+  NF_REQUIRE(dtype == NF_F32 || dtype == NF_F64, "%s: unsupported dtype %d", what, dtype);
+  const size_t elem = dtype == NF_F32 ? 4 : 8;
+  p.V = 1;
+  p.nd = 0;
+  for (int mu = 0; mu < 4; ++mu) p.L[mu] = 1;
+  for (int mu = 0; mu < 4; ++mu) {
+    NF_REQUIRE(lattice[mu] >= 1, "%s: lattice extents must be >= 1", what);
+    if (lattice[mu] > 1) {
+      for (int nu = 0; nu < 3; ++nu) p.L[nu] = p.L[nu + 1];
+      p.L[3] = lattice[mu];
+      ++p.nd;
+    }
+    p.V *= lattice[mu];
+    NF_REQUIRE(size_t(p.V) * elem <= kHmcFieldBytes,
+               "%s: a chain of the lattice (%d, %d, %d, %d) does not fit the %zu KiB LDS image of the fused kernel", what,
+               lattice[0], lattice[1], lattice[2], lattice[3], kHmcFieldBytes / 1024);
+  }
+  if (p.nd == 0) p.nd = 1;
+  p.ns = 1;
+  while ((p.V + p.ns - 1) / p.ns > kHmcMaxLanes) p.ns *= 2;
+  const int lanes = int((p.V + p.ns - 1) / p.ns);
+  p.nt = (lanes + kWave - 1) / kWave * kWave;
+  p.lds = kHmcScratchBytes + ((size_t(p.V) * elem + 15) & ~size_t(15));
+  return NF_OK;
+}
+
+struct HmcArgs {
+  void *phi;
+  double *action_out;
+  const void *pi_in;
+  void *pi_out;
+  double *dh_out;
+  uint8_t *accept_out;
+  void *record;
+  int64_t C, V;
+  int L[4];
+  double w0, w2, w4, dt;
+  int n_md, n_traj, record_every, force;
+  uint32_t k0n, k1n, k0a, k1a;   // keys of the normal and of the accept stream
+  uint64_t offset;
+};
+
+// Sum of (a, b) over the workgroup, valid in every lane and the same bits in every lane: lane partials -> shuffle tree ->
+// one slot per wave -> the waves added in order.  `slot` alternates between calls, so a slot is overwritten only after a
+// barrier that follows its last read.
+__device__ __forceinline__ void hmc_sum2(double &a, double &b, double *red, int &slot) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave, nw = blockDim.x / kWave;
+  double *r = red + slot * (2 * kHmcMaxLanes / kWave);
+  if (lane == 0) {
+    r[2 * w] = a;
+    r[2 * w + 1] = b;
+  }
+  __syncthreads();
+  a = 0.0;
+  b = 0.0;
+  for (int i = 0; i < nw; ++i) {
+    a += r[2 * i];
+    b += r[2 * i + 1];
+  }
+  slot ^= 1;
+}
+
+template <typename T, int NS, int D, int LANES>
+__global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcArgs A) {
+  extern __shared__ __align__(16) unsigned char hmc_lds[];
+  double *red = reinterpret_cast<double *>(hmc_lds);                       // 2 slots x 16 waves x 2 doubles = 512 B
+  int *s_ok = reinterpret_cast<int *>(hmc_lds + 512);
+  T *img = reinterpret_cast<T *>(hmc_lds + kHmcScratchBytes);
+  constexpr int PER = sizeof(T) == 4 ? 4 : 2;
+  const int tid = threadIdx.x, NT = blockDim.x;
+  const int V = int(A.V);
+  const int64_t c = blockIdx.x;
+  T *__restrict__ gphi = static_cast<T *>(A.phi) + c * A.V;
+  const T w0 = T(A.w0), w2x2 = T(2) * T(A.w2), w4x4 = T(4) * T(A.w4), dt = T(A.dt), hdt = T(0.5) * T(A.dt);
+  const int s3 = 1, s2 = A.L[3], s1 = A.L[3] * A.L[2], s0 = A.L[3] * A.L[2] * A.L[1];
+  const int st[4] = {s0, s1, s2, s3};
+  // A.L holds the D axes of extent > 1 (HmcPlan): axes 4 - D .. 3 have neighbours, the others are not looked at
+
+  // Slot k of a lane is site tid + k NT.  A slot past the last site shadows site V - 1: it reads what that site reads and
+  // computes what it computes, so the loops below have no divergent branch; only the stores and the energy sums ask
+  // whether the slot owns its site.  Per slot one byte of wrap flags (bit 2 mu: x_mu == 0, bit 2 mu + 1: x_mu == L_mu - 1),
+  // four slots per register.  The neighbour indices are three instructions each from a flag bit; left alone the compiler
+  // hoists all 8 NS of them (and the global addresses of the passes at a trajectory's end) out of the loops and spills,
+  // so every pass starts from `fresh()`: an empty asm that "writes" the lane index and the flag words keeps the index
+  // arithmetic inside the loop.  What the compiler reports with that (1024-lane bound = 128 registers; -Rpass-analysis=
+  // kernel-resource-usage): no scratch for float with 1 .. 8 sites per lane and double with 1 .. 4; float x 16 (24^3, 128^2)
+  // 116 B per lane and double x 8 (8192 sites) 200 B per lane, spent in this prologue (the coordinate divisions) and in the
+  // momentum draw of a trajectory (the double sincos); the MD loop of float x 16 has no scratch access, that of double x 8
+  // one reload per step.
+  uint32_t flg[(NS + 3) / 4] = {};
+  T phi[NS], pi[NS];
+  auto site = [&](int tv, int k) { const int i = tv + k * NT; return i < V ? i : V - 1; };
+  auto owns = [&](int tv, int k) { return tv + k * NT < V; };
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    const int i = site(tid, k);
+    int r = i;
+    const int x3 = r % A.L[3]; r /= A.L[3];
+    const int x2 = r % A.L[2]; r /= A.L[2];
+    const int x1 = r % A.L[1];
+    const int x0 = r / A.L[1];
+    const uint32_t f = uint32_t(x0 == 0) | uint32_t(x0 == A.L[0] - 1) << 1 | uint32_t(x1 == 0) << 2 |
+                       uint32_t(x1 == A.L[1] - 1) << 3 | uint32_t(x2 == 0) << 4 | uint32_t(x2 == A.L[2] - 1) << 5 |
+                       uint32_t(x3 == 0) << 6 | uint32_t(x3 == A.L[3] - 1) << 7;
+    flg[k >> 2] |= f << (8 * (k & 3));
+    phi[k] = gphi[i];
+    pi[k] = T(0);
+    __builtin_amdgcn_sched_barrier(0);                   // one slot's divisions at a time
+  }
+  auto fresh = [&]() {
+#pragma unroll
+    for (int w = 0; w < (NS + 3) / 4; ++w) asm volatile("" : "+v"(flg[w]));
+    int tv = tid;
+    asm volatile("" : "+v"(tv));
+    return tv;
+  };
+  auto back = [&](int i, uint32_t f, int mu) { return i + ((f >> (2 * mu)) & 1u ? st[mu] * (A.L[mu] - 1) : -st[mu]); };
+  auto fwd = [&](int i, uint32_t f, int mu) { return i + ((f >> (2 * mu + 1)) & 1u ? -st[mu] * (A.L[mu] - 1) : st[mu]); };
+
+  // pi -= step * F(phi), the neighbours from the image (which holds phi)
+  auto kick = [&](T step) {
+    const int tv = fresh();
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      const int i = site(tv, k);
+      const uint32_t f = (flg[k >> 2] >> (8 * (k & 3))) & 255u;
+      T nb = T(0);
+#pragma unroll
+      for (int mu = 4 - D; mu < 4; ++mu) nb += img[back(i, f, mu)] + img[fwd(i, f, mu)];
+      const T p = phi[k];
+      pi[k] -= step * (w2x2 * p + w4x4 * p * p * p - w0 * nb);
+      __builtin_amdgcn_sched_barrier(0);               // one slot's 8 reads in flight at a time: the registers go to phi and pi
+    }
+  };
+  // lane partials of sum pi^2 / 2 and of S(phi) = sum (w2 + w4 phi^2) phi^2 - w0 phi sum_mu phi(x - mu), in double on the
+  // values cast to double (explicit fma: the arithmetic does not depend on how the compiler contracts)
+  auto energy = [&](double &kin, double &pot) {
+    kin = 0.0;
+    pot = 0.0;
+    const int tv = fresh();
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      const int i = site(tv, k);
+      const uint32_t f = (flg[k >> 2] >> (8 * (k & 3))) & 255u;
+      double nb = 0.0;
+#pragma unroll
+      for (int mu = 4 - D; mu < 4; ++mu) nb += double(img[back(i, f, mu)]);
+      const double p = double(phi[k]), q = double(pi[k]), p2 = p * p;
+      const bool mine = owns(tv, k);
+      kin += mine ? 0.5 * q * q : 0.0;
+      pot += mine ? __builtin_fma(__builtin_fma(A.w4, p2, A.w2), p2, -(A.w0 * p) * nb) : 0.0;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  auto put_image = [&]() {
+    const int tv = fresh();
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+      if (owns(tv, k)) img[tv + k * NT] = phi[k];
+  };
+
+  double s_cur = 0.0;
+  int slot = 0;
+  const int64_t ngroups = (A.V + PER - 1) / PER;
+  for (int t = 0; t < A.n_traj; ++t) {
+    // ---- momenta: the image is the transit buffer from the Philox groups (PER consecutive sites) to the lanes' sites
+    if (A.pi_in) {
+      const T *__restrict__ gpi = static_cast<const T *>(A.pi_in) + c * A.V;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) pi[k] = gpi[site(tid, k)];
+    } else {
+      __syncthreads();                                   // the previous trajectory's reads of the image are done
+      const uint64_t off = A.offset + 2 * uint64_t(t);
+      for (int64_t q = tid; q < ngroups; q += NT) {
+        const uint64_t g = uint64_t(c) * uint64_t(ngroups) + uint64_t(q);
+        uint32_t r[4] = {uint32_t(g), uint32_t(g >> 32), uint32_t(off), uint32_t(off >> 32)};
+        philox4x32_10(r, A.k0n, A.k1n);
+        T z[PER];
+        philox_normals<T>(r, z);
+#pragma unroll
+        for (int j = 0; j < PER; ++j)
+          if (q * PER + j < A.V) img[q * PER + j] = z[j];
+      }
+      __syncthreads();
+      const int tv = fresh();
+#pragma unroll
+      for (int k = 0; k < NS; ++k) pi[k] = img[site(tv, k)];
+    }
+    __syncthreads();                                     // the momenta are read (with pi_in: nothing reads the image yet)
+    put_image();
+    __syncthreads();
+    double k0, e0;
+    energy(k0, e0);
+    hmc_sum2(k0, e0, red, slot);
+    // ---- leapfrog
+    kick(hdt);
+    for (int k = 1; k <= A.n_md; ++k) {
+#pragma unroll
+      for (int j = 0; j < NS; ++j) phi[j] += dt * pi[j];
+      __syncthreads();                                   // every lane has read the old image
+      put_image();
+      __syncthreads();
+      kick(k == A.n_md ? hdt : dt);
+    }
+    double k1, e1;
+    energy(k1, e1);
+    hmc_sum2(k1, e1, red, slot);
+    // ---- the decision: one lane decides, the workgroup reads it from LDS
+    if (tid == 0) {
+      const double dh = (k1 + e1) - (k0 + e0);
+      const uint64_t offa = A.offset + 2 * uint64_t(t) + 1;
+      uint32_t r[4] = {uint32_t(uint64_t(c)), uint32_t(uint64_t(c) >> 32), uint32_t(offa), uint32_t(offa >> 32)};
+      philox4x32_10(r, A.k0a, A.k1a);
+      const double logu = ::log(philox_u53(r[0], r[1]));
+      const bool ok = A.force || logu < -dh;             // a NaN energy difference rejects
+      A.dh_out[int64_t(t) * A.C + c] = dh;
+      A.accept_out[int64_t(t) * A.C + c] = uint8_t(ok);
+      *s_ok = int(ok);
+    }
+    __syncthreads();
+    const bool ok = *s_ok != 0;
+    s_cur = ok ? e1 : e0;
+    const int tg = fresh();                              // the global addresses of the passes below are not kept either
+    if (t + 1 == A.n_traj && A.pi_out) {
+      T *__restrict__ gpo = static_cast<T *>(A.pi_out) + c * A.V;
+#pragma unroll
+      for (int k = 0; k < NS; ++k)
+        if (owns(tg, k)) gpo[tg + k * NT] = pi[k];
+    }
+    if (ok) {
+#pragma unroll
+      for (int k = 0; k < NS; ++k)
+        if (owns(tg, k)) gphi[tg + k * NT] = phi[k];
+    } else {
+      // a lane reads back what it stored itself, or what nobody has written in this launch; a shadow slot reads site
+      // V - 1, which its owner may be storing in this very pass -- on accept only, and then no slot reads
+#pragma unroll
+      for (int k = 0; k < NS; ++k) phi[k] = gphi[site(tg, k)];
+    }
+    if (A.record && (t + 1) % A.record_every == 0) {
+      T *__restrict__ rec = static_cast<T *>(A.record) + (int64_t((t + 1) / A.record_every - 1) * A.C + c) * A.V;
+#pragma unroll
+      for (int k = 0; k < NS; ++k)
+        if (owns(tg, k)) rec[tg + k * NT] = phi[k];
+    }
+  }
+  if (tid == 0) A.action_out[c] = s_cur;
+}
+
+template <typename T, int NS, int D, int LANES>
+static int launch_hmc(const HmcArgs &A, const HmcPlan &p, hipStream_t s) {
+  auto kern = phi4_hmc_kernel<T, NS, D, LANES>;
+  if (p.lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          int(p.lds)) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("nf_phi4_hmc: cannot raise the dynamic LDS limit to %zu B", p.lds);
+    return NF_ELAUNCH;
+  }
+  hipLaunchKernelGGL(kern, dim3(unsigned(A.C)), dim3(unsigned(p.nt)), p.lds, s, A);
+  return check_launch("nf_phi4_hmc");
+}
+
+template <typename T, int D>
+static int dispatch_ns(const HmcArgs &A, const HmcPlan &p, hipStream_t s) {
+  switch (p.ns) {
+    // one site per lane on up to 256 lanes (V <= 256) is compiled for 256 lanes: twice the registers of the 1024-lane bound
+    case 1: return p.nt <= 256 ? launch_hmc<T, 1, D, 256>(A, p, s) : launch_hmc<T, 1, D, kHmcMaxLanes>(A, p, s);
+    case 2: return launch_hmc<T, 2, D, kHmcMaxLanes>(A, p, s);     // more than one site per lane: always above 512 lanes
+    case 4: return launch_hmc<T, 4, D, kHmcMaxLanes>(A, p, s);
+    case 8: return launch_hmc<T, 8, D, kHmcMaxLanes>(A, p, s);
+    case 16:
+      if constexpr (sizeof(T) == 4) return launch_hmc<T, 16, D, kHmcMaxLanes>(A, p, s);   // 8-byte fields end at 8 sites per lane
+  }
+  set_error("nf_phi4_hmc: no kernel for %d sites per lane", p.ns);
+  return NF_EINVAL;
+}
+
+template <typename T>
+static int dispatch_hmc(const HmcArgs &A, const HmcPlan &p, hipStream_t s) {
+  switch (p.nd) {
+    case 1: return dispatch_ns<T, 1>(A, p, s);
+    case 2: return dispatch_ns<T, 2>(A, p, s);
+    case 3: return dispatch_ns<T, 3>(A, p, s);
+    default: return dispatch_ns<T, 4>(A, p, s);
+  }
+}
+
+}  // namespace nf
+
+using namespace nf;
+
+extern "C" int nf_phi4_hmc_supported(const int32_t *lattice, int dtype) {
+  HmcPlan p;
+  return hmc_plan("nf_phi4_hmc_supported", lattice, dtype, p) == NF_OK ? 1 : 0;
+}
+
+extern "C" int nf_phi4_hmc(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                           uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
+                           double w0, double w2, double w4, int n_md, double dt, int n_traj, int force_accept,
+                           uint64_t seed, uint64_t offset, int dtype, void *stream) {
+  NF_REQUIRE(phi && action_out && dh_out && accept_out, "nf_phi4_hmc: NULL pointer argument");
+  NF_REQUIRE(C >= 1 && C <= 65535, "nf_phi4_hmc: C (%lld) must be in 1 .. 65535", (long long)C);
+  NF_REQUIRE(n_md >= 1 && n_traj >= 1 && record_every >= 1,
+             "nf_phi4_hmc: n_md (%d), n_traj (%d) and record_every (%d) must be >= 1", n_md, n_traj, record_every);
+  NF_REQUIRE(!pi_in || n_traj == 1, "nf_phi4_hmc: pi_in replaces the momenta of ONE trajectory (n_traj = %d)", n_traj);
+  HmcPlan p;
+  const int rc = hmc_plan("nf_phi4_hmc", lattice, dtype, p);
+  if (rc) return rc;
+  // an MD step costs two barriers however few the sites: below 256 sites the steps, not the sites, set the time; and the
+  // chains beyond the resident ones wait for a free CU: the time grows with every further 1024 chains
+  const int64_t work = int64_t(n_md) * int64_t(n_traj) * (p.V > 256 ? p.V : 256) * ((C + 1023) / 1024);
+  NF_REQUIRE(work <= NF_HMC_MAX_WORK,
+             "nf_phi4_hmc: n_md n_traj max(V, 256) ceil(C / 1024) = %lld exceeds NF_HMC_MAX_WORK (%lld): split the run into "
+             "several launches", (long long)work, (long long)NF_HMC_MAX_WORK);
+  HmcArgs A{};
+  A.phi = phi; A.action_out = action_out; A.pi_in = pi_in; A.pi_out = pi_out; A.dh_out = dh_out; A.accept_out = accept_out;
+  A.record = record; A.C = C; A.V = p.V;
+  for (int mu = 0; mu < 4; ++mu) A.L[mu] = p.L[mu];
+  A.w0 = p.V > 1 ? w0 : 0.0;     // the one site of a lattice of one site is read as its own neighbour: weight 0
+  A.w2 = w2; A.w4 = w4; A.dt = dt;
+  A.n_md = n_md; A.n_traj = n_traj; A.record_every = record_every; A.force = force_accept != 0;
+  A.k0n = uint32_t(seed); A.k1n = uint32_t(seed >> 32) ^ NF_PHILOX_KEY_DOMAIN;
+  A.k0a = uint32_t(seed); A.k1a = uint32_t(seed >> 32) ^ NF_PHILOX_ACCEPT_DOMAIN;
+  A.offset = offset;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return dtype == NF_F32 ? dispatch_hmc<float>(A, p, s) : dispatch_hmc<double>(A, p, s);
+}

@@ -1,1 +1,2 @@
 from .mcmc import MCMCSampler, BlockedMCMCSampler, MCMCHistory, Metropolis, ModifiedMetropolis
+from .hmc import HMCSampler, HMCHistory

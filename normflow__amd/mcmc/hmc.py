@@ -1,0 +1,215 @@
+"""Hybrid Monte Carlo on the target exp(-S) itself (MI355X-side extension, no counterpart in the reference): an exact
+sampler that does not go through the flow, for checking what the flow-based samplers produce at lambda != 0, for seeding
+them and for making training configurations.
+
+One definition, two implementations.  For C independent chains, per trajectory:
+    F(phi) = dS/dphi;  pi ~ N(0, 1);  H0 = sum pi^2 / 2 + S(phi)
+    pi -= (dt / 2) F(phi);  k = 1 .. n_md: phi += dt pi, pi -= (dt, or dt / 2 when k = n_md) F(phi)
+    H1 likewise;  accept iff log u < -(H1 - H0), u in (0, 1];  a rejected chain keeps its phi bit for bit.
+The energies are taken in double whatever the field dtype.
+  * fused:    nf_phi4_hmc (nf_hmc.hip), a whole run of trajectories of a chain in one launch with the chain resident in a
+              CU -- ScalarPhi4Action on a HIP device, lattices nf_phi4_hmc_supported takes;
+  * composed: the same algorithm from the pieces the package already has (nf_normal_sample for the momenta, the force by
+              autograd through `model.action`, torch ops for the updates, nf_block_accept for the decision and the
+              restore) -- any lattice, any action object; on CPU tensors with torch's CPU generator.
+On the device both draw from the same Philox positions of torch's CUDA generator (two per trajectory: momenta, uniform),
+so from the same seed they walk the same chain up to rounding."""
+import torch
+
+from .. import _hip
+from ..action.scalar_action import ScalarPhi4Action
+
+
+class HMCHistory:
+    _KEYS = ('accept_rate', 'exp_mdh', 'dh_rms')
+
+    def __init__(self):
+        self.reset_history()
+
+    def reset_history(self):
+        for k in self._KEYS:
+            setattr(self, k, [])
+
+
+class HMCSampler:
+    """`sample(batch_size, n_chains=C, n_md=10, dt=0.1, n_skip=0, path=None)` -> (batch_size, *L): row r is recorded
+    trajectory r // C of chain r % C (the layout of the other samplers), with n_skip unrecorded trajectories before every
+    recorded one.  `_ref` keeps the chains' phi (C, *L) and S (C) float64; the next call continues them, `start()` sets
+    them.  `path`: None = the fused kernel where it applies, else composed; 'fused' / 'composed' force one.
+    `history` gets, per call, accept_rate, exp_mdh (the mean of exp(-dH), 1 for an exact integrator of the measure) and
+    dh_rms, from one device-to-host read; `last` holds the call's dH and accept flags (trajectories, C) on the device."""
+
+    def __init__(self, model):
+        self._model = model
+        self.history = HMCHistory()
+        self._ref = dict(sample=None, action=None)
+        self.last = dict(dh=None, accept=None)
+
+    # ---- public
+    @torch.no_grad()
+    def sample(self, batch_size=1, **kwargs):
+        return self.sample_(batch_size=batch_size, **kwargs)[0]
+
+    @torch.no_grad()
+    def sample_(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None):
+        """(y, logp): batch_size // n_chains recorded trajectories of every chain and logp = -S(y) in the field dtype."""
+        n_chains = int(n_chains)
+        if n_chains < 1 or batch_size < 1 or batch_size % n_chains != 0:
+            raise ValueError(f"batch_size ({batch_size}) must be a positive multiple of n_chains ({n_chains})")
+        n_md, every = int(n_md), int(n_skip) + 1
+        if n_md < 1 or every < 1:
+            raise ValueError(f"n_md ({n_md}) must be >= 1 and n_skip ({n_skip}) >= 0")
+        s = self._ref['sample']
+        if s is None or s.shape[0] != n_chains:
+            print("Starting from scratch")
+            self.start(n_chains=n_chains)
+        phi, S = self._ref['sample'], self._ref['action']
+        fused = self._choose(phi, path)
+        rows = batch_size // n_chains
+        out = torch.empty((rows,) + tuple(phi.shape), dtype=phi.dtype, device=phi.device)
+        if fused:
+            phi, S, dh, acc = self._run_fused(phi, rows, every, n_md, dt, out)
+        else:
+            phi, S, dh, acc = self._run_composed(phi, S, rows, every, n_md, dt, out)
+        self._ref.update(sample=phi, action=S)
+        self.last = dict(dh=dh, accept=acc)          # (trajectories, C) of this call, left on the device
+        stats = torch.stack([acc.double().mean(), torch.exp(-dh).mean(), dh.square().mean().sqrt()]).cpu()   # the one read
+        for key, val in zip(HMCHistory._KEYS, stats.tolist()):
+            getattr(self.history, key).append(val)
+        y = out.reshape((batch_size,) + tuple(phi.shape[1:]))
+        return y, (-self._model.action(y)).to(y.dtype)
+
+    @torch.no_grad()
+    def start(self, phi=None, n_chains=1):
+        """Start the chains from phi (C, *L) -- flow samples, say -- or from model.prior.sample(n_chains)."""
+        if phi is None:
+            phi = self._model.prior.sample(int(n_chains))
+        phi = phi.detach().clone().contiguous()
+        if phi.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"HMCSampler supports float32 and float64 fields, got {phi.dtype}")
+        self._ref.update(sample=phi, action=self._model.action(phi.double()).double())
+        return self
+
+    @torch.no_grad()
+    def trajectory(self, phi, n_md=10, dt=0.1, pi=None, force_accept=False, path=None, position=None):
+        """ONE trajectory of the chains phi (C, *L), which are left alone; the stored chains are not touched.  Returns
+        dict(phi = the states after the decision, pi = the momenta at the end of the trajectory, dh (C) float64,
+        accept (C) uint8, action (C) float64 = S of the returned states).  `pi` replaces the drawn momenta.  `position`
+        = (seed, offset) fixes the Philox position of a device run instead of taking it from torch's CUDA generator."""
+        phi = phi.detach().clone().contiguous()
+        if self._choose(phi, path):
+            r = _hip.phi4_hmc(phi, *self._coef(phi.shape[1:]), n_md, dt, n_traj=1, pi_in=pi, want_pi=True,
+                              force_accept=force_accept, position=position)
+            return dict(phi=phi, pi=r['pi'], dh=r['dh'][0], accept=r['accept'][0], action=r['action'])
+        gen = None
+        if position is not None:
+            gen = torch.Generator(device=phi.device)
+            gen.manual_seed(position[0])
+            gen.set_offset(4 * position[1])
+        S0 = self._model.action(phi.double()).double()
+        phi, S, dh, acc, pi = self._trajectory_composed(phi, S0, n_md, dt, pi=pi, force_accept=force_accept, generator=gen)
+        return dict(phi=phi, pi=pi, dh=dh, accept=acc, action=S)
+
+    # ---- which path
+    def _fused_applies(self, phi):
+        return (isinstance(self._model.action, ScalarPhi4Action) and phi.is_cuda
+                and _hip.hmc_supported(tuple(phi.shape[1:]), phi.dtype))
+
+    def _choose(self, phi, path):
+        if path not in (None, 'fused', 'composed'):
+            raise ValueError(f"path must be None, 'fused' or 'composed', got {path!r}")
+        if path == 'composed':
+            return False
+        ok = self._fused_applies(phi)
+        if path == 'fused' and not ok:
+            raise _hip.NormflowHipError(
+                "HMCSampler(path='fused'): nf_phi4_hmc takes a ScalarPhi4Action on a HIP device and a lattice whose chain "
+                f"fits its LDS image; got {type(self._model.action).__name__}, a {phi.device} tensor of shape "
+                f"{tuple(phi.shape[1:])} and {phi.dtype}")
+        return ok
+
+    def _coef(self, lat):
+        """(w0, w2, w4) as nf_phi4_hmc takes them: ScalarPhi4Action.action's rule for a user axis of extent 1 (it is its own
+        neighbour: -w0 phi^2) folded into w2, as for nf_phi4_action."""
+        w0, w2, w4 = self._model.action.get_coef(len(lat))
+        own = sum(1 for n in lat if n == 1)
+        return float(w0), float(w2 - own * w0), float(w4)
+
+    # ---- fused
+    def _run_fused(self, phi, rows, every, n_md, dt, out):
+        """rows * every trajectories in as few launches as NF_HMC_MAX_WORK allows."""
+        phi = phi.clone()
+        coef = self._coef(phi.shape[1:])
+        V = phi[0].numel()
+        per = max(1, _hip.HMC_MAX_WORK // (n_md * max(V, 256) * ((phi.shape[0] + 1023) // 1024)))   # trajectories per launch
+        dhs, accs, action = [], [], None
+        if per >= every:
+            step, r0 = per // every, 0
+            while r0 < rows:
+                k = min(step, rows - r0)
+                r = _hip.phi4_hmc(phi, *coef, n_md, dt, n_traj=k * every, record_every=every)
+                out[r0:r0 + k] = r['record']
+                dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
+                r0 += k
+        else:
+            for r0 in range(rows):
+                left = every
+                while left:
+                    k = min(per, left)
+                    r = _hip.phi4_hmc(phi, *coef, n_md, dt, n_traj=k)
+                    dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
+                    left -= k
+                out[r0] = phi
+        return phi, action, torch.cat(dhs), torch.cat(accs)
+
+    # ---- composed
+    def _force(self, phi):
+        with torch.enable_grad():
+            p = phi.detach().requires_grad_(True)
+            (F,) = torch.autograd.grad(self._model.action(p).sum(), p)
+        return F
+
+    def _energy(self, phi, pi):
+        return 0.5 * pi.double().square().flatten(1).sum(dim=1) + self._model.action(phi.double()).double()
+
+    def _trajectory_composed(self, phi, S0, n_md, dt, pi=None, force_accept=False, generator=None):
+        C, shape = phi.shape[0], tuple(phi.shape[1:])
+        on_device = phi.is_cuda
+        if pi is None:
+            if on_device:
+                pi = _hip.normal_sample(None, None, C, shape, phi.dtype, phi.device, generator=generator)[0]
+            else:
+                pi = torch.randn(phi.shape, dtype=phi.dtype, device=phi.device)
+        elif on_device:
+            _hip._philox_position(phi.device, generator)      # handed-in momenta still take the position of the draw
+        H0 = 0.5 * pi.double().square().flatten(1).sum(dim=1) + S0
+        new = phi
+        pi = pi - (0.5 * dt) * self._force(new)
+        for k in range(1, n_md + 1):
+            new = new + dt * pi
+            pi = pi - (dt if k < n_md else 0.5 * dt) * self._force(new)
+        S1 = self._model.action(new.double()).double()
+        dh = 0.5 * pi.double().square().flatten(1).sum(dim=1) + S1 - H0
+        if on_device:
+            new = new.contiguous()
+            acc = torch.empty(C, dtype=torch.uint8, device=phi.device)
+            # the whole field as one block: accept iff log u < 0 - (dH - 0); the kernel restores the rejected chains
+            _hip.block_accept(new, phi.reshape(C, -1).contiguous(), dh.to(phi.dtype), torch.zeros(C, dtype=phi.dtype, device=phi.device),
+                              torch.zeros(C, dtype=torch.float64, device=phi.device), acc, new[0].numel(), 0,
+                              force_accept=force_accept, generator=generator)
+            ok = acc.bool()
+        else:
+            logu = torch.log(1.0 - torch.rand(C, dtype=torch.float64, device=phi.device))       # u in (0, 1]
+            ok = (logu < -dh) | bool(force_accept)
+            new = torch.where(ok.reshape((C,) + (1,) * len(shape)), new, phi)
+            acc = ok.to(torch.uint8)
+        return new, torch.where(ok, S1, S0), dh, acc, pi
+
+    def _run_composed(self, phi, S, rows, every, n_md, dt, out):
+        dhs, accs = [], []
+        for t in range(rows * every):
+            phi, S, dh, acc, _ = self._trajectory_composed(phi, S, n_md, dt)
+            dhs.append(dh); accs.append(acc)
+            if (t + 1) % every == 0:
+                out[(t + 1) // every - 1] = phi
+        return phi, S, torch.stack(dhs), torch.stack(accs)

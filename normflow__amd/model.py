@@ -7,7 +7,7 @@ import torch
 
 from .device import ModelDeviceHandler
 from .fitter import Fitter
-from .mcmc import MCMCSampler, BlockedMCMCSampler
+from .mcmc import MCMCSampler, BlockedMCMCSampler, HMCSampler
 
 
 class Posterior:
@@ -65,6 +65,7 @@ class Posterior:
 class Model:
     """Model(prior=..., net_=..., action=...): `.fit(...)` trains, `.posterior.sample(n)` draws,
     `.mcmc.sample(n)` draws with Metropolis correction, `.blocked_mcmc.sample(n, n_blocks=k)` with block-update Metropolis,
+    `.hmc.sample(n, n_chains=C)` with hybrid Monte Carlo on the action itself (no flow involved),
     `.device_handler` places / parallelises."""
 
     def __init__(self, *, prior, net_, action, name=None):
@@ -73,6 +74,7 @@ class Model:
         self.posterior = self.raw_dist = Posterior(self)
         self.mcmc = MCMCSampler(self)
         self.blocked_mcmc = BlockedMCMCSampler(self)
+        self.hmc = HMCSampler(self)
         self.device_handler = ModelDeviceHandler(self)
 
     def transform(self, x):

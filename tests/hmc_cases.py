@@ -1,0 +1,96 @@
+"""Shared by tests/test_hmc_host.py and tests/test_hmc.py: the fp64 torch restatement of the HMC trajectory of
+normflow__amd/mcmc/hmc.py (written from its definition with torch.roll, none of the package's code), the accept uniforms
+restated with the oracle's Philox, the exact <phi^2> of the four-site chain by quadrature, and the model builder."""
+import numpy as np
+import torch
+
+import normflow__amd as nf
+from normflow__amd.action import ScalarPhi4Action
+from normflow__amd.prior import NormalPrior
+from oracle import nf_oracle as O
+
+ACCEPT_DOMAIN = 0x6E666163          # NF_PHILOX_ACCEPT_DOMAIN
+INTERACTING = dict(kappa=0.67, m_sq=-2.68, lambd=0.5)
+FREE = dict(kappa=0.25, m_sq=1.5, lambd=0.0)
+FREE_PHI2 = 0.5164                  # tr K^-1 / V of the 16-site free chain (tests/test_mcmc_chains.py)
+
+
+def model(lattice, dtype, device, **couplings):
+    prior = NormalPrior(loc=torch.zeros(lattice, dtype=dtype, device=device),
+                        scale=torch.ones(lattice, dtype=dtype, device=device))
+    return nf.Model(net_=None, prior=prior, action=ScalarPhi4Action(**couplings))
+
+
+def ref_action(phi, action):
+    """S of (C, *L) fp64 configurations: the reference's formula, every axis rolled (an axis of extent 1 onto itself)."""
+    d = phi.ndim - 1
+    w0, w2, w4 = action.get_coef(d)
+    S = (w2 * phi ** 2 + w4 * phi ** 4).flatten(1).sum(1)
+    for mu in range(1, d + 1):
+        S = S - w0 * (phi * phi.roll(1, dims=mu)).flatten(1).sum(1)
+    return S
+
+
+def ref_force(phi, action):
+    d = phi.ndim - 1
+    w0, w2, w4 = action.get_coef(d)
+    F = 2 * w2 * phi + 4 * w4 * phi ** 3
+    for mu in range(1, d + 1):
+        F = F - w0 * (phi.roll(1, dims=mu) + phi.roll(-1, dims=mu))
+    return F
+
+
+def ref_trajectory(phi, pi, action, n_md, dt):
+    """(phi1, pi1, dH) of one leapfrog trajectory in fp64 on the CPU."""
+    phi, pi = phi.detach().double().cpu(), pi.detach().double().cpu()
+    H0 = 0.5 * (pi ** 2).flatten(1).sum(1) + ref_action(phi, action)
+    pi = pi - 0.5 * dt * ref_force(phi, action)
+    for k in range(1, n_md + 1):
+        phi = phi + dt * pi
+        pi = pi - (dt if k < n_md else 0.5 * dt) * ref_force(phi, action)
+    H1 = 0.5 * (pi ** 2).flatten(1).sum(1) + ref_action(phi, action)
+    return phi, pi, H1 - H0
+
+
+def log_uniforms(seed, offset, n):
+    """log u_c of the accept step at Philox position (seed, offset): counter (lo32 c, hi32 c, lo32 offset, hi32 offset),
+    key (lo32 seed, hi32 seed ^ accept domain), u = ((r0 << 21 ^ r1 >> 11) + 1) 2^-53."""
+    c = np.arange(n, dtype=np.uint64)
+    ctr = np.stack([c & np.uint64(0xFFFFFFFF), c >> np.uint64(32), np.full_like(c, offset & 0xFFFFFFFF),
+                    np.full_like(c, (offset >> 32) & 0xFFFFFFFF)], axis=-1).astype(np.uint32)
+    key = np.broadcast_to(np.array([seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ ACCEPT_DOMAIN], dtype=np.uint32),
+                          (n, 2))
+    r = O.philox4x32_10(ctr, key).astype(np.uint64)
+    a = (r[:, 0] << np.uint64(21)) ^ (r[:, 1] >> np.uint64(11))
+    return np.log((a.astype(np.float64) + 1.0) * 2.0 ** -53)
+
+
+_QUAD = {}
+
+
+def quadrature_phi2(n=49, half_width=4.5):
+    """<phi^2> (per site) of the four-site periodic chain at INTERACTING: n^4-point trapezoid of exp(-S) on
+    [-half_width, half_width]^4, S from ScalarPhi4Action.action on the grid (one slab of the first axis at a time)."""
+    if (n, half_width) not in _QUAD:
+        action = ScalarPhi4Action(**INTERACTING)
+        x = torch.linspace(-half_width, half_width, n, dtype=torch.float64, device='cpu')
+        w = torch.ones(n, dtype=torch.float64, device='cpu')
+        w[0] = w[-1] = 0.5
+        g = torch.cartesian_prod(x, x, x)
+        wg = torch.cartesian_prod(w, w, w).prod(1)
+        z = num = 0.0
+        for x0, w0 in zip(x.tolist(), w.tolist()):
+            pts = torch.cat([torch.full((g.shape[0], 1), x0, dtype=torch.float64, device='cpu'), g], dim=1)
+            e = torch.exp(-action.action(pts)) * wg * w0
+            z += e.sum().item()
+            num += (e * (pts ** 2).mean(1)).sum().item()
+        _QUAD[(n, half_width)] = num / z
+    return _QUAD[(n, half_width)]
+
+
+def chain_stats(y, n_chains, drop):
+    """(mean, standard error across chains) of <phi^2> from sampler rows (row r = trajectory r // C of chain r % C)."""
+    rows = y.shape[0] // n_chains
+    y = y.detach().double().cpu().reshape(rows, n_chains, -1)[drop:]
+    per_chain = (y ** 2).mean(dim=(0, 2))
+    return per_chain.mean().item(), per_chain.std().item() / n_chains ** 0.5

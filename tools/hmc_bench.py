@@ -1,0 +1,89 @@
+"""Trajectories per second of HMCSampler's two paths on one GPU, in one run (HIP events after a warm-up, no_grad):
+  fused     nf_phi4_hmc: `--traj` trajectories of every chain in ONE launch (the chain resident in a CU)
+  composed  the same algorithm from nf_normal_sample, the action and its VJP, torch ops and nf_block_accept,
+            trajectory by trajectory (what the sampler runs where the fused kernel does not apply)
+at n_md = 10, dt = 0.1, on 16^2 x 512 chains and 16^3 x 1024 chains, fp32 and fp64.  Also the fused kernel's time per MD
+step and site: the time of the bare launch / (chains * trajectories * n_md * V); it contains the momentum draw, the two
+energy passes and the accept step of every trajectory.  The sampler calls also record every trajectory, compute log p of
+the rows and read the statistics back.  The three are timed alternately, `--reps` times each; the figures are medians.
+
+    python tools/hmc_bench.py [--reps 5] [--traj 50] [--composed-traj 5]
+Prints one JSON line per shape and dtype."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+os.environ.setdefault("NORMFLOW_AMD_KEEP_TORCH_DEFAULTS", "1")
+import torch  # noqa: E402
+
+import normflow__amd as nf  # noqa: E402
+from normflow__amd import _hip  # noqa: E402
+from normflow__amd.prior import NormalPrior  # noqa: E402
+from normflow__amd.action import ScalarPhi4Action  # noqa: E402
+
+DEV = torch.device("cuda:0")
+N_MD, DT = 10, 0.1
+SHAPES = [((16, 16), 512), ((16, 16, 16), 1024)]
+
+
+def _ms(f):
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    f()
+    t1.record()
+    t1.synchronize()
+    return t0.elapsed_time(t1)
+
+
+def measure(lattice, C, dtype, reps, n_traj, n_traj_composed):
+    prior = NormalPrior(loc=torch.zeros(lattice, dtype=dtype, device=DEV), scale=torch.ones(lattice, dtype=dtype, device=DEV))
+    model = nf.Model(net_=None, prior=prior, action=ScalarPhi4Action(kappa=0.67, m_sq=-2.68, lambd=0.5))
+    s = model.hmc
+    assert _hip.hmc_supported(lattice, dtype)
+    torch.manual_seed(0)
+    s.start(n_chains=C)
+    fused = lambda: s.sample(n_traj * C, n_chains=C, n_md=N_MD, dt=DT, path='fused')
+    composed = lambda: s.sample(n_traj_composed * C, n_chains=C, n_md=N_MD, dt=DT, path='composed')
+    coef = s._coef(lattice)
+    kernel = lambda: _hip.phi4_hmc(s._ref['sample'].clone(), *coef, N_MD, DT, n_traj=n_traj)      # the launch alone, on a copy
+    with torch.no_grad():
+        for _ in range(2):                      # warm-up: code objects, the allocator, and the chains thermalise
+            fused()
+            composed()
+        kernel()
+        torch.cuda.synchronize()
+        tf, tc, tk = [], [], []
+        for _ in range(reps):                   # alternate them, so that a drift of the machine hits all
+            tf.append(_ms(fused))
+            tc.append(_ms(composed))
+            tk.append(_ms(kernel))
+    V = prior.nvar
+    ms_f, ms_c, ms_k = statistics.median(tf), statistics.median(tc), statistics.median(tk)
+    per_f, per_c = ms_f / n_traj, ms_c / n_traj_composed          # ms per trajectory of all C chains
+    return dict(lattice=list(lattice), chains=C, dtype=str(dtype).replace("torch.", ""), n_md=N_MD, dt=DT,
+                fused_traj_per_s=round(C / per_f * 1e3, 1), composed_traj_per_s=round(C / per_c * 1e3, 1),
+                fused_over_composed=round(per_c / per_f, 2),
+                fused_ms_per_call=round(ms_f, 3), fused_traj_per_call=n_traj, fused_ms_spread=[round(min(tf), 3), round(max(tf), 3)],
+                composed_ms_per_traj=round(per_c, 3), composed_ms_spread=[round(min(tc) / n_traj_composed, 3), round(max(tc) / n_traj_composed, 3)],
+                kernel_ms_per_launch=round(ms_k, 3),
+                fused_ns_per_md_step_site=round(ms_k * 1e6 / (C * n_traj * N_MD * V), 5),
+                accept_rate=round(s.history.accept_rate[-2], 3))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--traj", type=int, default=50, help="trajectories per fused call (one launch)")
+    ap.add_argument("--composed-traj", type=int, default=5, help="trajectories per composed call")
+    a = ap.parse_args()
+    for lattice, C in SHAPES:
+        for dtype in (torch.float32, torch.float64):
+            print(json.dumps(measure(lattice, C, dtype, a.reps, a.traj, a.composed_traj)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
