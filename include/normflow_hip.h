@@ -667,7 +667,53 @@ int nf_phi4_hmc(void *phi, double *action_out, const void *pi_in, void *pi_out, 
                 int n_md, double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset, int dtype,
                 void *stream);
 
-/* ---- VJP of the conv layer (K5) ---------------------------------------------------------------
+/* ---- the same hybrid Monte Carlo with the chains in HBM and many workgroups per chain (nf_hmc_tiled.hip): for lattices
+ * beyond nf_phi4_hmc's 64 KiB image.  The definition, the arguments, the energies in double, the accept rule and the two
+ * Philox positions per trajectory are nf_phi4_hmc's, word for word; from the same (seed, offset) both walk the same chain
+ * up to rounding.  Field arithmetic is in dtype; the energies are summed in a fixed order (lane partial, wave shuffle
+ * tree, waves in order, tiles in order): no atomics, the same inputs give the same bits, n_traj trajectories in one call
+ * equal n_traj calls of one at offsets offset + 2 t, and a chain's result does not depend on C or on the chains it shares
+ * a call with (the plan depends on the lattice and the dtype alone).  No neighbour is read along an axis of extent 1, on
+ * an axis of extent 2 the one neighbour counts twice, extents need not be even.  A rejected chain's phi is never written.
+ * A trajectory is n_md + 2 launches in a line on `stream`: begin (the momenta, the energies of the start, the first half
+ * kick), n_md fused steps (phi' = phi + dt pi and pi' = pi - eps F(phi') in one pass from one pair of workspace buffers
+ * into the other; the last also writes the energies of the end) and commit (the decision, dh_out / accept_out /
+ * action_out, the copy of the proposal into the accepted chains, the record row).  The call neither allocates nor
+ * synchronises and can be captured into a HIP graph.
+ * nf_hmc_tiled_plan, per axis of lattice[4]: a workgroup of `lanes` lanes owns a tile of tile[] sites (the last tile of an
+ * axis may be narrower), ntiles[] tiles per axis, `tiles` per chain.  With three or four axes of extent > 1 the slowest
+ * of them, march_axis, is walked plane by plane through a ring of ring_depth planes of phi' in LDS (tile[march_axis] is
+ * the length of a workgroup's segment); otherwise march_axis = -1 and ring_depth = 0.  An axis that one tile covers has
+ * no halo: its neighbours wrap inside the tile.  vec = sites per 16-byte access along the fastest axis (1 when its extent
+ * is no multiple of 16 / sizeof(dtype), or when a field handed in is not 16-byte aligned); lds_bytes <= lds_budget.
+ * nf_phi4_hmc_tiled_supported (pure host code): 1 for NF_F32 / NF_F64 on any lattice of extents >= 1 with V < 2^31 sites
+ * per chain, else 0 with the reason in nf_last_error_string.  nf_phi4_hmc_tiled_workspace (pure host code): the bytes of
+ * `workspace` for C chains (two phi and two pi buffers of (C, V) and the (C, tiles, 4) partials), 0 for an unsupported
+ * case; the caller owns the workspace (8-byte aligned; 16 for the wide accesses) and it need not be initialised.
+ * NF_EINVAL: what nf_phi4_hmc refuses (without its work cap), a short or NULL workspace, tiles x C above 2^24 - 1
+ * workgroups, or (n_md + 2) n_traj > NF_HMC_TILED_MAX_LAUNCHES. */
+#define NF_HMC_TILED_MAX_LAUNCHES 65536
+typedef struct nf_hmc_tiled_plan {
+  int32_t tile[4];
+  int32_t ntiles[4];
+  int32_t tiles;
+  int32_t march_axis;
+  int32_t ring_depth;
+  int32_t lanes;
+  int32_t vec;
+  int32_t reserved;
+  int64_t lds_bytes;
+  int64_t lds_budget;
+} nf_hmc_tiled_plan;
+int nf_phi4_hmc_tiled_supported(const int32_t *lattice, int dtype);
+int nf_phi4_hmc_tiled_plan(const int32_t *lattice, int dtype, nf_hmc_tiled_plan *out);
+size_t nf_phi4_hmc_tiled_workspace(int64_t C, const int32_t *lattice, int dtype);
+int nf_phi4_hmc_tiled(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out, uint8_t *accept_out,
+                      void *record, int record_every, int64_t C, const int32_t *lattice, double w0, double w2, double w4,
+                      int n_md, double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset, void *workspace,
+                      size_t workspace_bytes, int dtype, void *stream);
+
+/* ---- VJP of the conv layer (K5)---------------------------------------------------------------
  * grad_input is nf_conv_fwd itself applied to the pre-activation cotangent with the weights
  * flipped along every kernel axis and in/out channels swapped.  The two entry points below are
  * the rest of what autograd derives for ConvAct in Fitter.step (src/_normflowcore.py:288):

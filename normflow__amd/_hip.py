@@ -91,6 +91,11 @@ PROTOTYPES = {
     "nf_phi4_hmc_supported": (_I, [C.POINTER(C.c_int32), _I]),
     "nf_phi4_hmc": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, C.POINTER(C.c_int32), _D, _D, _D, _I, _D, _I, _I,
                          C.c_uint64, C.c_uint64, _I, _P]),
+    "nf_phi4_hmc_tiled_supported": (_I, [C.POINTER(C.c_int32), _I]),
+    "nf_phi4_hmc_tiled_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
+    "nf_phi4_hmc_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
+    "nf_phi4_hmc_tiled": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, C.POINTER(C.c_int32), _D, _D, _D, _I, _D, _I, _I,
+                               C.c_uint64, C.c_uint64, _P, _SZ, _I, _P]),
     "nf_act_vjp": (_I, [_P, _P, _P, _I64, _I, _I, _P]),
     "nf_conv_wgrad_cols": (_I, [_I, _I]),
     "nf_conv_wgrad": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, _P]),
@@ -1898,4 +1903,73 @@ def phi4_hmc(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in=None,
                               1 if record_every is None else int(record_every), Cn, _lat4(lat), float(w0), float(w2),
                               float(w4), int(n_md), float(dt), n_traj, int(bool(force_accept)), seed, offset,
                               _dtype_code(phi), _stream()), "nf_phi4_hmc")
+    return dict(action=action, dh=dh, accept=accept, record=record, pi=pi_out)
+
+
+# ========================================================================= the same, chains in HBM (nf_hmc_tiled.hip)
+HMC_TILED_MAX_LAUNCHES = 65536      # NF_HMC_TILED_MAX_LAUNCHES: the cap on (n_md + 2) * n_traj of one call
+
+
+class HmcTiledPlan(C.Structure):
+    """nf_hmc_tiled_plan (include/normflow_hip.h)."""
+    _fields_ = [("tile", C.c_int32 * 4), ("ntiles", C.c_int32 * 4), ("tiles", C.c_int32), ("march_axis", C.c_int32),
+                ("ring_depth", C.c_int32), ("lanes", C.c_int32), ("vec", C.c_int32), ("reserved", C.c_int32),
+                ("lds_bytes", C.c_int64), ("lds_budget", C.c_int64)]
+
+
+def _tiled_code(dtype):
+    return NF_F32 if dtype == torch.float32 else NF_F64 if dtype == torch.float64 else NF_F16
+
+
+def hmc_tiled_supported(lat, dtype):
+    """True if nf_phi4_hmc_tiled takes chains on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own planner,
+    pure host code."""
+    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
+        return False
+    return bool(load().nf_phi4_hmc_tiled_supported(_lat4(lat), _tiled_code(dtype)))
+
+
+def hmc_tiled_plan(lat, dtype):
+    """What nf_phi4_hmc_tiled will do on the lattice `lat` in `dtype`, per axis of `lat`: dict(tile, ntiles, tiles (per
+    chain), march_axis (None when no axis is marched), ring_depth, lanes, vec, lds_bytes, lds_budget).  Pure host code."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"hmc_tiled_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
+    out = HmcTiledPlan()
+    _check(load().nf_phi4_hmc_tiled_plan(_lat4(lat), _tiled_code(dtype), C.byref(out)), "nf_phi4_hmc_tiled_plan")
+    pad = 4 - len(lat)
+    return dict(tile=tuple(out.tile)[pad:], ntiles=tuple(out.ntiles)[pad:], tiles=out.tiles,
+                march_axis=None if out.march_axis < 0 else out.march_axis - pad, ring_depth=out.ring_depth, lanes=out.lanes,
+                vec=out.vec, lds_bytes=out.lds_bytes, lds_budget=out.lds_budget)
+
+
+def phi4_hmc_tiled(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in=None, want_pi=False, force_accept=False,
+                   position=None, generator=None, workspace=None):
+    """nf_phi4_hmc_tiled: `phi4_hmc` for chains that live in HBM, any lattice of 1 to 4 axes; the same arguments, the same
+    Philox positions and the same dict.  (n_md + 2) * n_traj launches on the current stream.  The workspace comes from
+    torch's caching allocator per call (stream-aware and graph-pool safe, like `_workspace`), or is `workspace`: a uint8
+    tensor of at least nf_phi4_hmc_tiled_workspace bytes."""
+    _require_device(phi, pi_in)
+    if not phi.is_contiguous() or (pi_in is not None and (not pi_in.is_contiguous() or pi_in.dtype != phi.dtype
+                                                            or pi_in.shape != phi.shape)):
+        raise NormflowHipError("phi4_hmc_tiled needs contiguous phi (C, *L) and pi_in of its shape and dtype")
+    Cn, lat, dev = phi.shape[0], tuple(phi.shape[1:]), phi.device
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"phi4_hmc_tiled: lattices of 1 to 4 axes, got {lat}")
+    n_traj = int(n_traj)
+    dh = torch.empty((max(n_traj, 0), Cn), dtype=torch.float64, device=dev)
+    accept = torch.empty((max(n_traj, 0), Cn), dtype=torch.uint8, device=dev)
+    action = torch.empty(Cn, dtype=torch.float64, device=dev)
+    record = None
+    if record_every is not None:
+        record = torch.empty((n_traj // int(record_every), Cn) + lat, dtype=phi.dtype, device=dev)
+    pi_out = torch.empty_like(phi) if want_pi else None
+    if workspace is None:
+        need = load().nf_phi4_hmc_tiled_workspace(Cn, _lat4(lat), _dtype_code(phi))
+        workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    seed, offset = position if position is not None else _philox_positions(dev, 2 * max(n_traj, 1), generator)
+    _check(load().nf_phi4_hmc_tiled(_ptr(phi), _ptr(action), _ptr(pi_in), _ptr(pi_out), _ptr(dh), _ptr(accept),
+                                    _ptr(record), 1 if record_every is None else int(record_every), Cn, _lat4(lat),
+                                    float(w0), float(w2), float(w4), int(n_md), float(dt), n_traj,
+                                    int(bool(force_accept)), seed, offset, _ptr(workspace), workspace.numel(),
+                                    _dtype_code(phi), _stream()), "nf_phi4_hmc_tiled")
     return dict(action=action, dh=dh, accept=accept, record=record, pi=pi_out)

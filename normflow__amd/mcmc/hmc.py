@@ -2,18 +2,21 @@
 sampler that does not go through the flow, for checking what the flow-based samplers produce at lambda != 0, for seeding
 them and for making training configurations.
 
-One definition, two implementations.  For C independent chains, per trajectory:
+One definition, three implementations.  For C independent chains, per trajectory:
     F(phi) = dS/dphi;  pi ~ N(0, 1);  H0 = sum pi^2 / 2 + S(phi)
     pi -= (dt / 2) F(phi);  k = 1 .. n_md: phi += dt pi, pi -= (dt, or dt / 2 when k = n_md) F(phi)
     H1 likewise;  accept iff log u < -(H1 - H0), u in (0, 1];  a rejected chain keeps its phi bit for bit.
 The energies are taken in double whatever the field dtype.
   * fused:    nf_phi4_hmc (nf_hmc.hip), a whole run of trajectories of a chain in one launch with the chain resident in a
               CU -- ScalarPhi4Action on a HIP device, lattices nf_phi4_hmc_supported takes;
+  * tiled:    nf_phi4_hmc_tiled (nf_hmc_tiled.hip), the chains in HBM and many workgroups per chain, n_md + 2 launches per
+              trajectory (begin, n_md fused leapfrog steps, commit) -- ScalarPhi4Action on a HIP device, any lattice of
+              one to four axes: the lattices beyond the fused kernel's 64 KiB image (32^3, 16^4, 32^4, 48^4);
   * composed: the same algorithm from the pieces the package already has (nf_normal_sample for the momenta, the force by
               autograd through `model.action`, torch ops for the updates, nf_block_accept for the decision and the
               restore) -- any lattice, any action object; on CPU tensors with torch's CPU generator.
-On the device both draw from the same Philox positions of torch's CUDA generator (two per trajectory: momenta, uniform),
-so from the same seed they walk the same chain up to rounding."""
+On the device all three draw from the same Philox positions of torch's CUDA generator (two per trajectory: momenta,
+uniform), so from the same seed they walk the same chain up to rounding."""
 import torch
 
 from .. import _hip
@@ -35,7 +38,8 @@ class HMCSampler:
     """`sample(batch_size, n_chains=C, n_md=10, dt=0.1, n_skip=0, path=None)` -> (batch_size, *L): row r is recorded
     trajectory r // C of chain r % C (the layout of the other samplers), with n_skip unrecorded trajectories before every
     recorded one.  `_ref` keeps the chains' phi (C, *L) and S (C) float64; the next call continues them, `start()` sets
-    them.  `path`: None = the fused kernel where it applies, else composed; 'fused' / 'composed' force one.
+    them.  `path`: None = the fused kernel where it applies, else the tiled kernels where they apply (they beat the composed path on
+    every shape class measured, README), else composed; 'fused' / 'tiled' / 'composed' force one.
     `history` gets, per call, accept_rate, exp_mdh (the mean of exp(-dH), 1 for an exact integrator of the measure) and
     dh_rms, from one device-to-host read; `last` holds the call's dH and accept flags (trajectories, C) on the device."""
 
@@ -64,11 +68,13 @@ class HMCSampler:
             print("Starting from scratch")
             self.start(n_chains=n_chains)
         phi, S = self._ref['sample'], self._ref['action']
-        fused = self._choose(phi, path)
+        path = self._choose(phi, path)
         rows = batch_size // n_chains
         out = torch.empty((rows,) + tuple(phi.shape), dtype=phi.dtype, device=phi.device)
-        if fused:
+        if path == 'fused':
             phi, S, dh, acc = self._run_fused(phi, rows, every, n_md, dt, out)
+        elif path == 'tiled':
+            phi, S, dh, acc = self._run_tiled(phi, rows, every, n_md, dt, out)
         else:
             phi, S, dh, acc = self._run_composed(phi, S, rows, every, n_md, dt, out)
         self._ref.update(sample=phi, action=S)
@@ -97,9 +103,11 @@ class HMCSampler:
         accept (C) uint8, action (C) float64 = S of the returned states).  `pi` replaces the drawn momenta.  `position`
         = (seed, offset) fixes the Philox position of a device run instead of taking it from torch's CUDA generator."""
         phi = phi.detach().clone().contiguous()
-        if self._choose(phi, path):
-            r = _hip.phi4_hmc(phi, *self._coef(phi.shape[1:]), n_md, dt, n_traj=1, pi_in=pi, want_pi=True,
-                              force_accept=force_accept, position=position)
+        path = self._choose(phi, path)
+        if path != 'composed':
+            kernel = _hip.phi4_hmc if path == 'fused' else _hip.phi4_hmc_tiled
+            r = kernel(phi, *self._coef(phi.shape[1:]), n_md, dt, n_traj=1, pi_in=pi, want_pi=True,
+                       force_accept=force_accept, position=position)
             return dict(phi=phi, pi=r['pi'], dh=r['dh'][0], accept=r['accept'][0], action=r['action'])
         gen = None
         if position is not None:
@@ -115,18 +123,37 @@ class HMCSampler:
         return (isinstance(self._model.action, ScalarPhi4Action) and phi.is_cuda
                 and _hip.hmc_supported(tuple(phi.shape[1:]), phi.dtype))
 
+    def _tiled_refusal(self, phi):
+        """Why nf_phi4_hmc_tiled does not take these chains, or None."""
+        if not isinstance(self._model.action, ScalarPhi4Action):
+            return f"the action is a {type(self._model.action).__name__}, not a ScalarPhi4Action"
+        if not phi.is_cuda:
+            return f"the chains are a {phi.device} tensor, not on a HIP device"
+        if phi.dtype not in (torch.float32, torch.float64):
+            return f"the chains are {phi.dtype}, not float32 or float64"
+        if not _hip.hmc_tiled_supported(tuple(phi.shape[1:]), phi.dtype):
+            return f"the lattice {tuple(phi.shape[1:])} has more than four axes or 2^31 sites or more"
+        return None
+
     def _choose(self, phi, path):
-        if path not in (None, 'fused', 'composed'):
-            raise ValueError(f"path must be None, 'fused' or 'composed', got {path!r}")
+        """'fused', 'tiled' or 'composed'."""
+        if path not in (None, 'fused', 'tiled', 'composed'):
+            raise ValueError(f"path must be None, 'fused', 'tiled' or 'composed', got {path!r}")
         if path == 'composed':
-            return False
-        ok = self._fused_applies(phi)
-        if path == 'fused' and not ok:
+            return path
+        if path == 'tiled':
+            why = self._tiled_refusal(phi)
+            if why is not None:
+                raise _hip.NormflowHipError(f"HMCSampler(path='tiled'): nf_phi4_hmc_tiled does not apply: {why}")
+            return path
+        if self._fused_applies(phi):
+            return 'fused'
+        if path == 'fused':
             raise _hip.NormflowHipError(
                 "HMCSampler(path='fused'): nf_phi4_hmc takes a ScalarPhi4Action on a HIP device and a lattice whose chain "
                 f"fits its LDS image; got {type(self._model.action).__name__}, a {phi.device} tensor of shape "
                 f"{tuple(phi.shape[1:])} and {phi.dtype}")
-        return ok
+        return 'tiled' if self._tiled_refusal(phi) is None else 'composed'
 
     def _coef(self, lat):
         """(w0, w2, w4) as nf_phi4_hmc takes them: ScalarPhi4Action.action's rule for a user axis of extent 1 (it is its own
@@ -157,6 +184,34 @@ class HMCSampler:
                 while left:
                     k = min(per, left)
                     r = _hip.phi4_hmc(phi, *coef, n_md, dt, n_traj=k)
+                    dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
+                    left -= k
+                out[r0] = phi
+        return phi, action, torch.cat(dhs), torch.cat(accs)
+
+    # ---- tiled
+    def _run_tiled(self, phi, rows, every, n_md, dt, out):
+        """rows * every trajectories in as few calls as NF_HMC_TILED_MAX_LAUNCHES allows; one workspace for all of them."""
+        phi = phi.clone()
+        coef = self._coef(phi.shape[1:])
+        need = _hip.load().nf_phi4_hmc_tiled_workspace(phi.shape[0], _hip._lat4(tuple(phi.shape[1:])), _hip._dtype_code(phi))
+        ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=phi.device)
+        per = max(1, _hip.HMC_TILED_MAX_LAUNCHES // (n_md + 2))           # trajectories per call
+        dhs, accs, action = [], [], None
+        if per >= every:
+            step, r0 = per // every, 0
+            while r0 < rows:
+                k = min(step, rows - r0)
+                r = _hip.phi4_hmc_tiled(phi, *coef, n_md, dt, n_traj=k * every, record_every=every, workspace=ws)
+                out[r0:r0 + k] = r['record']
+                dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
+                r0 += k
+        else:
+            for r0 in range(rows):
+                left = every
+                while left:
+                    k = min(per, left)
+                    r = _hip.phi4_hmc_tiled(phi, *coef, n_md, dt, n_traj=k, workspace=ws)
                     dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
                     left -= k
                 out[r0] = phi
