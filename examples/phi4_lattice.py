@@ -6,7 +6,8 @@ DistConvertor_), or a stack of RQ-spline couplings, assembled from the same name
     python examples/phi4_lattice.py --lat 8,8 --epochs 500
     python examples/phi4_lattice.py --lat 16,16,16 --kind rqs --layers 4 --epochs 100
     torchrun-free data parallel:  --nranks 8   (device_handler.spawnprocesses, one process per GPU)
-    python examples/phi4_lattice.py --lat 16,16 --hmc     after the fit: <phi^2> from model.mcmc next to model.hmc
+    python examples/phi4_lattice.py --lat 16,16 --hmc     after the fit: <phi^2> from model.mcmc next to model.hmc, then
+                                                          chi, the Binder cumulant, xi_2 and tau_int(m) of both
 """
 import argparse
 import os
@@ -16,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))) 
 
 import normflow__amd as nf          # the reference:  import normflow as nf
 from normflow__amd.action import ScalarPhi4Action
+from normflow__amd.lib import Ensemble, fmt_val_err
 from normflow__amd.mask import EvenOddMask
 from normflow__amd.nn import (AffineCoupling_, ConvAct, DistConvertor_, FFTNet_, MeanFieldNet_, ModuleList_,
                               PSDBlock_, RQSplineCoupling_)
@@ -53,13 +55,26 @@ def phi2(y, n_chains, drop):
     return per_chain.mean().item(), per_chain.std().item() / n_chains ** 0.5
 
 
+def observables(model, y, n_chains, drop):
+    """chi, the Binder cumulant, xi_2 (mean over the axes of a cubic lattice, else along axis 0) and tau_int(m) of sampler
+    rows, through model.measure (one pass over the rows on the device) and Ensemble (errors: jackknife over the chains)."""
+    e = Ensemble(model.measure(y), n_chains=n_chains, drop=drop)
+    axis = None if len(set(e.lattice)) == 1 else 0
+    tau, tau_err, window = e.tau_int('magnetization')
+    return "chi %s   U4 %s   xi_2 %s   tau_int(m) %s (W = %d)" % (
+        fmt_val_err(*e.susceptibility()), fmt_val_err(*e.binder()), fmt_val_err(*e.xi2(axis)), fmt_val_err(tau, tau_err), window)
+
+
 def compare_with_hmc(model, n_chains=64, rows=128):
     """<phi^2> of the trained flow + Metropolis next to hybrid Monte Carlo on the action itself (exact up to its own
-    statistical error; the first quarter of every chain is dropped as thermalisation)."""
+    statistical error; the first quarter of every chain is dropped as thermalisation), then the observables of both."""
     y = model.mcmc.sample(n_chains * rows, n_chains=n_chains)
     print("<phi^2>  model.mcmc  %.5f +- %.5f   (accept rate %.3f)" % (*phi2(y, n_chains, rows // 4), model.mcmc.history.accept_rate[-1]))
+    obs = observables(model, y, n_chains, rows // 4)
     y = model.hmc.sample(n_chains * rows, n_chains=n_chains, n_md=10, dt=0.1)
     print("<phi^2>  model.hmc   %.5f +- %.5f   (accept rate %.3f)" % (*phi2(y, n_chains, rows // 4), model.hmc.history.accept_rate[-1]))
+    print("model.mcmc  " + obs)
+    print("model.hmc   " + observables(model, y, n_chains, rows // 4))
 
 
 def main():

@@ -713,6 +713,57 @@ int nf_phi4_hmc_tiled(void *phi, double *action_out, const void *pi_in, void *pi
                       int n_md, double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset, void *workspace,
                       size_t workspace_bytes, int dtype, void *stream);
 
+/* ---- what the samplers' rows measure (nf_measure.hip; MI355X-side extension): every sufficient statistic of N
+ * configurations in one pass.  cfgs (N, V) of dtype NF_F32 / NF_F64 on lattice[4] (leading extents 1 for d < 4);
+ * out (N, n_out) DOUBLE, n_out = 7 + lattice[0] + lattice[1] + lattice[2] + lattice[3], per row
+ *   out[0], out[1], out[2]   sum phi, sum phi^2, sum phi^4
+ *   out[3 + mu]              sum_x phi(x) phi(x - mu), periodic; 0 for an axis of extent 1 (no neighbour is read, the
+ *                            convention of nf_phi4_action); on an axis of extent 2 the plain formula (the one neighbour
+ *                            once per site)
+ *   out[7 + off_mu + t]      S_mu(t) = sum over the sites with x_mu = t of phi(x), off_mu = sum_{nu < mu} lattice[nu]; an
+ *                            axis of extent 1 has the one entry sum phi
+ * so that S = w2 out[1] + w4 out[2] - w0 sum_mu out[3 + mu] is nf_phi4_action's action.  Every site value is converted
+ * to double before any arithmetic, for either dtype.  The sums have a fixed order (lane partial in site order, wave
+ * shuffle tree, waves in order; per slice fixed stripes in stripe order; segments in segment order) and there are no
+ * atomics: the same input gives the same bits, and a row's result depends on its values, the lattice and the dtype alone
+ * -- not on N, on its position in the batch, on the other rows or on the alignment of cfgs.  A row is read from HBM
+ * once (16-byte loads when the fastest extent is a multiple of 16 / sizeof(dtype) and cfgs is 16-byte aligned, one site
+ * at a time otherwise) into an LDS image that every sum is read from.  The call neither allocates nor synchronises and
+ * can be captured into a HIP graph.
+ * nf_measure_plan (a function of lattice and dtype alone): regime NF_MEASURE_PACKED (V <= 256 sites: rows_per_group = 4
+ * rows per workgroup, one wave each), NF_MEASURE_RESIDENT (V sizeof(dtype) <= 64 KiB: one workgroup per row) or
+ * NF_MEASURE_SEGMENTED (beyond: the slowest axis of extent > 1 is cut into `segments` runs of seg_len planes, the last
+ * may be shorter, every run a whole number of 16-byte units (seg_len x plane sites is a multiple of vec); a workgroup stages its run at once, stage_planes = seg_len, reads the one plane before it from HBM for
+ * the backward link and writes its partials to the workspace, and a second kernel adds them in segment order).  lanes =
+ * the lanes that share one image; vec = sites per 16-byte access (1: site by site); lds_bytes <= lds_budget.
+ * nf_lattice_measure_supported (pure host code): 1 for NF_F32 / NF_F64, extents >= 1, V and n_out < 2^31 and a plane of the slowest
+ * axis of extent > 1 that fits the LDS of a CU next to the reduction slots (32^4 in fp32 does, 32^4 in fp64 and 48^4 do
+ * not), else 0 with the reason in nf_last_error_string.  nf_lattice_measure_workspace (pure host code): the bytes of
+ * `workspace` for N rows, 0 when segments == 1 or the case is unsupported; the caller owns it (8-byte aligned, need not
+ * be initialised).
+ * NF_EINVAL: NULL cfgs / out / lattice, an unsupported lattice or dtype, N < 0, a short or NULL workspace where one is
+ * needed, or more than 2^24 - 1 workgroups (ceil(N / rows_per_group) segments, or ceil(N n_out / 256)).  N = 0: NF_OK. */
+#define NF_MEASURE_RESIDENT 0
+#define NF_MEASURE_PACKED 1
+#define NF_MEASURE_SEGMENTED 2
+typedef struct nf_measure_plan {
+  int32_t regime;
+  int32_t rows_per_group;
+  int32_t segments;
+  int32_t seg_len;
+  int32_t stage_planes;
+  int32_t lanes;
+  int32_t vec;
+  int32_t n_out;
+  int64_t lds_bytes;
+  int64_t lds_budget;
+} nf_measure_plan;
+int nf_lattice_measure_supported(const int32_t *lattice, int dtype);
+int nf_lattice_measure_plan(const int32_t *lattice, int dtype, nf_measure_plan *out);
+size_t nf_lattice_measure_workspace(int64_t N, const int32_t *lattice, int dtype);
+int nf_lattice_measure(const void *cfgs, double *out, int64_t N, const int32_t *lattice, void *workspace,
+                       size_t workspace_bytes, int dtype, void *stream);
+
 /* ---- VJP of the conv layer (K5)---------------------------------------------------------------
  * grad_input is nf_conv_fwd itself applied to the pre-activation cotangent with the weights
  * flipped along every kernel axis and in/out channels swapped.  The two entry points below are

@@ -96,6 +96,10 @@ PROTOTYPES = {
     "nf_phi4_hmc_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
     "nf_phi4_hmc_tiled": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, C.POINTER(C.c_int32), _D, _D, _D, _I, _D, _I, _I,
                                C.c_uint64, C.c_uint64, _P, _SZ, _I, _P]),
+    "nf_lattice_measure_supported": (_I, [C.POINTER(C.c_int32), _I]),
+    "nf_lattice_measure_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
+    "nf_lattice_measure_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
+    "nf_lattice_measure": (_I, [_P, _P, _I64, C.POINTER(C.c_int32), _P, _SZ, _I, _P]),
     "nf_act_vjp": (_I, [_P, _P, _P, _I64, _I, _I, _P]),
     "nf_conv_wgrad_cols": (_I, [_I, _I]),
     "nf_conv_wgrad": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, _P]),
@@ -1973,3 +1977,55 @@ def phi4_hmc_tiled(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in
                                     int(bool(force_accept)), seed, offset, _ptr(workspace), workspace.numel(),
                                     _dtype_code(phi), _stream()), "nf_phi4_hmc_tiled")
     return dict(action=action, dh=dh, accept=accept, record=record, pi=pi_out)
+
+
+# ========================================================================= observables of sampler rows (nf_measure.hip)
+MEASURE_REGIMES = ('resident', 'packed', 'segmented')       # NF_MEASURE_RESIDENT, _PACKED, _SEGMENTED
+
+
+class MeasurePlan(C.Structure):
+    """nf_measure_plan (include/normflow_hip.h)."""
+    _fields_ = [("regime", C.c_int32), ("rows_per_group", C.c_int32), ("segments", C.c_int32), ("seg_len", C.c_int32),
+                ("stage_planes", C.c_int32), ("lanes", C.c_int32), ("vec", C.c_int32), ("n_out", C.c_int32),
+                ("lds_bytes", C.c_int64), ("lds_budget", C.c_int64)]
+
+
+def measure_supported(lat, dtype):
+    """True if nf_lattice_measure takes rows on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own planner,
+    pure host code."""
+    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
+        return False
+    return bool(load().nf_lattice_measure_supported(_lat4(lat), _tiled_code(dtype)))
+
+
+def measure_plan(lat, dtype):
+    """What nf_lattice_measure will do on the lattice `lat` in `dtype`: dict(regime ('resident', 'packed' or 'segmented'),
+    rows_per_group, segments, seg_len, stage_planes, lanes, vec, n_out (of the lattice padded to four axes), march_axis
+    (the axis of `lat` that segments cut: its slowest of extent > 1), lds_bytes, lds_budget).  Pure host code."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"measure_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
+    out = MeasurePlan()
+    _check(load().nf_lattice_measure_plan(_lat4(lat), _tiled_code(dtype), C.byref(out)), "nf_lattice_measure_plan")
+    march = next((mu for mu, n in enumerate(lat) if n > 1), len(lat) - 1)
+    return dict(regime=MEASURE_REGIMES[out.regime], rows_per_group=out.rows_per_group, segments=out.segments,
+                seg_len=out.seg_len, stage_planes=out.stage_planes, lanes=out.lanes, vec=out.vec, n_out=out.n_out,
+                march_axis=march, lds_bytes=out.lds_bytes, lds_budget=out.lds_budget)
+
+
+def lattice_measure(cfgs, workspace=None):
+    """nf_lattice_measure: the (N, 7 + sum of the four padded extents) float64 statistics of the contiguous rows cfgs
+    (N, *L), 1 to 4 axes, fp32 or fp64, in one pass (two launches on the segmented regime).  The workspace comes from
+    torch's caching allocator per call (stream-aware and graph-pool safe, like `_workspace`), or is `workspace`: a uint8
+    tensor of at least nf_lattice_measure_workspace bytes."""
+    _require_device(cfgs)
+    lat = tuple(cfgs.shape[1:])
+    if not cfgs.is_contiguous() or not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"lattice_measure needs contiguous cfgs (N, *L) with 1 to 4 lattice axes, got {tuple(cfgs.shape)}")
+    N, lat4, code = cfgs.shape[0], _lat4(lat), _dtype_code(cfgs)
+    out = torch.empty((N, 7 + sum(lat) + 4 - len(lat)), dtype=torch.float64, device=cfgs.device)
+    if workspace is None:
+        need = load().nf_lattice_measure_workspace(N, lat4, code)
+        workspace = torch.empty(int(need), dtype=torch.uint8, device=cfgs.device) if need else None
+    _check(load().nf_lattice_measure(_ptr(cfgs), _ptr(out), N, lat4, _ptr(workspace),
+                                     0 if workspace is None else workspace.numel(), code, _stream()), "nf_lattice_measure")
+    return out

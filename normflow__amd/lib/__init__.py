@@ -1,1 +1,2 @@
 from .stats import Resampler, estimate_logz, fmt_val_err
+from .observables import measure, Measurement, Ensemble

@@ -1,0 +1,237 @@
+"""What the samplers' rows measure (MI355X-side extension; the reference stops at `Resampler` and `estimate_logz`).
+
+`measure(cfgs)` reduces every configuration (N, *L), 1 <= d <= 4, to its sufficient statistics in double -- on the device
+in ONE pass of the `nf_lattice_measure` kernel (include/normflow_hip.h), on host tensors by the same definitions composed
+from torch ops:
+    sum_phi, sum_phi2, sum_phi4      sum_x phi, phi^2, phi^4
+    links[:, mu]                     sum_x phi(x) phi(x - mu), periodic; 0 along an axis of extent 1
+    slices[mu][:, t]                 S_mu(t) = sum over the sites with x_mu = t of phi(x)
+Everything else is O(N sum L) host arithmetic on those: the action, the magnetisation m = sum phi / V and its moments, the
+time-slice correlator
+    G_mu(t) = (1 / L_mu) sum_s pbar_mu(s) pbar_mu(s + t),   pbar_mu = S_mu / (V / L_mu),
+and the on-axis momentum-space propagator |sum_t e^{ipt} S_mu(t)|^2 / V at p = 2 pi k / L_mu.
+
+`Ensemble` reads the rows as (steps, chains) -- row r = step r // C of chain r % C, the layout of model.mcmc,
+model.blocked_mcmc and model.hmc -- and gives every estimate as (value, error): leave-one-chain-out jackknife for
+C >= 2, binned jackknife (`Resampler('jackknife')`) for one chain; `tau_int` is the integrated autocorrelation time with
+the Madras-Sokal window."""
+import math
+
+import torch
+
+from .. import _hip
+from .stats import Resampler
+
+# the regimes of nf_lattice_measure_plan on which `measure` runs the kernel: those where tools/measure_bench.py measured
+# it no slower than the composed path on an MI355X (README, "Observables")
+KERNEL_REGIMES = ('packed', 'resident', 'segmented')
+
+
+def _compose(x):
+    """The statistics of (N, *L) rows from torch ops in double: d + 3 passes.  Returns (scalars (N, 3), links (N, d),
+    slices: list of (N, L_mu))."""
+    x = x.double()
+    d = x.ndim - 1
+    sq = x * x
+    tot = lambda t: t.flatten(1).sum(1)
+    scalars = torch.stack([tot(x), tot(sq), tot(sq * sq)], dim=1)
+    links = [tot(x * x.roll(1, dims=mu)) if x.shape[mu] > 1 else torch.zeros_like(scalars[:, 0]) for mu in range(1, d + 1)]
+    slices = [x.sum(dim=[nu for nu in range(1, d + 1) if nu != mu]) if d > 1 else x for mu in range(1, d + 1)]
+    return scalars, torch.stack(links, dim=1), slices
+
+
+def kernel_applies(cfgs):
+    """True where `measure` runs nf_lattice_measure: fp32 / fp64 rows on the device, on a lattice the launcher's planner
+    takes, in a regime of KERNEL_REGIMES."""
+    lat = tuple(cfgs.shape[1:])
+    if not (cfgs.is_cuda and cfgs.dtype in (torch.float32, torch.float64) and cfgs.shape[0] > 0):
+        return False
+    return _hip.measure_supported(lat, cfgs.dtype) and _hip.measure_plan(lat, cfgs.dtype)['regime'] in KERNEL_REGIMES
+
+
+@torch.no_grad()
+def measure(cfgs, action=None, path=None):
+    """(N, *L) configurations -> `Measurement`.  path=None: the kernel where `kernel_applies`, else the composed torch
+    path (host tensors, other dtypes, lattices the kernel does not take); 'kernel' / 'composed' force one (a kernel that
+    cannot run raises).  With a `ScalarPhi4Action` the measurement also carries the action of every row; any other
+    action object is a TypeError (its action does not follow from these statistics)."""
+    if path not in (None, 'kernel', 'composed'):
+        raise ValueError(f"path must be None, 'kernel' or 'composed', got {path!r}")
+    d = cfgs.ndim - 1
+    if not 1 <= d <= 4:
+        raise ValueError(f"measure: configurations (N, *L) with 1 to 4 lattice axes, got {tuple(cfgs.shape)}")
+    lat = tuple(cfgs.shape[1:])
+    if path == 'kernel' or (path is None and kernel_applies(cfgs)):
+        out = _hip.lattice_measure(cfgs.contiguous())
+        pad = 4 - d
+        scalars, links, at, slices = out[:, :3], out[:, 3 + pad:7], 7 + pad, []
+        for n in lat:
+            slices.append(out[:, at:at + n])
+            at += n
+    else:
+        scalars, links, slices = _compose(cfgs)
+    return Measurement(scalars, links, slices, lat, action)
+
+
+class Measurement:
+    """Per-row statistics of N configurations, all float64: sum_phi, sum_phi2, sum_phi4 (N), links (N, d), slices (list of
+    d tensors (N, L_mu)), volume, lattice, and `action` (N) when made with a ScalarPhi4Action (else None)."""
+
+    def __init__(self, scalars, links, slices, lattice, action=None):
+        self.sum_phi, self.sum_phi2, self.sum_phi4 = scalars[:, 0], scalars[:, 1], scalars[:, 2]
+        self.links, self.slices, self.lattice = links, list(slices), tuple(lattice)
+        self.volume = math.prod(self.lattice)
+        self.action = None
+        if action is not None:
+            if not hasattr(action, 'get_coef'):
+                raise TypeError(f"a Measurement derives the action of a ScalarPhi4Action (get_coef) from its sums, not of "
+                                f"{type(action).__name__}: measure without it")
+            w0, w2, w4 = action.get_coef(len(self.lattice))
+            own = sum(1 for n in self.lattice if n == 1)          # an axis of extent 1 is its own neighbour
+            self.action = (w2 - own * w0) * self.sum_phi2 + w4 * self.sum_phi4 - w0 * links.sum(dim=1)
+
+    def __len__(self):
+        return self.sum_phi.shape[0]
+
+    def magnetization(self):
+        return self.sum_phi / self.volume
+
+    def phi2(self):
+        return self.sum_phi2 / self.volume
+
+    def _axes(self, axis):
+        if axis is not None:
+            return [range(len(self.lattice))[axis]]
+        if len(set(self.lattice)) != 1:
+            raise ValueError(f"axis=None averages the axes, whose extents differ on the lattice {self.lattice}: name an axis")
+        return list(range(len(self.lattice)))
+
+    def correlator(self, axis=None):
+        """(N, L) time-slice correlator G_mu(t), t = 0 .. L - 1, of every row; axis=None: the mean over the axes."""
+        out = 0
+        for mu in self._axes(axis):
+            L = self.lattice[mu]
+            f = torch.fft.rfft(self.slices[mu] * (L / self.volume), dim=1)
+            out = out + torch.fft.irfft(f.real ** 2 + f.imag ** 2, n=L, dim=1) / L
+        return out / len(self._axes(axis))
+
+    def propagator(self, axis=None):
+        """(N, L) |sum_t e^{ipt} S_mu(t)|^2 / V at the on-axis momenta p = 2 pi k / L, k = 0 .. L - 1."""
+        out = 0
+        for mu in self._axes(axis):
+            f = torch.fft.fft(self.slices[mu], dim=1)
+            out = out + (f.real ** 2 + f.imag ** 2) / self.volume
+        return out / len(self._axes(axis))
+
+
+class Ensemble:
+    """Estimates with errors from a `Measurement` of sampler rows: (steps, n_chains) rows, the first `drop` steps left out."""
+
+    NAMES = ('magnetization', 'abs_magnetization', 'm2', 'm4', 'phi2', 'sum_phi', 'sum_phi2', 'sum_phi4', 'action')
+
+    def __init__(self, measurement, n_chains=1, drop=0):
+        n = len(measurement)
+        if n_chains < 1 or n % n_chains:
+            raise ValueError(f"{n} rows are no whole number of steps of {n_chains} chains")
+        self.m, self.n_chains, self.drop = measurement, int(n_chains), int(drop)
+        self.steps = n // n_chains - self.drop
+        if self.steps < 1:
+            raise ValueError(f"drop={drop} leaves no step of {n // n_chains}")
+        self.volume, self.lattice = measurement.volume, measurement.lattice
+
+    def series(self, name):
+        """The per-row quantity `name` (or any (N, ...) tensor) as (steps, chains, K) on the host."""
+        if torch.is_tensor(name):
+            t = name
+        elif name not in self.NAMES:
+            raise ValueError(f"unknown observable {name!r}: one of {self.NAMES}")
+        else:
+            mag = self.m.magnetization()
+            t = {'magnetization': mag, 'abs_magnetization': mag.abs(), 'm2': mag ** 2, 'm4': mag ** 4,
+                 'phi2': self.m.phi2(), 'sum_phi': self.m.sum_phi, 'sum_phi2': self.m.sum_phi2,
+                 'sum_phi4': self.m.sum_phi4, 'action': self.m.action}[name]
+            if t is None:
+                raise ValueError("the measurement carries no action: measure(cfgs, action)")
+        t = t.detach().double().cpu()
+        return t.reshape(self.steps + self.drop, self.n_chains, -1)[self.drop:]
+
+    def estimate(self, primaries, fn=lambda mean: mean, binsize=1):
+        """(value, error) of fn(<primaries>): primaries (steps, chains, K), fn maps (..., K) means to (..., R).  C >= 2:
+        leave-one-chain-out jackknife of the chains' means; C = 1: jackknife over bins of `binsize` steps."""
+        C = self.n_chains
+        value = fn(primaries.mean(dim=(0, 1)))
+        if C >= 2:
+            per_chain = primaries.mean(dim=0)
+            theta = fn((per_chain.sum(dim=0, keepdim=True) - per_chain) / (C - 1))
+            n = C
+        else:
+            theta = torch.stack([fn(r.mean(dim=0)) for r in Resampler('jackknife')(primaries[:, 0], binsize=binsize)])
+            n = theta.shape[0]
+        err = ((theta - theta.mean(dim=0)) ** 2).sum(dim=0).mul((n - 1) / n).sqrt()
+        if value.numel() == 1:
+            return value.item(), err.item()
+        return value, err
+
+    def mean(self, name, binsize=1):
+        return self.estimate(self.series(name), binsize=binsize)
+
+    def susceptibility(self, binsize=1):
+        """V (<m^2> - <|m|>^2)."""
+        p = torch.cat([self.series('m2'), self.series('abs_magnetization')], dim=2)
+        return self.estimate(p, lambda a: self.volume * (a[..., 0:1] - a[..., 1:2] ** 2), binsize)
+
+    def binder(self, binsize=1):
+        """1 - <m^4> / (3 <m^2>^2)."""
+        p = torch.cat([self.series('m2'), self.series('m4')], dim=2)
+        return self.estimate(p, lambda a: 1 - a[..., 1:2] / (3 * a[..., 0:1] ** 2), binsize)
+
+    def _corr(self, axis, connected):
+        p = torch.cat([self.series(self.m.correlator(axis)), self.series('magnetization')], dim=2)
+        return p, (lambda a: a[..., :-1] - a[..., -1:] ** 2) if connected else (lambda a: a[..., :-1])
+
+    def correlator(self, axis=None, connected=False, binsize=1):
+        """<G_mu(t)>, t = 0 .. L - 1; connected: minus <m>^2."""
+        p, fn = self._corr(axis, connected)
+        return self.estimate(p, fn, binsize)
+
+    def propagator(self, axis=None, binsize=1):
+        """<|sum_t e^{ipt} S_mu(t)|^2> / V at p = 2 pi k / L, k = 0 .. L - 1."""
+        return self.estimate(self.series(self.m.propagator(axis)), binsize=binsize)
+
+    def effective_mass(self, axis=None, connected=False, binsize=1):
+        """arccosh((G(t - 1) + G(t + 1)) / (2 G(t))) at t = 1 .. L - 2; NaN where the argument is < 1."""
+        p, fn = self._corr(axis, connected)
+
+        def mass(a):
+            g = fn(a)
+            arg = (g[..., :-2] + g[..., 2:]) / (2 * g[..., 1:-1])
+            return torch.where(arg >= 1, torch.acosh(arg.clamp(min=1)), torch.full_like(arg, float('nan')))
+        return self.estimate(p, mass, binsize)
+
+    def xi2(self, axis=None, binsize=1):
+        """The second-moment correlation length sqrt(G~(0) / G~(p_min) - 1) / (2 sin(pi / L)); NaN where the ratio is < 1."""
+        L = self.lattice[self.m._axes(axis)[0]]
+        p = self.series(self.m.propagator(axis)[:, :2])
+
+        def xi(a):
+            r = a[..., 0:1] / a[..., 1:2] - 1
+            return torch.where(r >= 0, r.clamp(min=0).sqrt(), torch.full_like(r, float('nan'))) / (2 * math.sin(math.pi / L))
+        return self.estimate(p, xi, binsize)
+
+    def tau_int(self, name, c=5.0):
+        """(tau, error, W): the integrated autocorrelation time of `name` in steps, tau(W) = 1/2 + sum_{t=1}^{W} rho(t), at
+        the Madras-Sokal window, the smallest W with W >= c tau(W); error tau sqrt(2 (2 W + 1) / (steps chains)).  The
+        autocovariance is computed per chain by FFT (around the mean of all chains) and averaged over the chains."""
+        x = self.series(name)[:, :, 0]
+        n, C = x.shape
+        x = x - x.mean()
+        f = torch.fft.rfft(x, n=2 * n, dim=0)
+        acov = torch.fft.irfft(f.real ** 2 + f.imag ** 2, n=2 * n, dim=0)[:n]
+        acov = acov.mean(dim=1) / torch.arange(n, 0, -1, dtype=torch.float64, device=x.device)
+        rho = acov / acov[0]
+        tau = 0.5 + torch.cumsum(rho[1:], dim=0)                    # tau(W) at W = 1 ..
+        W = torch.arange(1, n, dtype=torch.float64, device=x.device)
+        ok = torch.nonzero(W >= c * tau)
+        w = int(ok[0]) if ok.numel() else n - 2
+        t = tau[w].item()
+        return t, t * math.sqrt(2 * (2 * (w + 1) + 1) / (n * C)), w + 1

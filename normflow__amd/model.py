@@ -66,6 +66,7 @@ class Model:
     """Model(prior=..., net_=..., action=...): `.fit(...)` trains, `.posterior.sample(n)` draws,
     `.mcmc.sample(n)` draws with Metropolis correction, `.blocked_mcmc.sample(n, n_blocks=k)` with block-update Metropolis,
     `.hmc.sample(n, n_chains=C)` with hybrid Monte Carlo on the action itself (no flow involved),
+    `.measure(y)` reduces rows of any of them to their observables (lib/observables.py),
     `.device_handler` places / parallelises."""
 
     def __init__(self, *, prior, net_, action, name=None):
@@ -79,6 +80,12 @@ class Model:
 
     def transform(self, x):
         return self.net_(x)[0]
+
+    def measure(self, y):
+        """The `Measurement` of the configurations y (N, *L): one pass on the device.  It carries the rows' actions when
+        this model's action is a `ScalarPhi4Action` (the action follows from the measured sums), else none."""
+        from .lib.observables import measure
+        return measure(y, self.action if hasattr(self.action, 'get_coef') else None)
 
 
 @torch.no_grad()
