@@ -1744,24 +1744,20 @@ class NormalLogProbFn(torch.autograd.Function):
         return gx, None, None
 
 
-def _philox_position(device, generator=None):
-    """(seed, kernel offset) for one call of a Philox kernel, taken from torch's CUDA generator of `device` (or
-    `generator`), which is advanced by one call's worth: torch.manual_seed governs these kernels as it does torch's own."""
-    gen = generator if generator is not None else torch.cuda.default_generators[device.index if device.index is not None
-                                                                                  else torch.cuda.current_device()]
-    seed, offset = gen.initial_seed(), gen.get_offset()
-    gen.set_offset(offset + 4)            # torch keeps offsets in multiples of 4
-    return seed & (2 ** 64 - 1), offset // 4
-
-
 def _philox_positions(device, n, generator=None):
-    """`_philox_position` for a launch that consumes n consecutive kernel offsets: (seed, first offset); the generator is
-    advanced past all n."""
+    """(seed, first kernel offset) for a launch of a Philox kernel that consumes n consecutive kernel offsets, taken from
+    torch's CUDA generator of `device` (or `generator`), which is advanced past all n: torch.manual_seed governs these
+    kernels as it does torch's own."""
     gen = generator if generator is not None else torch.cuda.default_generators[device.index if device.index is not None
                                                                                   else torch.cuda.current_device()]
     seed, offset = gen.initial_seed(), gen.get_offset()
-    gen.set_offset(offset + 4 * int(n))
+    gen.set_offset(offset + 4 * int(n))   # torch keeps offsets in multiples of 4
     return seed & (2 ** 64 - 1), offset // 4
+
+
+def _philox_position(device, generator=None):
+    """(seed, kernel offset) for one call of a Philox kernel: `_philox_positions` with n = 1."""
+    return _philox_positions(device, 1, generator)
 
 
 def normal_sample(loc, scale, batch_size, shape, dtype, device, generator=None):
@@ -1872,12 +1868,60 @@ def metropolis_select(y, ref_sample, accept, keep, n_chains):
 HMC_MAX_WORK = 1 << 26        # NF_HMC_MAX_WORK: the cap on n_md * n_traj * max(V, 256) * ceil(C / 1024) of one launch
 
 
+def _planner_supported(symbol, lat, dtype):
+    """True if the planner `symbol` of the library takes the lattice `lat` (1 to 4 extents) in `dtype`: pure host code."""
+    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
+        return False
+    return bool(getattr(load(), symbol)(_lat4(lat), NF_F32 if dtype == torch.float32 else NF_F64))
+
+
+def _planner_plan(what, symbol, lat, dtype, out):
+    """`out` filled by the planner `symbol` for the lattice `lat` (1 to 4 axes) in `dtype`; a dtype that is neither float32
+    nor float64 goes down as NF_F16, which the planners refuse in their own words."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"{what}: lattices of 1 to 4 axes, got {tuple(lat)}")
+    code = NF_F32 if dtype == torch.float32 else NF_F64 if dtype == torch.float64 else NF_F16
+    _check(getattr(load(), symbol)(_lat4(lat), code, C.byref(out)), symbol)
+    return out
+
+
 def hmc_supported(lat, dtype):
     """True if nf_phi4_hmc takes chains on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own planner,
     pure host code."""
-    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
-        return False
-    return bool(load().nf_phi4_hmc_supported(_lat4(lat), NF_F32 if dtype == torch.float32 else NF_F64))
+    return _planner_supported("nf_phi4_hmc_supported", lat, dtype)
+
+
+def _phi4_hmc_call(what, phi, w0, w2, w4, n_md, dt, *, n_traj, record_every, pi_in, want_pi, force_accept, position,
+                   generator, workspace=None):
+    """The body of `phi4_hmc` and `phi4_hmc_tiled` (`what`; the library's entry point is nf_<what>): the argument checks,
+    the output tensors, the Philox positions, the call and the dict.  Only the tiled kernels have a workspace."""
+    tiled = what == "phi4_hmc_tiled"
+    _require_device(phi, pi_in)
+    if not phi.is_contiguous() or (pi_in is not None and (not pi_in.is_contiguous() or pi_in.dtype != phi.dtype
+                                                            or pi_in.shape != phi.shape)):
+        raise NormflowHipError(f"{what} needs contiguous phi (C, *L) and pi_in of its shape and dtype")
+    Cn, lat, dev = phi.shape[0], tuple(phi.shape[1:]), phi.device
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"{what}: lattices of 1 to 4 axes, got {lat}")
+    n_traj = int(n_traj)
+    dh = torch.empty((max(n_traj, 0), Cn), dtype=torch.float64, device=dev)
+    accept = torch.empty((max(n_traj, 0), Cn), dtype=torch.uint8, device=dev)
+    action = torch.empty(Cn, dtype=torch.float64, device=dev)
+    record = None
+    if record_every is not None:
+        record = torch.empty((n_traj // int(record_every), Cn) + lat, dtype=phi.dtype, device=dev)
+    pi_out = torch.empty_like(phi) if want_pi else None
+    if tiled and workspace is None:
+        need = load().nf_phi4_hmc_tiled_workspace(Cn, _lat4(lat), _dtype_code(phi))
+        workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    ws = (_ptr(workspace), workspace.numel()) if tiled else ()
+    seed, offset = position if position is not None else _philox_positions(dev, 2 * max(n_traj, 1), generator)
+    _check(getattr(load(), "nf_" + what)(_ptr(phi), _ptr(action), _ptr(pi_in), _ptr(pi_out), _ptr(dh), _ptr(accept),
+                                         _ptr(record), 1 if record_every is None else int(record_every), Cn, _lat4(lat),
+                                         float(w0), float(w2), float(w4), int(n_md), float(dt), n_traj,
+                                         int(bool(force_accept)), seed, offset, *ws, _dtype_code(phi), _stream()),
+           "nf_" + what)
+    return dict(action=action, dh=dh, accept=accept, record=record, pi=pi_out)
 
 
 def phi4_hmc(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in=None, want_pi=False, force_accept=False,
@@ -1887,27 +1931,8 @@ def phi4_hmc(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in=None,
     the final states, dh (n_traj, C) float64, accept (n_traj, C) uint8, record (n_traj // record_every, C, *L) or None,
     pi (C, *L) or None.  The launch takes 2 n_traj Philox positions from torch's CUDA generator, or starts at
     `position` = (seed, offset) and leaves the generator alone."""
-    _require_device(phi, pi_in)
-    if not phi.is_contiguous() or (pi_in is not None and (not pi_in.is_contiguous() or pi_in.dtype != phi.dtype
-                                                            or pi_in.shape != phi.shape)):
-        raise NormflowHipError("phi4_hmc needs contiguous phi (C, *L) and pi_in of its shape and dtype")
-    Cn, lat, dev = phi.shape[0], tuple(phi.shape[1:]), phi.device
-    if not 1 <= len(lat) <= 4:
-        raise NormflowHipError(f"phi4_hmc: lattices of 1 to 4 axes, got {lat}")
-    n_traj = int(n_traj)
-    dh = torch.empty((max(n_traj, 0), Cn), dtype=torch.float64, device=dev)
-    accept = torch.empty((max(n_traj, 0), Cn), dtype=torch.uint8, device=dev)
-    action = torch.empty(Cn, dtype=torch.float64, device=dev)
-    record = None
-    if record_every is not None:
-        record = torch.empty((n_traj // int(record_every), Cn) + lat, dtype=phi.dtype, device=dev)
-    pi_out = torch.empty_like(phi) if want_pi else None
-    seed, offset = position if position is not None else _philox_positions(dev, 2 * max(n_traj, 1), generator)
-    _check(load().nf_phi4_hmc(_ptr(phi), _ptr(action), _ptr(pi_in), _ptr(pi_out), _ptr(dh), _ptr(accept), _ptr(record),
-                              1 if record_every is None else int(record_every), Cn, _lat4(lat), float(w0), float(w2),
-                              float(w4), int(n_md), float(dt), n_traj, int(bool(force_accept)), seed, offset,
-                              _dtype_code(phi), _stream()), "nf_phi4_hmc")
-    return dict(action=action, dh=dh, accept=accept, record=record, pi=pi_out)
+    return _phi4_hmc_call("phi4_hmc", phi, w0, w2, w4, n_md, dt, n_traj=n_traj, record_every=record_every, pi_in=pi_in,
+                          want_pi=want_pi, force_accept=force_accept, position=position, generator=generator)
 
 
 # ========================================================================= the same, chains in HBM (nf_hmc_tiled.hip)
@@ -1921,25 +1946,16 @@ class HmcTiledPlan(C.Structure):
                 ("lds_bytes", C.c_int64), ("lds_budget", C.c_int64)]
 
 
-def _tiled_code(dtype):
-    return NF_F32 if dtype == torch.float32 else NF_F64 if dtype == torch.float64 else NF_F16
-
-
 def hmc_tiled_supported(lat, dtype):
     """True if nf_phi4_hmc_tiled takes chains on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own planner,
     pure host code."""
-    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
-        return False
-    return bool(load().nf_phi4_hmc_tiled_supported(_lat4(lat), _tiled_code(dtype)))
+    return _planner_supported("nf_phi4_hmc_tiled_supported", lat, dtype)
 
 
 def hmc_tiled_plan(lat, dtype):
     """What nf_phi4_hmc_tiled will do on the lattice `lat` in `dtype`, per axis of `lat`: dict(tile, ntiles, tiles (per
     chain), march_axis (None when no axis is marched), ring_depth, lanes, vec, lds_bytes, lds_budget).  Pure host code."""
-    if not 1 <= len(lat) <= 4:
-        raise NormflowHipError(f"hmc_tiled_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
-    out = HmcTiledPlan()
-    _check(load().nf_phi4_hmc_tiled_plan(_lat4(lat), _tiled_code(dtype), C.byref(out)), "nf_phi4_hmc_tiled_plan")
+    out = _planner_plan("hmc_tiled_plan", "nf_phi4_hmc_tiled_plan", lat, dtype, HmcTiledPlan())
     pad = 4 - len(lat)
     return dict(tile=tuple(out.tile)[pad:], ntiles=tuple(out.ntiles)[pad:], tiles=out.tiles,
                 march_axis=None if out.march_axis < 0 else out.march_axis - pad, ring_depth=out.ring_depth, lanes=out.lanes,
@@ -1952,31 +1968,9 @@ def phi4_hmc_tiled(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in
     Philox positions and the same dict.  (n_md + 2) * n_traj launches on the current stream.  The workspace comes from
     torch's caching allocator per call (stream-aware and graph-pool safe, like `_workspace`), or is `workspace`: a uint8
     tensor of at least nf_phi4_hmc_tiled_workspace bytes."""
-    _require_device(phi, pi_in)
-    if not phi.is_contiguous() or (pi_in is not None and (not pi_in.is_contiguous() or pi_in.dtype != phi.dtype
-                                                            or pi_in.shape != phi.shape)):
-        raise NormflowHipError("phi4_hmc_tiled needs contiguous phi (C, *L) and pi_in of its shape and dtype")
-    Cn, lat, dev = phi.shape[0], tuple(phi.shape[1:]), phi.device
-    if not 1 <= len(lat) <= 4:
-        raise NormflowHipError(f"phi4_hmc_tiled: lattices of 1 to 4 axes, got {lat}")
-    n_traj = int(n_traj)
-    dh = torch.empty((max(n_traj, 0), Cn), dtype=torch.float64, device=dev)
-    accept = torch.empty((max(n_traj, 0), Cn), dtype=torch.uint8, device=dev)
-    action = torch.empty(Cn, dtype=torch.float64, device=dev)
-    record = None
-    if record_every is not None:
-        record = torch.empty((n_traj // int(record_every), Cn) + lat, dtype=phi.dtype, device=dev)
-    pi_out = torch.empty_like(phi) if want_pi else None
-    if workspace is None:
-        need = load().nf_phi4_hmc_tiled_workspace(Cn, _lat4(lat), _dtype_code(phi))
-        workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
-    seed, offset = position if position is not None else _philox_positions(dev, 2 * max(n_traj, 1), generator)
-    _check(load().nf_phi4_hmc_tiled(_ptr(phi), _ptr(action), _ptr(pi_in), _ptr(pi_out), _ptr(dh), _ptr(accept),
-                                    _ptr(record), 1 if record_every is None else int(record_every), Cn, _lat4(lat),
-                                    float(w0), float(w2), float(w4), int(n_md), float(dt), n_traj,
-                                    int(bool(force_accept)), seed, offset, _ptr(workspace), workspace.numel(),
-                                    _dtype_code(phi), _stream()), "nf_phi4_hmc_tiled")
-    return dict(action=action, dh=dh, accept=accept, record=record, pi=pi_out)
+    return _phi4_hmc_call("phi4_hmc_tiled", phi, w0, w2, w4, n_md, dt, n_traj=n_traj, record_every=record_every,
+                          pi_in=pi_in, want_pi=want_pi, force_accept=force_accept, position=position, generator=generator,
+                          workspace=workspace)
 
 
 # ========================================================================= observables of sampler rows (nf_measure.hip)
@@ -1993,19 +1987,14 @@ class MeasurePlan(C.Structure):
 def measure_supported(lat, dtype):
     """True if nf_lattice_measure takes rows on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own planner,
     pure host code."""
-    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
-        return False
-    return bool(load().nf_lattice_measure_supported(_lat4(lat), _tiled_code(dtype)))
+    return _planner_supported("nf_lattice_measure_supported", lat, dtype)
 
 
 def measure_plan(lat, dtype):
     """What nf_lattice_measure will do on the lattice `lat` in `dtype`: dict(regime ('resident', 'packed' or 'segmented'),
     rows_per_group, segments, seg_len, stage_planes, lanes, vec, n_out (of the lattice padded to four axes), march_axis
     (the axis of `lat` that segments cut: its slowest of extent > 1), lds_bytes, lds_budget).  Pure host code."""
-    if not 1 <= len(lat) <= 4:
-        raise NormflowHipError(f"measure_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
-    out = MeasurePlan()
-    _check(load().nf_lattice_measure_plan(_lat4(lat), _tiled_code(dtype), C.byref(out)), "nf_lattice_measure_plan")
+    out = _planner_plan("measure_plan", "nf_lattice_measure_plan", lat, dtype, MeasurePlan())
     march = next((mu for mu, n in enumerate(lat) if n > 1), len(lat) - 1)
     return dict(regime=MEASURE_REGIMES[out.regime], rows_per_group=out.rows_per_group, segments=out.segments,
                 seg_len=out.seg_len, stage_planes=out.stage_planes, lanes=out.lanes, vec=out.vec, n_out=out.n_out,

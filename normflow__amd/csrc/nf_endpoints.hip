@@ -12,7 +12,7 @@
 //       s[b, x] = wm phi^2 + w4 phi^4 + (w0 / 4) sum_mu [(phi(x) - phi(x + mu))^2 + (phi(x) - phi(x - mu))^2]
 //     with wm = w2 - d w0; its sites sum to S[b].  One stencil pass, and one for its VJP (which
 //     also reads the cotangent at the 2d neighbours).
-#include "nf_internal.h"
+#include "nf_sampler_core.h"
 
 namespace nf {
 
@@ -179,14 +179,15 @@ static int run_density(EpArgs &A, int64_t B, hipStream_t stream) {
 // NormalPrior.sample_ (reference: src/prior/prior.py:26-29 + :30-36 = torch.distributions.Normal.sample, then a second
 // pass for log_prob and its per-sample sum): ONE kernel that draws x = loc + scale z and accumulates
 // logr[b] = sum_x [-z^2/2 - log scale - log sqrt(2 pi)] from the z it has in registers -- the field is written once and
-// never read back.  Generator: Philox4x32-10 (counter-based: any lane computes its numbers from (seed, offset, index),
-// no state in memory); layout of the draws: include/normflow_hip.h, restated by oracle/nf_oracle.py::normal_prior_sample.
+// never read back.  Generator: Philox4x32-10 (nf_sampler_core.h; counter-based: any lane computes its numbers from
+// (seed, offset, index), no state in memory); layout of the draws: include/normflow_hip.h, restated by
+// oracle/nf_oracle.py::normal_prior_sample.
 struct SampleArgs {
   void *x;
   const void *loc, *scale;
   double *partial;
   int64_t V, ngroups;
-  uint32_t k0, k1, o0, o1;
+  PhiloxPos pos;
   int iters;
 };
 
@@ -204,10 +205,8 @@ __global__ __launch_bounds__(kBlock) void normal_sample_kernel(SampleArgs A) {
     const int64_t q = base + int64_t(it) * kBlock;
     if (q >= A.ngroups) break;
     const uint64_t g = uint64_t(b) * uint64_t(A.ngroups) + uint64_t(q);
-    uint32_t c[4] = {uint32_t(g), uint32_t(g >> 32), A.o0, A.o1};
-    philox4x32_10(c, A.k0, A.k1);
     T z[PER];
-    philox_normals<T>(c, z);
+    philox_normal_group<T>(A.pos, g, z);
     const int64_t i0 = q * PER;
     T v[PER];
 #pragma unroll
@@ -358,7 +357,7 @@ extern "C" int nf_normal_sample(void *x, void *logr, const void *loc, const void
   // key = torch's seed with a fixed constant folded into its high word: torch's own Philox kernels key on the bare seed
   // with the counter words transposed ((offset, subsequence) against this kernel's (group, offset)), so without the
   // constant one of their threads could replay the raw words of one of this kernel's groups (same 128-bit space)
-  A.k0 = uint32_t(seed); A.k1 = uint32_t(seed >> 32) ^ NF_PHILOX_KEY_DOMAIN; A.o0 = uint32_t(offset); A.o1 = uint32_t(offset >> 32);
+  A.pos = philox_pos(seed, NF_PHILOX_KEY_DOMAIN, offset);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (dtype == NF_F32) return run_sample<float>(A, logr, B, workspace, workspace_bytes, s);
   if (dtype == NF_F64) return run_sample<double>(A, logr, B, workspace, workspace_bytes, s);

@@ -10,8 +10,9 @@
 // only when a trajectory is accepted and read back when one is rejected, so a rejected chain keeps its bits.
 // The energies are summed in double whatever the field dtype, in a fixed order (lane partial over k, wave shuffle tree,
 // waves in order): no atomics, the same inputs give the same bits, and a launch of n_traj trajectories equals n_traj
-// launches of one.  Random numbers: the streams of nf_normal_sample (momenta) and nf_block_accept (uniform), see the header.
-#include "nf_internal.h"
+// launches of one.  Random numbers: the streams of nf_normal_sample (momenta) and nf_block_accept (uniform), see the header;
+// the two draws, the accept rule and the site terms of F and S are nf_sampler_core.h's, shared with nf_hmc_tiled.hip.
+#include "nf_sampler_core.h"
 
 namespace nf {
 
@@ -163,12 +164,11 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcArgs A) {
 #pragma unroll
       for (int mu = 4 - D; mu < 4; ++mu) nb += img[back(i, f, mu)] + img[fwd(i, f, mu)];
       const T p = phi[k];
-      pi[k] -= step * (w2x2 * p + w4x4 * p * p * p - w0 * nb);
+      pi[k] -= step * phi4_force(p, nb, w2x2, w4x4, w0);
       __builtin_amdgcn_sched_barrier(0);               // one slot's 8 reads in flight at a time: the registers go to phi and pi
     }
   };
-  // lane partials of sum pi^2 / 2 and of S(phi) = sum (w2 + w4 phi^2) phi^2 - w0 phi sum_mu phi(x - mu), in double on the
-  // values cast to double (explicit fma: the arithmetic does not depend on how the compiler contracts)
+  // lane partials of sum pi^2 / 2 and of S(phi) (phi4_site_energy), in double on the values cast to double
   auto energy = [&](double &kin, double &pot) {
     kin = 0.0;
     pot = 0.0;
@@ -180,10 +180,10 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcArgs A) {
       double nb = 0.0;
 #pragma unroll
       for (int mu = 4 - D; mu < 4; ++mu) nb += double(img[back(i, f, mu)]);
-      const double p = double(phi[k]), q = double(pi[k]), p2 = p * p;
+      const double p = double(phi[k]), q = double(pi[k]);
       const bool mine = owns(tv, k);
       kin += mine ? 0.5 * q * q : 0.0;
-      pot += mine ? __builtin_fma(__builtin_fma(A.w4, p2, A.w2), p2, -(A.w0 * p) * nb) : 0.0;
+      pot += mine ? phi4_site_energy(p, nb, A.w0, A.w2, A.w4) : 0.0;
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -206,12 +206,10 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcArgs A) {
     } else {
       __syncthreads();                                   // the previous trajectory's reads of the image are done
       const uint64_t off = A.offset + 2 * uint64_t(t);
+      const PhiloxPos at{A.k0n, A.k1n, uint32_t(off), uint32_t(off >> 32)};
       for (int64_t q = tid; q < ngroups; q += NT) {
-        const uint64_t g = uint64_t(c) * uint64_t(ngroups) + uint64_t(q);
-        uint32_t r[4] = {uint32_t(g), uint32_t(g >> 32), uint32_t(off), uint32_t(off >> 32)};
-        philox4x32_10(r, A.k0n, A.k1n);
         T z[PER];
-        philox_normals<T>(r, z);
+        philox_normal_group<T>(at, uint64_t(c) * uint64_t(ngroups) + uint64_t(q), z);
 #pragma unroll
         for (int j = 0; j < PER; ++j)
           if (q * PER + j < A.V) img[q * PER + j] = z[j];
@@ -244,10 +242,8 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcArgs A) {
     if (tid == 0) {
       const double dh = (k1 + e1) - (k0 + e0);
       const uint64_t offa = A.offset + 2 * uint64_t(t) + 1;
-      uint32_t r[4] = {uint32_t(uint64_t(c)), uint32_t(uint64_t(c) >> 32), uint32_t(offa), uint32_t(offa >> 32)};
-      philox4x32_10(r, A.k0a, A.k1a);
-      const double logu = ::log(philox_u53(r[0], r[1]));
-      const bool ok = A.force || logu < -dh;             // a NaN energy difference rejects
+      const PhiloxPos at{A.k0a, A.k1a, uint32_t(offa), uint32_t(offa >> 32)};
+      const bool ok = hmc_accepts(philox_log_uniform(at, uint64_t(c)), dh, A.force);
       A.dh_out[int64_t(t) * A.C + c] = dh;
       A.accept_out[int64_t(t) * A.C + c] = uint8_t(ok);
       *s_ok = int(ok);
@@ -334,13 +330,11 @@ extern "C" int nf_phi4_hmc(void *phi, double *action_out, const void *pi_in, voi
                            uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
                            double w0, double w2, double w4, int n_md, double dt, int n_traj, int force_accept,
                            uint64_t seed, uint64_t offset, int dtype, void *stream) {
-  NF_REQUIRE(phi && action_out && dh_out && accept_out, "nf_phi4_hmc: NULL pointer argument");
-  NF_REQUIRE(C >= 1 && C <= 65535, "nf_phi4_hmc: C (%lld) must be in 1 .. 65535", (long long)C);
-  NF_REQUIRE(n_md >= 1 && n_traj >= 1 && record_every >= 1,
-             "nf_phi4_hmc: n_md (%d), n_traj (%d) and record_every (%d) must be >= 1", n_md, n_traj, record_every);
-  NF_REQUIRE(!pi_in || n_traj == 1, "nf_phi4_hmc: pi_in replaces the momenta of ONE trajectory (n_traj = %d)", n_traj);
+  const HmcCall K{phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C, n_md, n_traj,
+                  force_accept != 0, seed, offset};      // for the shared checks only: HmcArgs below keeps its kernel layout
   HmcPlan p;
-  const int rc = hmc_plan("nf_phi4_hmc", lattice, dtype, p);
+  int rc = hmc_call_checks("nf_phi4_hmc", K);
+  if (!rc) rc = hmc_plan("nf_phi4_hmc", lattice, dtype, p);
   if (rc) return rc;
   // an MD step costs two barriers however few the sites: below 256 sites the steps, not the sites, set the time; and the
   // chains beyond the resident ones wait for a free CU: the time grows with every further 1024 chains
@@ -355,8 +349,9 @@ extern "C" int nf_phi4_hmc(void *phi, double *action_out, const void *pi_in, voi
   A.w0 = p.V > 1 ? w0 : 0.0;     // the one site of a lattice of one site is read as its own neighbour: weight 0
   A.w2 = w2; A.w4 = w4; A.dt = dt;
   A.n_md = n_md; A.n_traj = n_traj; A.record_every = record_every; A.force = force_accept != 0;
-  A.k0n = uint32_t(seed); A.k1n = uint32_t(seed >> 32) ^ NF_PHILOX_KEY_DOMAIN;
-  A.k0a = uint32_t(seed); A.k1a = uint32_t(seed >> 32) ^ NF_PHILOX_ACCEPT_DOMAIN;
+  // the keys of the two streams; the kernel adds 2 t (+ 1) to the offset itself
+  const PhiloxPos kn = philox_pos(seed, NF_PHILOX_KEY_DOMAIN, offset), ka = philox_pos(seed, NF_PHILOX_ACCEPT_DOMAIN, offset);
+  A.k0n = kn.k0; A.k1n = kn.k1; A.k0a = ka.k0; A.k1a = ka.k1;
   A.offset = offset;
   hipStream_t s = static_cast<hipStream_t>(stream);
   return dtype == NF_F32 ? dispatch_hmc<float>(A, p, s) : dispatch_hmc<double>(A, p, s);

@@ -1,7 +1,8 @@
 // nf_hmc_tiled.hip -- hybrid Monte Carlo for the lattice phi^4 action with the chains in HBM and many workgroups per chain
 // (MI355X-side extension, no counterpart in the reference).  The third implementation of the one definition of
 // normflow__amd/mcmc/hmc.py, for the lattices whose chain does not fit the LDS image of nf_phi4_hmc (nf_hmc.hip): the same
-// leapfrog, the same energies in double, the same accept rule, the same two Philox draws per trajectory.
+// leapfrog, the same energies in double, the same accept rule, the same two Philox draws per trajectory -- the draws, the
+// rule and the site terms of F and S through nf_sampler_core.h, which both kernels call.
 //
 // A trajectory is n_md + 2 launches on the caller's stream:
 //   begin    pi <- the draw of nf_normal_sample at (seed, offset + 2 t), or pi_in;  per-tile partials of sum pi^2 / 2 and S(phi);
@@ -24,7 +25,7 @@
 // Energies: lane partial over the lane's sites in plane order, wave shuffle tree, waves in order, tiles in order -- all in
 // double, no atomics, the same inputs give the same bits; the plan does not depend on C, so a chain's result does not
 // depend on the chains it shares a launch with.
-#include "nf_internal.h"
+#include "nf_sampler_core.h"
 
 namespace nf {
 
@@ -122,8 +123,7 @@ struct TiledArgs {
   int L[4], T[4], n[4];
   int ring, tiles;
   double w0, w2, w4, dt, eps;
-  uint32_t k0, k1;                  // begin: the key and the offset of the momentum draw
-  uint64_t offset;
+  PhiloxPos pos;                    // begin: the position of the momentum draw
 };
 
 template <typename T, int W>
@@ -153,11 +153,8 @@ template <typename T, int W>
 __device__ __forceinline__ void draw_w(const TiledArgs &A, int64_t c, int64_t i, T (&v)[W]) {
   constexpr int PER = sizeof(T) == 4 ? 4 : 2;
   const int64_t ngroups = (A.V + PER - 1) / PER;
-  const uint64_t g = uint64_t(c) * uint64_t(ngroups) + uint64_t(i / PER);
-  uint32_t r[4] = {uint32_t(g), uint32_t(g >> 32), uint32_t(A.offset), uint32_t(A.offset >> 32)};
-  philox4x32_10(r, A.k0, A.k1);
   T z[PER];
-  philox_normals<T>(r, z);
+  philox_normal_group<T>(A.pos, uint64_t(c) * uint64_t(ngroups) + uint64_t(i / PER), z);
   if constexpr (W == PER) {
 #pragma unroll
     for (int j = 0; j < PER; ++j) v[j] = z[j];
@@ -347,13 +344,13 @@ __global__ __launch_bounds__(kTiledLanes) void hmc_tiled_step(TiledArgs A) {
             nbk += double(b);
           }
           const T pi0 = pb[v];
-          const T pi1 = pi0 - eps * (w2x2 * ph + w4x4 * ph * ph * ph - w0 * nb);
+          const T pi1 = pi0 - eps * phi4_force(ph, nb, w2x2, w4x4, w0);
           fo[v] = ph;
           po[v] = pi1;
           if constexpr (MODE != 1) {
-            const double pd = double(ph), qd = double(MODE == 0 ? pi0 : pi1), p2 = pd * pd;
+            const double qd = double(MODE == 0 ? pi0 : pi1);
             kin += 0.5 * qd * qd;
-            pot += __builtin_fma(__builtin_fma(A.w4, p2, A.w2), p2, -(A.w0 * pd) * nbk);
+            pot += phi4_site_energy(double(ph), nbk, A.w0, A.w2, A.w4);
           }
         }
         const int g = g0 + u_g[k];
@@ -406,8 +403,7 @@ struct CommitArgs {
   uint8_t *accept_out;
   int64_t V;
   int tiles, force;
-  uint32_t k0, k1;
-  uint64_t offset;
+  PhiloxPos pos;
 };
 
 // One chain per blockIdx.y, a slice of its sites per blockIdx.x.  Every workgroup of a chain adds the same partials in
@@ -426,10 +422,7 @@ __global__ __launch_bounds__(kTiledLanes) void hmc_tiled_commit(CommitArgs A) {
   __syncthreads();
   const double k0 = sums[0], e0 = sums[1], k1 = sums[2], e1 = sums[3];
   const double dh = (k1 + e1) - (k0 + e0);
-  uint32_t r[4] = {uint32_t(uint64_t(c)), uint32_t(uint64_t(c) >> 32), uint32_t(A.offset), uint32_t(A.offset >> 32)};
-  philox4x32_10(r, A.k0, A.k1);
-  const double logu = ::log(philox_u53(r[0], r[1]));
-  const bool ok = A.force || logu < -dh;                 // a NaN energy difference rejects
+  const bool ok = hmc_accepts(philox_log_uniform(A.pos, uint64_t(c)), dh, A.force);
   if (blockIdx.x == 0 && tid == 0) {
     A.dh_out[c] = dh;
     A.accept_out[c] = uint8_t(ok);
@@ -479,37 +472,20 @@ static int raise_lds(const TiledPlan &p) {
   return NF_OK;
 }
 
-struct TiledCall {
-  void *phi;
-  double *action_out;
-  const void *pi_in;
-  void *pi_out;
-  double *dh_out;
-  uint8_t *accept_out;
-  void *record;
-  int record_every;
-  int64_t C;
-  int n_md, n_traj, force;
-  uint64_t seed, offset;
-  unsigned char *ws;
-};
-
 template <typename T, int VEC>
-static int run_tiled(const TiledCall &K, TiledArgs A, const TiledPlan &p, hipStream_t s) {
+static int run_tiled(const HmcCall &K, unsigned char *ws, TiledArgs A, const TiledPlan &p, hipStream_t s) {
   int rc = raise_lds<T, VEC>(p);
   if (rc) return rc;
   const size_t field = round256(size_t(K.C) * size_t(p.V) * sizeof(T));
-  double *part = reinterpret_cast<double *>(K.ws);
-  unsigned char *base = K.ws + round256(size_t(K.C) * size_t(p.tiles) * 4 * sizeof(double));
+  double *part = reinterpret_cast<double *>(ws);
+  unsigned char *base = ws + round256(size_t(K.C) * size_t(p.tiles) * 4 * sizeof(double));
   void *fphi[2] = {base, base + field}, *fpi[2] = {base + 2 * field, base + 3 * field};
   const double dt = A.dt;
   A.part = part;
   const int64_t per_chain = (p.V + kTiledLanes * 8 - 1) / (kTiledLanes * 8);
   const unsigned cblocks = unsigned(per_chain < 1024 ? per_chain : 1024);
   for (int t = 0; t < K.n_traj; ++t) {
-    A.k0 = uint32_t(K.seed);
-    A.k1 = uint32_t(K.seed >> 32) ^ NF_PHILOX_KEY_DOMAIN;
-    A.offset = K.offset + 2 * uint64_t(t);
+    A.pos = philox_pos(K.seed, NF_PHILOX_KEY_DOMAIN, K.offset + 2 * uint64_t(t));
     A.phi_src = K.phi; A.pi_src = K.pi_in; A.phi_dst = nullptr; A.pi_dst = fpi[0];
     A.eps = 0.5 * dt;
     if ((rc = launch_tiled_step<T, VEC>(0, A, p, K.C, s))) return rc;
@@ -530,9 +506,7 @@ static int run_tiled(const TiledCall &K, TiledArgs A, const TiledPlan &p, hipStr
     Q.accept_out = K.accept_out + int64_t(t) * K.C;
     Q.action_out = K.action_out;
     Q.V = p.V; Q.tiles = p.tiles; Q.force = K.force;
-    Q.k0 = uint32_t(K.seed);
-    Q.k1 = uint32_t(K.seed >> 32) ^ NF_PHILOX_ACCEPT_DOMAIN;
-    Q.offset = K.offset + 2 * uint64_t(t) + 1;
+    Q.pos = philox_pos(K.seed, NF_PHILOX_ACCEPT_DOMAIN, K.offset + 2 * uint64_t(t) + 1);
     hipLaunchKernelGGL((hmc_tiled_commit<T>), dim3(cblocks, unsigned(K.C)), dim3(kTiledLanes), 0, s, Q);
     if ((rc = check_launch("nf_phi4_hmc_tiled (commit)"))) return rc;
   }
@@ -587,13 +561,11 @@ extern "C" int nf_phi4_hmc_tiled(void *phi, double *action_out, const void *pi_i
                                  double w0, double w2, double w4, int n_md, double dt, int n_traj, int force_accept,
                                  uint64_t seed, uint64_t offset, void *workspace, size_t workspace_bytes, int dtype,
                                  void *stream) {
-  NF_REQUIRE(phi && action_out && dh_out && accept_out, "nf_phi4_hmc_tiled: NULL pointer argument");
-  NF_REQUIRE(C >= 1 && C <= 65535, "nf_phi4_hmc_tiled: C (%lld) must be in 1 .. 65535", (long long)C);
-  NF_REQUIRE(n_md >= 1 && n_traj >= 1 && record_every >= 1,
-             "nf_phi4_hmc_tiled: n_md (%d), n_traj (%d) and record_every (%d) must be >= 1", n_md, n_traj, record_every);
-  NF_REQUIRE(!pi_in || n_traj == 1, "nf_phi4_hmc_tiled: pi_in replaces the momenta of ONE trajectory (n_traj = %d)", n_traj);
+  const HmcCall K{phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C, n_md, n_traj,
+                  force_accept != 0, seed, offset};
   TiledPlan p;
-  const int rc = tiled_plan("nf_phi4_hmc_tiled", lattice, dtype, p);
+  int rc = hmc_call_checks("nf_phi4_hmc_tiled", K);
+  if (!rc) rc = tiled_plan("nf_phi4_hmc_tiled", lattice, dtype, p);
   if (rc) return rc;
   NF_REQUIRE(int64_t(p.tiles) * C <= kTiledMaxGroups,
              "nf_phi4_hmc_tiled: %d tiles x %lld chains exceed the %lld workgroups of one launch: run the chains in several "
@@ -615,8 +587,6 @@ extern "C" int nf_phi4_hmc_tiled(void *phi, double *action_out, const void *pi_i
   }
   A.ring = p.ring; A.tiles = p.tiles;
   A.w0 = w0; A.w2 = w2; A.w4 = w4; A.dt = dt;
-  TiledCall K{phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C, n_md, n_traj,
-              force_accept != 0, seed, offset, static_cast<unsigned char *>(workspace)};
   // 16-byte accesses need every row to start on 16 bytes: the lattice's fastest extent a multiple of 16 / sizeof (the
   // plan's vec) and the caller's fields aligned; the workspace's fields are, when the workspace is
   const uintptr_t bits = reinterpret_cast<uintptr_t>(phi) | reinterpret_cast<uintptr_t>(pi_in) |
@@ -624,6 +594,7 @@ extern "C" int nf_phi4_hmc_tiled(void *phi, double *action_out, const void *pi_i
   const bool wide = p.vec > 1 && (bits & 15) == 0;
   NF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "nf_phi4_hmc_tiled: the workspace must be 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == NF_F32) return wide ? run_tiled<float, 4>(K, A, p, s) : run_tiled<float, 1>(K, A, p, s);
-  return wide ? run_tiled<double, 2>(K, A, p, s) : run_tiled<double, 1>(K, A, p, s);
+  unsigned char *ws = static_cast<unsigned char *>(workspace);
+  if (dtype == NF_F32) return wide ? run_tiled<float, 4>(K, ws, A, p, s) : run_tiled<float, 1>(K, ws, A, p, s);
+  return wide ? run_tiled<double, 2>(K, ws, A, p, s) : run_tiled<double, 1>(K, ws, A, p, s);
 }

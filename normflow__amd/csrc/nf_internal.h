@@ -102,52 +102,7 @@ template <typename T>
 int launch_finalize(const double *partial, int64_t n_part, const void *log0, void *logj, int64_t B,
                     hipStream_t stream);
 
-// ---------------------------------------------------------------- Philox4x32-10
-// Counter-based generator (Salmon et al., SC'11): the four output words of one counter under one key, no state in memory.
-// nf_normal_sample (nf_endpoints.hip) and the block-update kernels (nf_mcmc.hip) share it; their counter layouts are
-// written out in include/normflow_hip.h.
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
-
-// fp64 uniform in (0, 1] from 53 bits of two output words: ((ra << 21 ^ rb >> 11) + 1) 2^-53
-__device__ __forceinline__ double philox_u53(uint32_t ra, uint32_t rb) {
-  const uint64_t a = (uint64_t(ra) << 21) ^ (uint64_t(rb) >> 11);
-  return (double(a) + 1.0) * 1.1102230246251565e-16;
-}
-
-// Box-Muller on the output words of one Philox call: four standard normals (fp32) or two (fp64), the layout of
-// nf_normal_sample (include/normflow_hip.h)
-template <typename T>
-__device__ __forceinline__ void philox_normals(const uint32_t (&c)[4], T (&z)[sizeof(T) == 4 ? 4 : 2]) {
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const float u1 = (float(c[2 * h] >> 8) + (float(c[2 * h] & 255u) + 1.0f) * 0.00390625f) * 5.9604644775390625e-08f;   // (r + 1) 2^-32, no rounding to 0 or above 1
-      const float u2 = float(c[2 * h + 1]) * 2.3283064365386963e-10f;
-      const float rho = __builtin_sqrtf(-2.0f * logf(u1 > 1.0f ? 1.0f : u1));
-      float sn, cs;
-      sincospif(2.0f * u2, &sn, &cs);        // exact range reduction (the argument is in half-turns); the kernel stays near its HBM floor
-      z[2 * h] = rho * cs;
-      z[2 * h + 1] = rho * sn;
-    }
-  } else {
-    const uint64_t d = (uint64_t(c[2]) << 21) ^ (uint64_t(c[3]) >> 11);
-    const double u1 = philox_u53(c[0], c[1]), u2 = double(d) * 1.1102230246251565e-16;
-    const double rho = ::sqrt(-2.0 * ::log(u1));
-    double sn, cs;
-    ::sincos(6.283185307179586 * u2, &sn, &cs);
-    z[0] = rho * cs;
-    z[1] = rho * sn;
-  }
-}
+// The Philox4x32-10 generator and everything else the sampler kernels share: nf_sampler_core.h.
 
 // How a (B, units) problem is cut into workgroups: every workgroup owns `per_block`
 // consecutive units of ONE sample, so its partial log-det needs no atomics.

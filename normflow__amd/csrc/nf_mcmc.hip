@@ -9,8 +9,8 @@
 // and :304-328, two Python loops over the batch on the host, three index_select passes):
 //   * nf_metropolis_chains: every decision of C chains over S steps in one launch, with the kept row's index and log q / log p;
 //   * nf_metropolis_select: the rejected rows of the batch overwritten in place by the configuration their chain holds.
-// Random numbers: Philox4x32-10 (nf_internal.h); the counter layouts are written out in include/normflow_hip.h.
-#include "nf_internal.h"
+// Random numbers: Philox4x32-10 and the two draws (nf_sampler_core.h); the counter layouts: include/normflow_hip.h.
+#include "nf_sampler_core.h"
 
 namespace nf {
 
@@ -19,7 +19,7 @@ struct ProposeArgs {
   void *backup;
   const void *loc, *scale;     // (V) or null
   int64_t C, V, block_len, start, ngroups;
-  uint32_t k0, k1, o0, o1;
+  PhiloxPos pos;
 };
 
 // Grid-stride over (chain, Philox group): the group's normals are those nf_normal_sample draws for sample c of a
@@ -33,11 +33,8 @@ __global__ __launch_bounds__(kBlock) void block_propose_kernel(ProposeArgs A) {
   const int64_t total = A.C * A.ngroups;
   for (int64_t u = int64_t(blockIdx.x) * kBlock + threadIdx.x; u < total; u += int64_t(gridDim.x) * kBlock) {
     const int64_t c = u / A.ngroups, q = u - c * A.ngroups;
-    const uint64_t g = uint64_t(u);                     // = c * ngroups + q
-    uint32_t r[4] = {uint32_t(g), uint32_t(g >> 32), A.o0, A.o1};
-    philox4x32_10(r, A.k0, A.k1);
     T z[PER];
-    philox_normals<T>(r, z);
+    philox_normal_group<T>(A.pos, uint64_t(u), z);      // u = c * ngroups + q
     T *xc = x + c * A.V + A.start;
     T *bc = bk + c * A.block_len;
 #pragma unroll
@@ -60,7 +57,7 @@ struct AcceptArgs {
   uint8_t *accept;
   int64_t C, V, block_len, start;
   int force;
-  uint32_t k0, k1, o0, o1;
+  PhiloxPos pos;
 };
 
 // One workgroup per chain (grid-stride over chains): every lane draws the chain's uniform and takes the decision
@@ -71,9 +68,7 @@ __global__ __launch_bounds__(kBlock) void block_accept_kernel(AcceptArgs A) {
   const T *__restrict__ bk = static_cast<const T *>(A.backup);
   const T *lq = static_cast<const T *>(A.logq), *lp = static_cast<const T *>(A.logp);
   for (int64_t c = blockIdx.x; c < A.C; c += gridDim.x) {
-    uint32_t r[4] = {uint32_t(uint64_t(c)), uint32_t(uint64_t(c) >> 32), A.o0, A.o1};
-    philox4x32_10(r, A.k0, A.k1);
-    const double logu = ::log(philox_u53(r[0], r[1]));
+    const double logu = philox_log_uniform(A.pos, uint64_t(c));
     const double d = double(lq[c]) - double(lp[c]);
     const double ref = A.logqp_ref[c];
     const bool ok = A.force || logu < ref - d;
@@ -111,7 +106,7 @@ struct ChainsArgs {
   void *logq_sel, *logp_sel;
   int64_t S, C;
   int fresh;
-  uint32_t k0, k1, o0, o1;
+  PhiloxPos pos;
 };
 
 // Mapping: a workgroup owns a group of W <= 64 adjacent chains (grid-stride over the groups) and walks their steps in
@@ -155,9 +150,7 @@ __global__ __launch_bounds__(kBlock) void metropolis_chains_kernel(ChainsArgs A)
       for (int e = tid; e < n; e += kBlock) {
         const int sl = e / W, cl = e - sl * W;
         const uint64_t r = uint64_t((s0 + sl) * A.C + c0 + cl);
-        uint32_t x[4] = {uint32_t(r), uint32_t(r >> 32), A.o0, A.o1};
-        philox4x32_10(x, A.k0, A.k1);
-        s_logu[e] = ::log(philox_u53(x[0], x[1]));
+        s_logu[e] = philox_log_uniform(A.pos, r);
         s_lq[e] = lq[r];
         s_lp[e] = lp[r];
       }
@@ -252,7 +245,7 @@ extern "C" int nf_block_propose(void *x, void *backup, const void *loc, const vo
   const int per = dtype == NF_F32 ? 4 : 2;
   A.ngroups = (block_len + per - 1) / per;
   // the key of nf_normal_sample: a draw here is a draw of that kernel on a (C, block_len) field
-  A.k0 = uint32_t(seed); A.k1 = uint32_t(seed >> 32) ^ NF_PHILOX_KEY_DOMAIN; A.o0 = uint32_t(offset); A.o1 = uint32_t(offset >> 32);
+  A.pos = philox_pos(seed, NF_PHILOX_KEY_DOMAIN, offset);
   const int64_t total = C * A.ngroups;
   const int64_t blocks = (total + kBlock - 1) / kBlock;
   const unsigned grid = unsigned(blocks < 8192 ? blocks : 8192);
@@ -272,7 +265,7 @@ extern "C" int nf_block_accept(void *x, const void *backup, const void *logq, co
   AcceptArgs A{};
   A.x = x; A.backup = backup; A.logq = logq; A.logp = logp; A.logqp_ref = logqp_ref; A.accept = accept_out;
   A.C = C; A.V = V; A.block_len = block_len; A.start = block_ind * block_len; A.force = force_accept != 0;
-  A.k0 = uint32_t(seed); A.k1 = uint32_t(seed >> 32) ^ NF_PHILOX_ACCEPT_DOMAIN; A.o0 = uint32_t(offset); A.o1 = uint32_t(offset >> 32);
+  A.pos = philox_pos(seed, NF_PHILOX_ACCEPT_DOMAIN, offset);
   const unsigned grid = unsigned(C < 65536 ? C : 65536);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (dtype == NF_F32) hipLaunchKernelGGL((block_accept_kernel<float>), dim3(grid), dim3(kBlock), 0, s, A);
@@ -293,7 +286,7 @@ extern "C" int nf_metropolis_chains(const void *logq, const void *logp, double *
   A.logq = logq; A.logp = logp; A.logqp_ref = logqp_ref; A.ref_logq = ref_logq; A.ref_logp = ref_logp;
   A.accept = accept; A.keep = keep; A.logq_sel = logq_sel; A.logp_sel = logp_sel;
   A.S = S; A.C = C; A.fresh = fresh != 0;
-  A.k0 = uint32_t(seed); A.k1 = uint32_t(seed >> 32) ^ NF_PHILOX_CHAIN_DOMAIN; A.o0 = uint32_t(offset); A.o1 = uint32_t(offset >> 32);
+  A.pos = philox_pos(seed, NF_PHILOX_CHAIN_DOMAIN, offset);
   const int64_t groups = (C + kWave - 1) / kWave;
   const unsigned grid = unsigned(groups < 65536 ? groups : 65536);
   hipStream_t s = static_cast<hipStream_t>(stream);

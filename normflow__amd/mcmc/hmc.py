@@ -72,9 +72,14 @@ class HMCSampler:
         rows = batch_size // n_chains
         out = torch.empty((rows,) + tuple(phi.shape), dtype=phi.dtype, device=phi.device)
         if path == 'fused':
-            phi, S, dh, acc = self._run_fused(phi, rows, every, n_md, dt, out)
+            V, C = phi[0].numel(), phi.shape[0]
+            per = _hip.HMC_MAX_WORK // (n_md * max(V, 256) * ((C + 1023) // 1024))
+            phi, S, dh, acc = self._run_kernel('phi4_hmc', per, None, phi, rows, every, n_md, dt, out)
         elif path == 'tiled':
-            phi, S, dh, acc = self._run_tiled(phi, rows, every, n_md, dt, out)
+            need = _hip.load().nf_phi4_hmc_tiled_workspace(phi.shape[0], _hip._lat4(tuple(phi.shape[1:])), _hip._dtype_code(phi))
+            ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=phi.device)      # one workspace for all calls
+            per = _hip.HMC_TILED_MAX_LAUNCHES // (n_md + 2)
+            phi, S, dh, acc = self._run_kernel('phi4_hmc_tiled', per, ws, phi, rows, every, n_md, dt, out)
         else:
             phi, S, dh, acc = self._run_composed(phi, S, rows, every, n_md, dt, out)
         self._ref.update(sample=phi, action=S)
@@ -162,19 +167,20 @@ class HMCSampler:
         own = sum(1 for n in lat if n == 1)
         return float(w0), float(w2 - own * w0), float(w4)
 
-    # ---- fused
-    def _run_fused(self, phi, rows, every, n_md, dt, out):
-        """rows * every trajectories in as few launches as NF_HMC_MAX_WORK allows."""
+    # ---- fused and tiled
+    def _run_kernel(self, kernel, per, workspace, phi, rows, every, n_md, dt, out):
+        """rows * every trajectories by _hip.<kernel> in as few calls as `per`, the trajectories one call may hold under
+        NF_HMC_MAX_WORK (fused) or NF_HMC_TILED_MAX_LAUNCHES (tiled), allows."""
         phi = phi.clone()
         coef = self._coef(phi.shape[1:])
-        V = phi[0].numel()
-        per = max(1, _hip.HMC_MAX_WORK // (n_md * max(V, 256) * ((phi.shape[0] + 1023) // 1024)))   # trajectories per launch
+        per = max(1, per)
+        kw = {} if workspace is None else dict(workspace=workspace)
         dhs, accs, action = [], [], None
         if per >= every:
             step, r0 = per // every, 0
             while r0 < rows:
                 k = min(step, rows - r0)
-                r = _hip.phi4_hmc(phi, *coef, n_md, dt, n_traj=k * every, record_every=every)
+                r = getattr(_hip, kernel)(phi, *coef, n_md, dt, n_traj=k * every, record_every=every, **kw)
                 out[r0:r0 + k] = r['record']
                 dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
                 r0 += k
@@ -183,35 +189,7 @@ class HMCSampler:
                 left = every
                 while left:
                     k = min(per, left)
-                    r = _hip.phi4_hmc(phi, *coef, n_md, dt, n_traj=k)
-                    dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
-                    left -= k
-                out[r0] = phi
-        return phi, action, torch.cat(dhs), torch.cat(accs)
-
-    # ---- tiled
-    def _run_tiled(self, phi, rows, every, n_md, dt, out):
-        """rows * every trajectories in as few calls as NF_HMC_TILED_MAX_LAUNCHES allows; one workspace for all of them."""
-        phi = phi.clone()
-        coef = self._coef(phi.shape[1:])
-        need = _hip.load().nf_phi4_hmc_tiled_workspace(phi.shape[0], _hip._lat4(tuple(phi.shape[1:])), _hip._dtype_code(phi))
-        ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=phi.device)
-        per = max(1, _hip.HMC_TILED_MAX_LAUNCHES // (n_md + 2))           # trajectories per call
-        dhs, accs, action = [], [], None
-        if per >= every:
-            step, r0 = per // every, 0
-            while r0 < rows:
-                k = min(step, rows - r0)
-                r = _hip.phi4_hmc_tiled(phi, *coef, n_md, dt, n_traj=k * every, record_every=every, workspace=ws)
-                out[r0:r0 + k] = r['record']
-                dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
-                r0 += k
-        else:
-            for r0 in range(rows):
-                left = every
-                while left:
-                    k = min(per, left)
-                    r = _hip.phi4_hmc_tiled(phi, *coef, n_md, dt, n_traj=k, workspace=ws)
+                    r = getattr(_hip, kernel)(phi, *coef, n_md, dt, n_traj=k, **kw)
                     dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
                     left -= k
                 out[r0] = phi

@@ -1,6 +1,8 @@
-"""Shared by tests/test_hmc_host.py and tests/test_hmc.py: the fp64 torch restatement of the HMC trajectory of
-normflow__amd/mcmc/hmc.py (written from its definition with torch.roll, none of the package's code), the accept uniforms
-restated with the oracle's Philox, the exact <phi^2> of the four-site chain by quadrature, and the model builder."""
+"""Shared by tests/test_hmc_host.py, tests/test_hmc.py and tests/test_hmc_tiled.py: the fp64 torch restatement of the
+HMC trajectory of normflow__amd/mcmc/hmc.py (written from its definition with torch.roll, none of the package's code),
+the accept uniforms restated with the oracle's Philox, the exact <phi^2> of the four-site chain by quadrature, the
+model builder, and the helpers of the two device suites (test fields, the relative error, the fp32 bounds, one launch
+of either kernel)."""
 import numpy as np
 import torch
 
@@ -13,6 +15,7 @@ ACCEPT_DOMAIN = 0x6E666163          # NF_PHILOX_ACCEPT_DOMAIN
 INTERACTING = dict(kappa=0.67, m_sq=-2.68, lambd=0.5)
 FREE = dict(kappa=0.25, m_sq=1.5, lambd=0.0)
 FREE_PHI2 = 0.5164                  # tr K^-1 / V of the 16-site free chain (tests/test_mcmc_chains.py)
+DEV = torch.device("cuda", 0)
 
 
 def model(lattice, dtype, device, **couplings):
@@ -94,3 +97,32 @@ def chain_stats(y, n_chains, drop):
     y = y.detach().double().cpu().reshape(rows, n_chains, -1)[drop:]
     per_chain = (y ** 2).mean(dim=(0, 2))
     return per_chain.mean().item(), per_chain.std().item() / n_chains ** 0.5
+
+
+def field(shape, dtype, seed, scale=0.7):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return (scale * torch.randn(shape, generator=g, dtype=torch.float64, device="cpu")).to(device=DEV, dtype=dtype)
+
+
+def rel(a, b):
+    return ((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-300)).item()
+
+
+def fp32_bounds(name, f32, c32, ref, parity_report):
+    """A kernel's fp32 trajectory f32 against the fp64 reference: 4 x the composed path's own fp32 error c32."""
+    for key in ('phi', 'pi'):
+        bound = max(4 * rel(c32[key], ref[key]), 1e-6)
+        err = rel(f32[key], ref[key])
+        parity_report(name, key, err, bound, "4 x composed fp32, floor 1e-6")
+        assert err <= bound, (name, key, err, bound)
+    bound = 4 * (c32['dh'] - ref['dh']).abs().max().item() + 1e-4
+    err = (f32['dh'] - ref['dh']).abs().max().item()
+    parity_report(name, 'dH (abs)', err, bound, "4 x composed fp32 + 1e-4")
+    assert err <= bound, (name, err, bound)
+
+
+def launch(kernel, phi, coef, n_traj, pos, **kw):
+    """(the chains after, the kernel's dict) of `kernel` (_hip.phi4_hmc or _hip.phi4_hmc_tiled) on a copy of phi."""
+    phi = phi.clone()
+    r = kernel(phi, *coef, kw.pop('n_md', 4), kw.pop('dt', 0.1), n_traj=n_traj, position=pos, **kw)
+    return phi, r

@@ -13,10 +13,10 @@ import torch
 from normflow__amd import _hip
 
 import hmc_cases as H
+from hmc_cases import DEV, field as _field, rel as _rel
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda", 0)
 F32, F64 = torch.float32, torch.float64
 LATTICES = [(5,), (1, 7), (2, 6), (16, 16), (17, 16), (5, 7, 9), (3, 4, 5), (2, 3, 4, 5), (16, 16, 16)]
 CHAINS = [1, 3, 300]
@@ -26,15 +26,6 @@ CASES64 = [(lat, C) for lat in LATTICES for C in CHAINS] + [((8192,), 2)]
 CASES32 = [(lat, C) for lat in LATTICES for C in CHAINS] + [((90, 90), 2), ((24, 24, 24), 2), ((128, 128), 2)]
 _case = lambda v: f"{'x'.join(map(str, v[0]))}-C{v[1]}"
 _name = lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v).replace("torch.", "")
-
-
-def _field(shape, dtype, seed, scale=0.7):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return (scale * torch.randn(shape, generator=g, dtype=F64, device="cpu")).to(device=DEV, dtype=dtype)
-
-
-def _rel(a, b):
-    return ((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-300)).item()
 
 
 @pytest.mark.parametrize("case", CASES64, ids=_case)
@@ -78,16 +69,7 @@ def test_fused_fp32(case, parity_report):
     c32 = m32.hmc.trajectory(phi0, N_MD, DT, pi=pi0, force_accept=True, path='composed', position=pos)
     f32 = m32.hmc.trajectory(phi0, N_MD, DT, pi=pi0, force_accept=True, path='fused', position=pos)
     assert f32['phi'].dtype == F32 and f32['dh'].dtype == F64
-    case = f"hmc fp32 {_name(lattice)} C={C}"
-    for key in ('phi', 'pi'):
-        bound = max(4 * _rel(c32[key], ref[key]), 1e-6)
-        err = _rel(f32[key], ref[key])
-        parity_report(case, key, err, bound, "4 x composed fp32, floor 1e-6")
-        assert err <= bound, (case, key, err, bound)
-    bound = 4 * (c32['dh'] - ref['dh']).abs().max().item() + 1e-4
-    err = (f32['dh'] - ref['dh']).abs().max().item()
-    parity_report(case, 'dH (abs)', err, bound, "4 x composed fp32 + 1e-4")
-    assert err <= bound, (case, err, bound)
+    H.fp32_bounds(f"hmc fp32 {_name(lattice)} C={C}", f32, c32, ref, parity_report)
 
 
 def test_fused_fp32_draws_the_momenta_of_normal_sample(parity_report):
@@ -105,21 +87,11 @@ def test_fused_fp32_draws_the_momenta_of_normal_sample(parity_report):
     ref = m64.hmc.trajectory(phi0.double(), N_MD, DT, pi=pi0.double(), force_accept=True, path='composed', position=pos)
     c32 = m32.hmc.trajectory(phi0, N_MD, DT, force_accept=True, path='composed', position=pos)
     f32 = m32.hmc.trajectory(phi0, N_MD, DT, force_accept=True, path='fused', position=pos)
-    for key in ('phi', 'pi'):
-        bound = max(4 * _rel(c32[key], ref[key]), 1e-6)
-        err = _rel(f32[key], ref[key])
-        parity_report("hmc fp32 drawn momenta 5x7x9 C=3", key, err, bound, "4 x composed fp32, floor 1e-6")
-        assert err <= bound, (key, err, bound)
-    bound = 4 * (c32['dh'] - ref['dh']).abs().max().item() + 1e-4
-    err = (f32['dh'] - ref['dh']).abs().max().item()
-    parity_report("hmc fp32 drawn momenta 5x7x9 C=3", 'dH (abs)', err, bound, "4 x composed fp32 + 1e-4")
-    assert err <= bound
+    H.fp32_bounds("hmc fp32 drawn momenta 5x7x9 C=3", f32, c32, ref, parity_report)
 
 
-def _launch(phi, coef, n_traj, pos, **kw):
-    phi = phi.clone()
-    r = _hip.phi4_hmc(phi, *coef, kw.pop('n_md', 4), kw.pop('dt', 0.1), n_traj=n_traj, position=pos, **kw)
-    return phi, r
+def _launch(*args, **kw):
+    return H.launch(_hip.phi4_hmc, *args, **kw)
 
 
 @pytest.mark.parametrize("dtype", [F32, F64], ids=_name)
