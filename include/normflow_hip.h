@@ -566,6 +566,11 @@ int nf_normal_logprob_vjp(const void *x, const void *loc, const void *scale, con
  * CUDA generator, so torch.manual_seed governs this kernel too).  loc / scale: (V) or NULL (0 / 1). */
 int nf_normal_sample(void *x, void *logr, const void *loc, const void *scale, int64_t B, int64_t V, uint64_t seed,
                      uint64_t offset, void *workspace, size_t workspace_bytes, int dtype, void *stream);
+/* nf_normal_sample_rows: rows first_row .. first_row + B - 1 of the stream above, written to x (B, V) and logr (B): row b of
+ * the launch draws the groups g = (first_row + b) * ceil(V / per) + q.  A batch beyond the grid's 65535 rows is drawn in
+ * slabs at ONE offset, and is the same numbers however it is cut; nf_normal_sample is first_row = 0. */
+int nf_normal_sample_rows(void *x, void *logr, const void *loc, const void *scale, int64_t B, int64_t V, int64_t first_row,
+                          uint64_t seed, uint64_t offset, void *workspace, size_t workspace_bytes, int dtype, void *stream);
 
 /* ---- blocked Metropolis on the device (BlockedMCMCSampler, src/mcmc/mcmc.py:132-220; block updater
  * src/prior/prior.py:106-112, 161-178) for C independent chains.  x is the chains' prior-side field (C, V); block k is the

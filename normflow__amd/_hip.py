@@ -84,6 +84,7 @@ PROTOTYPES = {
     "nf_normal_logprob": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _SZ, _I, _P]),
     "nf_normal_logprob_vjp": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I, _P]),
     "nf_normal_sample": (_I, [_P, _P, _P, _P, _I64, _I64, C.c_uint64, C.c_uint64, _P, _SZ, _I, _P]),
+    "nf_normal_sample_rows": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, C.c_uint64, C.c_uint64, _P, _SZ, _I, _P]),
     "nf_block_propose": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_block_accept": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_metropolis_chains": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, C.c_uint64, C.c_uint64, _I, _P]),
@@ -239,8 +240,9 @@ def _log0_tensor(log0, like, B):
 MAX_B = 32768  # the batch is the grid's y extent; larger batches are cut into slabs
 
 
-def _slabs(B, step=MAX_B):
-    """(b0, b1) of the consecutive slabs of at most `step` samples that cover a batch of B (none when B == 0)."""
+def _slabs(B, step=None):
+    """(b0, b1) of the consecutive slabs of at most `step` (MAX_B) samples that cover a batch of B (none when B == 0)."""
+    step = MAX_B if step is None else step
     for b0 in range(0, B, step):
         yield b0, min(B, b0 + step)
 
@@ -1473,7 +1475,7 @@ class FusedLastRqsFn(torch.autograd.Function):
         b = None if bias is None else bias.detach().float().contiguous()
         y = torch.empty_like(x_active)
         logj = torch.empty(B, dtype=torch.float32, device=h.device)
-        ws = _workspace(min(B, MAX_B), V, h.device)
+        ws = _workspace(B, V, h.device)        # ONE launch over the whole batch (batch x boxes work items): no slabs here
         _check(lib.nf_conv_rqs_split16_train(_ptr(src), is16, _ptr(wsp), _ptr(b), weight.shape[0], _ptr(x_active), _ptr(log0),
                                              _ptr(y), _ptr(logj), B, lat4, int(parity), _ptr(bits), C.byref(opts),
                                              int(bool(inverse)), _ptr(ws), ws.numel(), _stream()), "nf_conv_rqs_split16_train")
@@ -1486,6 +1488,9 @@ class FusedLastRqsFn(torch.autograd.Function):
         h, weight, bias, xpt = ctx.saved_tensors
         lib = load()
         B, V = xpt.shape
+        if ctx.needs_input_grad[0] and B > 65535:      # before anything is launched: nf_conv_dgrad_split16 takes no more
+            raise NormflowHipError(f"FusedLastRqsFn.backward: batch {B} > 65535, the limit of the split-fp16 input-gradient "
+                                   "kernel (nf_conv_dgrad_split16): split the batch")
         lattice = tuple(h.shape[2:])
         lat4 = _lat4(lattice)
         cout = weight.shape[0]
@@ -1761,8 +1766,9 @@ def _philox_position(device, generator=None):
 
 
 def normal_sample(loc, scale, batch_size, shape, dtype, device, generator=None):
-    """(x (B, *shape), logr (B)) of a NormalPrior in one launch (nf_normal_sample), at the `_philox_position` of torch's
-    generator: torch.manual_seed(s) makes this kernel reproducible exactly as it does torch's own samplers."""
+    """(x (B, *shape), logr (B)) of a NormalPrior in one launch per slab (nf_normal_sample_rows), one stream for the whole
+    batch (row b draws the groups b * ngroups + q whatever the slabs), at the `_philox_position` of torch's generator:
+    torch.manual_seed(s) makes this kernel reproducible exactly as it does torch's own samplers."""
     seed, offset = _philox_position(device, generator)
     V = _sites(shape)
     x = torch.empty((batch_size,) + tuple(shape), dtype=dtype, device=device)
@@ -1771,10 +1777,10 @@ def normal_sample(loc, scale, batch_size, shape, dtype, device, generator=None):
     loc = None if loc is None else loc.to(device=device, dtype=dtype).contiguous()
     scale = None if scale is None else scale.to(device=device, dtype=dtype).contiguous()
     for b0, b1 in _slabs(batch_size):
-        # slabs of one call use disjoint counter ranges through the high word of the offset
-        _check(load().nf_normal_sample(_ptr(x[b0:b1]), _ptr(logr[b0:b1]), _ptr(loc), _ptr(scale), b1 - b0, V,
-                                       seed, offset + ((b0 // MAX_B) << 40), _ptr(ws), ws.numel(), _dtype_code(x),
-                                       _stream()), "nf_normal_sample")
+        # one call is one stream at one offset: a slab draws the rows b0 .. b1 of it
+        _check(load().nf_normal_sample_rows(_ptr(x[b0:b1]), _ptr(logr[b0:b1]), _ptr(loc), _ptr(scale), b1 - b0, V, b0,
+                                            seed, offset, _ptr(ws), ws.numel(), _dtype_code(x), _stream()),
+               "nf_normal_sample_rows")
     return x, logr
 
 

@@ -187,6 +187,7 @@ struct SampleArgs {
   const void *loc, *scale;
   double *partial;
   int64_t V, ngroups;
+  int64_t row0;                     // row of the stream that row 0 of this launch is (nf_normal_sample_rows)
   PhiloxPos pos;
   int iters;
 };
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(kBlock) void normal_sample_kernel(SampleArgs A) {
   for (int it = 0; it < A.iters; ++it) {
     const int64_t q = base + int64_t(it) * kBlock;
     if (q >= A.ngroups) break;
-    const uint64_t g = uint64_t(b) * uint64_t(A.ngroups) + uint64_t(q);
+    const uint64_t g = uint64_t(A.row0 + b) * uint64_t(A.ngroups) + uint64_t(q);
     T z[PER];
     philox_normal_group<T>(A.pos, g, z);
     const int64_t i0 = q * PER;
@@ -239,7 +240,7 @@ static int run_sample(SampleArgs &A, void *logr, int64_t B, void *ws, size_t ws_
   A.iters = t.iters;
   const size_t need = size_t(B) * size_t(t.blocks_x) * sizeof(double);
   if (ws == nullptr || ws_bytes < need) {
-    set_error("nf_normal_sample: workspace %zu B < %zu B needed", ws_bytes, need);
+    set_error("nf_normal_sample_rows: workspace %zu B < %zu B needed", ws_bytes, need);
     return NF_EWORKSPACE;
   }
   A.partial = static_cast<double *>(ws);
@@ -348,12 +349,12 @@ extern "C" int nf_normal_logprob_vjp(const void *x, const void *loc, const void 
   return NF_EINVAL;
 }
 
-extern "C" int nf_normal_sample(void *x, void *logr, const void *loc, const void *scale, int64_t B, int64_t V,
-                                uint64_t seed, uint64_t offset, void *workspace, size_t workspace_bytes, int dtype,
-                                void *stream) {
-  NF_REQUIRE(x && logr && B >= 0 && B <= 65535 && V >= 0, "nf_normal_sample: bad arguments");
+extern "C" int nf_normal_sample_rows(void *x, void *logr, const void *loc, const void *scale, int64_t B, int64_t V,
+                                     int64_t first_row, uint64_t seed, uint64_t offset, void *workspace,
+                                     size_t workspace_bytes, int dtype, void *stream) {
+  NF_REQUIRE(x && logr && B >= 0 && B <= 65535 && V >= 0 && first_row >= 0, "nf_normal_sample_rows: bad arguments");
   SampleArgs A{};
-  A.x = x; A.loc = loc; A.scale = scale; A.V = V;
+  A.x = x; A.loc = loc; A.scale = scale; A.V = V; A.row0 = first_row;
   // key = torch's seed with a fixed constant folded into its high word: torch's own Philox kernels key on the bare seed
   // with the counter words transposed ((offset, subsequence) against this kernel's (group, offset)), so without the
   // constant one of their threads could replay the raw words of one of this kernel's groups (same 128-bit space)
@@ -361,6 +362,12 @@ extern "C" int nf_normal_sample(void *x, void *logr, const void *loc, const void
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (dtype == NF_F32) return run_sample<float>(A, logr, B, workspace, workspace_bytes, s);
   if (dtype == NF_F64) return run_sample<double>(A, logr, B, workspace, workspace_bytes, s);
-  set_error("nf_normal_sample: unsupported dtype %d", dtype);
+  set_error("nf_normal_sample_rows: unsupported dtype %d", dtype);
   return NF_EINVAL;
+}
+
+extern "C" int nf_normal_sample(void *x, void *logr, const void *loc, const void *scale, int64_t B, int64_t V,
+                                uint64_t seed, uint64_t offset, void *workspace, size_t workspace_bytes, int dtype,
+                                void *stream) {
+  return nf_normal_sample_rows(x, logr, loc, scale, B, V, 0, seed, offset, workspace, workspace_bytes, dtype, stream);
 }

@@ -58,7 +58,7 @@ extern "C" int nf_spline_eval(const void *v, const void *knots_x, const void *kn
   NF_REQUIRE(B >= 0 && V >= 0, "nf_spline_eval: negative size (B=%lld, V=%lld)", (long long)B, (long long)V);
   NF_REQUIRE(K >= 2, "nf_spline_eval: a spline needs at least 2 knots, got %d", K);
   NF_REQUIRE(dtype == NF_F32 || dtype == NF_F64, "nf_spline_eval: unsupported dtype %d", dtype);
-  NF_REQUIRE(B <= 65535, "nf_spline_eval: batch %lld exceeds the grid's y extent; slab it", (long long)B);
+  NF_REQUIRE(B <= 65535, "nf_spline_eval: batch %lld > 65535 (the grid's y extent): slab it", (long long)B);
   if (B == 0 || V == 0) return NF_OK;
   NF_REQUIRE(v && knots_x && knots_y && knots_d && out, "nf_spline_eval: NULL tensor pointer");
   SplineArgs A{v, knots_x, knots_y, knots_d, out, deriv, V, K, shared_x != 0, shared_y != 0, shared_d != 0, inverse != 0};

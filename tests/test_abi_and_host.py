@@ -29,7 +29,7 @@ def test_library_exports_every_declared_symbol():
     declared = set(re.findall(r"\b(nf_[a-z0-9_]+)\s*\(", header))
     assert {"nf_rqs_fwd", "nf_rqs_inv", "nf_rqs_fwd_vjp", "nf_rqs_inv_vjp", "nf_affine_fwd", "nf_affine_inv",
             "nf_affine_vjp", "nf_distconv", "nf_distconv_vjp", "nf_version", "nf_last_error_string",
-            "nf_workspace_bytes"} <= declared
+            "nf_workspace_bytes", "nf_normal_sample", "nf_normal_sample_rows"} <= declared
     lib = ctypes.CDLL(_hip.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in the header but not exported"
