@@ -769,6 +769,56 @@ size_t nf_lattice_measure_workspace(int64_t N, const int32_t *lattice, int dtype
 int nf_lattice_measure(const void *cfgs, double *out, int64_t N, const int32_t *lattice, void *workspace,
                        size_t workspace_bytes, int dtype, void *stream);
 
+/* ---- the same statistics for rows that nf_lattice_measure refuses (nf_measure_tiled.hip): bricks.  cfgs, out (N, n_out),
+ * the definitions of every entry, the conversion to double and the extent-1 / extent-2 rules are nf_lattice_measure's,
+ * word for word.  The row is cut along its first two axes of extent > 1, axis0 and axis1 (axis1 = -1: the lattice has one
+ * such axis and is cut along it alone), into bricks of e0 planes of axis0 x e1 sub-planes of axis1 x all of the axes
+ * behind, one workgroup each, n0 x n1 = `bricks` per row, brick b = b0 n1 + b1 covering the planes b0 e0 .. and the
+ * sub-planes b1 e1 .. (the last of an axis may be shorter).
+ * nf_measure_tiled_plan (a function of lattice, dtype and brick_bytes alone, not of N): brick_bytes is the target size of
+ * a brick, 0 = the default (32 KiB).  axis1 is filled first, e1 = min(L_axis1, brick_bytes / bytes of a sub-plane), and
+ * axis0 is cut into pieces of more than one plane (e0 > 1) only when e1 = L_axis1; the pieces of an axis are as even as
+ * they get, and along the fastest axis they are whole 16-byte units (vec sites).  A sub-plane beyond brick_bytes is still
+ * taken, as one brick, while it fits the LDS of a CU next to the reduction slots; beyond that the lattice is refused
+ * ("does not fit": there is no cut along a third axis).  lanes = 512 for bricks above 4096 sites, else 256; n_part = 7 + e0
+ * + e1 + the uncut extents, the partial sums a brick writes; lds_bytes <= lds_budget.
+ * A brick is one run of consecutive sites: it is staged into LDS once (16-byte loads when vec > 1 and cfgs is 16-byte
+ * aligned, site by site otherwise: the same image) and every sum is read from the image as in nf_lattice_measure; the
+ * plane before the brick and the sub-plane before it are read from HBM for the backward links.  Sum order: inside a
+ * brick nf_lattice_measure's (lane partial in site order, wave shuffle tree, waves in order; per slice fixed stripes in
+ * stripe order); then a second kernel adds the bricks' partials (workspace: (N, bricks, n_part) doubles), one wave of 64
+ * lanes per (row, output): lane l adds the bricks l, l + 64, ... of the output's list in order, then the shuffle tree.
+ * The list of a slice of axis0 is the n1 bricks that hold it in b1 order, of a slice of axis1 the n0 bricks in b0 order,
+ * of everything else all bricks in brick order.  No atomics: a row's bits depend on its values, the lattice, the dtype
+ * and brick_bytes alone -- not on N, its position, the other rows or the alignment of cfgs.  Two launches; the call
+ * neither allocates nor synchronises and can be captured into a HIP graph.
+ * nf_lattice_measure_tiled_supported / _workspace (pure host code): as for nf_lattice_measure; the workspace is needed
+ * for every N >= 1 (8-byte aligned, need not be initialised).
+ * NF_EINVAL: NULL cfgs / out / lattice, extents < 1, V or n_out of 2^31 or more, a dtype other than NF_F32 / NF_F64, a
+ * brick_bytes below one element or above lds_budget, a brick that does not fit, N < 0, a short, NULL or misaligned
+ * workspace, or more than 2^24 - 1 workgroups (N bricks, or ceil(N n_out / 4)).  N = 0: NF_OK. */
+typedef struct nf_measure_tiled_plan {
+  int32_t axis0;
+  int32_t axis1;
+  int32_t e0;
+  int32_t e1;
+  int32_t n0;
+  int32_t n1;
+  int32_t bricks;
+  int32_t lanes;
+  int32_t vec;
+  int32_t n_out;
+  int32_t n_part;
+  int32_t reserved;
+  int64_t lds_bytes;
+  int64_t lds_budget;
+} nf_measure_tiled_plan;
+int nf_lattice_measure_tiled_supported(const int32_t *lattice, size_t brick_bytes, int dtype);
+int nf_lattice_measure_tiled_plan(const int32_t *lattice, size_t brick_bytes, int dtype, nf_measure_tiled_plan *out);
+size_t nf_lattice_measure_tiled_workspace(int64_t N, const int32_t *lattice, size_t brick_bytes, int dtype);
+int nf_lattice_measure_tiled(const void *cfgs, double *out, int64_t N, const int32_t *lattice, size_t brick_bytes,
+                             void *workspace, size_t workspace_bytes, int dtype, void *stream);
+
 /* ---- VJP of the conv layer (K5)---------------------------------------------------------------
  * grad_input is nf_conv_fwd itself applied to the pre-activation cotangent with the weights
  * flipped along every kernel axis and in/out channels swapped.  The two entry points below are

@@ -101,6 +101,10 @@ PROTOTYPES = {
     "nf_lattice_measure_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
     "nf_lattice_measure_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
     "nf_lattice_measure": (_I, [_P, _P, _I64, C.POINTER(C.c_int32), _P, _SZ, _I, _P]),
+    "nf_lattice_measure_tiled_supported": (_I, [C.POINTER(C.c_int32), _SZ, _I]),
+    "nf_lattice_measure_tiled_plan": (_I, [C.POINTER(C.c_int32), _SZ, _I, _P]),
+    "nf_lattice_measure_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _SZ, _I]),
+    "nf_lattice_measure_tiled": (_I, [_P, _P, _I64, C.POINTER(C.c_int32), _SZ, _P, _SZ, _I, _P]),
     "nf_act_vjp": (_I, [_P, _P, _P, _I64, _I, _I, _P]),
     "nf_conv_wgrad_cols": (_I, [_I, _I]),
     "nf_conv_wgrad": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, _P]),
@@ -2023,4 +2027,67 @@ def lattice_measure(cfgs, workspace=None):
         workspace = torch.empty(int(need), dtype=torch.uint8, device=cfgs.device) if need else None
     _check(load().nf_lattice_measure(_ptr(cfgs), _ptr(out), N, lat4, _ptr(workspace),
                                      0 if workspace is None else workspace.numel(), code, _stream()), "nf_lattice_measure")
+    return out
+
+
+# ========================================================================= the same by bricks (nf_measure_tiled.hip)
+class MeasureTiledPlan(C.Structure):
+    """nf_measure_tiled_plan (include/normflow_hip.h)."""
+    _fields_ = [("axis0", C.c_int32), ("axis1", C.c_int32), ("e0", C.c_int32), ("e1", C.c_int32), ("n0", C.c_int32),
+                ("n1", C.c_int32), ("bricks", C.c_int32), ("lanes", C.c_int32), ("vec", C.c_int32), ("n_out", C.c_int32),
+                ("n_part", C.c_int32), ("reserved", C.c_int32), ("lds_bytes", C.c_int64), ("lds_budget", C.c_int64)]
+
+
+def _brick_bytes(brick_bytes):
+    """None / 0: the library's default cap."""
+    b = 0 if brick_bytes is None else int(brick_bytes)
+    if b < 0:
+        raise NormflowHipError(f"brick_bytes must be None or >= 0, got {brick_bytes}")
+    return b
+
+
+def measure_tiled_supported(lat, dtype, brick_bytes=None):
+    """True if nf_lattice_measure_tiled takes rows on the lattice `lat` (1 to 4 extents) in `dtype` with bricks of at most
+    `brick_bytes` (None: the default cap): the launcher's own planner, pure host code."""
+    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
+        return False
+    return bool(load().nf_lattice_measure_tiled_supported(_lat4(lat), _brick_bytes(brick_bytes),
+                                                          NF_F32 if dtype == torch.float32 else NF_F64))
+
+
+def measure_tiled_plan(lat, dtype, brick_bytes=None):
+    """What nf_lattice_measure_tiled will do on the lattice `lat` in `dtype` with bricks of at most `brick_bytes`:
+    dict(axis0, axis1 (the cut axes of `lat`; axis1 None when `lat` has one axis of extent > 1), e0, e1 (planes of axis0
+    and sub-planes of axis1 per brick), n0, n1 (bricks along them), bricks (per row), lanes, vec, n_out (of the lattice
+    padded to four axes), n_part, lds_bytes, lds_budget).  Pure host code."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"measure_tiled_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
+    code = NF_F32 if dtype == torch.float32 else NF_F64 if dtype == torch.float64 else NF_F16
+    out = MeasureTiledPlan()
+    _check(load().nf_lattice_measure_tiled_plan(_lat4(lat), _brick_bytes(brick_bytes), code, C.byref(out)),
+           "nf_lattice_measure_tiled_plan")
+    pad = 4 - len(lat)
+    return dict(axis0=max(out.axis0 - pad, 0), axis1=None if out.axis1 < 0 else out.axis1 - pad, e0=out.e0, e1=out.e1,
+                n0=out.n0, n1=out.n1, bricks=out.bricks, lanes=out.lanes, vec=out.vec, n_out=out.n_out, n_part=out.n_part,
+                lds_bytes=out.lds_bytes, lds_budget=out.lds_budget)
+
+
+def lattice_measure_tiled(cfgs, brick_bytes=None, workspace=None):
+    """nf_lattice_measure_tiled: `lattice_measure`'s (N, 7 + sum of the four padded extents) float64 statistics of the
+    contiguous rows cfgs (N, *L) by bricks of at most `brick_bytes` (None: the default cap), for rows of any size: two
+    launches.  The workspace comes from torch's caching allocator per call (stream-aware and graph-pool safe, like
+    `_workspace`), or is `workspace`: a uint8 tensor of at least nf_lattice_measure_tiled_workspace bytes.  One call per
+    batch: there is no slab loop (N x bricks workgroups must fit one launch, 2^24 - 1)."""
+    _require_device(cfgs)
+    lat = tuple(cfgs.shape[1:])
+    if not cfgs.is_contiguous() or not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"lattice_measure_tiled needs contiguous cfgs (N, *L) with 1 to 4 lattice axes, got "
+                               f"{tuple(cfgs.shape)}")
+    N, lat4, code, cap = cfgs.shape[0], _lat4(lat), _dtype_code(cfgs), _brick_bytes(brick_bytes)
+    out = torch.empty((N, 7 + sum(lat) + 4 - len(lat)), dtype=torch.float64, device=cfgs.device)
+    if workspace is None:
+        need = load().nf_lattice_measure_tiled_workspace(N, lat4, cap, code)
+        workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=cfgs.device)
+    _check(load().nf_lattice_measure_tiled(_ptr(cfgs), _ptr(out), N, lat4, cap, _ptr(workspace), workspace.numel(), code,
+                                           _stream()), "nf_lattice_measure_tiled")
     return out

@@ -1,8 +1,8 @@
 """What the samplers' rows measure (MI355X-side extension; the reference stops at `Resampler` and `estimate_logz`).
 
 `measure(cfgs)` reduces every configuration (N, *L), 1 <= d <= 4, to its sufficient statistics in double -- on the device
-in ONE pass of the `nf_lattice_measure` kernel (include/normflow_hip.h), on host tensors by the same definitions composed
-from torch ops:
+in ONE pass of the `nf_lattice_measure` kernel or, for rows beyond it, of the brick-tiled `nf_lattice_measure_tiled`
+(include/normflow_hip.h; `route` says which), on host tensors by the same definitions composed from torch ops:
     sum_phi, sum_phi2, sum_phi4      sum_x phi, phi^2, phi^4
     links[:, mu]                     sum_x phi(x) phi(x - mu), periodic; 0 along an axis of extent 1
     slices[mu][:, t]                 S_mu(t) = sum over the sites with x_mu = t of phi(x)
@@ -25,6 +25,11 @@ from .stats import Resampler
 # the regimes of nf_lattice_measure_plan on which `measure` runs the kernel: those where tools/measure_bench.py measured
 # it no slower than the composed path on an MI355X (README, "Observables")
 KERNEL_REGIMES = ('packed', 'resident', 'segmented')
+# (dtype, least bytes of a row): the classes that nf_lattice_measure refuses and on which tools/measure_bench.py measured
+# the brick-tiled kernel faster than the composed path by its margin on an MI355X -- 32^4 in fp64, 48^4 in both dtypes
+# (README, "Observables").  `route` sends only these to it; a refused lattice outside them stays composed until measured
+TILED_CLASSES = ((torch.float64, 32 ** 4 * 8), (torch.float32, 48 ** 4 * 4))
+PATHS = (None, 'kernel', 'tiled', 'composed')
 
 
 def _compose(x):
@@ -40,6 +45,20 @@ def _compose(x):
     return scalars, torch.stack(links, dim=1), slices
 
 
+def _split(out, lat):
+    """The (N, 7 + sum of the padded extents) rows of either kernel as `_compose` returns them (views of `out`)."""
+    pad = 4 - len(lat)
+    at, slices = 7 + pad, []
+    for n in lat:
+        slices.append(out[:, at:at + n])
+        at += n
+    return out[:, :3], out[:, 3 + pad:7], slices
+
+
+def _on_device(cfgs):
+    return cfgs.is_cuda and cfgs.dtype in (torch.float32, torch.float64) and cfgs.shape[0] > 0 and 1 <= cfgs.ndim - 1 <= 4
+
+
 def kernel_applies(cfgs):
     """True where `measure` runs nf_lattice_measure: fp32 / fp64 rows on the device, on a lattice the launcher's planner
     takes, in a regime of KERNEL_REGIMES."""
@@ -49,25 +68,43 @@ def kernel_applies(cfgs):
     return _hip.measure_supported(lat, cfgs.dtype) and _hip.measure_plan(lat, cfgs.dtype)['regime'] in KERNEL_REGIMES
 
 
+def tiled_applies(cfgs):
+    """True where `measure(cfgs, path='tiled')` can run nf_lattice_measure_tiled: fp32 / fp64 rows on the device, on a
+    lattice its planner takes at the default cap.  Where `measure` takes it unasked is `route`'s matter."""
+    return bool(_on_device(cfgs) and _hip.measure_tiled_supported(tuple(cfgs.shape[1:]), cfgs.dtype))
+
+
+def route(cfgs):
+    """The path that `measure(cfgs)` takes: 'kernel' wherever `kernel_applies` (unchanged by the tiled kernel), 'tiled'
+    where only the brick-tiled kernel applies and the row falls into one of TILED_CLASSES, else 'composed'."""
+    if not _on_device(cfgs):
+        return 'composed'
+    if kernel_applies(cfgs):
+        return 'kernel'
+    row_bytes = math.prod(cfgs.shape[1:]) * cfgs.element_size()
+    if tiled_applies(cfgs) and any(cfgs.dtype == dt and row_bytes >= least for dt, least in TILED_CLASSES):
+        return 'tiled'
+    return 'composed'
+
+
 @torch.no_grad()
 def measure(cfgs, action=None, path=None):
-    """(N, *L) configurations -> `Measurement`.  path=None: the kernel where `kernel_applies`, else the composed torch
-    path (host tensors, other dtypes, lattices the kernel does not take); 'kernel' / 'composed' force one (a kernel that
-    cannot run raises).  With a `ScalarPhi4Action` the measurement also carries the action of every row; any other
-    action object is a TypeError (its action does not follow from these statistics)."""
-    if path not in (None, 'kernel', 'composed'):
-        raise ValueError(f"path must be None, 'kernel' or 'composed', got {path!r}")
+    """(N, *L) configurations -> `Measurement`.  path=None: what `route` says -- the kernel where `kernel_applies`, the
+    brick-tiled kernel on the classes of large rows where it was measured faster, else the composed torch path (host
+    tensors, other dtypes, lattices no kernel takes); 'kernel' / 'tiled' / 'composed' force one (a kernel that cannot run
+    raises).  With a `ScalarPhi4Action` the measurement also carries the action of every row; any other action object
+    is a TypeError (its action does not follow from these statistics)."""
+    if path not in PATHS:
+        raise ValueError(f"path must be None, 'kernel', 'tiled' or 'composed', got {path!r}")
     d = cfgs.ndim - 1
     if not 1 <= d <= 4:
         raise ValueError(f"measure: configurations (N, *L) with 1 to 4 lattice axes, got {tuple(cfgs.shape)}")
     lat = tuple(cfgs.shape[1:])
-    if path == 'kernel' or (path is None and kernel_applies(cfgs)):
-        out = _hip.lattice_measure(cfgs.contiguous())
-        pad = 4 - d
-        scalars, links, at, slices = out[:, :3], out[:, 3 + pad:7], 7 + pad, []
-        for n in lat:
-            slices.append(out[:, at:at + n])
-            at += n
+    if path is None:
+        path = route(cfgs)
+    if path in ('kernel', 'tiled'):
+        out = (_hip.lattice_measure if path == 'kernel' else _hip.lattice_measure_tiled)(cfgs.contiguous())
+        scalars, links, slices = _split(out, lat)
     else:
         scalars, links, slices = _compose(cfgs)
     return Measurement(scalars, links, slices, lat, action)
