@@ -664,13 +664,50 @@ int nf_metropolis_select(void *y, const void *ref_sample, const uint8_t *accept,
  * a free CU, so the time of a launch grows with every further 1024 chains).  Measured on an MI355X at n_md = 10
  * (tools/hmc_bench.py): 16^2 x 512 chains 0.7 us per MD step, 16^3 x 1024 chains 9 us per MD step; a launch at the cap
  * (with up to 1024 chains 2^18 MD steps at 16^2, 2^14 at 16^3; with 65535 chains a 64th of that) then takes about 0.2 s.
- * Longer runs are split into several launches by the caller. */
+ * Longer runs are split into several launches by the caller.
+ *
+ * nf_phi4_hmc_measure: nf_phi4_hmc, argument for argument, with the observables of the recorded states taken inside the
+ * launch:
+ *   measure_out (n_traj / record_every, C, n_out) double: row (r, c) is the row that nf_lattice_measure (below) gives for
+ *               the state of chain c after trajectory (r + 1) record_every - 1, BIT FOR BIT -- the 7 scalars and the
+ *               slice sums of the four extents of lattice[4], n_out = 7 + their sum as nf_lattice_measure_plan reports it
+ *   record      may be NULL (the use of this entry point: no configuration is stored) or given; with both, each output
+ *               is what it is alone.  phi, action_out, dh_out, accept_out and pi_out are nf_phi4_hmc's bits.
+ * After the decision of a recorded trajectory the workgroup writes the chain's state (the restored one on a reject) into
+ * its LDS image and the routine of nf_lattice_measure takes every sum from that image, on the first `lanes` lanes of the
+ * workgroup with `lanes` of nf_lattice_measure_plan for the lattice (64 up to 256 sites, 256 up to 4096, 512 beyond);
+ * the other waves wait at its barriers.  The same Philox positions as nf_phi4_hmc; it can be captured into a HIP graph.
+ * NF_EINVAL: what nf_phi4_hmc refuses, a NULL measure_out, or
+ *   (n_md n_traj + NF_HMC_MEASURE_MD_STEPS (n_traj / record_every)) max(V, 256) ceil(C / 1024) > NF_HMC_MAX_WORK:
+ * a measured trajectory counts as NF_HMC_MEASURE_MD_STEPS further MD steps.  From the code: an MD step is one pass over
+ * the image (2 d + 1 reads and one write per site on all lanes) and 2 barriers.  A measurement is one pass in double with
+ * d + 1 reads per site on the team (a quarter to all of the lanes), 7 wave sums of 6 dependent shuffle levels each, then
+ * per axis one more read of the whole image by at most 16 stripes per slice, serial within a stripe (extent x 16 lanes
+ * at work; 16^3: 256 of 1024 lanes), with 1 + 2 d barriers inside and 3 around the refill of the image: 12 barriers
+ * against an MD step's 2 and several times its dependent latency.  Measured on an MI355X (tools/hmc_bench.py --measure,
+ * whole sampler calls): about 7 MD steps at 16^3 x 1024 chains and on the order of 10 at 16^2 x 512; 16 covers both.
+ *
+ * nf_phi4_hmc_plan (pure host code, the launcher's own planner): sites_per_lane and lanes of the workgroup of a chain,
+ * the dynamic LDS of a launch of nf_phi4_hmc (lds_bytes) and of nf_phi4_hmc_measure (lds_bytes_measure: 5 KiB of
+ * measure slots more); NF_EINVAL where nf_phi4_hmc_supported answers 0. */
 #define NF_HMC_MAX_WORK 67108864 /* 2^26 */
+#define NF_HMC_MEASURE_MD_STEPS 16
+typedef struct nf_hmc_plan {
+  int32_t sites_per_lane;
+  int32_t lanes;
+  int64_t lds_bytes;
+  int64_t lds_bytes_measure;
+} nf_hmc_plan;
 int nf_phi4_hmc_supported(const int32_t *lattice, int dtype);
+int nf_phi4_hmc_plan(const int32_t *lattice, int dtype, nf_hmc_plan *out);
 int nf_phi4_hmc(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out, uint8_t *accept_out,
                 void *record, int record_every, int64_t C, const int32_t *lattice, double w0, double w2, double w4,
                 int n_md, double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset, int dtype,
                 void *stream);
+int nf_phi4_hmc_measure(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                        uint8_t *accept_out, void *record, double *measure_out, int record_every, int64_t C,
+                        const int32_t *lattice, double w0, double w2, double w4, int n_md, double dt, int n_traj,
+                        int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream);
 
 /* ---- the same hybrid Monte Carlo with the chains in HBM and many workgroups per chain (nf_hmc_tiled.hip): for lattices
  * beyond nf_phi4_hmc's 64 KiB image.  The definition, the arguments, the energies in double, the accept rule and the two

@@ -92,6 +92,9 @@ PROTOTYPES = {
     "nf_phi4_hmc_supported": (_I, [C.POINTER(C.c_int32), _I]),
     "nf_phi4_hmc": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, C.POINTER(C.c_int32), _D, _D, _D, _I, _D, _I, _I,
                          C.c_uint64, C.c_uint64, _I, _P]),
+    "nf_phi4_hmc_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
+    "nf_phi4_hmc_measure": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I64, C.POINTER(C.c_int32), _D, _D, _D, _I, _D, _I,
+                                 _I, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_phi4_hmc_tiled_supported": (_I, [C.POINTER(C.c_int32), _I]),
     "nf_phi4_hmc_tiled_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
     "nf_phi4_hmc_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
@@ -1895,6 +1898,23 @@ def _planner_plan(what, symbol, lat, dtype, out):
     return out
 
 
+HMC_MEASURE_MD_STEPS = 16     # NF_HMC_MEASURE_MD_STEPS: the MD steps a measured trajectory counts as under the cap
+
+
+class HmcPlan(C.Structure):
+    """nf_hmc_plan (include/normflow_hip.h)."""
+    _fields_ = [("sites_per_lane", C.c_int32), ("lanes", C.c_int32), ("lds_bytes", C.c_int64),
+                ("lds_bytes_measure", C.c_int64)]
+
+
+def hmc_plan(lat, dtype):
+    """What nf_phi4_hmc will do on the lattice `lat` in `dtype`: dict(sites_per_lane, lanes (of a chain's workgroup),
+    lds_bytes, lds_bytes_measure (of nf_phi4_hmc_measure)).  Pure host code."""
+    out = _planner_plan("hmc_plan", "nf_phi4_hmc_plan", lat, dtype, HmcPlan())
+    return dict(sites_per_lane=out.sites_per_lane, lanes=out.lanes, lds_bytes=out.lds_bytes,
+                lds_bytes_measure=out.lds_bytes_measure)
+
+
 def hmc_supported(lat, dtype):
     """True if nf_phi4_hmc takes chains on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own planner,
     pure host code."""
@@ -1902,10 +1922,11 @@ def hmc_supported(lat, dtype):
 
 
 def _phi4_hmc_call(what, phi, w0, w2, w4, n_md, dt, *, n_traj, record_every, pi_in, want_pi, force_accept, position,
-                   generator, workspace=None):
-    """The body of `phi4_hmc` and `phi4_hmc_tiled` (`what`; the library's entry point is nf_<what>): the argument checks,
-    the output tensors, the Philox positions, the call and the dict.  Only the tiled kernels have a workspace."""
-    tiled = what == "phi4_hmc_tiled"
+                   generator, workspace=None, record=True):
+    """The body of `phi4_hmc` and `phi4_hmc_tiled` (`what`; the library's entry point is nf_<what>; "phi4_hmc_measure" is
+    `phi4_hmc(measure=True)`): the argument checks, the output tensors, the Philox positions, the call and the dict.  Only
+    the tiled kernels have a workspace; only the measuring entry point has `measure`, and rows only where `record`."""
+    tiled, measures = what == "phi4_hmc_tiled", what == "phi4_hmc_measure"
     _require_device(phi, pi_in)
     if not phi.is_contiguous() or (pi_in is not None and (not pi_in.is_contiguous() or pi_in.dtype != phi.dtype
                                                             or pi_in.shape != phi.shape)):
@@ -1917,9 +1938,15 @@ def _phi4_hmc_call(what, phi, w0, w2, w4, n_md, dt, *, n_traj, record_every, pi_
     dh = torch.empty((max(n_traj, 0), Cn), dtype=torch.float64, device=dev)
     accept = torch.empty((max(n_traj, 0), Cn), dtype=torch.uint8, device=dev)
     action = torch.empty(Cn, dtype=torch.float64, device=dev)
-    record = None
-    if record_every is not None:
-        record = torch.empty((n_traj // int(record_every), Cn) + lat, dtype=phi.dtype, device=dev)
+    rows = None if record_every is None else (n_traj // int(record_every), Cn)
+    want_record, record = record, None
+    if rows is not None and want_record:
+        record = torch.empty(rows + lat, dtype=phi.dtype, device=dev)
+    measure = None
+    if measures:
+        if rows is None:
+            raise NormflowHipError("phi4_hmc(measure=True) needs record_every: which trajectories to measure")
+        measure = torch.empty(rows + (7 + sum(lat) + 4 - len(lat),), dtype=torch.float64, device=dev)
     pi_out = torch.empty_like(phi) if want_pi else None
     if tiled and workspace is None:
         need = load().nf_phi4_hmc_tiled_workspace(Cn, _lat4(lat), _dtype_code(phi))
@@ -1927,22 +1954,30 @@ def _phi4_hmc_call(what, phi, w0, w2, w4, n_md, dt, *, n_traj, record_every, pi_
     ws = (_ptr(workspace), workspace.numel()) if tiled else ()
     seed, offset = position if position is not None else _philox_positions(dev, 2 * max(n_traj, 1), generator)
     _check(getattr(load(), "nf_" + what)(_ptr(phi), _ptr(action), _ptr(pi_in), _ptr(pi_out), _ptr(dh), _ptr(accept),
-                                         _ptr(record), 1 if record_every is None else int(record_every), Cn, _lat4(lat),
+                                         _ptr(record), *((_ptr(measure),) if measures else ()),
+                                         1 if record_every is None else int(record_every), Cn, _lat4(lat),
                                          float(w0), float(w2), float(w4), int(n_md), float(dt), n_traj,
                                          int(bool(force_accept)), seed, offset, *ws, _dtype_code(phi), _stream()),
            "nf_" + what)
-    return dict(action=action, dh=dh, accept=accept, record=record, pi=pi_out)
+    out = dict(action=action, dh=dh, accept=accept, record=record, pi=pi_out)
+    if measures:
+        out['measure'] = measure
+    return out
 
 
 def phi4_hmc(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in=None, want_pi=False, force_accept=False,
-             position=None, generator=None):
+             position=None, generator=None, measure=False, record=True):
     """nf_phi4_hmc: n_traj HMC trajectories of the C chains phi (C, *L), in place, in ONE launch.  (w0, w2, w4) are the
     kernel's coefficients (a user axis of extent 1 already folded into w2).  Returns a dict with action (C) float64 of
     the final states, dh (n_traj, C) float64, accept (n_traj, C) uint8, record (n_traj // record_every, C, *L) or None,
     pi (C, *L) or None.  The launch takes 2 n_traj Philox positions from torch's CUDA generator, or starts at
-    `position` = (seed, offset) and leaves the generator alone."""
-    return _phi4_hmc_call("phi4_hmc", phi, w0, w2, w4, n_md, dt, n_traj=n_traj, record_every=record_every, pi_in=pi_in,
-                          want_pi=want_pi, force_accept=force_accept, position=position, generator=generator)
+    `position` = (seed, offset) and leaves the generator alone.
+    measure=True: nf_phi4_hmc_measure -- the dict gains measure (n_traj // record_every, C, n_out) float64, the rows that
+    `lattice_measure` gives for the recorded states, taken inside the launch; with record=False no rows are allocated
+    (record is None)."""
+    return _phi4_hmc_call("phi4_hmc_measure" if measure else "phi4_hmc", phi, w0, w2, w4, n_md, dt, n_traj=n_traj,
+                          record_every=record_every, pi_in=pi_in, want_pi=want_pi, force_accept=force_accept,
+                          position=position, generator=generator, record=record)
 
 
 # ========================================================================= the same, chains in HBM (nf_hmc_tiled.hip)
@@ -2011,17 +2046,28 @@ def measure_plan(lat, dtype):
                 march_axis=march, lds_bytes=out.lds_bytes, lds_budget=out.lds_budget)
 
 
-def lattice_measure(cfgs, workspace=None):
+def _measure_out(what, out, cfgs, n_out):
+    """`out` of a measure wrapper: a new (N, n_out) float64 tensor, or the caller's contiguous one of that shape."""
+    if out is None:
+        return torch.empty((cfgs.shape[0], n_out), dtype=torch.float64, device=cfgs.device)
+    _require_device(out)
+    if out.shape != (cfgs.shape[0], n_out) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise NormflowHipError(f"{what}: out must be a contiguous float64 tensor ({cfgs.shape[0]}, {n_out}), got "
+                               f"{tuple(out.shape)} {out.dtype}")
+    return out
+
+
+def lattice_measure(cfgs, workspace=None, out=None):
     """nf_lattice_measure: the (N, 7 + sum of the four padded extents) float64 statistics of the contiguous rows cfgs
     (N, *L), 1 to 4 axes, fp32 or fp64, in one pass (two launches on the segmented regime).  The workspace comes from
     torch's caching allocator per call (stream-aware and graph-pool safe, like `_workspace`), or is `workspace`: a uint8
-    tensor of at least nf_lattice_measure_workspace bytes."""
+    tensor of at least nf_lattice_measure_workspace bytes.  `out`: write the rows there instead of into a new tensor."""
     _require_device(cfgs)
     lat = tuple(cfgs.shape[1:])
     if not cfgs.is_contiguous() or not 1 <= len(lat) <= 4:
         raise NormflowHipError(f"lattice_measure needs contiguous cfgs (N, *L) with 1 to 4 lattice axes, got {tuple(cfgs.shape)}")
     N, lat4, code = cfgs.shape[0], _lat4(lat), _dtype_code(cfgs)
-    out = torch.empty((N, 7 + sum(lat) + 4 - len(lat)), dtype=torch.float64, device=cfgs.device)
+    out = _measure_out("lattice_measure", out, cfgs, 7 + sum(lat) + 4 - len(lat))
     if workspace is None:
         need = load().nf_lattice_measure_workspace(N, lat4, code)
         workspace = torch.empty(int(need), dtype=torch.uint8, device=cfgs.device) if need else None
@@ -2072,19 +2118,19 @@ def measure_tiled_plan(lat, dtype, brick_bytes=None):
                 lds_bytes=out.lds_bytes, lds_budget=out.lds_budget)
 
 
-def lattice_measure_tiled(cfgs, brick_bytes=None, workspace=None):
+def lattice_measure_tiled(cfgs, brick_bytes=None, workspace=None, out=None):
     """nf_lattice_measure_tiled: `lattice_measure`'s (N, 7 + sum of the four padded extents) float64 statistics of the
     contiguous rows cfgs (N, *L) by bricks of at most `brick_bytes` (None: the default cap), for rows of any size: two
     launches.  The workspace comes from torch's caching allocator per call (stream-aware and graph-pool safe, like
     `_workspace`), or is `workspace`: a uint8 tensor of at least nf_lattice_measure_tiled_workspace bytes.  One call per
-    batch: there is no slab loop (N x bricks workgroups must fit one launch, 2^24 - 1)."""
+    batch: there is no slab loop (N x bricks workgroups must fit one launch, 2^24 - 1).  `out` as for `lattice_measure`."""
     _require_device(cfgs)
     lat = tuple(cfgs.shape[1:])
     if not cfgs.is_contiguous() or not 1 <= len(lat) <= 4:
         raise NormflowHipError(f"lattice_measure_tiled needs contiguous cfgs (N, *L) with 1 to 4 lattice axes, got "
                                f"{tuple(cfgs.shape)}")
     N, lat4, code, cap = cfgs.shape[0], _lat4(lat), _dtype_code(cfgs), _brick_bytes(brick_bytes)
-    out = torch.empty((N, 7 + sum(lat) + 4 - len(lat)), dtype=torch.float64, device=cfgs.device)
+    out = _measure_out("lattice_measure_tiled", out, cfgs, 7 + sum(lat) + 4 - len(lat))
     if workspace is None:
         need = load().nf_lattice_measure_tiled_workspace(N, lat4, cap, code)
         workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=cfgs.device)

@@ -12,6 +12,12 @@
 // waves in order): no atomics, the same inputs give the same bits, and a launch of n_traj trajectories equals n_traj
 // launches of one.  Random numbers: the streams of nf_normal_sample (momenta) and nf_block_accept (uniform), see the header;
 // the two draws, the accept rule and the site terms of F and S are nf_sampler_core.h's, shared with nf_hmc_tiled.hip.
+// nf_phi4_hmc_measure is the same kernel compiled with MEASURE: after the decision of every record_every-th trajectory the
+// image is refilled with the chain's state and measure_image (nf_measure_core.h) takes nf_lattice_measure's row from it,
+// by that kernel's team for the lattice on the first lanes of the workgroup, so the row has nf_lattice_measure's bits.
+#include <type_traits>
+
+#include "nf_measure_core.h"
 #include "nf_sampler_core.h"
 
 namespace nf {
@@ -19,6 +25,12 @@ namespace nf {
 constexpr int kHmcMaxLanes = 1024;
 constexpr size_t kHmcFieldBytes = 64 * 1024;       // the LDS image of one chain: V sizeof(T) <= 64 KiB
 constexpr size_t kHmcScratchBytes = 1024;          // reduction slots and the broadcast of the decision, in front of the image
+// MEASURE: measure_image's slots between the two -- 8 doubles per wave of the WORKGROUP (a wave outside the team writes its
+// empty sums to its own slot, so the slots are sized for the 16 waves of kHmcMaxLanes, not for the team's) and one stripe
+// partial per lane of the widest team
+constexpr size_t kHmcMsRed = kHmcMaxLanes / kWave * 8;
+constexpr size_t kHmcMsScratchBytes = (kHmcMsRed + kMsMaxLanes) * sizeof(double);
+constexpr int kHmcIdleLane = 1 << 30;              // the team lane of a wave outside the team: beyond every loop bound of measure_image
 
 struct HmcPlan {
   int64_t V;
@@ -26,7 +38,7 @@ struct HmcPlan {
   int nd;        // how many there are (1 .. 4; a lattice of one site counts as one axis of extent 1)
   int ns;        // sites per lane (1, 2, 4, 8, 16): the smallest power of two with ceil(V / ns) <= 1024
   int nt;        // lanes per chain: ceil(V / ns) rounded up to whole waves
-  size_t lds;    // dynamic LDS of the launch
+  size_t lds;    // dynamic LDS of the launch (MEASURE: + kHmcMsScratchBytes)
 };
 
 // The one planner: nf_phi4_hmc_supported answers from it and nf_phi4_hmc launches by it.
@@ -74,6 +86,13 @@ struct HmcArgs {
   uint64_t offset;
 };
 
+// What MEASURE adds to the kernel's arguments; the kernels without it take HmcArgs as before.
+struct HmcMeasureArgs : HmcArgs {
+  double *measure;      // (n_traj / record_every, C, n_out)
+  int Lm[4], moff[4];   // the caller's four extents (NOT HmcPlan's compressed ones) and the slice sums' offsets in a row
+  int n_out, team;      // nf_lattice_measure_plan's n_out and lanes for the lattice
+};
+
 // Sum of (a, b) over the workgroup, valid in every lane and the same bits in every lane: lane partials -> shuffle tree ->
 // one slot per wave -> the waves added in order.  `slot` alternates between calls, so a slot is overwritten only after a
 // barrier that follows its last read.
@@ -96,12 +115,25 @@ __device__ __forceinline__ void hmc_sum2(double &a, double &b, double *red, int 
   slot ^= 1;
 }
 
-template <typename T, int NS, int D, int LANES>
-__global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcArgs A) {
+// measure_image out of line, for the instantiations that keep 32 bytes or more of phi per lane (float x 8 and x 16, double x 4
+// and x 8): inlined there it costs the MD loop scratch reloads; called, its registers are the callee's.  The LDS
+// is named here, not handed in, so that the reads stay LDS reads: every dynamic extern array starts at the same base.
+template <typename T>
+__device__ __noinline__ void hmc_measure_image(int e0, int e1, int e2, int e3, int o0, int o1, int o2, int o3, int tl, int nt,
+                                               double *dst, bool live) {
+  extern __shared__ __align__(16) unsigned char hmc_lds_m[];
+  double *mred = reinterpret_cast<double *>(hmc_lds_m + kHmcScratchBytes), *msp = mred + kHmcMsRed;
+  const T *img = reinterpret_cast<const T *>(hmc_lds_m + kHmcScratchBytes + kHmcMsScratchBytes);
+  const int E[4] = {e0, e1, e2, e3}, off[4] = {o0, o1, o2, o3};
+  measure_image<T, false>(img, nullptr, nullptr, E, E, off, 0, -1, tl, nt, 0, 0, mred, msp, dst, live);
+}
+
+template <typename T, int NS, int D, int LANES, bool MEASURE>
+__global__ __launch_bounds__(LANES) void phi4_hmc_kernel(std::conditional_t<MEASURE, HmcMeasureArgs, HmcArgs> A) {
   extern __shared__ __align__(16) unsigned char hmc_lds[];
   double *red = reinterpret_cast<double *>(hmc_lds);                       // 2 slots x 16 waves x 2 doubles = 512 B
   int *s_ok = reinterpret_cast<int *>(hmc_lds + 512);
-  T *img = reinterpret_cast<T *>(hmc_lds + kHmcScratchBytes);
+  T *img = reinterpret_cast<T *>(hmc_lds + kHmcScratchBytes + (MEASURE ? kHmcMsScratchBytes : 0));
   constexpr int PER = sizeof(T) == 4 ? 4 : 2;
   const int tid = threadIdx.x, NT = blockDim.x;
   const int V = int(A.V);
@@ -122,7 +154,8 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcArgs A) {
   // kernel-resource-usage): no scratch for float with 1 .. 8 sites per lane and double with 1 .. 4; float x 16 (24^3, 128^2)
   // 116 B per lane and double x 8 (8192 sites) 200 B per lane, spent in this prologue (the coordinate divisions) and in the
   // momentum draw of a trajectory (the double sincos); the MD loop of float x 16 has no scratch access, that of double x 8
-  // one reload per step.
+  // one reload per step.  With MEASURE the numbers are DESIGN.md's (section 4.9): more registers around the measurement,
+  // none of its scratch traffic in the MD loop; without it the instantiations report what they did before there was one.
   uint32_t flg[(NS + 3) / 4] = {};
   T phi[NS], pi[NS];
   auto site = [&](int tv, int k) { const int i = tv + k * NT; return i < V ? i : V - 1; };
@@ -274,26 +307,57 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcArgs A) {
       for (int k = 0; k < NS; ++k)
         if (owns(tg, k)) rec[tg + k * NT] = phi[k];
     }
+    if constexpr (MEASURE) {
+      if ((t + 1) % A.record_every == 0) {
+        // the image holds the proposal; the registers hold the chain's state (restored above on a reject)
+        __syncthreads();
+        put_image();
+        __syncthreads();
+        double *mred = reinterpret_cast<double *>(hmc_lds + kHmcScratchBytes), *msp = mred + kHmcMsRed;
+        int E[4], off[4];
+#pragma unroll
+        for (int mu = 0; mu < 4; ++mu) {
+          E[mu] = A.Lm[mu];
+          off[mu] = A.moff[mu];
+        }
+        // lanes 0 .. team - 1 are nf_lattice_measure's team for the lattice (its first wave 0, its first lane 0); the
+        // other waves run empty loops and meet the barriers
+        const bool team = tid < A.team;
+        double *dst = A.measure + (int64_t((t + 1) / A.record_every - 1) * A.C + c) * A.n_out;
+        if constexpr (NS * sizeof(T) >= 32)
+          hmc_measure_image<T>(E[0], E[1], E[2], E[3], off[0], off[1], off[2], off[3], team ? tid : kHmcIdleLane, A.team, dst,
+                               team);
+        else
+          measure_image<T, false>(img, nullptr, nullptr, E, E, off, 0, -1, team ? tid : kHmcIdleLane, A.team, 0, 0, mred, msp,
+                                  dst, team);
+        __syncthreads();                                 // before the next trajectory's momenta pass through the image
+      }
+    }
   }
   if (tid == 0) A.action_out[c] = s_cur;
 }
 
-template <typename T, int NS, int D, int LANES>
-static int launch_hmc(const HmcArgs &A, const HmcPlan &p, hipStream_t s) {
-  auto kern = phi4_hmc_kernel<T, NS, D, LANES>;
-  if (p.lds > 64 * 1024 &&
+// Args: HmcArgs launches the kernel as it always was, HmcMeasureArgs the one compiled with MEASURE
+template <typename Args> constexpr bool kHmcMeasures = std::is_same_v<Args, HmcMeasureArgs>;
+template <typename Args> constexpr const char *kHmcName = kHmcMeasures<Args> ? "nf_phi4_hmc_measure" : "nf_phi4_hmc";
+
+template <typename T, int NS, int D, int LANES, typename Args>
+static int launch_hmc(const Args &A, const HmcPlan &p, hipStream_t s) {
+  auto kern = phi4_hmc_kernel<T, NS, D, LANES, kHmcMeasures<Args>>;
+  const size_t lds = p.lds + (kHmcMeasures<Args> ? kHmcMsScratchBytes : 0);
+  if (lds > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          int(p.lds)) != hipSuccess) {
+                          int(lds)) != hipSuccess) {
     (void)hipGetLastError();
-    set_error("nf_phi4_hmc: cannot raise the dynamic LDS limit to %zu B", p.lds);
+    set_error("%s: cannot raise the dynamic LDS limit to %zu B", kHmcName<Args>, lds);
     return NF_ELAUNCH;
   }
-  hipLaunchKernelGGL(kern, dim3(unsigned(A.C)), dim3(unsigned(p.nt)), p.lds, s, A);
-  return check_launch("nf_phi4_hmc");
+  hipLaunchKernelGGL(kern, dim3(unsigned(A.C)), dim3(unsigned(p.nt)), lds, s, A);
+  return check_launch(kHmcName<Args>);
 }
 
-template <typename T, int D>
-static int dispatch_ns(const HmcArgs &A, const HmcPlan &p, hipStream_t s) {
+template <typename T, int D, typename Args>
+static int dispatch_ns(const Args &A, const HmcPlan &p, hipStream_t s) {
   switch (p.ns) {
     // one site per lane on up to 256 lanes (V <= 256) is compiled for 256 lanes: twice the registers of the 1024-lane bound
     case 1: return p.nt <= 256 ? launch_hmc<T, 1, D, 256>(A, p, s) : launch_hmc<T, 1, D, kHmcMaxLanes>(A, p, s);
@@ -303,12 +367,12 @@ static int dispatch_ns(const HmcArgs &A, const HmcPlan &p, hipStream_t s) {
     case 16:
       if constexpr (sizeof(T) == 4) return launch_hmc<T, 16, D, kHmcMaxLanes>(A, p, s);   // 8-byte fields end at 8 sites per lane
   }
-  set_error("nf_phi4_hmc: no kernel for %d sites per lane", p.ns);
+  set_error("%s: no kernel for %d sites per lane", kHmcName<Args>, p.ns);
   return NF_EINVAL;
 }
 
-template <typename T>
-static int dispatch_hmc(const HmcArgs &A, const HmcPlan &p, hipStream_t s) {
+template <typename T, typename Args>
+static int dispatch_hmc(const Args &A, const HmcPlan &p, hipStream_t s) {
   switch (p.nd) {
     case 1: return dispatch_ns<T, 1>(A, p, s);
     case 2: return dispatch_ns<T, 2>(A, p, s);
@@ -326,23 +390,34 @@ extern "C" int nf_phi4_hmc_supported(const int32_t *lattice, int dtype) {
   return hmc_plan("nf_phi4_hmc_supported", lattice, dtype, p) == NF_OK ? 1 : 0;
 }
 
-extern "C" int nf_phi4_hmc(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
-                           uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
-                           double w0, double w2, double w4, int n_md, double dt, int n_traj, int force_accept,
-                           uint64_t seed, uint64_t offset, int dtype, void *stream) {
+// The body of nf_phi4_hmc (measure_out unused, measures = false) and of nf_phi4_hmc_measure.
+static int hmc_entry(const char *what, bool measures, double *measure_out, void *phi, double *action_out, const void *pi_in,
+                     void *pi_out, double *dh_out, uint8_t *accept_out, void *record, int record_every, int64_t C,
+                     const int32_t *lattice, double w0, double w2, double w4, int n_md, double dt, int n_traj,
+                     int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream) {
   const HmcCall K{phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C, n_md, n_traj,
                   force_accept != 0, seed, offset};      // for the shared checks only: HmcArgs below keeps its kernel layout
   HmcPlan p;
-  int rc = hmc_call_checks("nf_phi4_hmc", K);
-  if (!rc) rc = hmc_plan("nf_phi4_hmc", lattice, dtype, p);
+  int rc = hmc_call_checks(what, K);
+  if (!rc) rc = hmc_plan(what, lattice, dtype, p);
   if (rc) return rc;
+  NF_REQUIRE(!measures || measure_out != nullptr, "%s: measure_out is NULL", what);
   // an MD step costs two barriers however few the sites: below 256 sites the steps, not the sites, set the time; and the
   // chains beyond the resident ones wait for a free CU: the time grows with every further 1024 chains
-  const int64_t work = int64_t(n_md) * int64_t(n_traj) * (p.V > 256 ? p.V : 256) * ((C + 1023) / 1024);
-  NF_REQUIRE(work <= NF_HMC_MAX_WORK,
-             "nf_phi4_hmc: n_md n_traj max(V, 256) ceil(C / 1024) = %lld exceeds NF_HMC_MAX_WORK (%lld): split the run into "
-             "several launches", (long long)work, (long long)NF_HMC_MAX_WORK);
-  HmcArgs A{};
+  const int64_t per_step = (p.V > 256 ? p.V : 256) * ((C + 1023) / 1024);
+  if (!measures) {
+    const int64_t work = int64_t(n_md) * int64_t(n_traj) * per_step;
+    NF_REQUIRE(work <= NF_HMC_MAX_WORK,
+               "nf_phi4_hmc: n_md n_traj max(V, 256) ceil(C / 1024) = %lld exceeds NF_HMC_MAX_WORK (%lld): split the run into "
+               "several launches", (long long)work, (long long)NF_HMC_MAX_WORK);
+  } else {
+    const int64_t work = (int64_t(n_md) * int64_t(n_traj) + int64_t(NF_HMC_MEASURE_MD_STEPS) * (n_traj / record_every)) * per_step;
+    NF_REQUIRE(work <= NF_HMC_MAX_WORK,
+               "nf_phi4_hmc_measure: (n_md n_traj + NF_HMC_MEASURE_MD_STEPS (n_traj / record_every)) max(V, 256) "
+               "ceil(C / 1024) = %lld exceeds NF_HMC_MAX_WORK (%lld): split the run into several launches",
+               (long long)work, (long long)NF_HMC_MAX_WORK);
+  }
+  HmcMeasureArgs A{};
   A.phi = phi; A.action_out = action_out; A.pi_in = pi_in; A.pi_out = pi_out; A.dh_out = dh_out; A.accept_out = accept_out;
   A.record = record; A.C = C; A.V = p.V;
   for (int mu = 0; mu < 4; ++mu) A.L[mu] = p.L[mu];
@@ -354,5 +429,54 @@ extern "C" int nf_phi4_hmc(void *phi, double *action_out, const void *pi_in, voi
   A.k0n = kn.k0; A.k1n = kn.k1; A.k0a = ka.k0; A.k1a = ka.k1;
   A.offset = offset;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!measures) {
+    const HmcArgs &B = A;
+    return dtype == NF_F32 ? dispatch_hmc<float>(B, p, s) : dispatch_hmc<double>(B, p, s);
+  }
+  // the team and the row layout are nf_lattice_measure's own plan for the lattice: a chain that fits the image is one of
+  // its packed or resident rows
+  nf_measure_plan mp;
+  rc = nf_lattice_measure_plan(lattice, dtype, &mp);
+  if (rc) return rc;
+  NF_REQUIRE(mp.segments == 1 && mp.lanes <= p.nt && mp.lanes <= kMsMaxLanes,
+             "%s: the measure team of %d lanes (%d segments) does not fit the %d lanes of a chain", what, mp.lanes,
+             mp.segments, p.nt);
+  A.measure = measure_out;
+  A.n_out = mp.n_out;
+  A.team = mp.lanes;
+  int at = 0;
+  for (int mu = 0; mu < 4; ++mu) {
+    A.Lm[mu] = lattice[mu];
+    A.moff[mu] = at;
+    at += lattice[mu];
+  }
   return dtype == NF_F32 ? dispatch_hmc<float>(A, p, s) : dispatch_hmc<double>(A, p, s);
+}
+
+extern "C" int nf_phi4_hmc_plan(const int32_t *lattice, int dtype, nf_hmc_plan *out) {
+  NF_REQUIRE(out != nullptr, "nf_phi4_hmc_plan: out is NULL");
+  HmcPlan p;
+  const int rc = hmc_plan("nf_phi4_hmc_plan", lattice, dtype, p);
+  if (rc) return rc;
+  out->sites_per_lane = p.ns;
+  out->lanes = p.nt;
+  out->lds_bytes = int64_t(p.lds);
+  out->lds_bytes_measure = int64_t(p.lds + kHmcMsScratchBytes);
+  return NF_OK;
+}
+
+extern "C" int nf_phi4_hmc(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                           uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
+                           double w0, double w2, double w4, int n_md, double dt, int n_traj, int force_accept,
+                           uint64_t seed, uint64_t offset, int dtype, void *stream) {
+  return hmc_entry("nf_phi4_hmc", false, nullptr, phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C,
+                   lattice, w0, w2, w4, n_md, dt, n_traj, force_accept, seed, offset, dtype, stream);
+}
+
+extern "C" int nf_phi4_hmc_measure(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                                   uint8_t *accept_out, void *record, double *measure_out, int record_every, int64_t C,
+                                   const int32_t *lattice, double w0, double w2, double w4, int n_md, double dt, int n_traj,
+                                   int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream) {
+  return hmc_entry("nf_phi4_hmc_measure", true, measure_out, phi, action_out, pi_in, pi_out, dh_out, accept_out, record,
+                   record_every, C, lattice, w0, w2, w4, n_md, dt, n_traj, force_accept, seed, offset, dtype, stream);
 }

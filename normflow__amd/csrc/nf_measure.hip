@@ -24,7 +24,6 @@
 namespace nf {
 namespace {
 
-constexpr int kMsPackedSites = 256;               // rows up to this many sites are packed, one wave per row
 constexpr int kMsPackedRows = kBlock / kWave;
 constexpr size_t kMsResident = 64 * 1024;         // a row up to this size is one image
 constexpr size_t kMsSegmentImage = 32 * 1024;     // a segment's image: four workgroups per CU
@@ -69,10 +68,10 @@ int ms_plan(const char *what, const int32_t *lattice, int dtype, MsPlan &p) {
     p.regime = NF_MEASURE_PACKED;
     p.rpg = kMsPackedRows;
     p.lanes = kBlock;
-    p.team = kWave;
+    p.team = ms_row_team(p.V);
   } else if (size_t(p.V) * elem <= kMsResident) {
     p.regime = NF_MEASURE_RESIDENT;
-    p.lanes = p.team = p.V > kMsWideTeam ? kMsMaxLanes : kBlock;
+    p.lanes = p.team = ms_row_team(p.V);
   } else {
     p.regime = NF_MEASURE_SEGMENTED;
     const size_t plane_bytes = size_t(p.plane) * elem;
@@ -87,7 +86,7 @@ int ms_plan(const char *what, const int32_t *lattice, int dtype, MsPlan &p) {
     // the marched axis IS the fastest one; then the segments are cut at multiples of vec (L[3] is one, so the last fits)
     if (p.plane % p.vec) p.seg_len = (p.seg_len + p.vec - 1) / p.vec * p.vec;
     p.segments = (p.L[p.a0] - 1) / p.seg_len + 1;
-    p.lanes = p.team = int64_t(p.seg_len) * p.plane > kMsWideTeam ? kMsMaxLanes : kBlock;
+    p.lanes = p.team = ms_image_team(int64_t(p.seg_len) * p.plane);
   }
   const size_t img = size_t(p.seg_len) * size_t(p.plane) * elem;
   p.img_bytes = (img + 15) & ~size_t(15);

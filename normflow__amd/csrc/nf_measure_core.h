@@ -7,7 +7,13 @@
 namespace nf {
 
 constexpr int kMsMaxLanes = 512;
+constexpr int kMsPackedSites = 256;               // rows up to this many sites are packed, one wave per row
 constexpr int kMsWideTeam = 4096;                 // images beyond this many sites get 512 lanes
+// The ONE team rule: the lanes that share an image of `sites` sites.  ms_image_team for an image that has a workgroup
+// to itself (a resident row, a segment, a brick), ms_row_team for a whole row (a packed row gets one wave).  The fused
+// HMC kernel (nf_hmc.hip) measures its LDS image by ms_row_team's lanes, which is why its rows are nf_lattice_measure's.
+constexpr int ms_image_team(int64_t sites) { return sites > kMsWideTeam ? kMsMaxLanes : kBlock; }
+constexpr int ms_row_team(int64_t sites) { return sites <= kMsPackedSites ? kWave : ms_image_team(sites); }
 constexpr int kMsMaxStripes = 16;                 // stripes per slice, at most: the serial tail of a slice sum
 constexpr size_t kMsRed = kMsMaxLanes / kWave * 8;               // doubles: 7 sums per wave
 constexpr size_t kMsScratch = (kMsRed + kMsMaxLanes) * sizeof(double);   // ... and one stripe partial per lane

@@ -95,7 +95,7 @@ int mt_plan(const char *what, const int32_t *lattice, size_t brick_bytes, int dt
              "the LDS (%zu B)", what, lattice[0], lattice[1], lattice[2], lattice[3], p.e0, p.e1, p.sub, img, avail);
   p.img_bytes = (img + 15) & ~size_t(15);
   p.lds = kMsScratch + p.img_bytes;
-  p.lanes = int64_t(p.e0) * p.e1 * p.sub > kMsWideTeam ? kMsMaxLanes : kBlock;
+  p.lanes = ms_image_team(int64_t(p.e0) * p.e1 * p.sub);
   int np = 7;
   for (int mu = 0; mu < 4; ++mu) {
     p.poff[mu] = np - 7;

@@ -41,7 +41,9 @@ class HMCSampler:
     them.  `path`: None = the fused kernel where it applies, else the tiled kernels where they apply (they beat the composed path on
     every shape class measured, README), else composed; 'fused' / 'tiled' / 'composed' force one.
     `history` gets, per call, accept_rate, exp_mdh (the mean of exp(-dH), 1 for an exact integrator of the measure) and
-    dh_rms, from one device-to-host read; `last` holds the call's dH and accept flags (trajectories, C) on the device."""
+    dh_rms, from one device-to-host read; `last` holds the call's dH and accept flags (trajectories, C) on the device.
+    `measure(batch_size, ...)` walks the same chain and returns the `Measurement` of those rows without storing them: a
+    run's length is then bounded by its 7 + sum L statistics per row, not by the rows."""
 
     def __init__(self, model):
         self._model = model
@@ -57,6 +59,30 @@ class HMCSampler:
     @torch.no_grad()
     def sample_(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None):
         """(y, logp): batch_size // n_chains recorded trajectories of every chain and logp = -S(y) in the field dtype."""
+        y, _ = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=True, want_stats=False)
+        return y, (-self._model.action(y)).to(y.dtype)
+
+    @torch.no_grad()
+    def measure(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, return_rows=False):
+        """The `Measurement` of the rows that `sample(batch_size, ...)` would return from the same chain and generator
+        state, WITHOUT storing them: every recorded state is measured where it is and only its 7 + sum L sums are kept.
+        The rows are in the samplers' layout (`Ensemble(m, n_chains=C)` takes it as is), the action is attached when the
+        model's action is a ScalarPhi4Action (as `model.measure` does), and `_ref`, `history`, `last` and the generator
+        are left as `sample_` leaves them.  On the device the tensors are those of `model.measure(hmc.sample(...))` bit
+        for bit.  Per path:
+          fused     nf_phi4_hmc_measure: the sums are taken from the kernel's LDS image inside the launch;
+          tiled     per recorded step nf_phi4_hmc_tiled on the chains in place, then the measure kernel that
+                    `observables.route` names for them, writing into that step's rows;
+          composed  the same with the composed trajectory.
+        return_rows=True: (Measurement, y), y as `sample` returns it."""
+        y, stats = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=return_rows, want_stats=True)
+        action = self._model.action
+        m = stats.measurement(action if hasattr(action, 'get_coef') else None)
+        return (m, y) if return_rows else m
+
+    def _advance(self, batch_size, n_chains, n_md, dt, n_skip, path, want_rows, want_stats):
+        """batch_size // n_chains recorded steps of the chains: (the rows (batch_size, *L) or None, the `_Stats` of the
+        recorded states or None); the chains, `last` and `history` updated."""
         n_chains = int(n_chains)
         if n_chains < 1 or batch_size < 1 or batch_size % n_chains != 0:
             raise ValueError(f"batch_size ({batch_size}) must be a positive multiple of n_chains ({n_chains})")
@@ -70,25 +96,29 @@ class HMCSampler:
         phi, S = self._ref['sample'], self._ref['action']
         path = self._choose(phi, path)
         rows = batch_size // n_chains
-        out = torch.empty((rows,) + tuple(phi.shape), dtype=phi.dtype, device=phi.device)
+        out = torch.empty((rows,) + tuple(phi.shape), dtype=phi.dtype, device=phi.device) if want_rows else None
+        stats = _Stats(phi, rows) if want_stats else None
         if path == 'fused':
             V, C = phi[0].numel(), phi.shape[0]
-            per = _hip.HMC_MAX_WORK // (n_md * max(V, 256) * ((C + 1023) // 1024))
-            phi, S, dh, acc = self._run_kernel('phi4_hmc', per, None, phi, rows, every, n_md, dt, out)
+            per = _hip.HMC_MAX_WORK // (max(V, 256) * ((C + 1023) // 1024))      # the MD steps of one launch
+            if stats is None:
+                phi, S, dh, acc = self._run_kernel('phi4_hmc', per // n_md, None, phi, rows, every, n_md, dt, out)
+            else:
+                phi, S, dh, acc = self._run_fused_measure(per, phi, rows, every, n_md, dt, out, stats)
         elif path == 'tiled':
             need = _hip.load().nf_phi4_hmc_tiled_workspace(phi.shape[0], _hip._lat4(tuple(phi.shape[1:])), _hip._dtype_code(phi))
             ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=phi.device)      # one workspace for all calls
             per = _hip.HMC_TILED_MAX_LAUNCHES // (n_md + 2)
-            phi, S, dh, acc = self._run_kernel('phi4_hmc_tiled', per, ws, phi, rows, every, n_md, dt, out)
+            phi, S, dh, acc = self._run_kernel('phi4_hmc_tiled', per, ws, phi, rows, every, n_md, dt, out, stats)
         else:
-            phi, S, dh, acc = self._run_composed(phi, S, rows, every, n_md, dt, out)
+            phi, S, dh, acc = self._run_composed(phi, S, rows, every, n_md, dt, out, stats)
         self._ref.update(sample=phi, action=S)
         self.last = dict(dh=dh, accept=acc)          # (trajectories, C) of this call, left on the device
-        stats = torch.stack([acc.double().mean(), torch.exp(-dh).mean(), dh.square().mean().sqrt()]).cpu()   # the one read
-        for key, val in zip(HMCHistory._KEYS, stats.tolist()):
+        stats_ = torch.stack([acc.double().mean(), torch.exp(-dh).mean(), dh.square().mean().sqrt()]).cpu()   # the one read
+        for key, val in zip(HMCHistory._KEYS, stats_.tolist()):
             getattr(self.history, key).append(val)
-        y = out.reshape((batch_size,) + tuple(phi.shape[1:]))
-        return y, (-self._model.action(y)).to(y.dtype)
+        y = None if out is None else out.reshape((batch_size,) + tuple(phi.shape[1:]))
+        return y, stats
 
     @torch.no_grad()
     def start(self, phi=None, n_chains=1):
@@ -168,15 +198,16 @@ class HMCSampler:
         return float(w0), float(w2 - own * w0), float(w4)
 
     # ---- fused and tiled
-    def _run_kernel(self, kernel, per, workspace, phi, rows, every, n_md, dt, out):
+    def _run_kernel(self, kernel, per, workspace, phi, rows, every, n_md, dt, out, stats=None):
         """rows * every trajectories by _hip.<kernel> in as few calls as `per`, the trajectories one call may hold under
-        NF_HMC_MAX_WORK (fused) or NF_HMC_TILED_MAX_LAUNCHES (tiled), allows."""
+        NF_HMC_MAX_WORK (fused) or NF_HMC_TILED_MAX_LAUNCHES (tiled), allows.  With `stats` (tiled only) every recorded
+        step is a call of its own on the chains in place, measured where they lie: no rows unless `out` wants them."""
         phi = phi.clone()
         coef = self._coef(phi.shape[1:])
         per = max(1, per)
         kw = {} if workspace is None else dict(workspace=workspace)
         dhs, accs, action = [], [], None
-        if per >= every:
+        if per >= every and stats is None:
             step, r0 = per // every, 0
             while r0 < rows:
                 k = min(step, rows - r0)
@@ -192,7 +223,48 @@ class HMCSampler:
                     r = getattr(_hip, kernel)(phi, *coef, n_md, dt, n_traj=k, **kw)
                     dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
                     left -= k
-                out[r0] = phi
+                if out is not None:
+                    out[r0] = phi
+                if stats is not None:
+                    stats.put(r0, phi)
+        return phi, action, torch.cat(dhs), torch.cat(accs)
+
+    def _run_fused_measure(self, steps, phi, rows, every, n_md, dt, out, stats):
+        """`_run_kernel` for nf_phi4_hmc_measure: `steps` is the MD steps one launch may hold under NF_HMC_MAX_WORK, of
+        which a recorded step takes every * n_md + NF_HMC_MEASURE_MD_STEPS.  Rows are allocated only for `out`."""
+        phi = phi.clone()
+        coef = self._coef(phi.shape[1:])
+        group = every * n_md + _hip.HMC_MEASURE_MD_STEPS
+        dhs, accs, action = [], [], None
+
+        def keep(r):
+            nonlocal action
+            dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
+
+        def measured(r0, k, n_traj, record_every):
+            r = _hip.phi4_hmc(phi, *coef, n_md, dt, n_traj=n_traj, record_every=record_every, measure=True,
+                              record=out is not None)
+            stats.put_rows(r0, r['measure'])
+            if out is not None:
+                out[r0:r0 + k] = r['record']
+            keep(r)
+        if steps >= group:
+            step, r0 = steps // group, 0
+            while r0 < rows:
+                k = min(step, rows - r0)
+                measured(r0, k, k * every, every)
+                r0 += k
+        else:
+            # one recorded step is more than a launch: unmeasured launches, then a measured one of the last trajectories
+            last = max(1, min(every, (steps - _hip.HMC_MEASURE_MD_STEPS) // n_md))
+            per = max(1, steps // n_md)
+            for r0 in range(rows):
+                left = every - last
+                while left:
+                    k = min(per, left)
+                    keep(_hip.phi4_hmc(phi, *coef, n_md, dt, n_traj=k))
+                    left -= k
+                measured(r0, 1, last, last)
         return phi, action, torch.cat(dhs), torch.cat(accs)
 
     # ---- composed
@@ -238,11 +310,56 @@ class HMCSampler:
             acc = ok.to(torch.uint8)
         return new, torch.where(ok, S1, S0), dh, acc, pi
 
-    def _run_composed(self, phi, S, rows, every, n_md, dt, out):
+    def _run_composed(self, phi, S, rows, every, n_md, dt, out, stats=None):
         dhs, accs = [], []
         for t in range(rows * every):
             phi, S, dh, acc, _ = self._trajectory_composed(phi, S, n_md, dt)
             dhs.append(dh); accs.append(acc)
             if (t + 1) % every == 0:
-                out[(t + 1) // every - 1] = phi
+                if out is not None:
+                    out[(t + 1) // every - 1] = phi
+                if stats is not None:
+                    stats.put((t + 1) // every - 1, phi)
         return phi, S, torch.stack(dhs), torch.stack(accs)
+
+
+class _Stats:
+    """The statistics of `rows` recorded steps of the chains phi (C, *L), gathered step by step, as
+    `observables.measure` takes them from the stored rows: by the kernel that `observables.route` names for the chains
+    (its rows do not depend on how many are measured at once), else by the composed sums."""
+
+    def __init__(self, phi, rows):
+        from ..lib import observables
+        self._ob = observables
+        self.lattice = tuple(phi.shape[1:])
+        self.path = observables.route(phi)
+        self.kernel = None
+        if self.path != 'composed':
+            self.kernel = _hip.lattice_measure if self.path == 'kernel' else _hip.lattice_measure_tiled
+            n_out = 7 + sum(self.lattice) + 4 - len(self.lattice)
+            self.out = torch.empty((rows, phi.shape[0], n_out), dtype=torch.float64, device=phi.device)
+        else:
+            self.parts = [None] * rows
+
+    def put(self, r, phi):
+        """Step r: the chains as they lie."""
+        if self.kernel is not None:
+            self.kernel(phi.contiguous(), out=self.out[r])
+        else:
+            self.parts[r] = self._ob._compose(phi)
+
+    def put_rows(self, r0, block):
+        """Steps r0 ..: (k, C, n_out) rows taken by nf_phi4_hmc_measure."""
+        if self.kernel is None:
+            raise _hip.NormflowHipError("HMCSampler.measure: the fused kernel's rows are nf_lattice_measure's, which "
+                                        f"`observables.route` does not name for the lattice {self.lattice}")
+        self.out[r0:r0 + block.shape[0]] = block
+
+    def measurement(self, action=None):
+        if self.kernel is not None:
+            scalars, links, slices = self._ob._split(self.out.flatten(0, 1), self.lattice)
+        else:
+            scalars = torch.cat([p[0] for p in self.parts])
+            links = torch.cat([p[1] for p in self.parts])
+            slices = [torch.cat([p[2][mu] for p in self.parts]) for mu in range(len(self.lattice))]
+        return self._ob.Measurement(scalars, links, slices, self.lattice, action)

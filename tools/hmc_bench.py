@@ -14,7 +14,14 @@ energy passes and the accept step of every trajectory.  The sampler calls also r
 the rows and read the statistics back.  The three are timed alternately, `--reps` times each; the figures are medians.
 
     python tools/hmc_bench.py [--reps 5] [--traj 50] [--composed-traj 5]
-Prints one JSON line per shape and dtype."""
+Prints one JSON line per shape and dtype.
+
+    python tools/hmc_bench.py --measure [--reps 5] [--traj 50] [--composed-traj 5]
+times `hmc.measure(...)` (the observables taken as the chain runs, no rows stored) against `model.measure(hmc.sample(...))`
+(the rows stored, then measured) instead: 16^2 x 512 and 16^3 x 1024 chains in fp32 and fp64 (fused, `--traj` recorded
+trajectories per call) and 32^4 x 16 chains in fp32 (tiled, `--composed-traj` per call).  Per shape: trajectories per
+second of both (medians of `--reps` alternating calls, with the spread) and the rise of torch.cuda.max_memory_allocated
+over one call of each."""
 import argparse
 import json
 import os
@@ -118,13 +125,61 @@ def measure(lattice, C, dtype, reps, n_traj, n_traj_composed):
                 accept_rate=round(s.history.accept_rate[-3], 3), tiled_over_composed=round(per_c / per_t, 2), **extra)
 
 
+MEASURE_SHAPES = [((16, 16), 512, torch.float32), ((16, 16), 512, torch.float64), ((16, 16, 16), 1024, torch.float32),
+                  ((16, 16, 16), 1024, torch.float64), ((32, 32, 32, 32), 16, torch.float32)]
+
+
+def measure_streaming(lattice, C, dtype, reps, n_traj):
+    prior = NormalPrior(loc=torch.zeros(lattice, dtype=dtype, device=DEV), scale=torch.ones(lattice, dtype=dtype, device=DEV))
+    model = nf.Model(net_=None, prior=prior, action=ScalarPhi4Action(kappa=0.67, m_sq=-2.68, lambd=0.5))
+    s = model.hmc
+    torch.manual_seed(0)
+    s.start(n_chains=C)
+    kw = dict(n_chains=C, n_md=N_MD, dt=DT)
+    stream = lambda: s.measure(n_traj * C, **kw)
+    store = lambda: model.measure(s.sample(n_traj * C, **kw))
+
+    def peak(f):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(DEV)
+        before = torch.cuda.memory_allocated(DEV)
+        f()
+        torch.cuda.synchronize()
+        return (torch.cuda.max_memory_allocated(DEV) - before) / 2 ** 20
+    with torch.no_grad():
+        for _ in range(2):                      # warm-up: code objects, the allocator, and the chains thermalise
+            stream()
+            store()
+        mem_stream, mem_store = peak(stream), peak(store)
+        ts, tr = [], []
+        for _ in range(reps):
+            ts.append(_ms(stream))
+            tr.append(_ms(store))
+    ms_s, ms_r = statistics.median(ts), statistics.median(tr)
+    rate = lambda ms: round(C * n_traj / ms * 1e3, 1)
+    return dict(lattice=list(lattice), chains=C, dtype=str(dtype).replace("torch.", ""), n_md=N_MD, dt=DT,
+                path=s._choose(s._ref['sample'], None), traj_per_call=n_traj,
+                measure_traj_per_s=rate(ms_s), measure_traj_per_s_spread=[rate(max(ts)), rate(min(ts))],
+                store_traj_per_s=rate(ms_r), store_traj_per_s_spread=[rate(max(tr)), rate(min(tr))],
+                measure_over_store=round(ms_r / ms_s, 3),
+                measure_peak_MiB=round(mem_stream, 2), store_peak_MiB=round(mem_store, 2),
+                rows_MiB=round(n_traj * C * prior.nvar * torch.empty((), dtype=dtype).element_size() / 2 ** 20, 2),
+                accept_rate=round(s.history.accept_rate[-1], 3))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--traj", type=int, default=50, help="trajectories per fused call (one launch)")
     ap.add_argument("--composed-traj", type=int, default=5, help="trajectories per composed call")
     ap.add_argument("--shapes", choices=("all", "small", "large"), default="all")
+    ap.add_argument("--measure", action="store_true", help="hmc.measure against measure(hmc.sample()) (module docstring)")
     a = ap.parse_args()
+    if a.measure:
+        for lattice, C, dtype in MEASURE_SHAPES:
+            n = a.traj if _hip.hmc_supported(lattice, dtype) else a.composed_traj
+            print(json.dumps(measure_streaming(lattice, C, dtype, a.reps, n)), flush=True)
+        return
     shapes = (SHAPES if a.shapes != "large" else []) + (LARGE if a.shapes != "small" else [])
     for lattice, C in shapes:
         for dtype in (torch.float32, torch.float64):
