@@ -755,6 +755,53 @@ int nf_phi4_hmc_tiled(void *phi, double *action_out, const void *pi_in, void *pi
                       int n_md, double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset, void *workspace,
                       size_t workspace_bytes, int dtype, void *stream);
 
+/* ---- coupling ladders: per-chain phi^4 couplings and replica exchange (nf_hmc.hip, nf_hmc_tiled.hip, nf_ladder.hip;
+ * MI355X-side extension).  C = K R chains; chain c belongs to replica set c / K and holds rung rung[c] in 0 .. K - 1;
+ * within a set the rungs are a permutation of 0 .. K - 1 (the identity state is rung[c] = c % K).
+ *   coef  (K, 3) double on the device: (w0, w2, w4) of rung k, a user axis of extent 1 already folded into w2
+ *   rung  (C) int32 on the device
+ * nf_phi4_hmc_ladder: nf_phi4_hmc_measure argument for argument, with (coef, K, rung) in place of (w0, w2, w4), and
+ * measure_out may be NULL (then the kernel compiled without the measure code runs, under nf_phi4_hmc's work cap; with
+ * measure_out, nf_phi4_hmc_measure's).  The same kernel template with one more compile-time flag: the workgroup of chain c
+ * reads rung[c], clamps it into 0 .. K - 1 (a corrupt entry reads inside the table), loads that row of coef once into
+ * scalar registers before the trajectory loop and from there on runs nf_phi4_hmc's code: a chain on rung k gets, bit for
+ * bit, what nf_phi4_hmc gives it with rung k's coefficients at the same (seed, offset).
+ * The time series are written RUNG-ORDERED: dh_out, accept_out, record and measure_out of chain c go to column
+ * (c / K) K + rung[c] of their step; the chain's own state stays at c: phi, pi_in, pi_out, action_out.  The Philox draws
+ * stay indexed by the chain c, at nf_phi4_hmc's positions.  rung is not written.
+ * nf_phi4_hmc_tiled_ladder: nf_phi4_hmc_tiled with the same replacement and the same rung-ordered dh_out, accept_out and
+ * record; the same launches, workspace and plan (begin and step take the coefficients of their workgroup's chain, commit
+ * writes at the rung-ordered column).
+ * NF_EINVAL: what the entry point without the ladder refuses, a NULL coef or rung, K < 1, or C % K != 0.
+ *
+ * nf_phi4_ladder_exchange: one exchange sweep.  rows (C, row_stride) double, indexed by CHAIN: nf_lattice_measure's row of
+ * the chain's current state (only its first 7 entries are read: Q = row[1], P = row[2], Lam = row[3] + .. + row[6]).  One
+ * workgroup per replica set builds the map rung -> chain in LDS; for every k with k % 2 == parity and k + 1 < K, with a
+ * the chain on rung k and b the chain on rung k + 1, in double
+ *   Delta = (w2_k - w2_{k+1}) (Q_a - Q_b) + (w4_k - w4_{k+1}) (P_a - P_b) - (w0_k - w0_{k+1}) (Lam_a - Lam_b)
+ * and the swap is accepted iff log u < Delta, u in (0, 1] the accept uniform's 53 bits from counter (lo32 i, hi32 i, lo32
+ * offset, hi32 offset), i = set K + k, under the key (lo32 seed, hi32 seed ^ NF_PHILOX_EXCHANGE_DOMAIN).  One call
+ * consumes one offset.  On accept rung[a] and rung[b] are swapped (no configuration moves), action[a] and action[b]
+ * (action (C) double or NULL) become w2 Q + w4 P - w0 Lam under the new rungs, and swapped[set, k] = 1; swapped
+ * (C / K, K - 1) uint8 gets 0 for every pair not tried or refused.  K = 1 makes no pair: nothing is written.  A rung
+ * outside 0 .. K - 1 is left out of the map and its pairs are not tried.  No atomics, plain vector stores, no allocation,
+ * no host synchronisation: the call can be captured into a HIP graph.
+ * NF_EINVAL: NULL rows / coef / rung (or swapped with K > 1), K outside 1 .. 1024, C < 1 or C % K != 0, row_stride < 7,
+ * parity outside {0, 1}. */
+#define NF_PHILOX_EXCHANGE_DOMAIN 0x6e666578u   /* 'nfex' */
+int nf_phi4_hmc_ladder(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                       uint8_t *accept_out, void *record, double *measure_out, int record_every, int64_t C,
+                       const int32_t *lattice, const double *coef, int K, const int32_t *rung, int n_md, double dt,
+                       int n_traj, int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream);
+int nf_phi4_hmc_tiled_ladder(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                             uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
+                             const double *coef, int K, const int32_t *rung, int n_md, double dt, int n_traj,
+                             int force_accept, uint64_t seed, uint64_t offset, void *workspace, size_t workspace_bytes,
+                             int dtype, void *stream);
+int nf_phi4_ladder_exchange(const double *rows, int64_t row_stride, const double *coef, int K, int32_t *rung,
+                            double *action, uint8_t *swapped, int64_t C, int parity, uint64_t seed, uint64_t offset,
+                            void *stream);
+
 /* ---- what the samplers' rows measure (nf_measure.hip; MI355X-side extension): every sufficient statistic of N
  * configurations in one pass.  cfgs (N, V) of dtype NF_F32 / NF_F64 on lattice[4] (leading extents 1 for d < 4);
  * out (N, n_out) DOUBLE, n_out = 7 + lattice[0] + lattice[1] + lattice[2] + lattice[3], per row

@@ -100,6 +100,11 @@ PROTOTYPES = {
     "nf_phi4_hmc_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
     "nf_phi4_hmc_tiled": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, C.POINTER(C.c_int32), _D, _D, _D, _I, _D, _I, _I,
                                C.c_uint64, C.c_uint64, _P, _SZ, _I, _P]),
+    "nf_phi4_hmc_ladder": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I64, C.POINTER(C.c_int32), _P, _I, _P, _I, _D, _I, _I,
+                                C.c_uint64, C.c_uint64, _I, _P]),
+    "nf_phi4_hmc_tiled_ladder": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, C.POINTER(C.c_int32), _P, _I, _P, _I, _D, _I,
+                                      _I, C.c_uint64, C.c_uint64, _P, _SZ, _I, _P]),
+    "nf_phi4_ladder_exchange": (_I, [_P, _I64, _P, _I, _P, _P, _P, _I64, _I, C.c_uint64, C.c_uint64, _P]),
     "nf_lattice_measure_supported": (_I, [C.POINTER(C.c_int32), _I]),
     "nf_lattice_measure_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
     "nf_lattice_measure_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
@@ -1921,12 +1926,33 @@ def hmc_supported(lat, dtype):
     return _planner_supported("nf_phi4_hmc_supported", lat, dtype)
 
 
+def _ladder_tensors(what, coef, rung, Cn, dev):
+    """(K, the ctypes arguments (coef, K, rung)) of a ladder call after the checks the library cannot make: device, dtype,
+    shape and contiguity of the table coef (K, 3) float64 and of rung (C) int32."""
+    for name, t, dt in (("coef", coef, torch.float64), ("rung", rung, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or not t.is_contiguous():
+            raise NormflowHipError(f"{what}: {name} must be a contiguous {dt} tensor on {dev}, got "
+                                   f"{getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', None)}")
+    if coef.ndim != 2 or coef.shape[1] != 3 or coef.shape[0] < 1:
+        raise NormflowHipError(f"{what}: coef must be (K, 3) with K >= 1: (w0, w2, w4) per rung, got {tuple(coef.shape)}")
+    K = coef.shape[0]
+    if tuple(rung.shape) != (Cn,):
+        raise NormflowHipError(f"{what}: rung must be ({Cn},), one rung per chain, got {tuple(rung.shape)}")
+    if Cn % K != 0:
+        raise NormflowHipError(f"{what}: the {Cn} chains are not a multiple of the K = {K} rungs")
+    return K, (_ptr(coef), K, _ptr(rung))
+
+
 def _phi4_hmc_call(what, phi, w0, w2, w4, n_md, dt, *, n_traj, record_every, pi_in, want_pi, force_accept, position,
-                   generator, workspace=None, record=True):
+                   generator, workspace=None, record=True, ladder=None, measure=False):
     """The body of `phi4_hmc` and `phi4_hmc_tiled` (`what`; the library's entry point is nf_<what>; "phi4_hmc_measure" is
-    `phi4_hmc(measure=True)`): the argument checks, the output tensors, the Philox positions, the call and the dict.  Only
-    the tiled kernels have a workspace; only the measuring entry point has `measure`, and rows only where `record`."""
-    tiled, measures = what == "phi4_hmc_tiled", what == "phi4_hmc_measure"
+    `phi4_hmc(measure=True)`) and of their ladder forms ("phi4_hmc_ladder", "phi4_hmc_tiled_ladder": `ladder` = (coef,
+    rung) replaces the three scalars): the argument checks, the output tensors, the Philox positions, the call and the
+    dict.  Only the tiled kernels have a workspace; only the measuring entry points have `measure` (the fused ladder
+    where asked: `measure`), and rows only where `record`."""
+    tiled = what in ("phi4_hmc_tiled", "phi4_hmc_tiled_ladder")
+    has_measure_arg = what in ("phi4_hmc_measure", "phi4_hmc_ladder")
+    measures = what == "phi4_hmc_measure" or (what == "phi4_hmc_ladder" and measure)
     _require_device(phi, pi_in)
     if not phi.is_contiguous() or (pi_in is not None and (not pi_in.is_contiguous() or pi_in.dtype != phi.dtype
                                                             or pi_in.shape != phi.shape)):
@@ -1952,11 +1978,12 @@ def _phi4_hmc_call(what, phi, w0, w2, w4, n_md, dt, *, n_traj, record_every, pi_
         need = load().nf_phi4_hmc_tiled_workspace(Cn, _lat4(lat), _dtype_code(phi))
         workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
     ws = (_ptr(workspace), workspace.numel()) if tiled else ()
+    couplings = (float(w0), float(w2), float(w4)) if ladder is None else _ladder_tensors(what, *ladder, Cn, dev)[1]
     seed, offset = position if position is not None else _philox_positions(dev, 2 * max(n_traj, 1), generator)
     _check(getattr(load(), "nf_" + what)(_ptr(phi), _ptr(action), _ptr(pi_in), _ptr(pi_out), _ptr(dh), _ptr(accept),
-                                         _ptr(record), *((_ptr(measure),) if measures else ()),
+                                         _ptr(record), *((_ptr(measure),) if has_measure_arg else ()),
                                          1 if record_every is None else int(record_every), Cn, _lat4(lat),
-                                         float(w0), float(w2), float(w4), int(n_md), float(dt), n_traj,
+                                         *couplings, int(n_md), float(dt), n_traj,
                                          int(bool(force_accept)), seed, offset, *ws, _dtype_code(phi), _stream()),
            "nf_" + what)
     out = dict(action=action, dh=dh, accept=accept, record=record, pi=pi_out)
@@ -2016,6 +2043,60 @@ def phi4_hmc_tiled(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in
     return _phi4_hmc_call("phi4_hmc_tiled", phi, w0, w2, w4, n_md, dt, n_traj=n_traj, record_every=record_every,
                           pi_in=pi_in, want_pi=want_pi, force_accept=force_accept, position=position, generator=generator,
                           workspace=workspace)
+
+
+# ========================================================================= coupling ladders (nf_hmc.hip, nf_hmc_tiled.hip, nf_ladder.hip)
+LADDER_MAX_K = 1024           # the rungs nf_phi4_ladder_exchange takes
+
+
+def phi4_hmc_ladder(phi, coef, rung, n_md, dt, n_traj=1, record_every=None, pi_in=None, want_pi=False, force_accept=False,
+                    position=None, generator=None, measure=False, record=True):
+    """nf_phi4_hmc_ladder: `phi4_hmc` with per-chain couplings.  coef (K, 3) float64 holds (w0, w2, w4) per rung (a user
+    axis of extent 1 folded into w2), rung (C) int32 the rung of every chain; chain c is in replica set c // K.  The dict
+    is `phi4_hmc`'s, with dh, accept, record and measure RUNG-ORDERED (column (c // K) K + rung[c]) and action, pi per
+    chain.  The same Philox positions."""
+    return _phi4_hmc_call("phi4_hmc_ladder", phi, None, None, None, n_md, dt, n_traj=n_traj, record_every=record_every,
+                          pi_in=pi_in, want_pi=want_pi, force_accept=force_accept, position=position, generator=generator,
+                          record=record, ladder=(coef, rung), measure=measure)
+
+
+def phi4_hmc_tiled_ladder(phi, coef, rung, n_md, dt, n_traj=1, record_every=None, pi_in=None, want_pi=False,
+                          force_accept=False, position=None, generator=None, workspace=None):
+    """nf_phi4_hmc_tiled_ladder: `phi4_hmc_tiled` with per-chain couplings, as `phi4_hmc_ladder`."""
+    return _phi4_hmc_call("phi4_hmc_tiled_ladder", phi, None, None, None, n_md, dt, n_traj=n_traj,
+                          record_every=record_every, pi_in=pi_in, want_pi=want_pi, force_accept=force_accept,
+                          position=position, generator=generator, workspace=workspace, ladder=(coef, rung))
+
+
+def ladder_exchange(rows, coef, rung, parity, action=None, position=None, generator=None):
+    """nf_phi4_ladder_exchange: one replica-exchange sweep of parity 0 / 1.  rows (C, n >= 7) float64 are the chains'
+    `lattice_measure` rows (indexed by chain; a view with a row stride is taken as it is), coef (K, 3) float64, rung (C)
+    int32 is updated in place, and so is action (C) float64 when given.  Returns swapped (C // K, K - 1) uint8.  One Philox
+    position from torch's CUDA generator, or `position` = (seed, offset)."""
+    what = "ladder_exchange"
+    _require_device(rows, coef, rung, action)
+    if not isinstance(rung, torch.Tensor) or rung.ndim != 1:
+        raise NormflowHipError(f"{what}: rung must be a (C,) int32 tensor")
+    Cn, dev = rung.shape[0], rung.device
+    K, (pc, _, pr) = _ladder_tensors(what, coef, rung, Cn, dev)
+    if K > LADDER_MAX_K:
+        raise NormflowHipError(f"{what}: K = {K} rungs exceed the {LADDER_MAX_K} of one workgroup's map")
+    if Cn < 1:
+        raise NormflowHipError(f"{what}: no chains")
+    if (rows.device != dev or rows.dtype != torch.float64 or rows.ndim != 2 or rows.shape[0] != Cn or rows.shape[1] < 7
+            or rows.stride(1) != 1 or rows.stride(0) < 7):
+        raise NormflowHipError(f"{what}: rows must be ({Cn}, n >= 7) float64 on {dev} with unit stride along a row, got "
+                               f"{tuple(rows.shape)} {rows.dtype} strides {rows.stride()}")
+    if action is not None and (action.device != dev or action.dtype != torch.float64 or tuple(action.shape) != (Cn,)
+                               or not action.is_contiguous()):
+        raise NormflowHipError(f"{what}: action must be a contiguous ({Cn},) float64 tensor on {dev}")
+    if int(parity) not in (0, 1):
+        raise NormflowHipError(f"{what}: parity must be 0 or 1, got {parity}")
+    swapped = torch.zeros((Cn // K, K - 1), dtype=torch.uint8, device=dev)
+    seed, offset = position if position is not None else _philox_position(dev, generator)
+    _check(load().nf_phi4_ladder_exchange(_ptr(rows), rows.stride(0), pc, K, pr, _ptr(action), _ptr(swapped), Cn,
+                                          int(parity), seed, offset, _stream()), "nf_phi4_ladder_exchange")
+    return swapped
 
 
 # ========================================================================= observables of sampler rows (nf_measure.hip)

@@ -1,1 +1,1 @@
-from .scalar_action import ScalarPhi4Action
+from .scalar_action import ScalarPhi4Action, ScalarPhi4Ladder

@@ -64,3 +64,67 @@ class ScalarPhi4Action:
     def log_prob(self, x, action_logz=0):
         """log density up to the constant `action_logz`."""
         return -self.action(x) - action_logz
+
+
+class ScalarPhi4Ladder:
+    """K phi^4 actions that differ in their couplings: the rungs of a coupling ladder (MI355X-side extension, for
+    `model.hmc.ladder`).  Each of m_sq, lambd, kappa, a is a scalar (the same on every rung) or a sequence of length K.
+    `len(ladder)` is K, `ladder.rung(k)` the ScalarPhi4Action of rung k, `ladder.coef_table(lattice, device)` the (K, 3)
+    float64 table (w0, w2, w4) that the ladder kernels take, and `ladder.action(cfgs, rung)` the action of every row under
+    its own rung."""
+
+    _NAMES = ('m_sq', 'lambd', 'kappa', 'a')
+
+    def __init__(self, *, m_sq, lambd, kappa=1, a=1):
+        given = dict(m_sq=m_sq, lambd=lambd, kappa=kappa, a=a)
+        seqs = {}
+        for name, v in given.items():
+            if torch.is_tensor(v):
+                v = v.tolist()
+            if isinstance(v, (list, tuple)):
+                seqs[name] = [float(x) for x in v]
+        lengths = {len(v) for v in seqs.values()}
+        if len(lengths) > 1 or 0 in lengths:
+            raise ValueError("ScalarPhi4Ladder: the sequences among m_sq, lambd, kappa, a must share one length K >= 1, got "
+                             + ", ".join(f"{n}: {len(v)}" for n, v in seqs.items()))
+        self._K = lengths.pop() if lengths else 1
+        for name in self._NAMES:
+            setattr(self, name, seqs.get(name, [given[name]] * self._K))
+
+    def __len__(self):
+        return self._K
+
+    def rung(self, k):
+        k = int(k)
+        if not 0 <= k < self._K:
+            raise IndexError(f"rung {k} of a ladder of {self._K}")
+        return ScalarPhi4Action(**{name: getattr(self, name)[k] for name in self._NAMES})
+
+    def get_coef(self, lat_ndim):
+        """[(w0, w2, w4)] per rung for a `lat_ndim`-dimensional lattice: ScalarPhi4Action.get_coef of every rung."""
+        return [self.rung(k).get_coef(lat_ndim) for k in range(self._K)]
+
+    def coef_table(self, lattice, device=None):
+        """(K, 3) float64 on `device`: (w0, w2, w4) per rung as the HMC kernels take them -- ScalarPhi4Action.action's
+        rule for a user axis of extent 1 (it is its own neighbour: -w0 phi^2) folded into w2."""
+        own = sum(1 for n in lattice if n == 1)
+        rows = [(float(w0), float(w2 - own * w0), float(w4)) for w0, w2, w4 in self.get_coef(len(lattice))]
+        return torch.tensor(rows, dtype=torch.float64, device=device)
+
+    def action(self, cfgs, rung):
+        """(B, *L) configurations and their rungs (B) -> (B,) actions: row b under the couplings of rung[b].  The host
+        formula of ScalarPhi4Action.action from torch ops on any device, with the coefficients broadcast per row: it is
+        differentiable in cfgs, so the composed HMC path takes its force from it."""
+        d = cfgs.ndim - 1
+        rung = torch.as_tensor(rung, device=cfgs.device).long()
+        table = torch.tensor(self.get_coef(d), dtype=torch.float64, device=cfgs.device).to(cfgs.dtype)
+        w = table[rung].reshape((cfgs.shape[0], 3) + (1,) * d)
+        w0, w2, w4 = table[rung][:, 0], w[:, 1], w[:, 2]       # w0 multiplies the rows' link sums, w2 and w4 the sites
+        flat = lambda t: t.flatten(1).sum(dim=1) if d >= 1 else t
+        sq = cfgs.square()
+        total = flat(sq * (w2 + w4 * sq))
+        for mu in range(1, d + 1):
+            total = total - w0 * flat(cfgs * cfgs.roll(1, dims=mu))
+        return total
+
+    __call__ = action

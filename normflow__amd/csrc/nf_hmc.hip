@@ -15,6 +15,11 @@
 // nf_phi4_hmc_measure is the same kernel compiled with MEASURE: after the decision of every record_every-th trajectory the
 // image is refilled with the chain's state and measure_image (nf_measure_core.h) takes nf_lattice_measure's row from it,
 // by that kernel's team for the lattice on the first lanes of the workgroup, so the row has nf_lattice_measure's bits.
+// nf_phi4_hmc_ladder is the same kernel compiled with LADDER (with or without MEASURE): the workgroup of chain c takes its
+// three coefficients from row rung[c] of a table instead of from the arguments, once, into scalar registers, and writes
+// its time series (dH, accept flag, record row, measure row) at the rung-ordered column (c / K) K + rung[c]; its state, its
+// momenta and its Philox draws stay at c.  From there on it is the code above: a chain on rung k has nf_phi4_hmc's bits
+// at rung k's coefficients.  The exchange sweep that permutes `rung` between launches is nf_ladder.hip.
 #include <type_traits>
 
 #include "nf_measure_core.h"
@@ -93,6 +98,25 @@ struct HmcMeasureArgs : HmcArgs {
   int n_out, team;      // nf_lattice_measure_plan's n_out and lanes for the lattice
 };
 
+// What LADDER adds: the table of the K rungs' coefficients and the rung every chain holds.  A ladder launch without
+// measure_out leaves the fields of HmcMeasureArgs unset; the kernel compiled without MEASURE does not read them.
+struct HmcLadderArgs : HmcMeasureArgs {
+  const double *coef;   // (K, 3): w0, w2, w4 of rung k, a user axis of extent 1 folded into w2
+  const int32_t *rung;  // (C): the rung of chain c, clamped into 0 .. K - 1 by the kernel
+  int K;
+};
+
+template <bool MEASURE, bool LADDER>
+using HmcKernelArgs = std::conditional_t<LADDER, HmcLadderArgs, std::conditional_t<MEASURE, HmcMeasureArgs, HmcArgs>>;
+
+// A value every lane of the workgroup holds, moved into scalar registers: the ladder's coefficients come from memory, not
+// from the kernel's arguments, and must not cost a vector register each.
+__device__ __forceinline__ double hmc_uniform(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(b)), hi = __builtin_amdgcn_readfirstlane(uint32_t(b >> 32));
+  return __builtin_bit_cast(double, uint64_t(hi) << 32 | lo);
+}
+
 // Sum of (a, b) over the workgroup, valid in every lane and the same bits in every lane: lane partials -> shuffle tree ->
 // one slot per wave -> the waves added in order.  `slot` alternates between calls, so a slot is overwritten only after a
 // barrier that follows its last read.
@@ -128,8 +152,8 @@ __device__ __noinline__ void hmc_measure_image(int e0, int e1, int e2, int e3, i
   measure_image<T, false>(img, nullptr, nullptr, E, E, off, 0, -1, tl, nt, 0, 0, mred, msp, dst, live);
 }
 
-template <typename T, int NS, int D, int LANES, bool MEASURE>
-__global__ __launch_bounds__(LANES) void phi4_hmc_kernel(std::conditional_t<MEASURE, HmcMeasureArgs, HmcArgs> A) {
+template <typename T, int NS, int D, int LANES, bool MEASURE, bool LADDER>
+__global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcKernelArgs<MEASURE, LADDER> A) {
   extern __shared__ __align__(16) unsigned char hmc_lds[];
   double *red = reinterpret_cast<double *>(hmc_lds);                       // 2 slots x 16 waves x 2 doubles = 512 B
   int *s_ok = reinterpret_cast<int *>(hmc_lds + 512);
@@ -139,7 +163,22 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(std::conditional_t<MEAS
   const int V = int(A.V);
   const int64_t c = blockIdx.x;
   T *__restrict__ gphi = static_cast<T *>(A.phi) + c * A.V;
-  const T w0 = T(A.w0), w2x2 = T(2) * T(A.w2), w4x4 = T(4) * T(A.w4), dt = T(A.dt), hdt = T(0.5) * T(A.dt);
+  // The chain's coefficients and its column `oc` in the time series (dh_out, accept_out, record, measure).  LADDER: the
+  // row rung[c] of the table, read once, and the column of that rung in the chain's replica set; the chain's own state
+  // (phi, pi_in, pi_out, action_out) and its Philox draws stay at c.
+  // Without LADDER the three are read from the arguments where they are used, as they always were.
+  double lw0 = 0.0, lw2 = 0.0, lw4 = 0.0;
+  int64_t oc = c;
+  if constexpr (LADDER) {
+    const int r = min(max(int(A.rung[c]), 0), A.K - 1);
+    const double *row = A.coef + 3 * int64_t(r);
+    lw0 = V > 1 ? hmc_uniform(row[0]) : 0.0;             // a lattice of one site: the site is read as its own neighbour
+    lw2 = hmc_uniform(row[1]);
+    lw4 = hmc_uniform(row[2]);
+    oc = c / A.K * A.K + r;
+  }
+  const T w0 = T(LADDER ? lw0 : A.w0), w2x2 = T(2) * T(LADDER ? lw2 : A.w2), w4x4 = T(4) * T(LADDER ? lw4 : A.w4), dt = T(A.dt),
+          hdt = T(0.5) * T(A.dt);
   const int s3 = 1, s2 = A.L[3], s1 = A.L[3] * A.L[2], s0 = A.L[3] * A.L[2] * A.L[1];
   const int st[4] = {s0, s1, s2, s3};
   // A.L holds the D axes of extent > 1 (HmcPlan): axes 4 - D .. 3 have neighbours, the others are not looked at
@@ -216,7 +255,7 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(std::conditional_t<MEAS
       const double p = double(phi[k]), q = double(pi[k]);
       const bool mine = owns(tv, k);
       kin += mine ? 0.5 * q * q : 0.0;
-      pot += mine ? phi4_site_energy(p, nb, A.w0, A.w2, A.w4) : 0.0;
+      pot += mine ? phi4_site_energy(p, nb, LADDER ? lw0 : A.w0, LADDER ? lw2 : A.w2, LADDER ? lw4 : A.w4) : 0.0;
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -277,8 +316,8 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(std::conditional_t<MEAS
       const uint64_t offa = A.offset + 2 * uint64_t(t) + 1;
       const PhiloxPos at{A.k0a, A.k1a, uint32_t(offa), uint32_t(offa >> 32)};
       const bool ok = hmc_accepts(philox_log_uniform(at, uint64_t(c)), dh, A.force);
-      A.dh_out[int64_t(t) * A.C + c] = dh;
-      A.accept_out[int64_t(t) * A.C + c] = uint8_t(ok);
+      A.dh_out[int64_t(t) * A.C + oc] = dh;
+      A.accept_out[int64_t(t) * A.C + oc] = uint8_t(ok);
       *s_ok = int(ok);
     }
     __syncthreads();
@@ -302,7 +341,7 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(std::conditional_t<MEAS
       for (int k = 0; k < NS; ++k) phi[k] = gphi[site(tg, k)];
     }
     if (A.record && (t + 1) % A.record_every == 0) {
-      T *__restrict__ rec = static_cast<T *>(A.record) + (int64_t((t + 1) / A.record_every - 1) * A.C + c) * A.V;
+      T *__restrict__ rec = static_cast<T *>(A.record) + (int64_t((t + 1) / A.record_every - 1) * A.C + oc) * A.V;
 #pragma unroll
       for (int k = 0; k < NS; ++k)
         if (owns(tg, k)) rec[tg + k * NT] = phi[k];
@@ -323,7 +362,7 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(std::conditional_t<MEAS
         // lanes 0 .. team - 1 are nf_lattice_measure's team for the lattice (its first wave 0, its first lane 0); the
         // other waves run empty loops and meet the barriers
         const bool team = tid < A.team;
-        double *dst = A.measure + (int64_t((t + 1) / A.record_every - 1) * A.C + c) * A.n_out;
+        double *dst = A.measure + (int64_t((t + 1) / A.record_every - 1) * A.C + oc) * A.n_out;
         if constexpr (NS * sizeof(T) >= 32)
           hmc_measure_image<T>(E[0], E[1], E[2], E[3], off[0], off[1], off[2], off[3], team ? tid : kHmcIdleLane, A.team, dst,
                                team);
@@ -337,47 +376,51 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(std::conditional_t<MEAS
   if (tid == 0) A.action_out[c] = s_cur;
 }
 
-// Args: HmcArgs launches the kernel as it always was, HmcMeasureArgs the one compiled with MEASURE
-template <typename Args> constexpr bool kHmcMeasures = std::is_same_v<Args, HmcMeasureArgs>;
-template <typename Args> constexpr const char *kHmcName = kHmcMeasures<Args> ? "nf_phi4_hmc_measure" : "nf_phi4_hmc";
+// Args: HmcArgs launches the kernel as it always was, HmcMeasureArgs the one compiled with MEASURE, HmcLadderArgs the
+// ones compiled with LADDER (with and without MEASURE: a ladder launch may leave measure_out NULL)
+template <typename Args> constexpr bool kHmcLadder = std::is_same_v<Args, HmcLadderArgs>;
+template <typename Args, bool MEASURE>
+constexpr const char *kHmcName = kHmcLadder<Args> ? "nf_phi4_hmc_ladder" : MEASURE ? "nf_phi4_hmc_measure" : "nf_phi4_hmc";
 
-template <typename T, int NS, int D, int LANES, typename Args>
+template <typename T, int NS, int D, int LANES, bool MEASURE, typename Args>
 static int launch_hmc(const Args &A, const HmcPlan &p, hipStream_t s) {
-  auto kern = phi4_hmc_kernel<T, NS, D, LANES, kHmcMeasures<Args>>;
-  const size_t lds = p.lds + (kHmcMeasures<Args> ? kHmcMsScratchBytes : 0);
+  static_assert(std::is_same_v<Args, HmcKernelArgs<MEASURE, kHmcLadder<Args>>>, "the arguments of another instantiation");
+  auto kern = phi4_hmc_kernel<T, NS, D, LANES, MEASURE, kHmcLadder<Args>>;
+  const size_t lds = p.lds + (MEASURE ? kHmcMsScratchBytes : 0);
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                           int(lds)) != hipSuccess) {
     (void)hipGetLastError();
-    set_error("%s: cannot raise the dynamic LDS limit to %zu B", kHmcName<Args>, lds);
+    set_error("%s: cannot raise the dynamic LDS limit to %zu B", kHmcName<Args, MEASURE>, lds);
     return NF_ELAUNCH;
   }
   hipLaunchKernelGGL(kern, dim3(unsigned(A.C)), dim3(unsigned(p.nt)), lds, s, A);
-  return check_launch(kHmcName<Args>);
+  return check_launch(kHmcName<Args, MEASURE>);
 }
 
-template <typename T, int D, typename Args>
+template <typename T, int D, bool MEASURE, typename Args>
 static int dispatch_ns(const Args &A, const HmcPlan &p, hipStream_t s) {
   switch (p.ns) {
     // one site per lane on up to 256 lanes (V <= 256) is compiled for 256 lanes: twice the registers of the 1024-lane bound
-    case 1: return p.nt <= 256 ? launch_hmc<T, 1, D, 256>(A, p, s) : launch_hmc<T, 1, D, kHmcMaxLanes>(A, p, s);
-    case 2: return launch_hmc<T, 2, D, kHmcMaxLanes>(A, p, s);     // more than one site per lane: always above 512 lanes
-    case 4: return launch_hmc<T, 4, D, kHmcMaxLanes>(A, p, s);
-    case 8: return launch_hmc<T, 8, D, kHmcMaxLanes>(A, p, s);
+    case 1:
+      return p.nt <= 256 ? launch_hmc<T, 1, D, 256, MEASURE>(A, p, s) : launch_hmc<T, 1, D, kHmcMaxLanes, MEASURE>(A, p, s);
+    case 2: return launch_hmc<T, 2, D, kHmcMaxLanes, MEASURE>(A, p, s);     // more than one site per lane: always above 512 lanes
+    case 4: return launch_hmc<T, 4, D, kHmcMaxLanes, MEASURE>(A, p, s);
+    case 8: return launch_hmc<T, 8, D, kHmcMaxLanes, MEASURE>(A, p, s);
     case 16:
-      if constexpr (sizeof(T) == 4) return launch_hmc<T, 16, D, kHmcMaxLanes>(A, p, s);   // 8-byte fields end at 8 sites per lane
+      if constexpr (sizeof(T) == 4) return launch_hmc<T, 16, D, kHmcMaxLanes, MEASURE>(A, p, s);   // 8-byte fields end at 8 sites per lane
   }
-  set_error("%s: no kernel for %d sites per lane", kHmcName<Args>, p.ns);
+  set_error("%s: no kernel for %d sites per lane", kHmcName<Args, MEASURE>, p.ns);
   return NF_EINVAL;
 }
 
-template <typename T, typename Args>
+template <typename T, bool MEASURE, typename Args>
 static int dispatch_hmc(const Args &A, const HmcPlan &p, hipStream_t s) {
   switch (p.nd) {
-    case 1: return dispatch_ns<T, 1>(A, p, s);
-    case 2: return dispatch_ns<T, 2>(A, p, s);
-    case 3: return dispatch_ns<T, 3>(A, p, s);
-    default: return dispatch_ns<T, 4>(A, p, s);
+    case 1: return dispatch_ns<T, 1, MEASURE>(A, p, s);
+    case 2: return dispatch_ns<T, 2, MEASURE>(A, p, s);
+    case 3: return dispatch_ns<T, 3, MEASURE>(A, p, s);
+    default: return dispatch_ns<T, 4, MEASURE>(A, p, s);
   }
 }
 
@@ -390,34 +433,37 @@ extern "C" int nf_phi4_hmc_supported(const int32_t *lattice, int dtype) {
   return hmc_plan("nf_phi4_hmc_supported", lattice, dtype, p) == NF_OK ? 1 : 0;
 }
 
-// The body of nf_phi4_hmc (measure_out unused, measures = false) and of nf_phi4_hmc_measure.
-static int hmc_entry(const char *what, bool measures, double *measure_out, void *phi, double *action_out, const void *pi_in,
-                     void *pi_out, double *dh_out, uint8_t *accept_out, void *record, int record_every, int64_t C,
-                     const int32_t *lattice, double w0, double w2, double w4, int n_md, double dt, int n_traj,
-                     int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream) {
-  const HmcCall K{phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C, n_md, n_traj,
-                  force_accept != 0, seed, offset};      // for the shared checks only: HmcArgs below keeps its kernel layout
+// The body of nf_phi4_hmc (measure_out unused, measures = false), of nf_phi4_hmc_measure and of nf_phi4_hmc_ladder
+// (coef != NULL or ladder: the three scalars unused, measures = measure_out given).
+static int hmc_entry(const char *what, bool ladder, bool measures, double *measure_out, void *phi, double *action_out,
+                     const void *pi_in, void *pi_out, double *dh_out, uint8_t *accept_out, void *record, int record_every,
+                     int64_t C, const int32_t *lattice, double w0, double w2, double w4, const double *coef, int K,
+                     const int32_t *rung, int n_md, double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset,
+                     int dtype, void *stream) {
+  const HmcCall Kc{phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C, n_md, n_traj,
+                   force_accept != 0, seed, offset};     // for the shared checks only: HmcArgs below keeps its kernel layout
   HmcPlan p;
-  int rc = hmc_call_checks(what, K);
+  int rc = hmc_call_checks(what, Kc);
+  if (!rc && ladder) rc = hmc_ladder_checks(what, coef, K, rung, C);
   if (!rc) rc = hmc_plan(what, lattice, dtype, p);
   if (rc) return rc;
-  NF_REQUIRE(!measures || measure_out != nullptr, "%s: measure_out is NULL", what);
+  NF_REQUIRE(ladder || !measures || measure_out != nullptr, "%s: measure_out is NULL", what);
   // an MD step costs two barriers however few the sites: below 256 sites the steps, not the sites, set the time; and the
   // chains beyond the resident ones wait for a free CU: the time grows with every further 1024 chains
   const int64_t per_step = (p.V > 256 ? p.V : 256) * ((C + 1023) / 1024);
   if (!measures) {
     const int64_t work = int64_t(n_md) * int64_t(n_traj) * per_step;
     NF_REQUIRE(work <= NF_HMC_MAX_WORK,
-               "nf_phi4_hmc: n_md n_traj max(V, 256) ceil(C / 1024) = %lld exceeds NF_HMC_MAX_WORK (%lld): split the run into "
-               "several launches", (long long)work, (long long)NF_HMC_MAX_WORK);
+               "%s: n_md n_traj max(V, 256) ceil(C / 1024) = %lld exceeds NF_HMC_MAX_WORK (%lld): split the run into "
+               "several launches", what, (long long)work, (long long)NF_HMC_MAX_WORK);
   } else {
     const int64_t work = (int64_t(n_md) * int64_t(n_traj) + int64_t(NF_HMC_MEASURE_MD_STEPS) * (n_traj / record_every)) * per_step;
     NF_REQUIRE(work <= NF_HMC_MAX_WORK,
-               "nf_phi4_hmc_measure: (n_md n_traj + NF_HMC_MEASURE_MD_STEPS (n_traj / record_every)) max(V, 256) "
-               "ceil(C / 1024) = %lld exceeds NF_HMC_MAX_WORK (%lld): split the run into several launches",
+               "%s: (n_md n_traj + NF_HMC_MEASURE_MD_STEPS (n_traj / record_every)) max(V, 256) "
+               "ceil(C / 1024) = %lld exceeds NF_HMC_MAX_WORK (%lld): split the run into several launches", what,
                (long long)work, (long long)NF_HMC_MAX_WORK);
   }
-  HmcMeasureArgs A{};
+  HmcLadderArgs A{};
   A.phi = phi; A.action_out = action_out; A.pi_in = pi_in; A.pi_out = pi_out; A.dh_out = dh_out; A.accept_out = accept_out;
   A.record = record; A.C = C; A.V = p.V;
   for (int mu = 0; mu < 4; ++mu) A.L[mu] = p.L[mu];
@@ -428,10 +474,12 @@ static int hmc_entry(const char *what, bool measures, double *measure_out, void 
   const PhiloxPos kn = philox_pos(seed, NF_PHILOX_KEY_DOMAIN, offset), ka = philox_pos(seed, NF_PHILOX_ACCEPT_DOMAIN, offset);
   A.k0n = kn.k0; A.k1n = kn.k1; A.k0a = ka.k0; A.k1a = ka.k1;
   A.offset = offset;
+  A.coef = coef; A.rung = rung; A.K = K;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (!measures) {
+    if (ladder) return dtype == NF_F32 ? dispatch_hmc<float, false>(A, p, s) : dispatch_hmc<double, false>(A, p, s);
     const HmcArgs &B = A;
-    return dtype == NF_F32 ? dispatch_hmc<float>(B, p, s) : dispatch_hmc<double>(B, p, s);
+    return dtype == NF_F32 ? dispatch_hmc<float, false>(B, p, s) : dispatch_hmc<double, false>(B, p, s);
   }
   // the team and the row layout are nf_lattice_measure's own plan for the lattice: a chain that fits the image is one of
   // its packed or resident rows
@@ -450,7 +498,9 @@ static int hmc_entry(const char *what, bool measures, double *measure_out, void 
     A.moff[mu] = at;
     at += lattice[mu];
   }
-  return dtype == NF_F32 ? dispatch_hmc<float>(A, p, s) : dispatch_hmc<double>(A, p, s);
+  if (ladder) return dtype == NF_F32 ? dispatch_hmc<float, true>(A, p, s) : dispatch_hmc<double, true>(A, p, s);
+  const HmcMeasureArgs &M = A;
+  return dtype == NF_F32 ? dispatch_hmc<float, true>(M, p, s) : dispatch_hmc<double, true>(M, p, s);
 }
 
 extern "C" int nf_phi4_hmc_plan(const int32_t *lattice, int dtype, nf_hmc_plan *out) {
@@ -469,14 +519,25 @@ extern "C" int nf_phi4_hmc(void *phi, double *action_out, const void *pi_in, voi
                            uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
                            double w0, double w2, double w4, int n_md, double dt, int n_traj, int force_accept,
                            uint64_t seed, uint64_t offset, int dtype, void *stream) {
-  return hmc_entry("nf_phi4_hmc", false, nullptr, phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C,
-                   lattice, w0, w2, w4, n_md, dt, n_traj, force_accept, seed, offset, dtype, stream);
+  return hmc_entry("nf_phi4_hmc", false, false, nullptr, phi, action_out, pi_in, pi_out, dh_out, accept_out, record,
+                   record_every, C, lattice, w0, w2, w4, nullptr, 0, nullptr, n_md, dt, n_traj, force_accept, seed, offset,
+                   dtype, stream);
 }
 
 extern "C" int nf_phi4_hmc_measure(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
                                    uint8_t *accept_out, void *record, double *measure_out, int record_every, int64_t C,
                                    const int32_t *lattice, double w0, double w2, double w4, int n_md, double dt, int n_traj,
                                    int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream) {
-  return hmc_entry("nf_phi4_hmc_measure", true, measure_out, phi, action_out, pi_in, pi_out, dh_out, accept_out, record,
-                   record_every, C, lattice, w0, w2, w4, n_md, dt, n_traj, force_accept, seed, offset, dtype, stream);
+  return hmc_entry("nf_phi4_hmc_measure", false, true, measure_out, phi, action_out, pi_in, pi_out, dh_out, accept_out,
+                   record, record_every, C, lattice, w0, w2, w4, nullptr, 0, nullptr, n_md, dt, n_traj, force_accept, seed,
+                   offset, dtype, stream);
+}
+
+extern "C" int nf_phi4_hmc_ladder(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                                  uint8_t *accept_out, void *record, double *measure_out, int record_every, int64_t C,
+                                  const int32_t *lattice, const double *coef, int K, const int32_t *rung, int n_md, double dt,
+                                  int n_traj, int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream) {
+  return hmc_entry("nf_phi4_hmc_ladder", true, measure_out != nullptr, measure_out, phi, action_out, pi_in, pi_out, dh_out,
+                   accept_out, record, record_every, C, lattice, 0.0, 0.0, 0.0, coef, K, rung, n_md, dt, n_traj,
+                   force_accept, seed, offset, dtype, stream);
 }

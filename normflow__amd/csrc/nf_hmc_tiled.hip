@@ -25,6 +25,11 @@
 // Energies: lane partial over the lane's sites in plane order, wave shuffle tree, waves in order, tiles in order -- all in
 // double, no atomics, the same inputs give the same bits; the plan does not depend on C, so a chain's result does not
 // depend on the chains it shares a launch with.
+// nf_phi4_hmc_tiled_ladder: the same kernels compiled with LADDER.  begin and step take the coefficients of the chain
+// their workgroup works on from row rung[c] of a table; commit writes dH, the accept flag and the record row at the
+// rung-ordered column (c / K) K + rung[c].  The same launches, the same workspace, the same plan.
+#include <type_traits>
+
 #include "nf_sampler_core.h"
 
 namespace nf {
@@ -126,6 +131,23 @@ struct TiledArgs {
   PhiloxPos pos;                    // begin: the position of the momentum draw
 };
 
+// What LADDER adds to the step kernels and to commit: the rungs' coefficient table and the rung every chain holds
+// (nf_phi4_hmc_tiled_ladder; the layout is nf_phi4_hmc_ladder's).
+struct TiledLadderArgs : TiledArgs {
+  const double *coef;   // (K, 3)
+  const int32_t *rung;  // (C), clamped into 0 .. K - 1 by the kernels
+  int K;
+};
+
+__device__ __forceinline__ int ladder_rung(const int32_t *rung, int64_t c, int K) { return min(max(int(rung[c]), 0), K - 1); }
+
+// A value every lane of the workgroup holds, moved into scalar registers
+__device__ __forceinline__ double tiled_uniform(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(b)), hi = __builtin_amdgcn_readfirstlane(uint32_t(b >> 32));
+  return __builtin_bit_cast(double, uint64_t(hi) << 32 | lo);
+}
+
 template <typename T, int W>
 __device__ __forceinline__ void load_w(const T *p, T (&v)[W]) {
   if constexpr (W == 1) {
@@ -169,8 +191,9 @@ __device__ __forceinline__ void draw_w(const TiledArgs &A, int64_t c, int64_t i,
 
 // MODE 0: begin (phi' = phi, the momenta drawn or handed in, energies of the start, phi not written);
 // MODE 1: a step;  MODE 2: the last step (energies of the end).
-template <typename T, int VEC, int MODE>
-__global__ __launch_bounds__(kTiledLanes) void hmc_tiled_step(TiledArgs A) {
+// LADDER: the coefficients are the row rung[c] of the table, read once by the workgroup; everything else is the same code.
+template <typename T, int VEC, int MODE, bool LADDER>
+__global__ __launch_bounds__(kTiledLanes) void hmc_tiled_step(std::conditional_t<LADDER, TiledLadderArgs, TiledArgs> A) {
   extern __shared__ __align__(16) unsigned char tiled_lds_raw[];
   double *red = reinterpret_cast<double *>(tiled_lds_raw);
   T *ring = reinterpret_cast<T *>(tiled_lds_raw + kTiledScratch);
@@ -180,7 +203,18 @@ __global__ __launch_bounds__(kTiledLanes) void hmc_tiled_step(TiledArgs A) {
   const T *__restrict__ gpi = A.pi_src ? static_cast<const T *>(A.pi_src) + c * A.V : nullptr;
   T *__restrict__ ophi = MODE == 0 ? nullptr : static_cast<T *>(A.phi_dst) + c * A.V;
   T *__restrict__ opi = static_cast<T *>(A.pi_dst) + c * A.V;
-  const T w0 = T(A.w0), w2x2 = T(2) * T(A.w2), w4x4 = T(4) * T(A.w4), dt = T(A.dt), eps = T(A.eps);
+  double lw0 = 0.0, lw2 = 0.0, lw4 = 0.0;
+  if constexpr (LADDER) {
+    const double *row = A.coef + 3 * int64_t(ladder_rung(A.rung, c, A.K));
+    lw0 = tiled_uniform(row[0]);
+    lw2 = tiled_uniform(row[1]);
+    lw4 = tiled_uniform(row[2]);
+  }
+  // without LADDER the three are read from the arguments where they are used, as they always were
+  auto cw0 = [&]() { if constexpr (LADDER) return lw0; else return A.w0; };
+  auto cw2 = [&]() { if constexpr (LADDER) return lw2; else return A.w2; };
+  auto cw4 = [&]() { if constexpr (LADDER) return lw4; else return A.w4; };
+  const T w0 = T(cw0()), w2x2 = T(2) * T(cw2()), w4x4 = T(4) * T(cw4()), dt = T(A.dt), eps = T(A.eps);
 
   // ---- the tile: origin o, extents t (the last tile of an axis may be narrower), halo h on the tiled axes of the plane
   int tl = blockIdx.x;
@@ -350,7 +384,7 @@ __global__ __launch_bounds__(kTiledLanes) void hmc_tiled_step(TiledArgs A) {
           if constexpr (MODE != 1) {
             const double qd = double(MODE == 0 ? pi0 : pi1);
             kin += 0.5 * qd * qd;
-            pot += phi4_site_energy(double(ph), nbk, A.w0, A.w2, A.w4);
+            pot += phi4_site_energy(double(ph), nbk, cw0(), cw2(), cw4());
           }
         }
         const int g = g0 + u_g[k];
@@ -406,13 +440,21 @@ struct CommitArgs {
   PhiloxPos pos;
 };
 
+struct CommitLadderArgs : CommitArgs {
+  const int32_t *rung;
+  int K;
+};
+
 // One chain per blockIdx.y, a slice of its sites per blockIdx.x.  Every workgroup of a chain adds the same partials in
 // the same order and takes the same decision; the first one writes it out.
-template <typename T>
-__global__ __launch_bounds__(kTiledLanes) void hmc_tiled_commit(CommitArgs A) {
+// LADDER: dh_out, accept_out and the record row go to the chain's rung-ordered column, (c / K) K + rung[c].
+template <typename T, bool LADDER>
+__global__ __launch_bounds__(kTiledLanes) void hmc_tiled_commit(std::conditional_t<LADDER, CommitLadderArgs, CommitArgs> A) {
   __shared__ double sums[4];
   const int tid = threadIdx.x;
   const int64_t c = blockIdx.y;
+  int64_t oc = c;
+  if constexpr (LADDER) oc = c / A.K * A.K + ladder_rung(A.rung, c, A.K);
   if (tid < 4) {
     const double *p = A.part + c * A.tiles * 4 + tid;
     double acc = 0.0;
@@ -424,14 +466,14 @@ __global__ __launch_bounds__(kTiledLanes) void hmc_tiled_commit(CommitArgs A) {
   const double dh = (k1 + e1) - (k0 + e0);
   const bool ok = hmc_accepts(philox_log_uniform(A.pos, uint64_t(c)), dh, A.force);
   if (blockIdx.x == 0 && tid == 0) {
-    A.dh_out[c] = dh;
-    A.accept_out[c] = uint8_t(ok);
+    A.dh_out[oc] = dh;
+    A.accept_out[oc] = uint8_t(ok);
     A.action_out[c] = ok ? e1 : e0;
   }
   T *__restrict__ phi = static_cast<T *>(A.phi) + c * A.V;
   const T *__restrict__ prop = static_cast<const T *>(A.prop) + c * A.V;
   const T *__restrict__ pif = static_cast<const T *>(A.pi_fin) + c * A.V;
-  T *rec = A.record ? static_cast<T *>(A.record) + c * A.V : nullptr;
+  T *rec = A.record ? static_cast<T *>(A.record) + oc * A.V : nullptr;
   T *pout = A.pi_out ? static_cast<T *>(A.pi_out) + c * A.V : nullptr;
   if (!ok && !rec && !pout) return;
   for (int64_t i = int64_t(blockIdx.x) * kTiledLanes + tid; i < A.V; i += int64_t(gridDim.x) * kTiledLanes) {
@@ -446,35 +488,40 @@ __global__ __launch_bounds__(kTiledLanes) void hmc_tiled_commit(CommitArgs A) {
   }
 }
 
-template <typename T, int VEC>
-static int launch_tiled_step(int mode, const TiledArgs &A, const TiledPlan &p, int64_t C, hipStream_t s) {
+template <typename Args> constexpr bool kTiledLadder = std::is_same_v<Args, TiledLadderArgs>;
+template <typename Args> constexpr const char *kTiledName = kTiledLadder<Args> ? "nf_phi4_hmc_tiled_ladder" : "nf_phi4_hmc_tiled";
+
+template <typename T, int VEC, typename Args>
+static int launch_tiled_step(int mode, const Args &A, const TiledPlan &p, int64_t C, hipStream_t s) {
   const dim3 grid(unsigned(p.tiles), unsigned(C)), block(kTiledLanes);
-  auto k0 = hmc_tiled_step<T, VEC, 0>;
-  auto k1 = hmc_tiled_step<T, VEC, 1>;
-  auto k2 = hmc_tiled_step<T, VEC, 2>;
+  auto k0 = hmc_tiled_step<T, VEC, 0, kTiledLadder<Args>>;
+  auto k1 = hmc_tiled_step<T, VEC, 1, kTiledLadder<Args>>;
+  auto k2 = hmc_tiled_step<T, VEC, 2, kTiledLadder<Args>>;
   auto kern = mode == 0 ? k0 : mode == 1 ? k1 : k2;
   hipLaunchKernelGGL(kern, grid, block, p.lds, s, A);
-  return check_launch("nf_phi4_hmc_tiled");
+  return check_launch(kTiledName<Args>);
 }
 
-template <typename T, int VEC>
+template <typename T, int VEC, bool LADDER>
 static int raise_lds(const TiledPlan &p) {
   if (p.lds <= 64 * 1024) return NF_OK;
-  const void *kerns[3] = {reinterpret_cast<const void *>(hmc_tiled_step<T, VEC, 0>),
-                          reinterpret_cast<const void *>(hmc_tiled_step<T, VEC, 1>),
-                          reinterpret_cast<const void *>(hmc_tiled_step<T, VEC, 2>)};
+  const void *kerns[3] = {reinterpret_cast<const void *>(hmc_tiled_step<T, VEC, 0, LADDER>),
+                          reinterpret_cast<const void *>(hmc_tiled_step<T, VEC, 1, LADDER>),
+                          reinterpret_cast<const void *>(hmc_tiled_step<T, VEC, 2, LADDER>)};
   for (const void *k : kerns)
     if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, int(p.lds)) != hipSuccess) {
       (void)hipGetLastError();
-      set_error("nf_phi4_hmc_tiled: cannot raise the dynamic LDS limit to %zu B", p.lds);
+      set_error("%s: cannot raise the dynamic LDS limit to %zu B", LADDER ? "nf_phi4_hmc_tiled_ladder" : "nf_phi4_hmc_tiled",
+                p.lds);
       return NF_ELAUNCH;
     }
   return NF_OK;
 }
 
-template <typename T, int VEC>
-static int run_tiled(const HmcCall &K, unsigned char *ws, TiledArgs A, const TiledPlan &p, hipStream_t s) {
-  int rc = raise_lds<T, VEC>(p);
+template <typename T, int VEC, typename Args>
+static int run_tiled(const HmcCall &K, unsigned char *ws, Args A, const TiledPlan &p, hipStream_t s) {
+  constexpr bool LADDER = kTiledLadder<Args>;
+  int rc = raise_lds<T, VEC, LADDER>(p);
   if (rc) return rc;
   const size_t field = round256(size_t(K.C) * size_t(p.V) * sizeof(T));
   double *part = reinterpret_cast<double *>(ws);
@@ -496,7 +543,7 @@ static int run_tiled(const HmcCall &K, unsigned char *ws, TiledArgs A, const Til
       if ((rc = launch_tiled_step<T, VEC>(k == K.n_md ? 2 : 1, A, p, K.C, s))) return rc;
       src = A.phi_dst;
     }
-    CommitArgs Q{};
+    std::conditional_t<LADDER, CommitLadderArgs, CommitArgs> Q{};
     Q.phi = K.phi; Q.prop = src; Q.pi_fin = fpi[K.n_md & 1];
     const bool due = K.record && (t + 1) % K.record_every == 0;
     Q.record = due ? static_cast<T *>(K.record) + int64_t((t + 1) / K.record_every - 1) * K.C * p.V : nullptr;
@@ -507,8 +554,12 @@ static int run_tiled(const HmcCall &K, unsigned char *ws, TiledArgs A, const Til
     Q.action_out = K.action_out;
     Q.V = p.V; Q.tiles = p.tiles; Q.force = K.force;
     Q.pos = philox_pos(K.seed, NF_PHILOX_ACCEPT_DOMAIN, K.offset + 2 * uint64_t(t) + 1);
-    hipLaunchKernelGGL((hmc_tiled_commit<T>), dim3(cblocks, unsigned(K.C)), dim3(kTiledLanes), 0, s, Q);
-    if ((rc = check_launch("nf_phi4_hmc_tiled (commit)"))) return rc;
+    if constexpr (LADDER) {
+      Q.rung = A.rung;
+      Q.K = A.K;
+    }
+    hipLaunchKernelGGL((hmc_tiled_commit<T, LADDER>), dim3(cblocks, unsigned(K.C)), dim3(kTiledLanes), 0, s, Q);
+    if ((rc = check_launch(LADDER ? "nf_phi4_hmc_tiled_ladder (commit)" : "nf_phi4_hmc_tiled (commit)"))) return rc;
   }
   return NF_OK;
 }
@@ -556,29 +607,31 @@ extern "C" size_t nf_phi4_hmc_tiled_workspace(int64_t C, const int32_t *lattice,
   return tiled_workspace(C, p, dtype == NF_F32 ? 4 : 8);
 }
 
-extern "C" int nf_phi4_hmc_tiled(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
-                                 uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
-                                 double w0, double w2, double w4, int n_md, double dt, int n_traj, int force_accept,
-                                 uint64_t seed, uint64_t offset, void *workspace, size_t workspace_bytes, int dtype,
-                                 void *stream) {
+// The body of nf_phi4_hmc_tiled (coef NULL: the three scalars) and of nf_phi4_hmc_tiled_ladder.
+static int tiled_entry(const char *what, bool ladder, void *phi, double *action_out, const void *pi_in, void *pi_out,
+                       double *dh_out, uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
+                       double w0, double w2, double w4, const double *coef, int Kr, const int32_t *rung, int n_md, double dt,
+                       int n_traj, int force_accept, uint64_t seed, uint64_t offset, void *workspace, size_t workspace_bytes,
+                       int dtype, void *stream) {
   const HmcCall K{phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C, n_md, n_traj,
                   force_accept != 0, seed, offset};
   TiledPlan p;
-  int rc = hmc_call_checks("nf_phi4_hmc_tiled", K);
-  if (!rc) rc = tiled_plan("nf_phi4_hmc_tiled", lattice, dtype, p);
+  int rc = hmc_call_checks(what, K);
+  if (!rc && ladder) rc = hmc_ladder_checks(what, coef, Kr, rung, C);
+  if (!rc) rc = tiled_plan(what, lattice, dtype, p);
   if (rc) return rc;
   NF_REQUIRE(int64_t(p.tiles) * C <= kTiledMaxGroups,
-             "nf_phi4_hmc_tiled: %d tiles x %lld chains exceed the %lld workgroups of one launch: run the chains in several "
-             "calls", p.tiles, (long long)C, (long long)kTiledMaxGroups);
+             "%s: %d tiles x %lld chains exceed the %lld workgroups of one launch: run the chains in several "
+             "calls", what, p.tiles, (long long)C, (long long)kTiledMaxGroups);
   const int64_t launches = (int64_t(n_md) + 2) * int64_t(n_traj);
   NF_REQUIRE(launches <= NF_HMC_TILED_MAX_LAUNCHES,
-             "nf_phi4_hmc_tiled: (n_md + 2) n_traj = %lld launches exceed NF_HMC_TILED_MAX_LAUNCHES (%d): split the run into "
-             "several calls", (long long)launches, NF_HMC_TILED_MAX_LAUNCHES);
+             "%s: (n_md + 2) n_traj = %lld launches exceed NF_HMC_TILED_MAX_LAUNCHES (%d): split the run into "
+             "several calls", what, (long long)launches, NF_HMC_TILED_MAX_LAUNCHES);
   const size_t elem = dtype == NF_F32 ? 4 : 8;
   const size_t need = tiled_workspace(C, p, elem);
-  NF_REQUIRE(workspace != nullptr && workspace_bytes >= need, "nf_phi4_hmc_tiled: workspace %zu B < %zu B needed",
+  NF_REQUIRE(workspace != nullptr && workspace_bytes >= need, "%s: workspace %zu B < %zu B needed", what,
              workspace ? workspace_bytes : size_t(0), need);
-  TiledArgs A{};
+  TiledLadderArgs A{};
   A.V = p.V;
   for (int a = 0; a < 4; ++a) {
     A.L[a] = p.L[a];
@@ -587,14 +640,40 @@ extern "C" int nf_phi4_hmc_tiled(void *phi, double *action_out, const void *pi_i
   }
   A.ring = p.ring; A.tiles = p.tiles;
   A.w0 = w0; A.w2 = w2; A.w4 = w4; A.dt = dt;
+  A.coef = coef; A.rung = rung; A.K = Kr;
   // 16-byte accesses need every row to start on 16 bytes: the lattice's fastest extent a multiple of 16 / sizeof (the
   // plan's vec) and the caller's fields aligned; the workspace's fields are, when the workspace is
   const uintptr_t bits = reinterpret_cast<uintptr_t>(phi) | reinterpret_cast<uintptr_t>(pi_in) |
                          reinterpret_cast<uintptr_t>(workspace);
   const bool wide = p.vec > 1 && (bits & 15) == 0;
-  NF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "nf_phi4_hmc_tiled: the workspace must be 8-byte aligned");
+  NF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "%s: the workspace must be 8-byte aligned", what);
   hipStream_t s = static_cast<hipStream_t>(stream);
   unsigned char *ws = static_cast<unsigned char *>(workspace);
-  if (dtype == NF_F32) return wide ? run_tiled<float, 4>(K, ws, A, p, s) : run_tiled<float, 1>(K, ws, A, p, s);
-  return wide ? run_tiled<double, 2>(K, ws, A, p, s) : run_tiled<double, 1>(K, ws, A, p, s);
+  if (ladder) {
+    if (dtype == NF_F32) return wide ? run_tiled<float, 4>(K, ws, A, p, s) : run_tiled<float, 1>(K, ws, A, p, s);
+    return wide ? run_tiled<double, 2>(K, ws, A, p, s) : run_tiled<double, 1>(K, ws, A, p, s);
+  }
+  const TiledArgs &B = A;
+  if (dtype == NF_F32) return wide ? run_tiled<float, 4>(K, ws, B, p, s) : run_tiled<float, 1>(K, ws, B, p, s);
+  return wide ? run_tiled<double, 2>(K, ws, B, p, s) : run_tiled<double, 1>(K, ws, B, p, s);
+}
+
+extern "C" int nf_phi4_hmc_tiled(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                                 uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
+                                 double w0, double w2, double w4, int n_md, double dt, int n_traj, int force_accept,
+                                 uint64_t seed, uint64_t offset, void *workspace, size_t workspace_bytes, int dtype,
+                                 void *stream) {
+  return tiled_entry("nf_phi4_hmc_tiled", false, phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C,
+                     lattice, w0, w2, w4, nullptr, 0, nullptr, n_md, dt, n_traj, force_accept, seed, offset, workspace,
+                     workspace_bytes, dtype, stream);
+}
+
+extern "C" int nf_phi4_hmc_tiled_ladder(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                                        uint8_t *accept_out, void *record, int record_every, int64_t C,
+                                        const int32_t *lattice, const double *coef, int K, const int32_t *rung, int n_md,
+                                        double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset,
+                                        void *workspace, size_t workspace_bytes, int dtype, void *stream) {
+  return tiled_entry("nf_phi4_hmc_tiled_ladder", true, phi, action_out, pi_in, pi_out, dh_out, accept_out, record,
+                     record_every, C, lattice, 0.0, 0.0, 0.0, coef, K, rung, n_md, dt, n_traj, force_accept, seed, offset,
+                     workspace, workspace_bytes, dtype, stream);
 }

@@ -1,6 +1,7 @@
 // nf_sampler_core.h -- what nf_normal_sample (nf_endpoints.hip), nf_mcmc.hip, nf_hmc.hip and nf_hmc_tiled.hip share,
 // stated ONCE: Philox4x32-10, a stream position, the normal draw of a group and the accept uniform (the counter layouts
-// of include/normflow_hip.h), the HMC accept rule, the phi^4 site terms and the entry checks of the two HMC kernels.
+// of include/normflow_hip.h), the HMC accept rule, the replica-exchange rule of the coupling ladders, the phi^4 site terms
+// and the entry checks of the HMC kernels.
 #pragma once
 #include "nf_internal.h"
 
@@ -78,6 +79,13 @@ __device__ __forceinline__ double philox_log_uniform(const PhiloxPos &pos, uint6
 // The HMC decision on dh = H1 - H0: a NaN energy difference rejects
 __device__ __forceinline__ bool hmc_accepts(double logu, double dh, bool force) { return force || logu < -dh; }
 
+// The replica-exchange decision between the chains a (on rung k) and b (on rung k + 1) of a coupling ladder.  S is linear
+// in (w0, w2, w4): S = w2 Q + w4 P - w0 Lam with Q = sum phi^2, P = sum phi^4, Lam = the sum of the links, so
+// Delta = [S_k(a) + S_{k+1}(b)] - [S_k(b) + S_{k+1}(a)]; the swap is accepted iff log u < Delta.  d* = rung k minus rung k + 1.
+__device__ __forceinline__ double ladder_delta(double dw0, double dw2, double dw4, double dQ, double dP, double dLam) {
+  return dw2 * dQ + dw4 * dP - dw0 * dLam;
+}
+
 // ---------------------------------------------------------------- phi^4 site terms of the HMC kernels
 // F(phi)(x) = 2 w2 phi + 4 w4 phi^3 - w0 nb, nb the sum of the 2 d neighbours
 template <typename T> __device__ __forceinline__ T phi4_force(T p, T nb, T w2x2, T w4x4, T w0) {
@@ -112,6 +120,14 @@ inline int hmc_call_checks(const char *what, const HmcCall &K) {
   NF_REQUIRE(K.n_md >= 1 && K.n_traj >= 1 && K.record_every >= 1,
              "%s: n_md (%d), n_traj (%d) and record_every (%d) must be >= 1", what, K.n_md, K.n_traj, K.record_every);
   NF_REQUIRE(!K.pi_in || K.n_traj == 1, "%s: pi_in replaces the momenta of ONE trajectory (n_traj = %d)", what, K.n_traj);
+  return NF_OK;
+}
+
+// What the ladder entry points add to them: chain c of the C = K R chains is in replica set c / K.
+inline int hmc_ladder_checks(const char *what, const double *coef, int K, const int32_t *rung, int64_t C) {
+  NF_REQUIRE(coef != nullptr && rung != nullptr, "%s: coef or rung is NULL", what);
+  NF_REQUIRE(K >= 1, "%s: K (%d) must be >= 1", what, K);
+  NF_REQUIRE(C % K == 0, "%s: C (%lld) is not a multiple of K (%d)", what, (long long)C, K);
   return NF_OK;
 }
 

@@ -153,6 +153,12 @@ class HMCSampler:
         phi, S, dh, acc, pi = self._trajectory_composed(phi, S0, n_md, dt, pi=pi, force_accept=force_accept, generator=gen)
         return dict(phi=phi, pi=pi, dh=dh, accept=acc, action=S)
 
+    def ladder(self, ladder):
+        """The sampler of the coupling ladder `ladder` (a ScalarPhi4Ladder) with this model's prior: per-chain couplings in
+        one launch and replica exchange between neighbouring rungs (mcmc/ladder.py)."""
+        from .ladder import LadderHMCSampler
+        return LadderHMCSampler(self._model, ladder)
+
     # ---- which path
     def _fused_applies(self, phi):
         return (isinstance(self._model.action, ScalarPhi4Action) and phi.is_cuda
