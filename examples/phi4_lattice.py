@@ -11,6 +11,8 @@ DistConvertor_), or a stack of RQ-spline couplings, assembled from the same name
                                                            with replica exchange
     python examples/phi4_lattice.py --lat 16,16 --hmc     after the fit: <phi^2> from model.mcmc next to model.hmc, then
                                                           chi, the Binder cumulant, xi_2 and tau_int(m) of both
+    python examples/phi4_lattice.py --lat 8,8 --hmc --cluster    the same, and model.hmc once more with a cluster sweep of
+                                                          the signs before every step: tau_int(m) with and without sweeps
 """
 import argparse
 import os
@@ -68,9 +70,11 @@ def observables(model, y, n_chains, drop):
         fmt_val_err(*e.susceptibility()), fmt_val_err(*e.binder()), fmt_val_err(*e.xi2(axis)), fmt_val_err(tau, tau_err), window)
 
 
-def compare_with_hmc(model, n_chains=64, rows=128):
+def compare_with_hmc(model, n_chains=64, rows=128, cluster=False):
     """<phi^2> of the trained flow + Metropolis next to hybrid Monte Carlo on the action itself (exact up to its own
-    statistical error; the first quarter of every chain is dropped as thermalisation), then the observables of both."""
+    statistical error; the first quarter of every chain is dropped as thermalisation), then the observables of both.
+    `cluster`: also model.hmc with a Swendsen-Wang sweep of the signs before every recorded step (cluster_every=1), so
+    that tau_int(m) stands next to the one without sweeps."""
     y = model.mcmc.sample(n_chains * rows, n_chains=n_chains)
     print("<phi^2>  model.mcmc  %.5f +- %.5f   (accept rate %.3f)" % (*phi2(y, n_chains, rows // 4), model.mcmc.history.accept_rate[-1]))
     obs = observables(model, y, n_chains, rows // 4)
@@ -78,6 +82,13 @@ def compare_with_hmc(model, n_chains=64, rows=128):
     print("<phi^2>  model.hmc   %.5f +- %.5f   (accept rate %.3f)" % (*phi2(y, n_chains, rows // 4), model.hmc.history.accept_rate[-1]))
     print("model.mcmc  " + obs)
     print("model.hmc   " + observables(model, y, n_chains, rows // 4))
+    if cluster:
+        model.hmc.start(n_chains=n_chains)
+        y = model.hmc.sample(n_chains * rows, n_chains=n_chains, n_md=10, dt=0.1, cluster_every=1)
+        big = model.hmc.last['cluster'][..., 2].double().mean().item() / model.prior.nvar
+        print("<phi^2>  model.hmc, cluster_every=1   %.5f +- %.5f   (accept rate %.3f, mean largest cluster %.2f of the lattice)"
+              % (*phi2(y, n_chains, rows // 4), model.hmc.history.accept_rate[-1], big))
+        print("model.hmc, cluster_every=1   " + observables(model, y, n_chains, rows // 4))
 
 
 def ladder_scan(lat, m_sq, lambd, kappas, replicas=32, steps=600):
@@ -117,6 +128,8 @@ def main():
                     help="how the spectral block filters: torch.fft, or the LDS-resident Hartley kernel (lattices up to 64 KiB per sample)")
     ap.add_argument("--hmc", action="store_true",
                     help="after the fit, print <phi^2> from model.hmc (hybrid Monte Carlo on the action) next to model.mcmc")
+    ap.add_argument("--cluster", action="store_true",
+                    help="with --hmc: model.hmc once more with cluster_every=1, tau_int(m) with and without cluster sweeps")
     ap.add_argument("--ladder", action="store_true",
                     help="no fit: a ladder of 6 kappas from --kappa down to 0.4 of it in one HMC launch per step, chi, U4 and "
                          "tau_int(m) per rung without and with replica exchange")
@@ -135,7 +148,7 @@ def main():
         model.fit(**kw)
         nf.backward_sanitychecker(model)
         if a.hmc:
-            compare_with_hmc(model)
+            compare_with_hmc(model, cluster=a.cluster)
 
 
 if __name__ == "__main__":

@@ -802,6 +802,60 @@ int nf_phi4_ladder_exchange(const double *rows, int64_t row_stride, const double
                             double *action, uint8_t *swapped, int64_t C, int parity, uint64_t seed, uint64_t offset,
                             void *stream);
 
+/* ---- cluster updates of phi^4 chains (nf_cluster.hip; MI355X-side extension): one Swendsen-Wang sweep of the embedded
+ * Ising signs (Brower-Tamayo: phi = s |phi|).  A sweep is never rejected, leaves sum phi^2 and sum phi^4 alone and
+ * flips every cluster half of the time.  The sweep, stated once:
+ * There are C chains on lattice[4], with leading extents 1 for d < 4.  x is the row-major site index in 0 .. V - 1.
+ * y = x + mu is the periodic forward neighbour along axis mu.
+ * 1. Links.  Every pair (x, mu) with lattice[mu] > 1 is a link.
+ *    - An axis of extent 1 has none.  Its self-term -w0 phi^2 is even in phi.
+ *    - On an axis of extent 2 the pairs (x, mu) and (y, mu) are two links between the same two sites.  This matches the
+ *      action, which counts that neighbour twice.
+ * 2. Bonds.  Compute t = (w0 phi(x)) phi(y), in double on values cast to double, left to right.
+ *    - The link is active iff t > 0 && u < -expm1(-2.0 * t).
+ *    - A NaN or a zero makes no bond.  Either sign of w0 is legal.
+ *    - The uniform is u = (r[mu] + 0.5) 2^-32, from word mu of ONE Philox4x32-10 call per site.
+ *    - The counter is (lo32 i, hi32 i, lo32 offset, hi32 offset), with i = c V + x.
+ *    - The key is (lo32 seed, hi32 seed ^ NF_PHILOX_CLUSTER_DOMAIN), where NF_PHILOX_CLUSTER_DOMAIN = 0x6e66636cu ('nfcl').
+ * 3. Clusters.  These are the connected components of the active links.  label(x) is the smallest site index of x's
+ *    component.
+ * 4. Flips.  The cluster with label rho of chain c flips iff r[0] >> 31 of the Philox call with i = c V + rho at position
+ *    offset + 1, under the same key.
+ *    - A flipped site becomes -phi, a sign-bit flip.
+ *    - Every other site keeps its bits.
+ * 5. One sweep consumes 2 offsets.
+ * The labels are a unique fixed point, so a sweep is a pure function of (phi, w0, seed, offset): the kernel's schedule
+ * cannot show in its result.
+ *
+ * nf_phi4_cluster: the sweep of C chains phi (C, V), in place, one workgroup per chain with the labels (int32) and one
+ * byte of bond bits per site in LDS (lds_bytes of the plan, about 5 V), for the lattices nf_phi4_hmc_supported takes
+ * (V sizeof <= 64 KiB; NF_F32 and NF_F64).  phi is read once for the bonds; only the flipped sites are written back, with
+ * plain vector stores.  Labelling is min-label propagation over the active links (integer minimum on LDS) with pointer
+ * jumping, round after round until a round changes nothing, AT MOST V ROUNDS (a label travels at least one link per
+ * round); every barrier is in uniform control flow and the exit test is a workgroup-wide flag every lane reads.
+ *   stats       (C, 4) int32: clusters, sites flipped, size of the largest cluster, rounds used.  A chain that hits the
+ *               bound is left untouched with (0, 0, 0, -1): it cannot happen, the bound keeps a bug from being a hang.
+ *   labels_out  (C, V) int32 or NULL
+ * C is 1 .. 65535.  No allocation, no host synchronisation: the call can be captured into a HIP graph.
+ * NF_EINVAL: NULL phi / stats / lattice, an unsupported lattice or dtype, C out of range.
+ * nf_phi4_cluster_plan / nf_phi4_cluster_supported: pure host; the lane map is nf_phi4_hmc's.
+ *
+ * nf_phi4_cluster_draws: the draws of the sweep at (seed, offset), element-wise, for any lattice with V < 2^31 and C in
+ * 1 .. 65535: u_out (C, V, 4) double = the uniforms of step 2 (all four words, whatever the extents), flip_out (C, V)
+ * uint8 = the bit of step 4 for every site index taken as a label.  A sweep composed from other pieces walks the kernel's
+ * stream with these. */
+#define NF_PHILOX_CLUSTER_DOMAIN 0x6e66636cu   /* 'nfcl' */
+typedef struct nf_cluster_plan {
+  int32_t sites_per_lane, lanes;
+  int64_t lds_bytes;
+} nf_cluster_plan;
+int nf_phi4_cluster_supported(const int32_t *lattice, int dtype);
+int nf_phi4_cluster_plan(const int32_t *lattice, int dtype, nf_cluster_plan *out);
+int nf_phi4_cluster(void *phi, int32_t *stats, int32_t *labels_out, int64_t C, const int32_t *lattice, double w0,
+                    uint64_t seed, uint64_t offset, int dtype, void *stream);
+int nf_phi4_cluster_draws(double *u_out, uint8_t *flip_out, int64_t C, const int32_t *lattice, uint64_t seed,
+                          uint64_t offset, void *stream);
+
 /* ---- what the samplers' rows measure (nf_measure.hip; MI355X-side extension): every sufficient statistic of N
  * configurations in one pass.  cfgs (N, V) of dtype NF_F32 / NF_F64 on lattice[4] (leading extents 1 for d < 4);
  * out (N, n_out) DOUBLE, n_out = 7 + lattice[0] + lattice[1] + lattice[2] + lattice[3], per row

@@ -105,6 +105,10 @@ PROTOTYPES = {
     "nf_phi4_hmc_tiled_ladder": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, C.POINTER(C.c_int32), _P, _I, _P, _I, _D, _I,
                                       _I, C.c_uint64, C.c_uint64, _P, _SZ, _I, _P]),
     "nf_phi4_ladder_exchange": (_I, [_P, _I64, _P, _I, _P, _P, _P, _I64, _I, C.c_uint64, C.c_uint64, _P]),
+    "nf_phi4_cluster_supported": (_I, [C.POINTER(C.c_int32), _I]),
+    "nf_phi4_cluster_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
+    "nf_phi4_cluster": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _D, C.c_uint64, C.c_uint64, _I, _P]),
+    "nf_phi4_cluster_draws": (_I, [_P, _P, _I64, C.POINTER(C.c_int32), C.c_uint64, C.c_uint64, _P]),
     "nf_lattice_measure_supported": (_I, [C.POINTER(C.c_int32), _I]),
     "nf_lattice_measure_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
     "nf_lattice_measure_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
@@ -2097,6 +2101,62 @@ def ladder_exchange(rows, coef, rung, parity, action=None, position=None, genera
     _check(load().nf_phi4_ladder_exchange(_ptr(rows), rows.stride(0), pc, K, pr, _ptr(action), _ptr(swapped), Cn,
                                           int(parity), seed, offset, _stream()), "nf_phi4_ladder_exchange")
     return swapped
+
+
+# ========================================================================= cluster sweeps of phi^4 chains (nf_cluster.hip)
+class ClusterPlan(C.Structure):
+    """nf_cluster_plan (include/normflow_hip.h)."""
+    _fields_ = [("sites_per_lane", C.c_int32), ("lanes", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
+def cluster_supported(lat, dtype):
+    """True if nf_phi4_cluster takes chains on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own planner,
+    pure host code."""
+    return _planner_supported("nf_phi4_cluster_supported", lat, dtype)
+
+
+def cluster_plan(lat, dtype):
+    """What nf_phi4_cluster will do on the lattice `lat` in `dtype`: dict(sites_per_lane, lanes (of a chain's workgroup),
+    lds_bytes).  Pure host code."""
+    out = _planner_plan("cluster_plan", "nf_phi4_cluster_plan", lat, dtype, ClusterPlan())
+    return dict(sites_per_lane=out.sites_per_lane, lanes=out.lanes, lds_bytes=out.lds_bytes)
+
+
+def phi4_cluster(phi, w0, position=None, want_labels=False, generator=None):
+    """nf_phi4_cluster: one Swendsen-Wang sweep of the signs of the C chains phi (C, *L), in place, in ONE launch.  w0 is
+    the action's hopping coefficient.  Returns dict(stats (C, 4) int32 = clusters, sites flipped, size of the largest
+    cluster, rounds; labels (C, *L) int32 or None).  The sweep takes 2 Philox positions from torch's CUDA generator, or
+    starts at `position` = (seed, offset) and leaves the generator alone."""
+    _require_device(phi)
+    if not phi.is_contiguous():
+        raise NormflowHipError("phi4_cluster needs contiguous phi (C, *L)")
+    Cn, lat, dev = phi.shape[0], tuple(phi.shape[1:]), phi.device
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"phi4_cluster: lattices of 1 to 4 axes, got {lat}")
+    stats = torch.empty((Cn, 4), dtype=torch.int32, device=dev)
+    labels = torch.empty((Cn,) + lat, dtype=torch.int32, device=dev) if want_labels else None
+    seed, offset = position if position is not None else _philox_positions(dev, 2, generator)
+    _check(load().nf_phi4_cluster(_ptr(phi), _ptr(stats), _ptr(labels), Cn, _lat4(lat), float(w0), seed, offset,
+                                  _dtype_code(phi), _stream()), "nf_phi4_cluster")
+    return dict(stats=stats, labels=labels)
+
+
+def phi4_cluster_draws(Cn, lattice, device, position=None, generator=None):
+    """nf_phi4_cluster_draws: (u (C, V, 4) float64, flip (C, V) uint8), the bond uniforms and the flip bits of the sweep
+    that `phi4_cluster` makes of C chains on `lattice` from the same position; 2 positions, taken as `phi4_cluster`
+    takes them."""
+    lat, device = tuple(lattice), torch.device(device)
+    if device.type != 'cuda':
+        raise NormflowHipError(f"phi4_cluster_draws writes on an MI355X (torch device 'cuda'), got {device}")
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"phi4_cluster_draws: lattices of 1 to 4 axes, got {lat}")
+    Cn, V = int(Cn), _sites(lat)
+    u = torch.empty((max(Cn, 0), V, 4), dtype=torch.float64, device=device)
+    flip = torch.empty((max(Cn, 0), V), dtype=torch.uint8, device=device)
+    seed, offset = position if position is not None else _philox_positions(device, 2, generator)
+    _check(load().nf_phi4_cluster_draws(_ptr(u), _ptr(flip), Cn, _lat4(lat), seed, offset, _stream()),
+           "nf_phi4_cluster_draws")
+    return u, flip
 
 
 # ========================================================================= observables of sampler rows (nf_measure.hip)

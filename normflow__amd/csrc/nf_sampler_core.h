@@ -1,7 +1,7 @@
 // nf_sampler_core.h -- what nf_normal_sample (nf_endpoints.hip), nf_mcmc.hip, nf_hmc.hip and nf_hmc_tiled.hip share,
 // stated ONCE: Philox4x32-10, a stream position, the normal draw of a group and the accept uniform (the counter layouts
-// of include/normflow_hip.h), the HMC accept rule, the replica-exchange rule of the coupling ladders, the phi^4 site terms
-// and the entry checks of the HMC kernels.
+// of include/normflow_hip.h), the HMC accept rule, the replica-exchange rule of the coupling ladders, the draws and the
+// bond test of the cluster sweep (nf_cluster.hip), the phi^4 site terms and the entry checks of the HMC kernels.
 #pragma once
 #include "nf_internal.h"
 
@@ -74,6 +74,36 @@ __device__ __forceinline__ double philox_log_uniform(const PhiloxPos &pos, uint6
   uint32_t r[4] = {uint32_t(i), uint32_t(i >> 32), pos.o0, pos.o1};
   philox4x32_10(r, pos.k0, pos.k1);
   return ::log(philox_u53(r[0], r[1]));
+}
+
+// `pos` moved on by n kernel offsets
+inline PhiloxPos philox_pos_after(const PhiloxPos &pos, uint64_t n) {
+  const uint64_t off = (uint64_t(pos.o1) << 32 | pos.o0) + n;
+  return PhiloxPos{pos.k0, pos.k1, uint32_t(off), uint32_t(off >> 32)};
+}
+
+// ---------------------------------------------------------------- the cluster sweep (nf_cluster.hip, include/normflow_hip.h)
+// The four output words of index i at `pos`: ONE Philox call under the counter (lo32 i, hi32 i, lo32 offset, hi32 offset).
+__device__ __forceinline__ void philox_words(const PhiloxPos &pos, uint64_t i, uint32_t (&r)[4]) {
+  r[0] = uint32_t(i); r[1] = uint32_t(i >> 32); r[2] = pos.o0; r[3] = pos.o1;
+  philox4x32_10(r, pos.k0, pos.k1);
+}
+
+// The bond uniform of one output word: (r + 0.5) 2^-32, in (0, 1) and exact in double
+__device__ __forceinline__ double philox_u32_mid(uint32_t r) { return (double(r) + 0.5) * 2.3283064365386963e-10; }
+
+// Is the link between the sites holding a and b active under the uniform u?  t = (w0 a) b left to right in double; a NaN
+// or a zero makes no bond, either sign of w0 is legal.
+__device__ __forceinline__ bool cluster_bond(double w0, double a, double b, double u) {
+  const double t = (w0 * a) * b;
+  return t > 0.0 && u < -::expm1(-2.0 * t);
+}
+
+// Does the cluster with label rho of chain c flip?  The top bit of word 0 at the sweep's SECOND offset (`flip_pos`), i = c V + rho.
+__device__ __forceinline__ bool cluster_flips(const PhiloxPos &flip_pos, uint64_t i) {
+  uint32_t r[4];
+  philox_words(flip_pos, i, r);
+  return (r[0] >> 31) != 0;
 }
 
 // The HMC decision on dh = H1 - H0: a NaN energy difference rejects

@@ -43,13 +43,22 @@ class HMCSampler:
     `history` gets, per call, accept_rate, exp_mdh (the mean of exp(-dH), 1 for an exact integrator of the measure) and
     dh_rms, from one device-to-host read; `last` holds the call's dH and accept flags (trajectories, C) on the device.
     `measure(batch_size, ...)` walks the same chain and returns the `Measurement` of those rows without storing them: a
-    run's length is then bounded by its 7 + sum L statistics per row, not by the rows."""
+    run's length is then bounded by its 7 + sum L statistics per row, not by the rows.
+    `cluster_every=E` (sample, sample_, measure; 0 = none, the sampler as it was): one Swendsen-Wang sweep of the signs of
+    all chains (include/normflow_hip.h, "cluster updates") BEFORE the trajectories of every recorded step s with
+    s % E == 0, s counted across calls since `start()`.  The launches are cut at the sweeps (at most E recorded steps
+    each); the Philox positions are taken in call order, 2 per sweep and 2 per trajectory; a call still ends with an HMC
+    launch, so `_ref`, `history` and `last['dh' | 'accept']` are the HMC's own, and `last['cluster']` holds the sweeps'
+    stats (sweeps, C, 4) int32 on the device: clusters, sites flipped, largest cluster, rounds.  nf_phi4_cluster where
+    `_hip.cluster_supported` takes the chains, else the composed `cluster_sweep` (mcmc/cluster.py).  `cluster(phi)` is the
+    bare sweep on given chains."""
 
     def __init__(self, model):
         self._model = model
         self.history = HMCHistory()
         self._ref = dict(sample=None, action=None)
         self.last = dict(dh=None, accept=None)
+        self._steps = 0           # the recorded steps since `start()`: where the cluster sweeps fall
 
     # ---- public
     @torch.no_grad()
@@ -57,13 +66,14 @@ class HMCSampler:
         return self.sample_(batch_size=batch_size, **kwargs)[0]
 
     @torch.no_grad()
-    def sample_(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None):
+    def sample_(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, cluster_every=0):
         """(y, logp): batch_size // n_chains recorded trajectories of every chain and logp = -S(y) in the field dtype."""
-        y, _ = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=True, want_stats=False)
+        y, _ = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=True, want_stats=False,
+                             cluster_every=cluster_every)
         return y, (-self._model.action(y)).to(y.dtype)
 
     @torch.no_grad()
-    def measure(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, return_rows=False):
+    def measure(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, return_rows=False, cluster_every=0):
         """The `Measurement` of the rows that `sample(batch_size, ...)` would return from the same chain and generator
         state, WITHOUT storing them: every recorded state is measured where it is and only its 7 + sum L sums are kept.
         The rows are in the samplers' layout (`Ensemble(m, n_chains=C)` takes it as is), the action is attached when the
@@ -75,15 +85,20 @@ class HMCSampler:
                     `observables.route` names for them, writing into that step's rows;
           composed  the same with the composed trajectory.
         return_rows=True: (Measurement, y), y as `sample` returns it."""
-        y, stats = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=return_rows, want_stats=True)
+        y, stats = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=return_rows, want_stats=True,
+                                 cluster_every=cluster_every)
         action = self._model.action
         m = stats.measurement(action if hasattr(action, 'get_coef') else None)
         return (m, y) if return_rows else m
 
-    def _advance(self, batch_size, n_chains, n_md, dt, n_skip, path, want_rows, want_stats):
+    def _advance(self, batch_size, n_chains, n_md, dt, n_skip, path, want_rows, want_stats, cluster_every=0):
         """batch_size // n_chains recorded steps of the chains: (the rows (batch_size, *L) or None, the `_Stats` of the
-        recorded states or None); the chains, `last` and `history` updated."""
-        n_chains = int(n_chains)
+        recorded states or None); the chains, `last` and `history` updated.  cluster_every = E >= 1: the recorded steps
+        are run in spans that end before the next step s (counted across calls) with s % E == 0, with one cluster sweep
+        of all chains in front of each such step; the span's launches are those of a call of that many steps."""
+        n_chains, E = int(n_chains), int(cluster_every)
+        if E < 0:
+            raise ValueError(f"cluster_every ({cluster_every}) must be >= 0")
         if n_chains < 1 or batch_size < 1 or batch_size % n_chains != 0:
             raise ValueError(f"batch_size ({batch_size}) must be a positive multiple of n_chains ({n_chains})")
         n_md, every = int(n_md), int(n_skip) + 1
@@ -101,19 +116,40 @@ class HMCSampler:
         if path == 'fused':
             V, C = phi[0].numel(), phi.shape[0]
             per = _hip.HMC_MAX_WORK // (max(V, 256) * ((C + 1023) // 1024))      # the MD steps of one launch
-            if stats is None:
-                phi, S, dh, acc = self._run_kernel('phi4_hmc', per // n_md, None, phi, rows, every, n_md, dt, out)
-            else:
-                phi, S, dh, acc = self._run_fused_measure(per, phi, rows, every, n_md, dt, out, stats)
         elif path == 'tiled':
             need = _hip.load().nf_phi4_hmc_tiled_workspace(phi.shape[0], _hip._lat4(tuple(phi.shape[1:])), _hip._dtype_code(phi))
             ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=phi.device)      # one workspace for all calls
             per = _hip.HMC_TILED_MAX_LAUNCHES // (n_md + 2)
-            phi, S, dh, acc = self._run_kernel('phi4_hmc_tiled', per, ws, phi, rows, every, n_md, dt, out, stats)
-        else:
-            phi, S, dh, acc = self._run_composed(phi, S, rows, every, n_md, dt, out, stats)
+        dhs, accs, sweeps, r0 = [], [], [], 0
+        while r0 < rows:
+            k = rows - r0
+            if E:
+                if (self._steps + r0) % E == 0:
+                    phi, st = self._sweep(phi)
+                    sweeps.append(st)
+                    if path == 'composed':
+                        S = self._model.action(phi.double()).double()
+                k = min(k, E - (self._steps + r0) % E)
+            out_k = None if out is None else out[r0:r0 + k]
+            stats_k = None if stats is None else _StatsSpan(stats, r0)
+            if path == 'fused':
+                if stats is None:
+                    phi, S, dh, acc = self._run_kernel('phi4_hmc', per // n_md, None, phi, k, every, n_md, dt, out_k)
+                else:
+                    phi, S, dh, acc = self._run_fused_measure(per, phi, k, every, n_md, dt, out_k, stats_k)
+            elif path == 'tiled':
+                phi, S, dh, acc = self._run_kernel('phi4_hmc_tiled', per, ws, phi, k, every, n_md, dt, out_k, stats_k)
+            else:
+                phi, S, dh, acc = self._run_composed(phi, S, k, every, n_md, dt, out_k, stats_k)
+            dhs.append(dh); accs.append(acc)
+            r0 += k
+        dh, acc = (dhs[0], accs[0]) if len(dhs) == 1 else (torch.cat(dhs), torch.cat(accs))
+        self._steps += rows
         self._ref.update(sample=phi, action=S)
         self.last = dict(dh=dh, accept=acc)          # (trajectories, C) of this call, left on the device
+        if E:
+            self.last['cluster'] = (torch.stack(sweeps) if sweeps else
+                                    torch.empty((0, phi.shape[0], 4), dtype=torch.int32, device=phi.device))
         stats_ = torch.stack([acc.double().mean(), torch.exp(-dh).mean(), dh.square().mean().sqrt()]).cpu()   # the one read
         for key, val in zip(HMCHistory._KEYS, stats_.tolist()):
             getattr(self.history, key).append(val)
@@ -129,7 +165,42 @@ class HMCSampler:
         if phi.dtype not in (torch.float32, torch.float64):
             raise TypeError(f"HMCSampler supports float32 and float64 fields, got {phi.dtype}")
         self._ref.update(sample=phi, action=self._model.action(phi.double()).double())
+        self._steps = 0
         return self
+
+    @torch.no_grad()
+    def cluster(self, phi, position=None):
+        """ONE Swendsen-Wang sweep of the signs of the chains phi (C, *L), which are left alone; the stored chains are
+        not touched.  Returns dict(phi = the swept chains, labels (C, *L) int32 = the smallest site index of every
+        site's cluster, stats (C, 4) int32 = clusters, sites flipped, size of the largest cluster, rounds).  `position`
+        = (seed, offset) fixes the two Philox positions of a device sweep instead of taking them from torch's CUDA
+        generator.  nf_phi4_cluster where it takes the chains, else `cluster_sweep` (mcmc/cluster.py)."""
+        new, stats, labels = self._sweep(phi.detach(), position=position, want_labels=True)
+        return dict(phi=new, labels=labels, stats=stats)
+
+    def _sweep(self, phi, position=None, want_labels=False):
+        """(the swept copy of phi, stats[, labels]): by the kernel for a ScalarPhi4Action on a HIP device and a lattice
+        `cluster_supported` takes (it beats the composed sweep on every class measured, README), else composed -- on the
+        device with the kernel's draws from the same two positions, on CPU tensors with torch's CPU generator."""
+        action = self._model.action
+        if not hasattr(action, 'get_coef'):
+            raise TypeError("cluster sweeps need the hopping coefficient of a phi^4 action (get_coef), got a "
+                            f"{type(action).__name__}")
+        lat = tuple(phi.shape[1:])
+        w0 = float(action.get_coef(len(lat))[0])
+        if phi.is_cuda and isinstance(action, ScalarPhi4Action) and _hip.cluster_supported(lat, phi.dtype):
+            new = phi.clone().contiguous()
+            r = _hip.phi4_cluster(new, w0, position=position, want_labels=want_labels)
+            return (new, r['stats'], r['labels']) if want_labels else (new, r['stats'])
+        from .cluster import cluster_sweep
+        C, V = phi.shape[0], phi[0].numel()
+        if phi.is_cuda:
+            u, flip = _hip.phi4_cluster_draws(C, lat, phi.device, position=position)
+        else:
+            u = torch.rand((C, V, 4), dtype=torch.float64, device=phi.device)
+            flip = torch.rand((C, V), dtype=torch.float64, device=phi.device) < 0.5
+        new, labels, stats = cluster_sweep(phi, w0, u, flip)
+        return (new, stats, labels) if want_labels else (new, stats)
 
     @torch.no_grad()
     def trajectory(self, phi, n_md=10, dt=0.1, pi=None, force_accept=False, path=None, position=None):
@@ -369,3 +440,16 @@ class _Stats:
             links = torch.cat([p[1] for p in self.parts])
             slices = [torch.cat([p[2][mu] for p in self.parts]) for mu in range(len(self.lattice))]
         return self._ob.Measurement(scalars, links, slices, self.lattice, action)
+
+
+class _StatsSpan:
+    """The steps first .. of a `_Stats`, numbered from 0: what a span of a call writes into."""
+
+    def __init__(self, stats, first):
+        self._stats, self._first = stats, first
+
+    def put(self, r, phi):
+        self._stats.put(self._first + r, phi)
+
+    def put_rows(self, r0, block):
+        self._stats.put_rows(self._first + r0, block)
