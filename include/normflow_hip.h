@@ -856,6 +856,46 @@ int nf_phi4_cluster(void *phi, int32_t *stats, int32_t *labels_out, int64_t C, c
 int nf_phi4_cluster_draws(double *u_out, uint8_t *flip_out, int64_t C, const int32_t *lattice, uint64_t seed,
                           uint64_t offset, void *stream);
 
+/* ---- the same sweep with the chains in HBM and many workgroups per chain (nf_cluster_tiled.hip): for lattices beyond
+ * nf_phi4_cluster's class (32^3, 16^4, 32^4, 48^4, ...).  The rule, the draws and the label convention are those above,
+ * word for word, and the labels are a unique fixed point: fields, labels and stats[:, 0 .. 2] are nf_phi4_cluster's bit for
+ * bit where both apply, whatever the tiles.  Any lattice of extents >= 1 with V < 2^31 sites per chain, NF_F32 and NF_F64,
+ * C in 1 .. 65535.
+ * A chain is cut into tiles, runs of tile_sites consecutive site indices (the last may be short; a tile may be cut in the
+ * middle of a row).  tile_sites = 0 is the default (16384); any value from 1 to 32704 (what the 160 KiB of LDS hold at 5
+ * bytes per site) is legal, and a value above V means V.  Four launches in a line on `stream`, after one memset of the
+ * workspace's flags: (1) bonds, and the labels of the links inside a tile in LDS, by nf_phi4_cluster's rounds, at most
+ * tile_sites of them; (2) the links that cross tiles, by a lock-free union on the label array in HBM (chase to the roots,
+ * atomic minimum of the larger root's label; at most V - 1 atomics per link and V steps per chase; no lane waits for
+ * another workgroup); (3) every site's root and the clusters' sizes (integer atomics); (4) flips and stats.  The call
+ * neither allocates nor synchronises and can be captured into a HIP graph.
+ *   stats       (C, 4) int32: clusters, sites flipped, size of the largest cluster, and the number of tiles of a chain
+ *               (>= 1; not a round count: the rounds of phase 1 depend on the lanes' schedule, and all four columns are
+ *               a pure function of the inputs).  A chain that hits one of the bounds is left untouched with
+ *               (0, 0, 0, -1): it cannot happen, the bounds keep a bug from being a hang.
+ *   labels_out  (C, V) int32 or NULL
+ *   workspace   nf_phi4_cluster_tiled_workspace bytes, 16-byte aligned, owned by the caller, need not be initialised:
+ *               per chain 4 V of labels, 4 V of sizes and V of bond bytes, plus 8 bytes of flags: 9 C V + 8 C.  After the
+ *               call the int32 pair of chain c at byte 8 C V + 8 c holds (a bound was hit, the most rounds phase 1 took
+ *               on a tile of the chain).
+ * nf_phi4_cluster_tiled_plan (pure host): tiles per chain, the tile_sites in force, the lanes of a tile's workgroup and
+ * its LDS bytes (256 + 4 tile_sites + tile_sites, the two arrays rounded up to 16).  nf_phi4_cluster_tiled_supported (pure
+ * host): 1 or 0 with the reason in nf_last_error_string.  nf_phi4_cluster_tiled_workspace (pure host): the bytes, 0 for
+ * a case the planner refuses or C outside 1 .. 65535.
+ * NF_EINVAL: NULL phi / stats / lattice, an extent < 1, 2^31 sites or more, another dtype, C out of range, tile_sites
+ * outside 0 .. 32704 or so small that tiles x lanes reaches 2^32, a NULL, short or misaligned workspace. */
+typedef struct nf_cluster_tiled_plan {
+  int64_t tiles;
+  int32_t tile_sites, lanes;
+  int64_t lds_bytes;
+} nf_cluster_tiled_plan;
+int nf_phi4_cluster_tiled_supported(const int32_t *lattice, int dtype, int64_t tile_sites);
+int nf_phi4_cluster_tiled_plan(const int32_t *lattice, int dtype, int64_t tile_sites, nf_cluster_tiled_plan *out);
+size_t nf_phi4_cluster_tiled_workspace(int64_t C, const int32_t *lattice, int64_t tile_sites);
+int nf_phi4_cluster_tiled(void *phi, int32_t *stats, int32_t *labels_out, int64_t C, const int32_t *lattice, double w0,
+                          uint64_t seed, uint64_t offset, int dtype, int64_t tile_sites, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* ---- what the samplers' rows measure (nf_measure.hip; MI355X-side extension): every sufficient statistic of N
  * configurations in one pass.  cfgs (N, V) of dtype NF_F32 / NF_F64 on lattice[4] (leading extents 1 for d < 4);
  * out (N, n_out) DOUBLE, n_out = 7 + lattice[0] + lattice[1] + lattice[2] + lattice[3], per row

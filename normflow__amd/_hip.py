@@ -109,6 +109,11 @@ PROTOTYPES = {
     "nf_phi4_cluster_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
     "nf_phi4_cluster": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _D, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_phi4_cluster_draws": (_I, [_P, _P, _I64, C.POINTER(C.c_int32), C.c_uint64, C.c_uint64, _P]),
+    "nf_phi4_cluster_tiled_supported": (_I, [C.POINTER(C.c_int32), _I, _I64]),
+    "nf_phi4_cluster_tiled_plan": (_I, [C.POINTER(C.c_int32), _I, _I64, _P]),
+    "nf_phi4_cluster_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I64]),
+    "nf_phi4_cluster_tiled": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _D, C.c_uint64, C.c_uint64, _I, _I64, _P, _SZ,
+                                   _P]),
     "nf_lattice_measure_supported": (_I, [C.POINTER(C.c_int32), _I]),
     "nf_lattice_measure_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
     "nf_lattice_measure_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
@@ -2157,6 +2162,73 @@ def phi4_cluster_draws(Cn, lattice, device, position=None, generator=None):
     _check(load().nf_phi4_cluster_draws(_ptr(u), _ptr(flip), Cn, _lat4(lat), seed, offset, _stream()),
            "nf_phi4_cluster_draws")
     return u, flip
+
+
+# ========================================================================= the same, chains in HBM (nf_cluster_tiled.hip)
+class ClusterTiledPlan(C.Structure):
+    """nf_cluster_tiled_plan (include/normflow_hip.h)."""
+    _fields_ = [("tiles", C.c_int64), ("tile_sites", C.c_int32), ("lanes", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
+def _tile_sites(tile_sites):
+    """None / 0: the library's default tile."""
+    t = 0 if tile_sites is None else int(tile_sites)
+    if t < 0:
+        raise NormflowHipError(f"tile_sites must be None or >= 0, got {tile_sites}")
+    return t
+
+
+def cluster_tiled_supported(lat, dtype, tile_sites=0):
+    """True if nf_phi4_cluster_tiled takes chains on the lattice `lat` (1 to 4 extents) in `dtype` with tiles of
+    `tile_sites` sites (0: the default): the launcher's own planner, pure host code."""
+    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
+        return False
+    return bool(load().nf_phi4_cluster_tiled_supported(_lat4(lat), NF_F32 if dtype == torch.float32 else NF_F64,
+                                                       _tile_sites(tile_sites)))
+
+
+def cluster_tiled_plan(lat, dtype, tile_sites=0):
+    """What nf_phi4_cluster_tiled will do on the lattice `lat` in `dtype` with tiles of `tile_sites` sites (0: the
+    default): dict(tiles (per chain), tile_sites (in force), lanes (of a tile's workgroup), lds_bytes, workspace_bytes (ONE
+    chain's share of nf_phi4_cluster_tiled_workspace, without its 8 bytes of flags)).  Pure host code."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"cluster_tiled_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
+    code = NF_F32 if dtype == torch.float32 else NF_F64 if dtype == torch.float64 else NF_F16
+    out = ClusterTiledPlan()
+    _check(load().nf_phi4_cluster_tiled_plan(_lat4(lat), code, _tile_sites(tile_sites), C.byref(out)),
+           "nf_phi4_cluster_tiled_plan")
+    return dict(tiles=out.tiles, tile_sites=out.tile_sites, lanes=out.lanes, lds_bytes=out.lds_bytes,
+                workspace_bytes=cluster_tiled_workspace(1, lat, tile_sites) - 8)
+
+
+def cluster_tiled_workspace(Cn, lat, tile_sites=0):
+    """nf_phi4_cluster_tiled_workspace: the bytes of the workspace of a sweep of Cn chains on `lat`; pure host code."""
+    return int(load().nf_phi4_cluster_tiled_workspace(int(Cn), _lat4(tuple(lat)), _tile_sites(tile_sites)))
+
+
+def phi4_cluster_tiled(phi, w0, position=None, want_labels=False, tile_sites=0, workspace=None, generator=None):
+    """nf_phi4_cluster_tiled: `phi4_cluster` for chains that live in HBM, any lattice of 1 to 4 axes; the same Philox
+    positions and the same dict, with stats[:, 3] = the tiles of a chain.  Four launches and one memset on the
+    current stream.  `tile_sites`: the sites of a tile (0: the default).  The workspace comes from torch's caching
+    allocator per call (stream-aware and graph-pool safe, like `_workspace`), or is `workspace`: a uint8 tensor of at least
+    nf_phi4_cluster_tiled_workspace bytes."""
+    _require_device(phi)
+    if not phi.is_contiguous():
+        raise NormflowHipError("phi4_cluster_tiled needs contiguous phi (C, *L)")
+    Cn, lat, dev = phi.shape[0], tuple(phi.shape[1:]), phi.device
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"phi4_cluster_tiled: lattices of 1 to 4 axes, got {lat}")
+    ts = _tile_sites(tile_sites)
+    if workspace is None:
+        need = load().nf_phi4_cluster_tiled_workspace(Cn, _lat4(lat), ts)
+        workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    stats = torch.empty((Cn, 4), dtype=torch.int32, device=dev)
+    labels = torch.empty((Cn,) + lat, dtype=torch.int32, device=dev) if want_labels else None
+    seed, offset = position if position is not None else _philox_positions(dev, 2, generator)
+    _check(load().nf_phi4_cluster_tiled(_ptr(phi), _ptr(stats), _ptr(labels), Cn, _lat4(lat), float(w0), seed, offset,
+                                        _dtype_code(phi), ts, _ptr(workspace), workspace.numel(), _stream()),
+           "nf_phi4_cluster_tiled")
+    return dict(stats=stats, labels=labels)
 
 
 # ========================================================================= observables of sampler rows (nf_measure.hip)

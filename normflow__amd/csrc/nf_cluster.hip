@@ -67,23 +67,6 @@ struct ClusterArgs {
   PhiloxPos bond_pos, flip_pos;
 };
 
-// the site with the sign bit of v flipped: a NaN flips its sign bit too
-__device__ __forceinline__ float flip_sign(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, v) ^ 0x80000000u); }
-__device__ __forceinline__ double flip_sign(double v) {
-  return __builtin_bit_cast(double, __builtin_bit_cast(uint64_t, v) ^ 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-  return v;      // valid in lane 0
-}
-__device__ __forceinline__ int wave_max_int(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = max(v, __shfl_down(v, off, kWave));
-  return v;
-}
-
 template <typename T, int NS>
 __global__ __launch_bounds__(kClMaxLanes) void phi4_cluster_kernel(ClusterArgs A) {
   extern __shared__ __align__(16) unsigned char cl_lds[];

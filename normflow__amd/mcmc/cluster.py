@@ -1,8 +1,19 @@
 """One Swendsen-Wang sweep of the embedded Ising signs of phi^4 chains (Brower-Tamayo), composed from torch ops: the rule
 of include/normflow_hip.h (section "cluster updates") on any device.  `HMCSampler(cluster_every=E)` uses it for CPU
-tensors and for device lattices beyond the class of nf_phi4_cluster (32^3, 16^4, ...); on the device its `u` and `flip`
-come from nf_phi4_cluster_draws at the positions the kernel would use, so that it walks the kernel's chain."""
+tensors and for the device lattices that neither nf_phi4_cluster nor, by TILED_CLASSES, nf_phi4_cluster_tiled is routed
+to; on the device its `u` and `flip` come from nf_phi4_cluster_draws at the positions the kernels would use, so that it
+walks the kernels' chain."""
 import torch
+
+PATHS = (None, 'kernel', 'tiled', 'composed')
+# (dtype, axes of extent > 1, least sites of a chain): the classes beyond nf_phi4_cluster on which tools/cluster_bench.py
+# --tiled measured nf_phi4_cluster_tiled faster than the composed sweep below by more than its margin on an MI355X: 32^3
+# (3 axes) and 16^4, 32^4, 48^4 (4 axes) in both dtypes, 15 to 59 times (README, "Cluster updates").  A class is the
+# number of axes and everything from its smallest measured lattice up: the share of links that cross tiles, which is
+# what the merge costs, depends on both.  `HMCSampler._sweep_path` sends only these to the tiled kernel; lattices of 1
+# or 2 axes and smaller ones of 3 or 4 were not measured and stay composed
+TILED_CLASSES = ((torch.float32, 3, 32 ** 3), (torch.float64, 3, 32 ** 3),
+                 (torch.float32, 4, 16 ** 4), (torch.float64, 4, 16 ** 4))
 
 
 def cluster_sweep(phi, w0, u, flip):

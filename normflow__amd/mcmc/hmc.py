@@ -49,9 +49,11 @@ class HMCSampler:
     s % E == 0, s counted across calls since `start()`.  The launches are cut at the sweeps (at most E recorded steps
     each); the Philox positions are taken in call order, 2 per sweep and 2 per trajectory; a call still ends with an HMC
     launch, so `_ref`, `history` and `last['dh' | 'accept']` are the HMC's own, and `last['cluster']` holds the sweeps'
-    stats (sweeps, C, 4) int32 on the device: clusters, sites flipped, largest cluster, rounds.  nf_phi4_cluster where
-    `_hip.cluster_supported` takes the chains, else the composed `cluster_sweep` (mcmc/cluster.py).  `cluster(phi)` is the
-    bare sweep on given chains."""
+    stats (sweeps, C, 4) int32 on the device: clusters, sites flipped, largest cluster, and a positive count of the path
+    that swept (-1: a loop bound was hit and the chain was left alone) -- the labelling rounds of nf_phi4_cluster and of
+    the composed sweep, the tiles of a chain of nf_phi4_cluster_tiled.  The path is nf_phi4_cluster where
+    `_hip.cluster_supported` takes the chains, nf_phi4_cluster_tiled on the classes of `cluster.TILED_CLASSES`, else the
+    composed `cluster_sweep` (mcmc/cluster.py).  `cluster(phi)` is the bare sweep on given chains."""
 
     def __init__(self, model):
         self._model = model
@@ -120,12 +122,16 @@ class HMCSampler:
             need = _hip.load().nf_phi4_hmc_tiled_workspace(phi.shape[0], _hip._lat4(tuple(phi.shape[1:])), _hip._dtype_code(phi))
             ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=phi.device)      # one workspace for all calls
             per = _hip.HMC_TILED_MAX_LAUNCHES // (n_md + 2)
+        sweep_ws = None
+        if E and self._sweep_path(phi) == 'tiled':                # one workspace for all sweeps of the call
+            need = _hip.cluster_tiled_workspace(phi.shape[0], tuple(phi.shape[1:]))
+            sweep_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=phi.device)
         dhs, accs, sweeps, r0 = [], [], [], 0
         while r0 < rows:
             k = rows - r0
             if E:
                 if (self._steps + r0) % E == 0:
-                    phi, st = self._sweep(phi)
+                    phi, st = self._sweep(phi, workspace=sweep_ws)
                     sweeps.append(st)
                     if path == 'composed':
                         S = self._model.action(phi.double()).double()
@@ -169,28 +175,59 @@ class HMCSampler:
         return self
 
     @torch.no_grad()
-    def cluster(self, phi, position=None):
+    def cluster(self, phi, position=None, path=None):
         """ONE Swendsen-Wang sweep of the signs of the chains phi (C, *L), which are left alone; the stored chains are
         not touched.  Returns dict(phi = the swept chains, labels (C, *L) int32 = the smallest site index of every
-        site's cluster, stats (C, 4) int32 = clusters, sites flipped, size of the largest cluster, rounds).  `position`
-        = (seed, offset) fixes the two Philox positions of a device sweep instead of taking them from torch's CUDA
-        generator.  nf_phi4_cluster where it takes the chains, else `cluster_sweep` (mcmc/cluster.py)."""
-        new, stats, labels = self._sweep(phi.detach(), position=position, want_labels=True)
+        site's cluster, stats (C, 4) int32 = clusters, sites flipped, size of the largest cluster, and the count of
+        `last['cluster']`: rounds, or the tiles of a chain on the tiled path).  `position` = (seed, offset) fixes the two
+        Philox positions of a device sweep instead of taking them from torch's CUDA generator.  `path`: None (the
+        sampler's own choice, `_sweep_path`), 'kernel' (nf_phi4_cluster), 'tiled' (nf_phi4_cluster_tiled) or 'composed'
+        (`cluster_sweep`, mcmc/cluster.py); a forced path that does not apply raises."""
+        new, stats, labels = self._sweep(phi.detach(), position=position, want_labels=True, path=path)
         return dict(phi=new, labels=labels, stats=stats)
 
-    def _sweep(self, phi, position=None, want_labels=False):
-        """(the swept copy of phi, stats[, labels]): by the kernel for a ScalarPhi4Action on a HIP device and a lattice
-        `cluster_supported` takes (it beats the composed sweep on every class measured, README), else composed -- on the
-        device with the kernel's draws from the same two positions, on CPU tensors with torch's CPU generator."""
+    def _sweep_path(self, phi, path=None):
+        """'kernel', 'tiled' or 'composed'.  None: nf_phi4_cluster wherever it takes the chains (it beats the composed
+        sweep on every class measured, README); else nf_phi4_cluster_tiled on the classes of cluster.TILED_CLASSES
+        (3 or 4 axes of extent > 1, from the smallest lattice of that many axes on which tools/cluster_bench.py --tiled
+        measured it faster than the composed sweep by more than the margin); else composed.  The kernels take a ScalarPhi4Action on a HIP device."""
+        from .cluster import PATHS, TILED_CLASSES
+        if path not in PATHS:
+            raise ValueError(f"path must be None, 'kernel', 'tiled' or 'composed', got {path!r}")
+        if path == 'composed':
+            return path
+        lat = tuple(phi.shape[1:])
+        on_device = phi.is_cuda and isinstance(self._model.action, ScalarPhi4Action)
+        if path != 'tiled' and on_device and _hip.cluster_supported(lat, phi.dtype):
+            return 'kernel'
+        tiled = on_device and _hip.cluster_tiled_supported(lat, phi.dtype)
+        if path is None:
+            V, axes = phi[0].numel(), sum(1 for n in lat if n > 1)
+            measured = any(phi.dtype == dt and axes == d and V >= least for dt, d, least in TILED_CLASSES)
+            return 'tiled' if tiled and measured else 'composed'
+        if path == 'tiled' and tiled:
+            return path
+        raise _hip.NormflowHipError(
+            f"HMCSampler.cluster(path={path!r}): nf_phi4_cluster{'_tiled' if path == 'tiled' else ''} does not apply to a "
+            f"{type(self._model.action).__name__} and a {phi.device} tensor of shape {lat} and {phi.dtype}")
+
+    def _sweep(self, phi, position=None, want_labels=False, path=None, workspace=None):
+        """(the swept copy of phi, stats[, labels]) by the path `_sweep_path` names: a kernel, or composed -- on the device
+        with the kernel's draws from the same two positions, on CPU tensors with torch's CPU generator.  `workspace`: the
+        tiled kernel's, when the caller keeps one for several sweeps."""
         action = self._model.action
         if not hasattr(action, 'get_coef'):
             raise TypeError("cluster sweeps need the hopping coefficient of a phi^4 action (get_coef), got a "
                             f"{type(action).__name__}")
         lat = tuple(phi.shape[1:])
         w0 = float(action.get_coef(len(lat))[0])
-        if phi.is_cuda and isinstance(action, ScalarPhi4Action) and _hip.cluster_supported(lat, phi.dtype):
+        path = self._sweep_path(phi, path)
+        if path != 'composed':
             new = phi.clone().contiguous()
-            r = _hip.phi4_cluster(new, w0, position=position, want_labels=want_labels)
+            if path == 'kernel':
+                r = _hip.phi4_cluster(new, w0, position=position, want_labels=want_labels)
+            else:
+                r = _hip.phi4_cluster_tiled(new, w0, position=position, want_labels=want_labels, workspace=workspace)
             return (new, r['stats'], r['labels']) if want_labels else (new, r['stats'])
         from .cluster import cluster_sweep
         C, V = phi.shape[0], phi[0].numel()

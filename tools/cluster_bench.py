@@ -11,7 +11,14 @@
       chains, `--steps` recorded steps after as many of thermalisation, fp32) with cluster_every = 0 and 1, and the mean
       fraction of the lattice in the largest cluster.
 
-    python tools/cluster_bench.py [--reps 5] [--inner 20] [--steps 1500] [--skip-tau]
+  --tiled: instead of (a) .. (c), nf_phi4_cluster_tiled on the lattices beyond nf_phi4_cluster -- 32^3 x 256, 16^4 x 64,
+      32^4 x 16, 48^4 x 4, fp32 and fp64, thermalised by 20 steps of tiled sweep + tiled trajectory -- at tile_sites 4096,
+      8192 and 16384: the sweep (`--inner` in a row per timing, one workspace) against the composed sweep of the same build
+      on the same chains and against one trajectory (n_md = 10) of nf_phi4_hmc_tiled, with the same margin rule; the share
+      of the active-or-not forward links that cross tiles; and the tiled sweep against nf_phi4_cluster at 16^3 x 1024,
+      where both apply.  The ratios and the verdict are those of the library's default tile.
+
+    python tools/cluster_bench.py [--reps 5] [--inner 20] [--steps 1500] [--skip-tau] [--tiled]
 Prints one JSON line per shape and dtype and one for (c)."""
 import argparse
 import json
@@ -98,6 +105,97 @@ def launches(lattice, C, dtype, reps, inner):
                 max_rounds=int(stats[:, 3].max().item()), composed_rounds=int(c[2][0, 3].item()))
 
 
+TILED_SHAPES = [((32, 32, 32), 256), ((16, 16, 16, 16), 64), ((32, 32, 32, 32), 16), ((48, 48, 48, 48), 4)]
+TILES = (4096, 8192, 16384)
+
+
+def crossing_share(lattice, tile_sites):
+    """The share of the forward links (x, mu) whose ends lie in different tiles (runs of tile_sites site indices)."""
+    V = 1
+    for n in lattice:
+        V *= n
+    x = torch.arange(V, device=DEV).reshape(lattice)
+    cross = sum(((x // tile_sites) != (torch.roll(x, -1, dims=a) // tile_sites)).sum().item() for a in range(len(lattice)))
+    return cross / (V * len(lattice))
+
+
+def tiled(lattice, C, dtype, reps, inner, both=False):
+    """`both`: a lattice nf_phi4_cluster takes too -- the tiled sweep against it instead of against the composed sweep."""
+    model = _model(lattice, dtype)
+    s = model.hmc
+    torch.manual_seed(0)
+    s.start(n_chains=C)
+    with torch.no_grad():
+        phi = s._ref['sample'].clone()
+        coef, w0 = s._coef(lattice), float(model.action.get_coef(len(lattice))[0])
+        ws = torch.empty(_hip.cluster_tiled_workspace(C, lattice), dtype=torch.uint8, device=DEV)
+        hmc = _hip.phi4_hmc if both else _hip.phi4_hmc_tiled
+        for _ in range(20):                                                          # thermalise, sweeps included
+            _hip.phi4_cluster_tiled(phi, w0, workspace=ws)
+            hmc(phi, *coef, N_MD, DT, n_traj=1)
+        work = phi.clone()
+
+        def sweep(tile):
+            def f():
+                for _ in range(inner):
+                    _hip.phi4_cluster_tiled(work, w0, tile_sites=tile, workspace=ws)
+            return f
+
+        def other():
+            if both:
+                for _ in range(inner):
+                    _hip.phi4_cluster(work, w0)
+                return None
+            u, flip = _hip.phi4_cluster_draws(C, lattice, DEV)
+            return cluster_sweep(work, w0, u, flip)
+
+        traj = lambda: hmc(work, *coef, N_MD, DT, n_traj=inner)
+        for _ in range(2):
+            for tile in TILES:
+                sweep(tile)()
+            traj(); other()
+        torch.cuda.synchronize()
+        # the sweeps against each other at the timed size, from one position
+        k = phi.clone()
+        r = _hip.phi4_cluster_tiled(k, w0, position=(1, 0), want_labels=True, workspace=ws)
+        if both:
+            k2 = phi.clone()
+            r2 = _hip.phi4_cluster(k2, w0, position=(1, 0), want_labels=True)
+            same = bool(torch.equal(k2, k) and torch.equal(r2['labels'], r['labels']))
+            other_rounds = int(r2['stats'][:, 3].max().item())
+        else:
+            c = cluster_sweep(phi, w0, *_hip.phi4_cluster_draws(C, lattice, DEV, position=(1, 0)))
+            same = bool(torch.equal(c[0], k) and torch.equal(c[1], r['labels']) and torch.equal(c[2][:, :3], r['stats'][:, :3]))
+            other_rounds = int(c[2][0, 3].item())
+            del c
+        stats = r['stats'].double()
+        local_rounds = int(ws[8 * phi.numel():8 * phi.numel() + 8 * C].view(torch.int32).view(C, 2)[:, 1].max().item())
+        ts, tt, to = {tile: [] for tile in TILES}, [], []
+        for _ in range(reps):
+            for tile in TILES:
+                ts[tile].append(_ms(sweep(tile)) / inner)
+            tt.append(_ms(traj) / inner)
+            to.append(_ms(other) / (inner if both else 1))
+    med = {tile: statistics.median(t) for tile, t in ts.items()}
+    best = min(TILES, key=lambda tile: med[tile])
+    plan = _hip.cluster_tiled_plan(lattice, dtype)
+    default = _hip.cluster_tiled_plan((48, 48, 48, 48), dtype)['tile_sites']         # the library's default, one of TILES
+    ms, mt, mo = med[default], statistics.median(tt), statistics.median(to)           # the ratios are those of the default
+    spread = max((max(t) - min(t)) / statistics.median(t) for t in (ts[default], tt, to))
+    margin = max(0.10, spread)
+    rnd = lambda t: [round(min(t), 4), round(max(t), 4)]
+    V = phi[0].numel()
+    return dict(lattice=list(lattice), chains=C, dtype=str(dtype).replace("torch.", ""), n_md=N_MD, launches_per_timing=inner,
+                tiled_ms={tile: round(med[tile], 4) for tile in TILES}, tiled_ms_spread={tile: rnd(ts[tile]) for tile in TILES},
+                best_tile=best, default_tile=default, trajectory_ms=round(mt, 4), trajectory_ms_spread=rnd(tt), sweep_over_trajectory=round(ms / mt, 3),
+                **{("kernel_ms" if both else "composed_ms"): round(mo, 4), ("kernel_ms_spread" if both else "composed_ms_spread"): rnd(to)},
+                other_over_tiled=round(mo / ms, 2), margin=round(margin, 3), tiled_wins=bool(mo / ms > 1 + margin),
+                same_bits=same, plan=plan, workspace_bytes=_hip.cluster_tiled_workspace(C, lattice),
+                crossing_share={tile: round(crossing_share(lattice, min(tile, V)), 4) for tile in TILES},
+                mean_clusters=round(stats[:, 0].mean().item(), 1), mean_largest_fraction=round(stats[:, 2].mean().item() / V, 4),
+                tiles=int(stats[:, 3].max().item()), local_rounds=local_rounds, other_rounds=other_rounds)
+
+
 def tunnelling(steps):
     lattice, C = (8, 8), 32
     out = dict(lattice=list(lattice), chains=C, steps=steps, **COUPLINGS)
@@ -125,7 +223,15 @@ def main():
     ap.add_argument("--inner", type=int, default=20, help="launches (sweeps) or trajectories per timing")
     ap.add_argument("--steps", type=int, default=1500, help="recorded steps of the tau_int run (and of its thermalisation)")
     ap.add_argument("--skip-tau", action="store_true")
+    ap.add_argument("--tiled", action="store_true", help="nf_phi4_cluster_tiled on the lattices beyond nf_phi4_cluster")
     a = ap.parse_args()
+    if a.tiled:
+        for dtype in (torch.float32, torch.float64):
+            print(json.dumps(tiled((16, 16, 16), 1024, dtype, a.reps, a.inner, both=True)), flush=True)
+        for lattice, C in TILED_SHAPES:
+            for dtype in (torch.float32, torch.float64):
+                print(json.dumps(tiled(lattice, C, dtype, a.reps, a.inner)), flush=True)
+        return
     for lattice, C in SHAPES:
         for dtype in (torch.float32, torch.float64):
             print(json.dumps(launches(lattice, C, dtype, a.reps, a.inner)), flush=True)
