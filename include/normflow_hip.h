@@ -443,7 +443,11 @@ int nf_conv_fwd(const void *in, const void *wfrag, const void *bias, void *out, 
  *       slice 7*j3 + i = tap j3 (fastest axis) of kernel rows 4i..4i+3 ((j0, j1, j2) row-major; row 27 = zeros);
  *       lane = 16*g + n holds, for column 16*tile + n, the 8 input channels of kernel row 4i + g;
  *       hi = fp16(1024 w), lo = fp16(1024 w - hi) (the factor 2^10 keeps the lo parts of typical weights out of
- *       fp16's subnormal range; the kernel scales the accumulators back).  Needs max|w| < 29.
+ *       fp16's subnormal range; the kernel scales the accumulators back).  Needs finite weights with
+ *       max|w| < 3.0e4 / 1024 = 29.296875 (normflow__amd._hip.SPLIT16_WEIGHT_LIMIT: 29.29 runs here, 29.30 and NaN / inf
+ *       weights run the fp32 kernels).  Weights of any smaller size are taken: where the lo parts fall below fp16's
+ *       subnormal step the error of an output degrades to the floor 2^-25 sum|w| + 2^-35 sum|x| over its terms, never to
+ *       NaN (tests/split16_range_cases.py states the bound, tests/test_split16_range.py holds every entry point to it).
  * `fused`: bit 0 = the layer is the fused last layer (nf_conv_rqs), bit 1 = NF_CONV_UNIT_INPUT will be passed, bit 2 =
  * NF_CONV_SPLIT16_INPUT will be passed (the split-fp16 kernel takes fastest axes other than 32 sites only from a pair tensor).
  * Returns the code, or -1 for invalid arguments. */
@@ -472,8 +476,12 @@ int nf_conv_affine_split16(const void *in16, const void *wsplit, const void *bia
                            void *y, void *logj, int64_t B, const int32_t *lattice, int active_parity, int inverse,
                            int flags, void *workspace, size_t workspace_bytes, void *stream);
 /* The FIRST ConvAct layer (1 -> 8 channels, 3^4 kernel, tanh / logistic) in front of the two entry points above (nf_conv_c.hip):
- * fp32 field in, fp16 pair tensor out, every fp32 product as three fp16 matrix-core products (x = x_hi + x_lo, |x| below the
- * fp16 range: beyond 6.5e4 the outputs are NaN, never silently wrong).
+ * fp32 field in, fp16 pair tensor out, every fp32 product as three fp16 matrix-core products (x = x_hi + x_lo, |x| up to
+ * fp16's largest finite number: 65519 still rounds to 65504 and is taken; a site of 65520 and beyond, inf or NaN makes every
+ * output whose window holds it NaN -- never a finite wrong number -- and leaves the outputs further away than the window
+ * plus the two zero-weight taps of the two-site columns bit for bit as they were.  Small |x| lose nothing that matters: the
+ * lo part carries an absolute error of 2^-25 = 3e-8.  Saturated pre-activations give exactly +-1 (tanh), 0 or 1 (logistic)
+ * with a zero lo part).
  *   in (B, V) fp32 (the frozen half of the field, one channel); out16 (B, V, 16) halfs; bias (8) fp32 or NULL;
  *   wsplit: [K slice (4)][hi|lo][64 lanes][8] halfs: K index = 4 r + t, r = kernel row (j0, j1, j2) row-major (27, padded to
  *   32 with zeros), t = tap of the site pair (sites 2p-1 .. 2p+2); lane 16*g + n (column n = 8*shift + co) holds rows
@@ -1079,8 +1087,25 @@ int nf_conv_wgrad_split16(const void *in, const void *gz, void *gw, int64_t B, c
                           const int32_t *ksize, int cin, int cout, const void *absmax_bits, int compact_parity,
                           void *workspace, size_t workspace_bytes, void *stream);
 /* max |x| of an fp32 tensor of n elements, as the bits of a float in 4 bytes of device memory: what the training kernels
- * (nf_conv_wgrad_split16, nf_planes_to_split16 / nf_conv_dgrad_split16) scale a cotangent by; one pass serves both. */
+ * (nf_conv_wgrad_split16, nf_planes_to_split16 / nf_conv_dgrad_split16) scale a cotangent by; one pass serves both.
+ * Equal to max|x| bit for bit (+0 for an empty or all-zero tensor; a NaN entry is skipped, an inf entry gives inf).
+ * The kernels that read it multiply their operand by 2^(13 - e), max|x| = f 2^e with f in [0.5, 1), and the result by the
+ * inverse, both carried as exponents (never as one float: 2^(13 - e) overflows below 2^-115).  For an operand whose
+ * largest entry is a NORMAL fp32 number, multiplying the operand by 2^k multiplies every output by exactly 2^k wherever
+ * the scaled output is a normal number or zero (tests/test_split16_range.py: k from -120, a largest entry of about
+ * 2^-118, to 100); the operand's own subnormal entries count with the bits fp32 keeps of them.  Below that nothing is
+ * promised but finite results: nf_conv_last_logits_split16 and the fused last layer return zeros for a maximum below
+ * 2^-127 (their descale 2^(-23 + e) is one float and underflows there).  An all-zero operand gives exact zeros; a
+ * non-finite maximum leaves the operand unscaled (the inf meets the products and gives non-finite outputs, a NaN entry
+ * likewise in its window).  A bias is carried in the scaled accumulators as
+ * bias 2^(23 - e): with a bias, |bias| / max|x| must stay below 2^100. */
 int nf_absmax_bits(const void *x, int64_t n, void *bits, void *stream);
+/* The power of two 2^c that brings the larger of max|a| and max|b| (fp32 tensors of na, nb elements) to [1, 2), and 2^-c:
+ * work (16 bytes of device memory) = [bits of max|a|][bits of max|b|][2^c][2^-c], the last two as floats.  A zero or
+ * subnormal maximum gives c = 126, an inf one c = 0; NaN entries do not count.  The fused last layer's backward pass
+ * multiplies its two cotangents by 2^c and its gradients by 2^-c, so that the fp32 logit cotangent it materialises
+ * keeps its bits for cotangents of any size. */
+int nf_cotangent_pow2(const void *a, int64_t na, const void *b, int64_t nb, void *work, void *stream);
 
 #ifdef __cplusplus
 }

@@ -128,6 +128,7 @@ PROTOTYPES = {
     "nf_planes_to_split16": (_I, [_P, _P, _P, _I64, _I, C.POINTER(C.c_int32), _I, _P]),
     "nf_conv_dgrad_split16": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _I, _P]),
     "nf_absmax_bits": (_I, [_P, _I64, _P, _P]),
+    "nf_cotangent_pow2": (_I, [_P, _I64, _P, _I64, _P, _P]),
     "nf_conv_last_logits_split16": (_I, [_P, _I, _P, _P, _P, _I64, C.POINTER(C.c_int32), _I, _P, _P]),
     "nf_conv_last_logits_split16_acc": (_I, [_P, _I, _P, _P, _P, _I64, C.POINTER(C.c_int32), _I, _P, _I, _I, _P]),
     "nf_expand_pairs": (_I, [_P, _P, _I64, C.POINTER(C.c_int32), _I, _I, _P]),
@@ -868,6 +869,9 @@ def conv_weight_for_layer(w, lat4, k4, cin, cout, compact, fused, dtype_code):
 # would put the lo parts into fp16's subnormal range -- absolute resolution 6e-8, i.e. 5e-7 RELATIVE to w and, unlike
 # activation rounding, the same error at every site: it showed up as a coherent 1.7e-5 shift of log|J| on 32^4.
 SPLIT16_WEIGHT_SCALE = 1024.0
+# The split-fp16 kernels take weights with max|w| BELOW this (`_weights_fit_fp16`; graphs.GraphedTrainStep's guard): 1024 w
+# then stays under 3.0e4, well inside fp16 (65504), and hi = fp16(1024 w) is finite.  29.296875: 29.29 fits, 29.30 does not.
+SPLIT16_WEIGHT_LIMIT = 3.0e4 / SPLIT16_WEIGHT_SCALE
 
 
 def pack_conv_weight_split16(w):
@@ -1088,9 +1092,9 @@ def _weights_fit_fp16(w):
     ok = _UNIT_OK.lookup(w, None, state)
     if ok is not _UNIT_OK.MISS:
         return ok
-    if torch.cuda.is_current_stream_capturing():
+    if w.is_cuda and torch.cuda.is_current_stream_capturing():
         return False            # cannot synchronise here; the fp32 kernels are always valid
-    ok = bool(torch.isfinite(w.detach()).all()) and float(w.detach().abs().max()) * SPLIT16_WEIGHT_SCALE < 3.0e4
+    ok = bool(torch.isfinite(w.detach()).all()) and float(w.detach().abs().max()) < SPLIT16_WEIGHT_LIMIT
     return _UNIT_OK.store(w, None, state, ok)
 
 
@@ -1521,8 +1525,15 @@ class FusedLastRqsFn(torch.autograd.Function):
         b = None if bias is None else bias.detach().float().contiguous()
         gz = torch.empty((B, cout, V // 2), dtype=torch.float32, device=h.device)
         gx = torch.empty_like(xpt)
-        _check(lib.nf_conv_rqs_split16_vjp(_ptr(src), is16, _ptr(wsp), _ptr(b), cout, _ptr(xpt), _ptr(gy.contiguous()),
-                                           _ptr(glogj.contiguous()), _ptr(gz), _ptr(gx), B, lat4, int(ctx.parity), _ptr(bits),
+        # The logit cotangent gz is a materialised fp32 tensor of products cotangent x spline derivative: below cotangents of
+        # ~1e-30 its entries are subnormal and lose bits.  Everything here is linear in (gy, glogj): run it on the cotangents
+        # times the power of two that brings their largest entry to [1, 2) and scale the gradients back (exact, no sync).
+        gy, glogj = gy.contiguous(), glogj.contiguous()
+        work = torch.empty(4, dtype=torch.float32, device=h.device)           # [bits of the two maxima][2^c][2^-c]
+        _check(lib.nf_cotangent_pow2(_ptr(gy), gy.numel(), _ptr(glogj), glogj.numel(), _ptr(work), _stream()), "nf_cotangent_pow2")
+        gys, gls = torch._foreach_mul([gy, glogj], work[2])
+        _check(lib.nf_conv_rqs_split16_vjp(_ptr(src), is16, _ptr(wsp), _ptr(b), cout, _ptr(xpt), _ptr(gys),
+                                           _ptr(gls), _ptr(gz), _ptr(gx), B, lat4, int(ctx.parity), _ptr(bits),
                                            C.byref(ctx.opts), int(bool(ctx.inverse)), _stream()), "nf_conv_rqs_split16_vjp")
         gh = gw = gb = None
         gbits = absmax_bits(gz)
@@ -1537,6 +1548,7 @@ class FusedLastRqsFn(torch.autograd.Function):
             raise NormflowHipError("FusedLastRqsFn.backward: the split-fp16 gradient kernels refused a layer the forward pass took")
         if bias is None:
             gb = None
+        torch._foreach_mul_([t for t in (gh, gw, gb, gx) if t is not None], work[3])
         return gh, gw, gb, gx, (glogj if ctx.has_log0 else None), None, None, None
 
 

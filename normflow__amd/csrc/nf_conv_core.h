@@ -78,14 +78,18 @@ struct ConvArgs {
 };
 
 // The power of two that brings a tensor whose largest magnitude has the bits *absmax to [2^12, 2^13): cotangents of a mean
-// over a batch are far below fp16's normal range (nf_conv_w.hip, nf_conv_dgrad_split16).
-__device__ __forceinline__ float pow2_scale_for(const unsigned *absmax) {
-  if (!absmax) return 1.f;
+// over a batch are far below fp16's normal range (nf_conv_w.hip, nf_conv_dgrad_split16).  It is handed round as its EXPONENT
+// and applied with ldexpf (one v_ldexp_f32, as exact as a multiplication by a power of two) or, where a kernel keeps its
+// multiplication (nf_conv_h.hip), as factors that are floats: as ONE float, 2^(13 - e) is inf for a maximum below 2^-115,
+// and 0 * inf made NaN of what should be a tiny gradient.  0 (no scaling) for a null pointer, an all-zero tensor and a
+// non-finite maximum.
+__device__ __forceinline__ int pow2_exp_for(const unsigned *absmax) {
+  if (!absmax) return 0;
   const float mx = __uint_as_float(*absmax);
-  if (!(mx > 0.f) || !(mx < 3.0e38f)) return 1.f;
+  if (!(mx > 0.f) || !(mx < 3.0e38f)) return 0;
   int e;
   (void)frexpf(mx, &e);                       // mx = f 2^e, f in [0.5, 1)
-  return ldexpf(1.f, 13 - e);
+  return 13 - e;                              // -115 .. 161 (a subnormal maximum has e down to -148)
 }
 
 // The fp16 (hi, lo) pair tensor exchanged by the split-fp16 kernels (include/normflow_hip.h, NF_OUT_SPLIT16) is row-major:

@@ -164,7 +164,7 @@ __global__ __launch_bounds__(512, 2) void conv_g2_kernel(ConvArgs A) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) kc0[r] = kcs * bv4[r];
   const float kc1 = kcs * kInvWScale;
-  [[maybe_unused]] const float descale = kInvWScale / pow2_scale_for(A.gscale_bits);      // EPI = 3
+  [[maybe_unused]] const int descale_exp = -10 - pow2_exp_for(A.gscale_bits);      // EPI = 3: kInvWScale over the input's power of two, as an exponent
 
   // ---- A-fragment addressing.  Lane (pair p, k-group g) reads tap g of its pair q = 16 hs + p: site 2q + g - 1 -- parity block
   // (g + 1) & 1, slot q + (g >> 1) of the pair tensor's row (pair_row_offset), i.e. LOCAL slot j = p + (g >> 1) of the segment's
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(512, 2) void conv_g2_kernel(ConvArgs A) {
         float *d = static_cast<float *>(A.out) + pfield + int64_t(4 * (g & 1)) * A.V;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float v = (prev[r] + pa[r]) * descale + bv4[r];
+          float v = ldexpf(prev[r] + pa[r], descale_exp) + bv4[r];
           if (A.accumulate) v += pold[r];                            // (the old values were requested a step ago)
           if (A.act == kActTanh) v = tanh_affine(v, 2.885390081777927f, 0.f);      // of the SUM: the last group pass of a layer with more than 8 input channels
           d[int64_t(r) * A.V] = v;

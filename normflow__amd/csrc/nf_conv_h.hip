@@ -53,7 +53,7 @@ __host__ __device__ constexpr int rowidx(int r) { return ((r / 9) * H1 + (r / 3)
 // rows 4i .. 4i+3 (row 27 is padding: zero weights).  Same j3 for the four k-groups => same parity sub-image.
 constexpr int NS = 21;
 constexpr int UNITS = 128;                                // active sites per box
-constexpr float kWScale = 1024.0f, kInvWScale = 1.0f / 1024.0f;      // normflow__amd/_hip.py: SPLIT16_WEIGHT_SCALE
+constexpr float kWScale = 1024.0f, kInvWScale = 1.0f / 1024.0f; constexpr int kInvWExp = -10;      // normflow__amd/_hip.py: SPLIT16_WEIGHT_SCALE
 constexpr int C = 46, M = 16;                            // the LARGEST logit count / knots_len (3 column tiles); a layer may have fewer:
                                                           // cout = 3 m - 2 <= 46 at run time (columns >= cout: zero weights, never stored)
 constexpr int PTS = UNITS + 4;                            // row stride of the logit scratch in floats: +4 spreads the 16 channels a
@@ -230,7 +230,9 @@ __global__ __launch_bounds__(256, 1) void conv_h_kernel(ConvArgs A) {
   };
 
   // the input may come scaled by a power of two (training: activations of unknown range, nf_conv_last_logits_split16)
-  const float in_scale = pow2_scale_for(A.gscale_bits), out_scale = kInvWScale / in_scale;
+  const int in_exp = pow2_exp_for(A.gscale_bits);                      // (an exponent, see pow2_exp_for: 2^in_exp is no float beyond 127)
+  const float in_scale = ldexpf(1.f, in_exp < 127 ? in_exp : 127), in_scale2 = ldexpf(1.f, in_exp < 127 ? 0 : in_exp - 127);
+  const float out_scale = ldexpf(1.f, kInvWExp - in_exp);              // 2^-10 / 2^in_exp: a power of two down to 2^-149 (in_exp <= 139: one multiplication, one rounding); 0 for a maximum below 2^-127
   // HALF ITEMS (round 3).  When a row is a whole number of segments plus 8 pairs (L3 = 48, 80, ...), the last segment of a box
   // holds 8 pairs per row: as one site tile per row half of every tile's lanes were padding (48^4 ran at 0.71 of the per-site
   // rate of 32^4).  Such an item now packs the two rows (z2 = 0, 1) of a (z0, z1) position into ONE site tile -- lanes 0-7 row
@@ -313,7 +315,7 @@ __global__ __launch_bounds__(256, 1) void conv_h_kernel(ConvArgs A) {
     f32x4 acc0;               // what slot 0 starts from
     {
       const int co = (W << 4) + (lane & 15);
-      const float b0 = (A.bias && co < A.cout) ? static_cast<const float *>(A.bias)[co] * kWScale * in_scale : 0.f;
+      const float b0 = (A.bias && co < A.cout) ? ldexpf(static_cast<const float *>(A.bias)[co], in_exp - kInvWExp) : 0.f;
       acc0 = f32x4{b0, b0, b0, b0};
     }
     f32x4 acc[8][3];
@@ -518,7 +520,7 @@ __global__ __launch_bounds__(256, 1) void conv_h_kernel(ConvArgs A) {
         f16x8 hi, lo;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-          const float sv = v[j][c] * in_scale;
+          const float sv = (v[j][c] * in_scale2) * in_scale;      // (in_scale2 = 1 unless the maximum is below 2^-114)
           const _Float16 hh = static_cast<_Float16>(sv);
           hi[c] = hh;
           lo[c] = static_cast<_Float16>(sv - static_cast<float>(hh));

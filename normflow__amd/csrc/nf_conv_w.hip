@@ -53,7 +53,7 @@ struct Args {
 
 extern __shared__ __align__(16) unsigned char smem_w[];
 
-__device__ __forceinline__ float gz_scale(const unsigned *absmax) { return pow2_scale_for(absmax); }
+__device__ __forceinline__ int gz_exp(const unsigned *absmax) { return pow2_exp_for(absmax); }
 
 __global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ p, int64_t n, unsigned *out) {
   float m = 0.f;
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kThreads, 4) void wgrad16_kernel(Args A) {
   const int L0 = A.L[0], L1 = A.L[1], L2 = A.L[2];
   const int L3 = A.L[3], NSEG = (L3 + 31) >> 5; // a lattice row is cut into segments of 32 sites (the last one may hold 16)
   const int64_t rowsz = L3;                     // sites of a lattice row (the fastest axis)
-  const float scale = gz_scale(A.absmax);
+  const int sexp = gz_exp(A.absmax);
 
   // zero the gz images once: channels cout .. 47 are never written
   for (int i = threadIdx.x; i < 2 * 48 * GS / 4; i += kThreads) reinterpret_cast<unsigned *>(gbuf)[i] = 0u;
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(kThreads, 4) void wgrad16_kernel(Args A) {
         const int f = lane + 64 * it, co = f >> 2, q4 = f & 3;
         if (co < A.cout) {
           float4 s = 8 * q4 < nv ? S.gv[it] : float4{0.f, 0.f, 0.f, 0.f};
-          s.x *= scale; s.y *= scale; s.z *= scale; s.w *= scale;
+          s.x = ldexpf(s.x, sexp); s.y = ldexpf(s.y, sexp); s.z = ldexpf(s.z, sexp); s.w = ldexpf(s.w, sexp);
           f16x4 hi, lo;
           split4(s, hi, lo);
           const _Float16 z = static_cast<_Float16>(0.f);
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(kThreads, 4) void wgrad16_kernel(Args A) {
       const int f = lane + 64 * it, co = f >> 3, q4 = f & 7;
       if (co < A.cout) {
         float4 s = 4 * q4 < nv ? S.gv[it] : float4{0.f, 0.f, 0.f, 0.f};
-        s.x *= scale; s.y *= scale; s.z *= scale; s.w *= scale;
+        s.x = ldexpf(s.x, sexp); s.y = ldexpf(s.y, sexp); s.z = ldexpf(s.z, sexp); s.w = ldexpf(s.w, sexp);
         f16x4 hi, lo;
         split4(s, hi, lo);
         *reinterpret_cast<f16x4 *>(gb + co * GS + 8 * q4) = hi;
@@ -413,7 +413,7 @@ __global__ __launch_bounds__(256) void expand_pairs_kernel(const T *__restrict__
 __global__ __launch_bounds__(256) void planes_to_pairs_kernel(const float *__restrict__ src, unsigned char *__restrict__ dst, int64_t B,
                                                               int C, int64_t V, int L3, const unsigned *absmax, int compact, int parity,
                                                               int L1, int L2) {
-  const float scale = pow2_scale_for(absmax);
+  const int sexp = pow2_exp_for(absmax);
   const int G = (C + 7) >> 3;
   const int64_t total = int64_t(G) * B * V;
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < total; i += int64_t(gridDim.x) * 256) {
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(256) void planes_to_pairs_kernel(const float *__res
     }
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      const float v = (8 * g + c < C && live) ? raw[c] * scale : 0.f;
+      const float v = (8 * g + c < C && live) ? ldexpf(raw[c], sexp) : 0.f;
       const _Float16 h = static_cast<_Float16>(v);
       hi[c] = h;
       lo[c] = static_cast<_Float16>(v - static_cast<float>(h));
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(256) void wgrad16_reduce_kernel(const float *__rest
   const int o = idx / nused, c = idx - o * nused;
   double s = 0.0;
   for (int p = 0; p < nparts; ++p) s += double(partial[(int64_t(p) * 48 + o) * ncols + c]);
-  gw[int64_t(o) * ncols + c] += float(s / double(gz_scale(absmax)));
+  gw[int64_t(o) * ncols + c] += float(ldexp(s, -gz_exp(absmax)));
 }
 
 }  // namespace wg
@@ -580,6 +580,33 @@ extern "C" int nf_absmax_bits(const void *x, int64_t n, void *bits, void *stream
   if (n == 0) return NF_OK;
   hipLaunchKernelGGL(wg::absmax_kernel, dim3(2048), dim3(256), 0, s, static_cast<const float *>(x), n, static_cast<unsigned *>(bits));
   return check_launch("absmax kernel");
+}
+
+// The power of two that brings the larger of max|a| and max|b| to [1, 2), and its inverse, as two floats in device memory:
+// work = 16 bytes, [bits of max|a|][bits of max|b|][2^c][2^-c].  c = 127 - E for the biased exponent E of the maximum; a
+// zero or subnormal maximum gets 2^126, an inf one 1 (NaN entries are skipped by the maximum).  FusedLastRqsFn.backward runs
+// on cotangents scaled like this (normflow__amd/_hip.py).
+namespace nf {
+namespace wg {
+__global__ void pow2_pair_kernel(unsigned *work) {
+  const unsigned m = work[0] > work[1] ? work[0] : work[1];       // (non-negative floats order like their bits)
+  const int E = int(m >> 23);
+  const int f = E == 255 ? 127 : (254 - E < 1 ? 1 : (254 - E > 253 ? 253 : 254 - E));
+  work[2] = unsigned(f) << 23;
+  work[3] = unsigned(254 - f) << 23;
+}
+}  // namespace wg
+}  // namespace nf
+
+extern "C" int nf_cotangent_pow2(const void *a, int64_t na, const void *b, int64_t nb, void *work, void *stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  NF_REQUIRE(work && na >= 0 && nb >= 0 && (a || na == 0) && (b || nb == 0), "nf_cotangent_pow2: bad arguments");
+  NF_REQUIRE(hipMemsetAsync(work, 0, 8, s) == hipSuccess, "nf_cotangent_pow2: hipMemsetAsync failed");
+  unsigned *w = static_cast<unsigned *>(work);
+  if (na > 0) hipLaunchKernelGGL(wg::absmax_kernel, dim3(2048), dim3(256), 0, s, static_cast<const float *>(a), na, w);
+  if (nb > 0) hipLaunchKernelGGL(wg::absmax_kernel, dim3(nb < 65536 ? 8 : 2048), dim3(256), 0, s, static_cast<const float *>(b), nb, w + 1);
+  hipLaunchKernelGGL(wg::pow2_pair_kernel, dim3(1), dim3(1), 0, s, w);
+  return check_launch("cotangent power-of-two kernels");
 }
 
 // fp32 channel planes (B, C, V) as the split-fp16 kernels read them: ceil(C / 8) pair tensors (G, B, V, 16 halfs), multiplied

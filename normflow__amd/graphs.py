@@ -73,8 +73,8 @@ class GraphedTrainStep:
 
     * the random draw, the gradient all-reduce and the optimiser stay outside the graph;
     * weight repacking is captured with the pass (`_hip.pack_inside_capture`), so a replay always uses the current values;
-    * the kernel choice frozen into the graph (split-fp16 products need |w| < 29) is guarded: the graph also computes
-      max |parameter|, read back with the loss; outside the validated range the graph is captured again on the exact
+    * the kernel choice frozen into the graph (split-fp16 products need |w| < `_hip.SPLIT16_WEIGHT_LIMIT`) is guarded: the
+      graph also computes max |parameter|, read back with the loss; outside the validated range the graph is captured again on the exact
       fp32 kernels (valid for any weights) and the step repeated;
     * the parameters' .grad tensors live in the graph's memory pool and are overwritten by every replay: do not call
       `optimizer.zero_grad()` between replay and `optimizer.step()` (Fitter does not, in this mode).
@@ -128,7 +128,7 @@ class GraphedTrainStep:
             wmax = torch.stack(torch._foreach_norm([p.detach() for p in self._params], float('inf'))).max()
         self._loss, self._d, self._wmax = loss.detach(), d.detach(), wmax
         self._grads = [p.grad for p in self._params]
-        self._limit = 2.9e4 / _hip.SPLIT16_WEIGHT_SCALE
+        self._limit = _hip.SPLIT16_WEIGHT_LIMIT
 
     def __call__(self, x, logr):
         if tuple(x.shape) != tuple(self._x.shape) or x.dtype != self._x.dtype:
