@@ -1907,6 +1907,12 @@ def metropolis_select(y, ref_sample, accept, keep, n_chains):
 HMC_MAX_WORK = 1 << 26        # NF_HMC_MAX_WORK: the cap on n_md * n_traj * max(V, 256) * ceil(C / 1024) of one launch
 
 
+def hmc_fused_budget(V, Cn):
+    """The MD steps (n_md * n_traj, and NF_HMC_MEASURE_MD_STEPS per measured trajectory) that one launch of nf_phi4_hmc and
+    its measuring and ladder forms may hold for Cn chains of V sites: hmc_entry's rule (nf_hmc.hip)."""
+    return HMC_MAX_WORK // (max(int(V), 256) * ((int(Cn) + 1023) // 1024))
+
+
 def _planner_supported(symbol, lat, dtype):
     """True if the planner `symbol` of the library takes the lattice `lat` (1 to 4 extents) in `dtype`: pure host code."""
     if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
@@ -1993,11 +1999,10 @@ def _phi4_hmc_call(what, phi, w0, w2, w4, n_md, dt, *, n_traj, record_every, pi_
     if measures:
         if rows is None:
             raise NormflowHipError("phi4_hmc(measure=True) needs record_every: which trajectories to measure")
-        measure = torch.empty(rows + (7 + sum(lat) + 4 - len(lat),), dtype=torch.float64, device=dev)
+        measure = torch.empty(rows + (measure_n_out(lat),), dtype=torch.float64, device=dev)
     pi_out = torch.empty_like(phi) if want_pi else None
     if tiled and workspace is None:
-        need = load().nf_phi4_hmc_tiled_workspace(Cn, _lat4(lat), _dtype_code(phi))
-        workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+        workspace = torch.empty(max(hmc_tiled_workspace(Cn, lat, phi.dtype), 256), dtype=torch.uint8, device=dev)
     ws = (_ptr(workspace), workspace.numel()) if tiled else ()
     couplings = (float(w0), float(w2), float(w4)) if ladder is None else _ladder_tensors(what, *ladder, Cn, dev)[1]
     seed, offset = position if position is not None else _philox_positions(dev, 2 * max(n_traj, 1), generator)
@@ -2030,6 +2035,17 @@ def phi4_hmc(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in=None,
 
 # ========================================================================= the same, chains in HBM (nf_hmc_tiled.hip)
 HMC_TILED_MAX_LAUNCHES = 65536      # NF_HMC_TILED_MAX_LAUNCHES: the cap on (n_md + 2) * n_traj of one call
+
+
+def hmc_tiled_budget(n_md):
+    """The trajectories that one call of nf_phi4_hmc_tiled and its ladder form may hold."""
+    return HMC_TILED_MAX_LAUNCHES // (int(n_md) + 2)
+
+
+def hmc_tiled_workspace(Cn, lat, dtype):
+    """nf_phi4_hmc_tiled_workspace: the bytes of the workspace of a call on Cn chains on `lat` in `dtype`; pure host code."""
+    code = NF_F32 if dtype == torch.float32 else NF_F64 if dtype == torch.float64 else NF_F16
+    return int(load().nf_phi4_hmc_tiled_workspace(int(Cn), _lat4(tuple(lat)), code))
 
 
 class HmcTiledPlan(C.Structure):
@@ -2271,6 +2287,12 @@ def measure_plan(lat, dtype):
                 march_axis=march, lds_bytes=out.lds_bytes, lds_budget=out.lds_budget)
 
 
+def measure_n_out(lat):
+    """The width of a measure row of the lattice `lat` (1 to 4 axes), which the kernels pad to four axes with extents of 1:
+    7 scalars (sum phi, phi^2, phi^4, the links of the four axes) and one slice sum per plane of every axis."""
+    return 7 + sum(lat) + 4 - len(lat)
+
+
 def _measure_out(what, out, cfgs, n_out):
     """`out` of a measure wrapper: a new (N, n_out) float64 tensor, or the caller's contiguous one of that shape."""
     if out is None:
@@ -2292,7 +2314,7 @@ def lattice_measure(cfgs, workspace=None, out=None):
     if not cfgs.is_contiguous() or not 1 <= len(lat) <= 4:
         raise NormflowHipError(f"lattice_measure needs contiguous cfgs (N, *L) with 1 to 4 lattice axes, got {tuple(cfgs.shape)}")
     N, lat4, code = cfgs.shape[0], _lat4(lat), _dtype_code(cfgs)
-    out = _measure_out("lattice_measure", out, cfgs, 7 + sum(lat) + 4 - len(lat))
+    out = _measure_out("lattice_measure", out, cfgs, measure_n_out(lat))
     if workspace is None:
         need = load().nf_lattice_measure_workspace(N, lat4, code)
         workspace = torch.empty(int(need), dtype=torch.uint8, device=cfgs.device) if need else None
@@ -2355,7 +2377,7 @@ def lattice_measure_tiled(cfgs, brick_bytes=None, workspace=None, out=None):
         raise NormflowHipError(f"lattice_measure_tiled needs contiguous cfgs (N, *L) with 1 to 4 lattice axes, got "
                                f"{tuple(cfgs.shape)}")
     N, lat4, code, cap = cfgs.shape[0], _lat4(lat), _dtype_code(cfgs), _brick_bytes(brick_bytes)
-    out = _measure_out("lattice_measure_tiled", out, cfgs, 7 + sum(lat) + 4 - len(lat))
+    out = _measure_out("lattice_measure_tiled", out, cfgs, measure_n_out(lat))
     if workspace is None:
         need = load().nf_lattice_measure_tiled_workspace(N, lat4, cap, code)
         workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=cfgs.device)

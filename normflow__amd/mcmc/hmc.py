@@ -21,6 +21,7 @@ import torch
 
 from .. import _hip
 from ..action.scalar_action import ScalarPhi4Action
+from .schedule import Take, schedule
 
 
 class HMCHistory:
@@ -98,69 +99,84 @@ class HMCSampler:
         recorded states or None); the chains, `last` and `history` updated.  cluster_every = E >= 1: the recorded steps
         are run in spans that end before the next step s (counted across calls) with s % E == 0, with one cluster sweep
         of all chains in front of each such step; the span's launches are those of a call of that many steps."""
-        n_chains, E = int(n_chains), int(cluster_every)
-        if E < 0:
-            raise ValueError(f"cluster_every ({cluster_every}) must be >= 0")
-        if n_chains < 1 or batch_size < 1 or batch_size % n_chains != 0:
-            raise ValueError(f"batch_size ({batch_size}) must be a positive multiple of n_chains ({n_chains})")
-        n_md, every = int(n_md), int(n_skip) + 1
-        if n_md < 1 or every < 1:
-            raise ValueError(f"n_md ({n_md}) must be >= 1 and n_skip ({n_skip}) >= 0")
-        s = self._ref['sample']
-        if s is None or s.shape[0] != n_chains:
-            print("Starting from scratch")
-            self.start(n_chains=n_chains)
+        n_chains, n_md, every, E = self._checked(batch_size, n_chains, n_md, n_skip, cluster_every, 'cluster_every')
+        self._restart(n_chains)
         phi, S = self._ref['sample'], self._ref['action']
         path = self._choose(phi, path)
         rows = batch_size // n_chains
         out = torch.empty((rows,) + tuple(phi.shape), dtype=phi.dtype, device=phi.device) if want_rows else None
         stats = _Stats(phi, rows) if want_stats else None
-        if path == 'fused':
-            V, C = phi[0].numel(), phi.shape[0]
-            per = _hip.HMC_MAX_WORK // (max(V, 256) * ((C + 1023) // 1024))      # the MD steps of one launch
-        elif path == 'tiled':
-            need = _hip.load().nf_phi4_hmc_tiled_workspace(phi.shape[0], _hip._lat4(tuple(phi.shape[1:])), _hip._dtype_code(phi))
-            ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=phi.device)      # one workspace for all calls
-            per = _hip.HMC_TILED_MAX_LAUNCHES // (n_md + 2)
+        ws = self._tiled_workspace(phi) if path == 'tiled' else None       # one workspace for all calls
         sweep_ws = None
         if E and self._sweep_path(phi) == 'tiled':                # one workspace for all sweeps of the call
             need = _hip.cluster_tiled_workspace(phi.shape[0], tuple(phi.shape[1:]))
             sweep_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=phi.device)
+        if path != 'composed':
+            phi = phi.clone()                                     # the kernels run in place
         dhs, accs, sweeps, r0 = [], [], [], 0
         while r0 < rows:
-            k = rows - r0
-            if E:
-                if (self._steps + r0) % E == 0:
-                    phi, st = self._sweep(phi, workspace=sweep_ws)
-                    sweeps.append(st)
-                    if path == 'composed':
-                        S = self._model.action(phi.double()).double()
-                k = min(k, E - (self._steps + r0) % E)
-            out_k = None if out is None else out[r0:r0 + k]
-            stats_k = None if stats is None else _StatsSpan(stats, r0)
-            if path == 'fused':
-                if stats is None:
-                    phi, S, dh, acc = self._run_kernel('phi4_hmc', per // n_md, None, phi, k, every, n_md, dt, out_k)
-                else:
-                    phi, S, dh, acc = self._run_fused_measure(per, phi, k, every, n_md, dt, out_k, stats_k)
-            elif path == 'tiled':
-                phi, S, dh, acc = self._run_kernel('phi4_hmc_tiled', per, ws, phi, k, every, n_md, dt, out_k, stats_k)
+            if E and (self._steps + r0) % E == 0:
+                phi, st = self._sweep(phi, workspace=sweep_ws)
+                sweeps.append(st)
+                if path == 'composed':
+                    S = self._model.action(phi.double()).double()
+            k = self._span(self._steps + r0, rows - r0, E)
+            sink = _Span(out, stats, r0)
+            if path == 'composed':
+                phi, S = self._run_composed(phi, S, k, every, n_md, dt, sink, dhs, accs)
             else:
-                phi, S, dh, acc = self._run_composed(phi, S, k, every, n_md, dt, out_k, stats_k)
-            dhs.append(dh); accs.append(acc)
+                S = self._run(path, phi, self._coef(phi.shape[1:]), k, every, n_md, dt, ws, sink, dhs, accs)
             r0 += k
-        dh, acc = (dhs[0], accs[0]) if len(dhs) == 1 else (torch.cat(dhs), torch.cat(accs))
         self._steps += rows
         self._ref.update(sample=phi, action=S)
-        self.last = dict(dh=dh, accept=acc)          # (trajectories, C) of this call, left on the device
+        self._finish(dhs, accs)
         if E:
             self.last['cluster'] = (torch.stack(sweeps) if sweeps else
                                     torch.empty((0, phi.shape[0], 4), dtype=torch.int32, device=phi.device))
-        stats_ = torch.stack([acc.double().mean(), torch.exp(-dh).mean(), dh.square().mean().sqrt()]).cpu()   # the one read
-        for key, val in zip(HMCHistory._KEYS, stats_.tolist()):
-            getattr(self.history, key).append(val)
         y = None if out is None else out.reshape((batch_size,) + tuple(phi.shape[1:]))
         return y, stats
+
+    # ---- what every sampler of this family does around its launches
+    @staticmethod
+    def _checked(batch_size, n_chains, n_md, n_skip, E, name):
+        """(n_chains, n_md, every = n_skip + 1, E) as integers, checked; `name` is the caller's word for E."""
+        n_chains, n_md, every, E = int(n_chains), int(n_md), int(n_skip) + 1, int(E)
+        if n_chains < 1 or batch_size < 1 or batch_size % n_chains != 0:
+            raise ValueError(f"batch_size ({batch_size}) must be a positive multiple of n_chains ({n_chains})")
+        if n_md < 1 or every < 1:
+            raise ValueError(f"n_md ({n_md}) must be >= 1 and n_skip ({n_skip}) >= 0")
+        if E < 0:
+            raise ValueError(f"{name} ({E}) must be >= 0")
+        return n_chains, n_md, every, E
+
+    def _restart(self, n_chains):
+        """Chains from the prior where there are none, or not n_chains of them."""
+        s = self._ref['sample']
+        if s is None or s.shape[0] != n_chains:
+            print("Starting from scratch")
+            self.start(n_chains=n_chains)
+
+    @staticmethod
+    def _span(done, left, E):
+        """The recorded steps of the next span, `done` steps after `start()` with `left` to go: up to the next multiple
+        of E (the cluster sweep falls before a span, the exchange sweep after it); E = 0: all of them."""
+        return min(left, E - done % E) if E else left
+
+    @staticmethod
+    def _tiled_workspace(phi):
+        need = _hip.hmc_tiled_workspace(phi.shape[0], tuple(phi.shape[1:]), phi.dtype)
+        return torch.empty(max(need, 256), dtype=torch.uint8, device=phi.device)
+
+    def _finish(self, dhs, accs, extra=None):
+        """`last` = the call's dH and accept flags (trajectories, C), left on the device, and `history`'s three entries,
+        by the call's ONE device-to-host read; the float64 vector `extra` rides in it and comes back as a list."""
+        dh, acc = (dhs[0], accs[0]) if len(dhs) == 1 else (torch.cat(dhs), torch.cat(accs))
+        self.last = dict(dh=dh, accept=acc)
+        got = torch.stack([acc.double().mean(), torch.exp(-dh).mean(), dh.square().mean().sqrt()])
+        got = (got if extra is None else torch.cat([got, extra])).cpu().tolist()
+        for key, val in zip(HMCHistory._KEYS, got):
+            getattr(self.history, key).append(val)
+        return got[len(HMCHistory._KEYS):]
 
     @torch.no_grad()
     def start(self, phi=None, n_chains=1):
@@ -312,74 +328,24 @@ class HMCSampler:
         return float(w0), float(w2 - own * w0), float(w4)
 
     # ---- fused and tiled
-    def _run_kernel(self, kernel, per, workspace, phi, rows, every, n_md, dt, out, stats=None):
-        """rows * every trajectories by _hip.<kernel> in as few calls as `per`, the trajectories one call may hold under
-        NF_HMC_MAX_WORK (fused) or NF_HMC_TILED_MAX_LAUNCHES (tiled), allows.  With `stats` (tiled only) every recorded
-        step is a call of its own on the chains in place, measured where they lie: no rows unless `out` wants them."""
-        phi = phi.clone()
-        coef = self._coef(phi.shape[1:])
-        per = max(1, per)
-        kw = {} if workspace is None else dict(workspace=workspace)
-        dhs, accs, action = [], [], None
-        if per >= every and stats is None:
-            step, r0 = per // every, 0
-            while r0 < rows:
-                k = min(step, rows - r0)
-                r = getattr(_hip, kernel)(phi, *coef, n_md, dt, n_traj=k * every, record_every=every, **kw)
-                out[r0:r0 + k] = r['record']
-                dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
-                r0 += k
-        else:
-            for r0 in range(rows):
-                left = every
-                while left:
-                    k = min(per, left)
-                    r = getattr(_hip, kernel)(phi, *coef, n_md, dt, n_traj=k, **kw)
-                    dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
-                    left -= k
-                if out is not None:
-                    out[r0] = phi
-                if stats is not None:
-                    stats.put(r0, phi)
-        return phi, action, torch.cat(dhs), torch.cat(accs)
-
-    def _run_fused_measure(self, steps, phi, rows, every, n_md, dt, out, stats):
-        """`_run_kernel` for nf_phi4_hmc_measure: `steps` is the MD steps one launch may hold under NF_HMC_MAX_WORK, of
-        which a recorded step takes every * n_md + NF_HMC_MEASURE_MD_STEPS.  Rows are allocated only for `out`."""
-        phi = phi.clone()
-        coef = self._coef(phi.shape[1:])
-        group = every * n_md + _hip.HMC_MEASURE_MD_STEPS
-        dhs, accs, action = [], [], None
-
-        def keep(r):
-            nonlocal action
-            dhs.append(r['dh']); accs.append(r['accept']); action = r['action']
-
-        def measured(r0, k, n_traj, record_every):
-            r = _hip.phi4_hmc(phi, *coef, n_md, dt, n_traj=n_traj, record_every=record_every, measure=True,
-                              record=out is not None)
-            stats.put_rows(r0, r['measure'])
-            if out is not None:
-                out[r0:r0 + k] = r['record']
-            keep(r)
-        if steps >= group:
-            step, r0 = steps // group, 0
-            while r0 < rows:
-                k = min(step, rows - r0)
-                measured(r0, k, k * every, every)
-                r0 += k
-        else:
-            # one recorded step is more than a launch: unmeasured launches, then a measured one of the last trajectories
-            last = max(1, min(every, (steps - _hip.HMC_MEASURE_MD_STEPS) // n_md))
-            per = max(1, steps // n_md)
-            for r0 in range(rows):
-                left = every - last
-                while left:
-                    k = min(per, left)
-                    keep(_hip.phi4_hmc(phi, *coef, n_md, dt, n_traj=k))
-                    left -= k
-                measured(r0, 1, last, last)
-        return phi, action, torch.cat(dhs), torch.cat(accs)
+    def _run(self, path, phi, couplings, rows, every, n_md, dt, ws, sink, dhs, accs):
+        """`rows` recorded steps of the chains phi, IN PLACE, by the kernel of `path`, in the launches that `schedule`
+        (mcmc/schedule.py) cuts them into under the kernel's work cap (`_hip.hmc_fused_budget`, `_hip.hmc_tiled_budget`).
+        `couplings`: (w0, w2, w4), or the ladder kernels' (coef, rung).  Rows and statistics go to `sink` (a `_Span`), dH
+        and the accept flags of every launch to the lists.  Returns S (C) of the chains."""
+        tiled, ladder = path == 'tiled', len(couplings) == 2
+        kernel = getattr(_hip, 'phi4_hmc' + ('_tiled' if tiled else '') + ('_ladder' if ladder else ''))
+        budget = _hip.hmc_tiled_budget(n_md) if tiled else _hip.hmc_fused_budget(phi[0].numel(), phi.shape[0])
+        for a in schedule(rows, every, n_md, budget, tiled=tiled, ladder=ladder, stats=sink.stats is not None,
+                          want_rows=sink.out is not None, measure_cost=_hip.HMC_MEASURE_MD_STEPS):
+            if isinstance(a, Take):
+                sink.take(a.row, phi, a.copy)
+                continue
+            kw = dict(workspace=ws) if tiled else dict(measure=a.measure, record=a.record)
+            r = kernel(phi, *couplings, n_md, dt, n_traj=a.n_traj, record_every=a.record_every, **kw)
+            dhs.append(r['dh']); accs.append(r['accept'])
+            sink.launch(a.row0, r)
+        return r['action']
 
     # ---- composed
     def _force(self, phi):
@@ -424,17 +390,13 @@ class HMCSampler:
             acc = ok.to(torch.uint8)
         return new, torch.where(ok, S1, S0), dh, acc, pi
 
-    def _run_composed(self, phi, S, rows, every, n_md, dt, out, stats=None):
-        dhs, accs = [], []
+    def _run_composed(self, phi, S, rows, every, n_md, dt, sink, dhs, accs):
         for t in range(rows * every):
             phi, S, dh, acc, _ = self._trajectory_composed(phi, S, n_md, dt)
-            dhs.append(dh); accs.append(acc)
+            dhs.append(dh.unsqueeze(0)); accs.append(acc.unsqueeze(0))
             if (t + 1) % every == 0:
-                if out is not None:
-                    out[(t + 1) // every - 1] = phi
-                if stats is not None:
-                    stats.put((t + 1) // every - 1, phi)
-        return phi, S, torch.stack(dhs), torch.stack(accs)
+                sink.take((t + 1) // every - 1, phi)
+        return phi, S
 
 
 class _Stats:
@@ -450,8 +412,7 @@ class _Stats:
         self.kernel = None
         if self.path != 'composed':
             self.kernel = _hip.lattice_measure if self.path == 'kernel' else _hip.lattice_measure_tiled
-            n_out = 7 + sum(self.lattice) + 4 - len(self.lattice)
-            self.out = torch.empty((rows, phi.shape[0], n_out), dtype=torch.float64, device=phi.device)
+            self.out = torch.empty((rows, phi.shape[0], _hip.measure_n_out(self.lattice)), dtype=torch.float64, device=phi.device)
         else:
             self.parts = [None] * rows
 
@@ -479,14 +440,29 @@ class _Stats:
         return self._ob.Measurement(scalars, links, slices, self.lattice, action)
 
 
-class _StatsSpan:
-    """The steps first .. of a `_Stats`, numbered from 0: what a span of a call writes into."""
+class _Span:
+    """What the recorded steps first .. of a call, numbered from 0, write into: the call's rows `out` and its statistics
+    `stats` (a `_Stats`; the ladder's `_RungStats`), either of them None where not wanted.  `col`: the chains hold rungs,
+    and a row taken from the chains is laid out by the column `col` of every chain."""
 
-    def __init__(self, stats, first):
-        self._stats, self._first = stats, first
+    def __init__(self, out, stats, first, col=None):
+        self.out, self.stats, self._first, self._col = out, stats, first, col
 
-    def put(self, r, phi):
-        self._stats.put(self._first + r, phi)
+    def launch(self, r0, r):
+        """Steps r0 ..: what the launch with the dict r recorded and measured, if it did."""
+        r0 += self._first
+        if r['record'] is not None:
+            self.out[r0:r0 + r['record'].shape[0]] = r['record']
+        if 'measure' in r:
+            self.stats.put_rows(r0, r['measure'])
 
-    def put_rows(self, r0, block):
-        self._stats.put_rows(self._first + r0, block)
+    def take(self, r, phi, copy=True):
+        """Step r from the chains as they lie: its statistics, and the row itself unless a launch recorded it."""
+        r += self._first
+        if copy and self.out is not None:
+            if self._col is None:
+                self.out[r] = phi
+            else:
+                self.out[r].index_copy_(0, self._col, phi)
+        if self.stats is not None:
+            self.stats.put(r, phi)

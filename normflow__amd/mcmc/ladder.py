@@ -14,7 +14,7 @@ import torch
 
 from .. import _hip
 from ..action.scalar_action import ScalarPhi4Action
-from .hmc import HMCSampler, HMCHistory
+from .hmc import HMCSampler, HMCHistory, _Span
 
 
 def exchange_sweep(rows, coef, rung, action, parity, logu):
@@ -183,15 +183,8 @@ class LadderHMCSampler(HMCSampler):
         C = int(K if n_chains is None else n_chains)
         if C < 1 or C % K != 0:
             raise ValueError(f"n_chains ({C}) must be a positive multiple of the K = {K} rungs")
-        if batch_size < 1 or batch_size % C != 0:
-            raise ValueError(f"batch_size ({batch_size}) must be a positive multiple of n_chains ({C})")
-        n_md, every, E = int(n_md), int(n_skip) + 1, int(exchange_every)
-        if n_md < 1 or every < 1 or E < 0:
-            raise ValueError(f"n_md ({n_md}) must be >= 1, n_skip ({n_skip}) >= 0 and exchange_every ({exchange_every}) >= 0")
-        s = self._ref['sample']
-        if s is None or s.shape[0] != C:
-            print("Starting from scratch")
-            self.start(n_chains=C)
+        C, n_md, every, E = self._checked(batch_size, C, n_md, n_skip, exchange_every, 'exchange_every')
+        self._restart(C)
         phi, S, rung = self._ref['sample'].clone(), self._ref['action'], self._ref['rung'].clone()
         path = self._choose(phi, path)
         dev, lat = phi.device, tuple(phi.shape[1:])
@@ -199,25 +192,26 @@ class LadderHMCSampler(HMCSampler):
         coef = self._ladder.coef_table(lat, dev)
         base = (torch.arange(C, device=dev) // K) * K
         out = torch.empty((rows, C) + lat, dtype=phi.dtype, device=dev) if want_rows else None
-        n_out = 7 + sum(lat) + 4 - len(lat)
-        stats = torch.empty((rows, C, n_out), dtype=torch.float64, device=dev) if want_stats else None
-        ws = None
-        if path == 'tiled':
-            need = _hip.load().nf_phi4_hmc_tiled_workspace(C, _hip._lat4(lat), _hip._dtype_code(phi))
-            ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+        stats = _RungStats(rows, C, lat, dev) if want_stats else None
+        ws = self._tiled_workspace(phi) if path == 'tiled' else None
         dhs, accs, swaps, parities = [], [], [], []
         r0 = 0
         while r0 < rows:
-            g = rows - r0 if E == 0 else min(rows - r0, E - self._steps % E)
+            g = self._span(self._steps, rows - r0, E)
             self._ref['rung'] = rung                     # what the composed path's action reads
-            S, chain_rows = self._block(path, phi, S, coef, rung, base, g, every, n_md, dt, ws,
-                                        None if out is None else out[r0:r0 + g], None if stats is None else stats[r0:r0 + g],
-                                        dhs, accs)
+            col = base + rung.long()                     # the rung-ordered column of every chain
+            if stats is not None:
+                stats.col = col
+            sink = _Span(out, stats, r0, col)
+            if path == 'composed':
+                S = self._run_composed(phi, S, g, every, n_md, dt, sink, dhs, accs, col)
+            else:
+                S = self._run(path, phi, (coef, rung), g, every, n_md, dt, ws, sink, dhs, accs)
             r0 += g
             self._steps += g
             if E and self._steps % E == 0 and K > 1:
-                if chain_rows is None:
-                    chain_rows = measure_rows(phi)
+                # the chains' measure rows: the span's last where it measured, else the chains measured where they lie
+                chain_rows = stats.chain_rows if stats is not None else measure_rows(phi)
                 parity = self._sweeps % 2
                 if phi.is_cuda:
                     S = S.contiguous()
@@ -229,89 +223,41 @@ class LadderHMCSampler(HMCSampler):
                 parities.append(parity)
                 self._sweeps += 1
         self._ref.update(sample=phi, action=S, rung=rung)
-        dh, acc = torch.cat(dhs), torch.cat(accs)
         swapped = torch.stack(swaps) if swaps else torch.zeros((0, C // K, K - 1), dtype=torch.uint8, device=dev)
-        self.last = dict(dh=dh, accept=acc, swapped=swapped)
-        # the one read: the three HMC statistics and the accepted swaps per pair
-        got = torch.cat([torch.stack([acc.double().mean(), torch.exp(-dh).mean(), dh.square().mean().sqrt()]),
-                         swapped.double().sum(dim=(0, 1))]).cpu().tolist()
-        for key, val in zip(HMCHistory._KEYS, got[:3]):
-            getattr(self.history, key).append(val)
+        accepted = self._finish(dhs, accs, extra=swapped.double().sum(dim=(0, 1)))    # the accepted swaps per pair
+        self.last['swapped'] = swapped
         tried = [sum(1 for p in parities if p == k % 2) * (C // K) for k in range(K - 1)]
-        self.history.exchange_rate.append([n / t if t else float('nan') for n, t in zip(got[3:], tried)])
+        self.history.exchange_rate.append([n / t if t else float('nan') for n, t in zip(accepted, tried)])
         y = None if out is None else out.reshape((batch_size,) + lat)
-        return y, stats
+        return y, None if stats is None else stats.out
 
-    def _block(self, path, phi, S, coef, rung, base, g, every, n_md, dt, ws, out, stats, dhs, accs):
-        """g recorded steps of the chains phi (in place) under the rungs `rung`, in as few launches as the caps allow; the
-        rung-ordered rows go to out (g, C, *L) and stats (g, C, n_out) where given, dh and accept to the lists.  Returns
-        (S (C) of the chains, the chains' measure rows after the last step where they are at hand, else None)."""
-        C, V = phi.shape[0], phi[0].numel()
-        col = (base + rung.long())                        # the rung-ordered column of every chain
-        chain_rows = None
+    def _run_composed(self, phi, S, rows, every, n_md, dt, sink, dhs, accs, col):
+        """HMCSampler's, with the chains updated in place and dH and the accept flags rung-ordered.  Returns S."""
+        for t in range(rows * every):
+            phi_new, S, dh, acc, _ = self._trajectory_composed(phi, S, n_md, dt)
+            phi.copy_(phi_new)
+            dhs.append(torch.empty_like(dh).index_copy_(0, col, dh).unsqueeze(0))
+            accs.append(torch.empty_like(acc).index_copy_(0, col, acc).unsqueeze(0))
+            if (t + 1) % every == 0:
+                sink.take((t + 1) // every - 1, phi)
+        return S
 
-        def put(dst, r, values):                          # chain-indexed values into the rung-ordered row r
-            dst[r].index_copy_(0, col, values)
 
-        if path == 'composed':
-            for t in range(g * every):
-                phi_new, S, dh, acc, _ = self._trajectory_composed(phi, S, n_md, dt)
-                phi.copy_(phi_new)
-                dhs.append(torch.empty_like(dh).index_copy_(0, col, dh).unsqueeze(0))
-                accs.append(torch.empty_like(acc).index_copy_(0, col, acc).unsqueeze(0))
-                if (t + 1) % every == 0:
-                    r = (t + 1) // every - 1
-                    if out is not None:
-                        put(out, r, phi)
-                    if stats is not None:
-                        chain_rows = measure_rows(phi)
-                        put(stats, r, chain_rows)
-            return S, chain_rows
-        fused = path == 'fused'
-        if fused:
-            steps = _hip.HMC_MAX_WORK // (max(V, 256) * ((C + 1023) // 1024))            # the MD steps of one launch
-            group = every * n_md + (_hip.HMC_MEASURE_MD_STEPS if stats is not None else 0)
-            fit = steps // group
-            per = max(1, steps // n_md)
-        else:
-            per = max(1, _hip.HMC_TILED_MAX_LAUNCHES // (n_md + 2))
-            fit = per // every if stats is None else min(1, per // every)     # measured where they lie: a call per step
-        kw = dict(workspace=ws) if not fused else {}
-        kernel = _hip.phi4_hmc_ladder if fused else _hip.phi4_hmc_tiled_ladder
-        r = None
-        if fit >= 1:
-            r0 = 0
-            while r0 < g:
-                k = min(fit, g - r0)
-                if fused:
-                    kw = dict(measure=stats is not None, record=out is not None)
-                elif out is None:
-                    kw = dict(workspace=ws)
-                r = kernel(phi, coef, rung, n_md, dt, n_traj=k * every,
-                           record_every=every if (fused or out is not None) else None, **kw)
-                dhs.append(r['dh']); accs.append(r['accept'])
-                if out is not None:
-                    out[r0:r0 + k] = r['record']
-                if stats is not None:
-                    if fused:
-                        stats[r0:r0 + k] = r['measure']
-                        chain_rows = r['measure'][-1][col]          # rung-ordered -> by chain
-                    else:
-                        chain_rows = measure_rows(phi)
-                        put(stats, r0, chain_rows)
-                r0 += k
-        else:
-            # one recorded step is more than a launch: unrecorded launches, the step taken from the chains where they lie
-            for r0 in range(g):
-                left = every
-                while left:
-                    k = min(per, left)
-                    r = kernel(phi, coef, rung, n_md, dt, n_traj=k, **({} if fused else dict(workspace=ws)))
-                    dhs.append(r['dh']); accs.append(r['accept'])
-                    left -= k
-                if out is not None:
-                    put(out, r0, phi)
-                if stats is not None:
-                    chain_rows = measure_rows(phi)
-                    put(stats, r0, chain_rows)
-        return r['action'], chain_rows
+class _RungStats:
+    """`hmc._Stats` for the ladder: the rung-ordered measure rows `out` (steps, C, n_out) of a call.  `col` is the column
+    of every chain during the span being written, `chain_rows` the chains' own rows (C, n_out) after the last step
+    written: the exchange sweep decides by them."""
+
+    def __init__(self, rows, C, lat, device):
+        self.out = torch.empty((rows, C, _hip.measure_n_out(lat)), dtype=torch.float64, device=device)
+        self.col = self.chain_rows = None
+
+    def put(self, r, phi):
+        """Step r: the chains as they lie."""
+        self.chain_rows = measure_rows(phi)
+        self.out[r].index_copy_(0, self.col, self.chain_rows)
+
+    def put_rows(self, r0, block):
+        """Steps r0 ..: (k, C, n_out) rows measured inside a launch, rung-ordered as they come."""
+        self.out[r0:r0 + block.shape[0]] = block
+        self.chain_rows = block[-1][self.col]             # rung-ordered -> by chain
