@@ -493,10 +493,44 @@ int nf_conv_first_split16(const void *in, const void *wsplit, const void *bias, 
                           const int32_t *lattice, int act, void *stream);
 int nf_conv_fwd_split16(const void *in16, const void *wsplit, const void *bias, void *out16, int64_t B,
                         const int32_t *lattice, int act, void *stream);
+/* What nf_conv_fwd (fused = 0; compact = 0, 1 or 2 = NF_OUT_SPLIT16) or nf_conv_rqs (fused bit 0 set; bits 1 and 2 as for
+ * nf_conv_weight_layout, knots_len = (cout + 2) / 3) will do with this layer for a batch of B under the current options:
+ * the planner the two entry points execute, pure host code (no device needed, no pointer but the extents looked at).
+ *   path               the code nf_conv_last_path reports after the launch: 0 one box per workgroup, 1 persistent pipelined
+ *                      kernel, 2 single-input-channel kernel, 3 split-fp16 fused kernel
+ *   weight_layout      NF_WLAYOUT_* that kernel reads (what nf_conv_weight_layout returns)
+ *   mt                 16-site tiles per wave: a box holds 4 mt 16 output units (0 for path 3, whose box is fixed)
+ *   two_site, packed   two-site column packing (cout <= 8), K-packed reduction (cin % 4 != 0, cin < 8)
+ *   box, nbox          sites of a box and boxes per axis; a workgroup (or work item of a persistent kernel) is one box of one sample
+ *   plane_stride       elements between the channel planes of the staged box + halo in LDS (0 for path 3)
+ *   channels_per_pass  input channels staged per pass of the reduction loop
+ *   launches           kernel launches (path 0: one per 48 output columns)
+ *   lds_bytes          dynamic LDS of a launch
+ *   partials           log-det partials per sample (fused layers: the workspace must hold B x partials doubles), else 0
+ * Grid sizes are not part of the plan: the persistent kernels size theirs by the device's CU count and occupancy.
+ * Returns what the entry point would: NF_EINVAL with its message for a layer or batch it refuses.  nf_conv_weight_layout is
+ * this plan's weight_layout at B = 1, except that a pair-tensor layer (bit 2) which the split-fp16 kernel does not take is
+ * answered with the layout of the fp32 kernel it would need, not refused.  An added entry point leaves NF_VERSION as it is. */
+typedef struct nf_conv_layer_plan {
+  int32_t path;
+  int32_t weight_layout;
+  int32_t mt;
+  int32_t two_site;
+  int32_t packed;
+  int32_t box[4];
+  int32_t nbox[4];
+  int32_t plane_stride;
+  int32_t channels_per_pass;
+  int32_t launches;
+  int64_t lds_bytes;
+  int64_t partials;
+} nf_conv_layer_plan;
+int nf_conv_plan(const int32_t *lattice, const int32_t *ksize, int cin, int cout, int compact, int fused, int dtype,
+                 int64_t B, nf_conv_layer_plan *out);
 /* Which kernel the calling thread's last nf_conv_fwd / nf_conv_rqs launched: 0 = one box per workgroup
  * (nf_conv.hip), 1 = persistent workgroups with staging overlapped with the MFMAs (nf_conv_pipe.hip;
  * fp32, cin % 4 == 0, kernel extent 3 on the fastest axis), 2 = the single-input-channel kernel of the first
- * ConvAct layer (nf_conv_pipe.hip, conv_c1_kernel).  Same results either way; for tests and benches. */
+ * ConvAct layer (nf_conv_pipe.hip, conv_c1_kernel), 3 = the split-fp16 fused kernel (nf_conv_h.hip).  For tests and benches. */
 int nf_conv_last_path(void);
 
 /* ---- K5+K2 fused: last conv layer of the parameter net + RQ-spline coupling ---------------

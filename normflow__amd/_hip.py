@@ -155,6 +155,7 @@ PROTOTYPES = {
     "nf_conv_first_split16_supported": (_I, [_P, _P, _I, _I]),
     "nf_conv_first_split16": (_I, [_P, _P, _P, _P, _I64, _P, _I, _P]),
     "nf_conv_weight_layout": (_I, [_P, _P, _I, _I, _I, _I, _I]),
+    "nf_conv_plan": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, _I, _I, _I64, _P]),
     "nf_conv_rqs": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I,
                          C.POINTER(RqsOpts), _I, _I, _P, _SZ, _I, _P]),
     "nf_conv_fwd": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, _I, _I,
@@ -1945,6 +1946,31 @@ def hmc_plan(lat, dtype):
     out = _planner_plan("hmc_plan", "nf_phi4_hmc_plan", lat, dtype, HmcPlan())
     return dict(sites_per_lane=out.sites_per_lane, lanes=out.lanes, lds_bytes=out.lds_bytes,
                 lds_bytes_measure=out.lds_bytes_measure)
+
+
+class ConvPlan(C.Structure):
+    """nf_conv_layer_plan (include/normflow_hip.h)."""
+    _fields_ = [("path", C.c_int32), ("weight_layout", C.c_int32), ("mt", C.c_int32), ("two_site", C.c_int32),
+                ("packed", C.c_int32), ("box", C.c_int32 * 4), ("nbox", C.c_int32 * 4), ("plane_stride", C.c_int32),
+                ("channels_per_pass", C.c_int32), ("launches", C.c_int32), ("lds_bytes", C.c_int64),
+                ("partials", C.c_int64)]
+
+
+def conv_plan(lat, ksize, cin, cout, compact=0, fused=0, dtype=torch.float32, B=1):
+    """What nf_conv_fwd (fused = 0; compact 0, 1 or 2 = NF_OUT_SPLIT16) or nf_conv_rqs (fused = 1, | 2 unit input, | 4
+    pair-tensor input: nf_conv_weight_layout's bits) will do with a layer of `cin` -> `cout` channels and kernel extents
+    `ksize` on the lattice `lat` (1 to 4 axes) for a batch of B, under the library's current options: dict(path (the
+    nf_conv_last_path code), weight_layout, mt, two_site, packed, box, nbox, plane_stride, channels_per_pass, launches,
+    lds_bytes, partials (log-det partials per sample)).  A layer the library refuses raises with its message.  Pure host
+    code."""
+    if not 1 <= len(lat) <= 4 or len(ksize) != len(lat):
+        raise NormflowHipError(f"conv_plan: lattices of 1 to 4 axes and one kernel extent per axis, got {tuple(lat)}, {tuple(ksize)}")
+    code = NF_F32 if dtype == torch.float32 else NF_F64 if dtype == torch.float64 else NF_F16
+    lat4, k4 = _lat4(list(lat), list(ksize))
+    out = ConvPlan()
+    _check(load().nf_conv_plan(lat4, k4, int(cin), int(cout), int(compact), int(fused), code, int(B), C.byref(out)),
+           "nf_conv_plan")
+    return {name: (list(getattr(out, name)) if name in ("box", "nbox") else getattr(out, name)) for name, _ in ConvPlan._fields_}
 
 
 def hmc_supported(lat, dtype):

@@ -19,6 +19,25 @@ void set_error(const char *fmt, ...) {
   va_end(ap);
 }
 
+int cu_count() {
+  constexpr int kMaxDev = 64;
+  static int ncu[kMaxDev] = {};      // 0 = not asked yet; every thread that races here writes the same value
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return 0;
+  if (!ncu[dev]) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    ncu[dev] = n;
+  }
+  return ncu[dev];
+}
+
+int64_t persistent_grid(int blocks_per_cu, int64_t n_items, bool round_to_8) {
+  int64_t grid = int64_t(blocks_per_cu) * cu_count();
+  if (grid > n_items) grid = n_items;
+  return round_to_8 ? (grid + 7) & ~int64_t(7) : grid;
+}
+
 int check_launch(const char *what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

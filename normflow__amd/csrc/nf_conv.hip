@@ -450,29 +450,46 @@ extern "C" int nf_conv_packed_steps(int cin, int ntaps) {
 extern "C" int nf_conv_ntiles(int cout) { return (cout + 15) >> 4; }
 
 static thread_local int g_last_path = 0;
-static thread_local int *g_dry_layout = nullptr;     // non-null: plan only (nf_conv_weight_layout)
 extern "C" int nf_conv_last_path(void) { return g_last_path; }
 
-struct FuseInfo {           // non-null => the coupling epilogue replaces the store
-  int flags;                 // NF_CONV_UNIT_INPUT: |input| <= 1 guaranteed -> the split-fp16 kernel (nf_conv_h.hip) may run
-  int mode;                 // 1 forward, 2 inverse
-  const float *xact;
-  float *yout;
-  double *partial;
-  size_t partial_bytes;
-  RqsParams P;
-  int64_t *blocks_out;
-};
+namespace nf {
+int conv_launch_error(const char *who, const char *kernel, bool too_many) {
+  if (too_many) {
+    set_error("%s: batch x boxes >= 2^31 work items, split the batch", who);
+    return NF_EINVAL;
+  }
+  set_error("%s: could not launch the %s", who, kernel);
+  return NF_ELAUNCH;
+}
+}  // namespace nf
 
-template <typename T>
-static int run_conv_t(const void *in, const void *wfrag, const void *bias, void *out, int64_t B,
-                      const int32_t *lattice, const int32_t *ksize, int cin, int cout, int act, int compact,
-                      int active_parity, hipStream_t stream, const FuseInfo *fz) {
-  NF_REQUIRE(in && wfrag && (out || fz) && lattice && ksize, "nf_conv_fwd: NULL pointer");
+// bytes of an element, or 0 (with the message) for a dtype the layer has no kernel for
+static size_t conv_esize(int dtype, bool fused) {
+  if (dtype == NF_F32) return 4;
+  if (dtype == NF_F64 && !fused) return 8;
+  set_error("nf_conv: unsupported dtype %d (fp32 and fp64; the fused coupling epilogue is fp32 only)", dtype);
+  return 0;
+}
+
+// nf_conv_weight_layout's question: a pair-tensor layer that the split-fp16 kernel does not take is not refused but planned
+// on the fp32 kernels, whose weight layout is then the answer (private to this file, next to the NF_CONV_* flags)
+constexpr int kFlagLayoutQuery = 1 << 30;
+
+// Every check and every decision of nf_conv_fwd (fuse = 0) and nf_conv_rqs (fuse = 1 forward, 2 inverse; flags: NF_CONV_*; m:
+// knots_len) for a batch of B: pure, no pointer but the two extents arrays is looked at and no HIP call is made.  A batch the
+// chosen kernel cannot index is not an error here (p.too_many): the launcher reports it after the workspace check, as ever.
+// p.launches = 0: nothing to do.
+static int plan_conv(ConvPlan &p, const int32_t *lattice, const int32_t *ksize, int cin, int cout, int act, int compact,
+                     int active_parity, int dtype, int64_t B, int fuse, int flags, int m) {
+  p = ConvPlan{};
+  const size_t esize = conv_esize(dtype, fuse != 0);
+  if (!esize) return NF_EINVAL;
+  const bool f32 = esize == 4;
+  NF_REQUIRE(lattice && ksize, "nf_conv_fwd: NULL pointer");
   NF_REQUIRE(B >= 0 && B <= 65535, "nf_conv_fwd: batch %lld outside [0, 65535]", (long long)B);
   NF_REQUIRE(cin >= 1 && cout >= 1, "nf_conv_fwd: bad channel counts");
   NF_REQUIRE(act >= kActNone && act <= kActSigmoid, "nf_conv_fwd: unknown activation code %d", act);
-  ConvArgs A{};
+  ConvArgs &A = p.A;
   int64_t V = 1;
   for (int mu = 0; mu < 4; ++mu) {
     NF_REQUIRE(lattice[mu] >= 1 && ksize[mu] >= 1 && (ksize[mu] & 1), "nf_conv_fwd: lattice dims >= 1 and odd kernel sizes needed");
@@ -484,21 +501,16 @@ static int run_conv_t(const void *in, const void *wfrag, const void *bias, void 
   if (out_split16) compact = 0;
   if (compact) NF_REQUIRE(A.L[3] % 2 == 0, "nf_conv_fwd: pair-compact output needs an even fastest axis");
   if (B == 0 || V == 0) return NF_OK;
-  A.in = in;
-  A.wfrag = wfrag;
-  A.bias = bias;
-  A.out = out;
   A.V = V;
   A.cin = cin; A.cin_pad = (cin + 3) & ~3; A.cout = cout; A.kq = A.cin_pad / 4;
   A.kq_total = A.kq; A.cchunk = A.cin_pad;
-  A.sh2 = (!fz && nf_conv_two_site(cout, compact, A.L[3], A.k[3])) ? 1 : 0;
+  A.sh2 = (!fuse && nf_conv_two_site(cout, compact, A.L[3], A.k[3])) ? 1 : 0;
   A.kt3 = A.k[3] + A.sh2;
-  if (A.sh2) A.nt_total = 1;
   A.nt_total = (cout + 15) >> 4;
   A.act = act; A.compact = compact ? 1 : 0; A.parity = active_parity & 1;
   A.out_split16 = out_split16;
   if (out_split16)
-    NF_REQUIRE(sizeof(T) == 4 && cout == 8 && A.sh2 && A.L[3] % 4 == 0 && !fz,
+    NF_REQUIRE(f32 && cout == 8 && A.sh2 && A.L[3] % 4 == 0 && !fuse,
                "nf_conv_fwd: split-fp16 output needs fp32, 8 output channels and a fastest axis that is a multiple of 4");
   A.packed = (cin % 4) != 0 && cin < 8;   // larger odd channel counts: zero-pad to a multiple of 4 and chunk
   if (A.packed) {
@@ -521,7 +533,7 @@ static int run_conv_t(const void *in, const void *wfrag, const void *bias, void 
   static const int mt_first = NF_DIAG_ENV_INT("NF_CONV_MT", 4);
   // layers the persistent kernel (nf_conv_pipe.hip) can take are planned with its MT = 2 boxes straight away
   const int pipe_off = !option(NF_OPT_PIPE);
-  const bool pipe_candidate = sizeof(T) == 4 && !pipe_off && !A.packed && A.k[3] == 3 &&
+  const bool pipe_candidate = f32 && !pipe_off && !A.packed && A.k[3] == 3 &&
                               A.k[0] * A.k[1] * A.k[2] >= 2 && A.nt_total <= 3 && !NF_DBG(A, 15);   // (dbg bits >= 16 are timing ablations inside the persistent kernels)
   int MT = (mt_first == 2 || pipe_candidate) ? 2 : 4;
   int box[4];
@@ -557,7 +569,7 @@ static int run_conv_t(const void *in, const void *wfrag, const void *bias, void 
     for (int mu = 0; mu < 4; ++mu) hv *= box[mu] + A.k[mu] - 1;
     static const int cplan_max = NF_DIAG_ENV_INT("NF_CONV_CPLAN", 8);
     const int cplan = A.packed ? cin : (A.cin_pad < cplan_max ? A.cin_pad : cplan_max);   // channels planned per K pass
-    if (MT == 2 || hv * cplan * int64_t(sizeof(T)) <= int64_t(lds_cap_kb) * 1024) break;
+    if (MT == 2 || hv * cplan * int64_t(esize) <= int64_t(lds_cap_kb) * 1024) break;
     MT = 2;
   }
   int64_t nblocks = 1;
@@ -579,19 +591,19 @@ static int run_conv_t(const void *in, const void *wfrag, const void *bias, void 
   for (int mu = 0; mu < 3; ++mu) rows *= A.hal[mu];
   NF_REQUIRE(V < (int64_t(1) << 31), "nf_conv_fwd: lattice volume must be < 2^31");
   if (!A.packed) {   // channels per K pass: as many as fit ~78 KiB (at least 4), in steps the pipelined loop knows
-    const int fit = int((int64_t(lds_cap_kb) * 1024) / (int64_t(S) * sizeof(T)));
+    const int fit = int((int64_t(lds_cap_kb) * 1024) / (int64_t(S) * esize));
     int cc = A.cin_pad;
     if (cc > fit) cc = fit >= 16 ? 16 : (fit >= 8 ? 8 : 4);
     A.cchunk = cc;
   }
-  size_t lds = size_t(A.cchunk) * S * sizeof(T) + size_t(rows) * 2 * sizeof(int) +
+  size_t lds = size_t(A.cchunk) * S * esize + size_t(rows) * 2 * sizeof(int) +
                      (A.packed ? size_t(4) * A.ns * sizeof(int) + 16 : 0);
-  if (fz) {
+  if (fuse) {
     const size_t stage = size_t(48) * ((kBlock / kWave) * MT * 16 + 4) * sizeof(float);
     if (lds < stage) lds = stage;
   }
   if (A.sh2) {       // the two-site epilogue transposes the box through LDS: 8 channels x (sites of the box + 8)
-    const size_t stage = size_t(8) * (2 * (kBlock / kWave) * MT * 16 + 8) * sizeof(T);
+    const size_t stage = size_t(8) * (2 * (kBlock / kWave) * MT * 16 + 8) * esize;
     if (lds < stage) lds = stage;
   }
   {
@@ -601,147 +613,177 @@ static int run_conv_t(const void *in, const void *wfrag, const void *bias, void 
   NF_REQUIRE(lds <= 160 * 1024, "nf_conv_fwd: input box needs %zu B of LDS (> 160 KiB): cin=%d, kernel %dx%dx%dx%d",
              lds, cin, A.k[0], A.k[1], A.k[2], A.k[3]);
   NF_REQUIRE(nblocks <= 0x7fffffff, "nf_conv_fwd: lattice too large");
-  const dim3 grid = dim3(static_cast<unsigned>(nblocks), static_cast<unsigned>(B), 1u);
-  int fuse = 0;
-  if (fz) {
-    fuse = fz->mode;
-    A.xact = fz->xact; A.yout = fz->yout; A.partial = fz->partial; A.P = fz->P;
-    A.field16 = (fz->flags & NF_CONV_FIELD_F16) ? 1 : 0;
+  if (fuse) {
+    A.P.m = m;
+    A.field16 = (flags & NF_CONV_FIELD_F16) ? 1 : 0;
     NF_REQUIRE(A.nt_total <= 3, "nf_conv_rqs: at most 48 logit channels can be fused");
   }
-  g_last_path = 0;
+  p.MT = MT; p.fuse = fuse; p.lds = lds; p.nblocks = nblocks; p.launches = 1;
+  p.partials = fuse ? nblocks : 0;
+  auto taken = [&](int path, int layout, PlanVerdict v) {
+    p.path = path; p.layout = layout; p.too_many = v == kPlanTooManyItems;
+    return NF_OK;
+  };
   // the split-fp16 fused kernel (nf_conv_h.hip) first: it has its own box (2 x 2 x 2 rows x a 32-site segment), hence its own
   // number of log-det partials per sample
-  if (fz && (fz->flags & NF_CONV_UNIT_INPUT)) {
-    if constexpr (sizeof(T) == 4) {
-      if (fz->flags & NF_CONV_SPLIT16_INPUT) A.in_split16 = 1;
-      int64_t nbh = 0;
-      if (conv_h_eligible(A, fuse, &nbh)) {
-        if (g_dry_layout) { *g_dry_layout = NF_WLAYOUT_SPLIT16; return NF_OK; }
-        const size_t need = size_t(B) * size_t(nbh) * sizeof(double);
-        if (fz->partial == nullptr || fz->partial_bytes < need) {
-          set_error("nf_conv_rqs: workspace %zu B < %zu B needed", fz->partial_bytes, need);
-          return NF_EWORKSPACE;
-        }
-        *fz->blocks_out = nbh;
-        const int pr = launch_conv_h(A, B, fuse, stream, false);
-        if (pr == -2) { set_error("nf_conv_rqs: batch x boxes >= 2^31 work items, split the batch"); return NF_EINVAL; }
-        if (pr != 1) { set_error("nf_conv_rqs: could not launch the split-fp16 kernel"); return NF_ELAUNCH; }
-        g_last_path = 3;
-        return check_launch("conv split-fp16 kernel");
-      }
+  if (fuse && f32 && (flags & NF_CONV_UNIT_INPUT)) {
+    if (flags & NF_CONV_SPLIT16_INPUT) A.in_split16 = 1;
+    const PlanVerdict v = plan_h(A, fuse, B, &p.lds);
+    if (v != kPlanNotMine) {
+      p.MT = 0;
+      p.partials = p.nblocks = A.nboxes;
+      return taken(kPathH, NF_WLAYOUT_SPLIT16, v);
     }
   }
-  if (fz && (fz->flags & NF_CONV_SPLIT16_INPUT) && !g_dry_layout) {
+  if (fuse && (flags & NF_CONV_SPLIT16_INPUT) && !(flags & kFlagLayoutQuery)) {
     set_error("nf_conv_rqs: split-fp16 input but the layer is not eligible for the split-fp16 kernel");
     return NF_EINVAL;
   }
-  if (fz) {
-    const size_t need = size_t(B) * size_t(nblocks) * sizeof(double);
-    if (fz->partial == nullptr || fz->partial_bytes < need) {
-      set_error("nf_conv_rqs: workspace %zu B < %zu B needed", fz->partial_bytes, need);
-      return NF_EWORKSPACE;
-    }
-    *fz->blocks_out = nblocks;
+  if (f32 && cin == 1 && A.sh2 && !fuse) {     // first ConvAct layer: data-movement kernel (nf_conv_pipe.hip, K5c)
+    const PlanVerdict v = plan_c1(A, MT, B, nblocks, &p.lds);
+    if (v != kPlanNotMine) return taken(kPathC1, NF_WLAYOUT_FRAGMENT, v);
   }
-  if (g_dry_layout) {                  // nf_conv_weight_layout: report which kernel (hence weight layout) this layer gets
-    int pr = 0;
-    if constexpr (sizeof(T) == 4) {
-      if (MT == 2) { A.nt0 = 0; pr = launch_conv_pipe(A, B, nblocks, fuse, stream, true); }
-    }
-    *g_dry_layout = pr == 1 ? 1 : 0;
-    return NF_OK;
+  if (f32) {     // persistent, staging-overlapped variant (nf_conv_pipe.hip) when the layer is eligible
+    const PlanVerdict v = plan_pipe(A, MT, B, nblocks, fuse, &p.lds);
+    if (v != kPlanNotMine) return taken(kPathPipe, NF_WLAYOUT_ROWPACK, v);
   }
-  if constexpr (sizeof(T) == 4) {
-    if (cin == 1 && A.sh2 && !fz) {     // first ConvAct layer: data-movement kernel (nf_conv_pipe.hip, K5c)
-      const int pr = launch_conv_c1(A, MT, B, nblocks, stream);
-      if (pr == -2) { set_error("nf_conv_fwd: batch x boxes >= 2^31 work items, split the batch"); return NF_EINVAL; }
-      if (pr < 0) { set_error("nf_conv_fwd: could not launch the single-channel kernel"); return NF_ELAUNCH; }
-      if (pr == 1) { g_last_path = 2; return check_launch("conv c1 kernel"); }
-    }
-  }
-  if constexpr (sizeof(T) == 4) {
-    if (MT == 2) {     // persistent, staging-overlapped variant (nf_conv_pipe.hip) when the layer is eligible
-      A.nt0 = 0;
-      const int pr = launch_conv_pipe(A, B, nblocks, fuse, stream, false);
-      if (pr == -2) { set_error("nf_conv_fwd: batch x boxes >= 2^31 work items, split the batch"); return NF_EINVAL; }
-      if (pr < 0) { set_error("nf_conv_fwd: could not launch the pipelined kernel"); return NF_ELAUNCH; }
-      if (pr == 1) { g_last_path = 1; return check_launch("conv pipe kernel"); }
-    }
-  }
+  p.launches = (A.nt_total + 2) / 3;
+  return taken(kPathBox, NF_WLAYOUT_FRAGMENT, kPlanTaken);
+}
+
+#ifdef NF_DIAG
+// DIAGNOSTIC ONLY (NF_CONV_STAMPS): the one-box kernel's clock stamps.  Allocates and synchronises.
+static unsigned long long *stamps_alloc() {
   static const int want_stamps = NF_DIAG_ENV_INT("NF_CONV_STAMPS", 0);
   unsigned long long *d_stamps = nullptr;
-  if (want_stamps) {      // DIAGNOSTIC ONLY: allocates and synchronises, never enabled in product use
+  if (want_stamps) {
     (void)hipMalloc(&d_stamps, 4096 * 8 * sizeof(unsigned long long));
     (void)hipMemset(d_stamps, 0, 4096 * 8 * sizeof(unsigned long long));
-    A.stamps = d_stamps;
   }
+  return d_stamps;
+}
+
+static void stamps_report(const ConvPlan &p, unsigned long long *d_stamps, hipStream_t stream) {
+  const ConvArgs &A = p.A;
+  (void)hipStreamSynchronize(stream);
+  static unsigned long long h[4096 * 8];
+  (void)hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost);
+  (void)hipFree(d_stamps);
+  double seg[6] = {0, 0, 0, 0, 0, 0};
+  int n = 0;
+  for (int i = 1024; i < 4096; ++i) {     // skip the first dispatch round
+    const unsigned long long *t = h + i * 8;
+    if (!t[0] || !t[5]) continue;
+    ++n;
+    seg[0] += double(t[1] - t[0]); seg[1] += double(t[2] - t[1]);
+    seg[2] += t[3] ? double(t[3] - t[2]) : double(t[5] - t[2]);
+    seg[3] += t[3] ? double(t[4] - t[3]) : 0.0;
+    seg[4] += t[3] ? double(t[5] - t[4]) : 0.0;
+    seg[5] += t[6] ? double(t[6] - t[5]) : 0.0;
+  }
+  {
+    // mean number of co-resident workgroups per CU (per-CU windows: clock counters differ between XCDs)
+    static double busy[16 * 256];
+    static unsigned long long lo[16 * 256], hi[16 * 256];
+    for (int k = 0; k < 16 * 256; ++k) { busy[k] = 0; lo[k] = ~0ull; hi[k] = 0; }
+    for (int i = 0; i < 4096; ++i) {
+      const unsigned long long *t = h + i * 8;
+      const unsigned long long end = t[6] ? t[6] : t[5];
+      if (!t[0] || !end) continue;
+      const int key = int(((t[7] >> 16) & 0xf) * 256 + (t[7] & 0xff));
+      busy[key] += double(end - t[0]);
+      if (t[0] < lo[key]) lo[key] = t[0];
+      if (end > hi[key]) hi[key] = end;
+    }
+    double conc = 0; int cus = 0;
+    for (int k = 0; k < 16 * 256; ++k)
+      if (hi[k] > lo[k]) { conc += busy[k] / double(hi[k] - lo[k]); ++cus; }
+    if (cus) fprintf(stderr, "[nf_conv stamps] %d CUs seen, mean co-resident workgroups per CU (first 4096 workgroups) %.2f\n", cus, conc / cus);
+  }
+  if (n) fprintf(stderr, "[nf_conv stamps] cin=%d cout=%d compact=%d fuse=%d blocks=%d | cycles: prologue %.0f  stage0 %.0f  mma0 %.0f  stage1 %.0f  mma1 %.0f  epilogue %.0f\n",
+                 A.cin, A.cout, A.compact, p.fuse, n, seg[0] / n, seg[1] / n, seg[2] / n, seg[3] / n, seg[4] / n, seg[5] / n);
+}
+#endif
+
+// the one-box kernel: one launch per 3 column tiles
+template <typename T>
+static int launch_conv_box(ConvPlan &p, int64_t B, hipStream_t stream) {
+  ConvArgs &A = p.A;
+  const dim3 grid = dim3(static_cast<unsigned>(p.nblocks), static_cast<unsigned>(B), 1u);
+#ifdef NF_DIAG
+  A.stamps = stamps_alloc();
+#endif
   for (int nt0 = 0; nt0 < A.nt_total; nt0 += 3) {
     A.nt0 = nt0;
     const int n = A.nt_total - nt0 >= 3 ? 3 : A.nt_total - nt0;
-    if (MT == 4) {
-      if (n == 3) launch<T, 4, 3>(A, grid, lds, fuse, stream);
-      else if (n == 2) launch<T, 4, 2>(A, grid, lds, fuse, stream);
-      else launch<T, 4, 1>(A, grid, lds, fuse, stream);
+    if (p.MT == 4) {
+      if (n == 3) launch<T, 4, 3>(A, grid, p.lds, p.fuse, stream);
+      else if (n == 2) launch<T, 4, 2>(A, grid, p.lds, p.fuse, stream);
+      else launch<T, 4, 1>(A, grid, p.lds, p.fuse, stream);
     } else {
-      if (n == 3) launch<T, 2, 3>(A, grid, lds, fuse, stream);
-      else if (n == 2) launch<T, 2, 2>(A, grid, lds, fuse, stream);
-      else launch<T, 2, 1>(A, grid, lds, fuse, stream);
+      if (n == 3) launch<T, 2, 3>(A, grid, p.lds, p.fuse, stream);
+      else if (n == 2) launch<T, 2, 2>(A, grid, p.lds, p.fuse, stream);
+      else launch<T, 2, 1>(A, grid, p.lds, p.fuse, stream);
     }
     const int rc = check_launch("conv kernel");
     if (rc) return rc;
   }
-  if (want_stamps) {
-    (void)hipStreamSynchronize(stream);
-    static unsigned long long h[4096 * 8];
-    (void)hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipFree(d_stamps);
-    double seg[6] = {0, 0, 0, 0, 0, 0};
-    int n = 0;
-    for (int i = 1024; i < 4096; ++i) {     // skip the first dispatch round
-      const unsigned long long *t = h + i * 8;
-      if (!t[0] || !t[5]) continue;
-      ++n;
-      seg[0] += double(t[1] - t[0]); seg[1] += double(t[2] - t[1]);
-      seg[2] += t[3] ? double(t[3] - t[2]) : double(t[5] - t[2]);
-      seg[3] += t[3] ? double(t[4] - t[3]) : 0.0;
-      seg[4] += t[3] ? double(t[5] - t[4]) : 0.0;
-      seg[5] += t[6] ? double(t[6] - t[5]) : 0.0;
-    }
-    {
-      // mean number of co-resident workgroups per CU (per-CU windows: clock counters differ between XCDs)
-      static double busy[16 * 256];
-      static unsigned long long lo[16 * 256], hi[16 * 256];
-      for (int k = 0; k < 16 * 256; ++k) { busy[k] = 0; lo[k] = ~0ull; hi[k] = 0; }
-      for (int i = 0; i < 4096; ++i) {
-        const unsigned long long *t = h + i * 8;
-        const unsigned long long end = t[6] ? t[6] : t[5];
-        if (!t[0] || !end) continue;
-        const int key = int(((t[7] >> 16) & 0xf) * 256 + (t[7] & 0xff));
-        busy[key] += double(end - t[0]);
-        if (t[0] < lo[key]) lo[key] = t[0];
-        if (end > hi[key]) hi[key] = end;
-      }
-      double conc = 0; int cus = 0;
-      for (int k = 0; k < 16 * 256; ++k)
-        if (hi[k] > lo[k]) { conc += busy[k] / double(hi[k] - lo[k]); ++cus; }
-      if (cus) fprintf(stderr, "[nf_conv stamps] %d CUs seen, mean co-resident workgroups per CU (first 4096 workgroups) %.2f\n", cus, conc / cus);
-    }
-    if (n) fprintf(stderr, "[nf_conv stamps] cin=%d cout=%d compact=%d fuse=%d blocks=%d | cycles: prologue %.0f  stage0 %.0f  mma0 %.0f  stage1 %.0f  mma1 %.0f  epilogue %.0f\n",
-                   cin, cout, compact, fuse, n, seg[0] / n, seg[1] / n, seg[2] / n, seg[3] / n, seg[4] / n, seg[5] / n);
-  }
+#ifdef NF_DIAG
+  if (A.stamps) stamps_report(p, A.stamps, stream);
+#endif
   return NF_OK;
 }
 
+struct FuseInfo {           // non-null => the coupling epilogue replaces the store
+  int flags;                 // NF_CONV_UNIT_INPUT: |input| <= 1 guaranteed -> the split-fp16 kernel (nf_conv_h.hip) may run
+  int mode;                 // 1 forward, 2 inverse
+  const float *xact;
+  float *yout;
+  double *partial;
+  size_t partial_bytes;
+  RqsParams P;
+  int64_t *blocks_out;
+};
+
+// plan, check the workspace against the plan's partials, launch by the plan's path, check the launch
 static int run_conv(const void *in, const void *wfrag, const void *bias, void *out, int64_t B,
                     const int32_t *lattice, const int32_t *ksize, int cin, int cout, int act, int compact,
                     int active_parity, int dtype, hipStream_t stream, const FuseInfo *fz) {
-  if (dtype == NF_F32)
-    return run_conv_t<float>(in, wfrag, bias, out, B, lattice, ksize, cin, cout, act, compact, active_parity, stream, fz);
-  if (dtype == NF_F64 && fz == nullptr)
-    return run_conv_t<double>(in, wfrag, bias, out, B, lattice, ksize, cin, cout, act, compact, active_parity, stream, fz);
-  set_error("nf_conv: unsupported dtype %d (fp32 and fp64; the fused coupling epilogue is fp32 only)", dtype);
-  return NF_EINVAL;
+  if (!conv_esize(dtype, fz != nullptr)) return NF_EINVAL;
+  NF_REQUIRE(in && wfrag && (out || fz) && lattice && ksize, "nf_conv_fwd: NULL pointer");
+  ConvPlan p;
+  const int rc = plan_conv(p, lattice, ksize, cin, cout, act, compact, active_parity, dtype, B, fz ? fz->mode : 0,
+                           fz ? fz->flags : 0, fz ? fz->P.m : 0);
+  if (rc || !p.launches) return rc;
+  g_last_path = 0;
+  ConvArgs &A = p.A;
+  A.in = in; A.wfrag = wfrag; A.bias = bias; A.out = out;
+  if (fz) {
+    const size_t need = size_t(B) * size_t(p.partials) * sizeof(double);
+    if (fz->partial == nullptr || fz->partial_bytes < need) {
+      set_error("nf_conv_rqs: workspace %zu B < %zu B needed", fz->partial_bytes, need);
+      return NF_EWORKSPACE;
+    }
+    *fz->blocks_out = p.partials;
+    A.xact = fz->xact; A.yout = fz->yout; A.partial = fz->partial; A.P = fz->P;
+  }
+  const char *who = p.path == kPathH ? "nf_conv_rqs" : "nf_conv_fwd";
+  if (p.too_many) return conv_launch_error(who, "", true);
+  int launched;
+  const char *kernel, *what;
+  switch (p.path) {
+    case kPathH:
+      kernel = "split-fp16 kernel"; what = "conv split-fp16 kernel"; launched = launch_conv_h(A, p.fuse, stream); break;
+    case kPathC1:
+      kernel = "single-channel kernel"; what = "conv c1 kernel"; launched = launch_conv_c1(A, p.MT, p.lds, stream); break;
+    case kPathPipe:
+      kernel = "pipelined kernel"; what = "conv pipe kernel"; launched = launch_conv_pipe(A, p.fuse, p.lds, stream); break;
+    default:
+      return dtype == NF_F32 ? launch_conv_box<float>(p, B, stream) : launch_conv_box<double>(p, B, stream);
+  }
+  if (launched != 1) return conv_launch_error(who, kernel, false);
+  g_last_path = p.path;
+  return check_launch(what);
 }
 
 extern "C" int nf_conv_fwd(const void *in, const void *wfrag, const void *bias, void *out, int64_t B,
@@ -751,24 +793,39 @@ extern "C" int nf_conv_fwd(const void *in, const void *wfrag, const void *bias, 
                   static_cast<hipStream_t>(stream), nullptr);
 }
 
+// fused: bit 0 the layer is nf_conv_rqs's, bit 1 NF_CONV_UNIT_INPUT, bit 2 NF_CONV_SPLIT16_INPUT (include/normflow_hip.h)
+static int plan_for_query(ConvPlan &p, const int32_t *lattice, const int32_t *ksize, int cin, int cout, int compact,
+                          int fused, int dtype, int64_t B, int more_flags) {
+  const int flags = ((fused & 2) ? NF_CONV_UNIT_INPUT : 0) | ((fused & 4) ? NF_CONV_SPLIT16_INPUT : 0) | more_flags;
+  return plan_conv(p, lattice, ksize, cin, cout, 0, fused ? 1 : compact, 0, dtype, B, fused ? 1 : 0, flags,
+                   (cout + 2) / 3);                         // knots_len of the fused spline
+}
+
+extern "C" int nf_conv_plan(const int32_t *lattice, const int32_t *ksize, int cin, int cout, int compact, int fused,
+                            int dtype, int64_t B, nf_conv_layer_plan *out) {
+  NF_REQUIRE(out != nullptr, "nf_conv_plan: out is NULL");
+  ConvPlan p;
+  const int rc = plan_for_query(p, lattice, ksize, cin, cout, compact, fused, dtype, B, 0);
+  if (rc) return rc;
+  if (p.too_many) return conv_launch_error(p.path == kPathH ? "nf_conv_rqs" : "nf_conv_fwd", "", true);
+  const ConvArgs &A = p.A;
+  const bool h = p.path == kPathH;      // a box of its own, 8 channels in one pass
+  *out = nf_conv_layer_plan{};
+  out->path = p.path; out->weight_layout = p.layout; out->mt = p.MT;
+  out->two_site = A.sh2; out->packed = A.packed;
+  for (int mu = 0; mu < 4; ++mu) { out->box[mu] = A.box[mu]; out->nbox[mu] = A.nbox[mu]; }
+  out->plane_stride = h ? 0 : A.S;
+  out->channels_per_pass = h ? 8 : A.cchunk;
+  out->launches = p.launches;
+  out->lds_bytes = int64_t(p.lds);
+  out->partials = p.partials;
+  return NF_OK;
+}
+
 extern "C" int nf_conv_weight_layout(const int32_t *lattice, const int32_t *ksize, int cin, int cout, int compact,
                                      int fused, int dtype) {
-  if (!lattice || !ksize) return -1;
-  int layout = 0;
-  int64_t blocks = 0;
-  FuseInfo fz{};
-  fz.mode = 1;
-  fz.flags = ((fused & 2) ? NF_CONV_UNIT_INPUT : 0) | ((fused & 4) ? NF_CONV_SPLIT16_INPUT : 0);
-  fz.P.m = (cout + 2) / 3;                                  // knots_len of the fused spline (planning only)
-  fz.partial = reinterpret_cast<double *>(uintptr_t(8));
-  fz.partial_bytes = ~size_t(0);
-  fz.blocks_out = &blocks;
-  void *dummy = reinterpret_cast<void *>(uintptr_t(8));   // never dereferenced: planning only
-  g_dry_layout = &layout;
-  const int rc = run_conv(dummy, dummy, nullptr, dummy, 1, lattice, ksize, cin, cout, 0, fused ? 1 : compact, 0, dtype,
-                          nullptr, fused ? &fz : nullptr);
-  g_dry_layout = nullptr;
-  return rc ? -1 : layout;
+  ConvPlan p;
+  return plan_for_query(p, lattice, ksize, cin, cout, compact, fused, dtype, 1, kFlagLayoutQuery) ? -1 : p.layout;
 }
 
 extern "C" int nf_conv_rqs_supported(int cout, int m) {
@@ -779,10 +836,7 @@ extern "C" int nf_conv_rqs_supported(int cout, int m) {
 // 32 + 16 n sites, 3^4 kernel, 8 hidden channels): a host-side planning query, no launch.
 extern "C" int nf_conv_rqs_split16_supported(const int32_t *lattice, int cout, int m) {
   if (!lattice || m < 2 || m > 16 || cout != 3 * m - 2 || !option(NF_OPT_SPLIT16)) return 0;
-  if (lattice[3] < 32 || (lattice[3] & 15)) return 0;
-  for (int mu = 0; mu < 3; ++mu)
-    if (lattice[mu] < 2 || (lattice[mu] & 1)) return 0;
-  return 1;
+  return split16_lattice_ok(lattice) ? 1 : 0;
 }
 
 extern "C" int nf_conv_rqs(const void *in, const void *wfrag, const void *bias, const void *x_active,
@@ -808,9 +862,7 @@ extern "C" int nf_conv_rqs(const void *in, const void *wfrag, const void *bias, 
   fz.yout = static_cast<float *>(y);
   fz.partial = static_cast<double *>(workspace);
   fz.partial_bytes = workspace_bytes;
-  fz.P.xlo = opts->xlo; fz.P.xhi = opts->xhi; fz.P.ylo = opts->ylo; fz.P.yhi = opts->yhi;
-  fz.P.fx = nullptr; fz.P.fy = nullptr;
-  fz.P.m = opts->m; fz.P.el = opts->extrap_left; fz.P.er = opts->extrap_right;
+  fz.P = rqs_params(opts);
   fz.blocks_out = &blocks;
   const int rc = run_conv(in, wfrag, bias, nullptr, B, lattice, ksize, cin, cout, 0, 1, active_parity, dtype,
                           stream, &fz);

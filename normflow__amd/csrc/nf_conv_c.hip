@@ -318,10 +318,7 @@ extern "C" int nf_conv_first_split16_supported(const int32_t *lattice, const int
   if (act != kActTanh && act != kActSigmoid) return 0;
   for (int mu = 0; mu < 4; ++mu)
     if (ksize[mu] != 3) return 0;
-  if (lattice[3] < 32 || (lattice[3] & 15)) return 0;                     // whole or half segments of 32 sites
-  for (int mu = 0; mu < 3; ++mu)
-    if (lattice[mu] < 2 || (lattice[mu] & 1)) return 0;
-  return 1;
+  return split16_lattice_ok(lattice) ? 1 : 0;
 }
 
 extern "C" int nf_conv_first_split16(const void *in, const void *wsplit, const void *bias, void *out16, int64_t B,
@@ -334,29 +331,17 @@ extern "C" int nf_conv_first_split16(const void *in, const void *wsplit, const v
   if (B == 0) return NF_OK;
   ConvArgs A{};
   A.in = in; A.wfrag = wsplit; A.bias = bias; A.out = out16;
-  A.V = 1;
-  for (int mu = 0; mu < 4; ++mu) {
-    A.L[mu] = lattice[mu]; A.k[mu] = 3;
-    A.V *= lattice[mu];
-  }
+  set_lattice_k3(A, lattice);
   A.cin = 1; A.cout = 8; A.act = act;
   A.box[0] = lattice[0] % 4 == 0 ? 4 : 2;                              // cross-section of a column
   A.box[1] = lattice[1] % 4 == 0 ? 4 : 2;
   A.nitems = B * int64_t(lattice[0] / A.box[0]) * int64_t(lattice[1] / A.box[1]) * int64_t((lattice[3] / 2 + 15) / 16);   // columns x segments
   NF_REQUIRE(B * A.V < (int64_t(1) << 31), "nf_conv_first_split16: batch x volume >= 2^31 sites, split the batch");
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    NF_REQUIRE(hipGetDeviceProperties(&prop, dev) == hipSuccess, "nf_conv_first_split16: no device properties");
-    ncu = prop.multiProcessorCount;
-  }
+  NF_REQUIRE(cu_count() > 0, "nf_conv_first_split16: no device properties");
   const int nseg = (lattice[3] / 2 + 15) / 16;
   const int64_t per_seg = A.nitems / nseg;
   auto go = [&](bool hk) {
-    int64_t grid = int64_t(2) * ncu;           // two persistent workgroups per CU
-    if (grid > A.nitems) grid = A.nitems;
+    const int64_t grid = persistent_grid(2, A.nitems, false);      // two persistent workgroups per CU
     if (hk)
       hipLaunchKernelGGL(conv_c2_kernel<true>, dim3(unsigned(grid)), dim3(512), c2::LDS_BYTES, stream, A);
     else

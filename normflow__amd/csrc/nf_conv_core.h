@@ -1,5 +1,6 @@
 // nf_conv_core.h -- device code shared by the convolution kernels (nf_conv.hip: one box per
 // workgroup; nf_conv_pipe.hip: persistent workgroups with staging overlapped with the MFMAs).
+// At the end, the host side: the plan of a layer (ConvPlan) and what its planners and launchers share.
 #pragma once
 #include <hip/hip_fp16.h>
 #include "nf_rqs_core.h"
@@ -419,10 +420,56 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &A, const int (&o)[
   }
 }
 
-// nf_conv_pipe.hip: 1 = launched (dry: would launch), 0 = layer not eligible (use the one-box kernel), < 0 = error
-int conv_h_eligible(const ConvArgs &A, int fuse, int64_t *nboxes);
-int launch_conv_h(const ConvArgs &A0, int64_t B, int fuse, hipStream_t stream, bool dry);
-int launch_conv_c1(const ConvArgs &A0, int MT, int64_t B, int64_t nboxes, hipStream_t stream);
-int launch_conv_pipe(const ConvArgs &A0, int64_t B, int64_t nboxes, int fuse, hipStream_t stream, bool dry);
+// ------------------------------------------------------------------------------------------------- host side
+// A layer is PLANNED by pure functions (no pointer looked at, no HIP call: they run without a device, nf_conv_plan) and then
+// LAUNCHED from the finished plan.  plan_conv (nf_conv.hip) checks the arguments, chooses box, MT and LDS for the one-box
+// kernel and then offers the layer to the kernels with plans of their own, which re-plan the fields they own in A.
+enum ConvPath { kPathBox = 0, kPathPipe = 1, kPathC1 = 2, kPathH = 3 };      // the codes of nf_conv_last_path
+enum PlanVerdict { kPlanTaken, kPlanNotMine, kPlanTooManyItems };             // too many: batch x boxes >= 2^31 - 4096 items
+
+struct ConvPlan {
+  ConvArgs A;           // geometry and modes; the pointers are the caller's to fill
+  int path;             // ConvPath
+  int layout;           // NF_WLAYOUT_* the kernel of `path` reads
+  int MT;               // site tiles per wave of the box (0: the split-fp16 kernel has a box of its own)
+  int fuse;             // 0, or the coupling epilogue: 1 forward, 2 inverse
+  int launches;         // one-box kernel: one launch per 3 column tiles; 1 otherwise; 0: nothing to do (empty batch)
+  bool too_many;        // the kernel of `path` cannot index batch x boxes items: the call is refused, not re-routed
+  size_t lds;           // dynamic LDS of a launch
+  int64_t nblocks;      // boxes per sample
+  int64_t partials;     // log-det partials per sample (fused layers: the workspace holds B x partials doubles), else 0
+};
+
+inline void set_lattice_k3(ConvArgs &A, const int32_t *lattice) {      // the split-fp16 entries: 3^4 kernel
+  A.V = 1;
+  for (int mu = 0; mu < 4; ++mu) { A.L[mu] = lattice[mu]; A.k[mu] = 3; A.V *= lattice[mu]; }
+}
+inline RqsParams rqs_params(const nf_rqs_opts *o) {                    // a fused spline never has fixed knots
+  RqsParams P{};
+  P.xlo = o->xlo; P.xhi = o->xhi; P.ylo = o->ylo; P.yhi = o->yhi;
+  P.fx = nullptr; P.fy = nullptr; P.m = o->m; P.el = o->extrap_left; P.er = o->extrap_right;
+  return P;
+}
+// The lattices of the split-fp16 kernels: a fastest axis of whole or half 32-site segments (32 + 16 n sites) ...
+inline bool split16_axis_ok(int L3) { return L3 >= 32 && (L3 & 15) == 0; }
+// ... and even extents elsewhere (whole 2 x 2 x 2 boxes, row parity independent of the box)
+inline bool split16_lattice_ok(const int32_t *lattice) {
+  for (int mu = 0; mu < 3; ++mu)
+    if (lattice[mu] < 2 || (lattice[mu] & 1)) return false;
+  return split16_axis_ok(lattice[3]);
+}
+
+// `who`: could not launch its `kernel`, or (too_many) has too many work items; sets the message, returns the code
+int conv_launch_error(const char *who, const char *kernel, bool too_many);
+
+// Each plan_* says whether the layer is its kernel's and fills what that kernel re-plans: S, cchunk, wide_no, wide_llpr,
+// nitems, nboxes in A and the LDS size (plan_h: its own box and nbox as well); each launch_* takes the finished A and only
+// launches: 1 = launched, < 0 = the runtime refused.
+PlanVerdict plan_pipe(ConvArgs &A, int MT, int64_t B, int64_t nboxes, int fuse, size_t *lds);      // nf_conv_pipe.hip
+PlanVerdict plan_c1(ConvArgs &A, int MT, int64_t B, int64_t nboxes, size_t *lds);
+PlanVerdict plan_h(ConvArgs &A, int fuse, int64_t B, size_t *lds);                                 // nf_conv_h.hip
+int launch_conv_pipe(const ConvArgs &A, int fuse, size_t lds, hipStream_t stream);
+int launch_conv_c1(const ConvArgs &A, int MT, size_t lds, hipStream_t stream);
+int launch_conv_h(const ConvArgs &A, int fuse, hipStream_t stream);
 
 }  // namespace nf

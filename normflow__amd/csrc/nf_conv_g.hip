@@ -634,18 +634,11 @@ extern "C" int nf_conv_split16_supported(const int32_t *lattice, const int32_t *
   if (act != kActTanh && act != kActSigmoid) return 0;                    // the OUTPUT must be fp16-safe as well
   for (int mu = 0; mu < 4; ++mu)
     if (ksize[mu] != 3) return 0;
-  if (lattice[3] < 32 || (lattice[3] & 15)) return 0;                     // whole or half segments of 32 sites
-  for (int mu = 0; mu < 3; ++mu)
-    if (lattice[mu] < 2 || (lattice[mu] & 1)) return 0;
-  return 1;
+  return split16_lattice_ok(lattice) ? 1 : 0;
 }
 
 static int launch_g2(ConvArgs &A, const int32_t *lattice, int64_t B, int epi, hipStream_t stream, const char *what) {
-  A.V = 1;
-  for (int mu = 0; mu < 4; ++mu) {
-    A.L[mu] = lattice[mu]; A.k[mu] = 3;
-    A.V *= lattice[mu];
-  }
+  set_lattice_k3(A, lattice);
   A.cin = 8; A.cout = 8;
   const bool segm = lattice[3] != 32;
   A.nitems = B * int64_t(lattice[0] / 2) * int64_t(lattice[1] / 2) * int64_t(segm ? (lattice[3] / 2 + 15) / 16 : 1);      // columns (x segments)

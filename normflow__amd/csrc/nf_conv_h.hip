@@ -815,49 +815,35 @@ __global__ __launch_bounds__(256, 1) void conv_h_kernel(ConvArgs A) {
   }
 }
 
-// Is this fused layer the split-fp16 kernel's, and with how many boxes per sample?  (The kernel has its own box: 2 x 2 x 2
-// lattice rows x one 32-site segment of the fastest axis.)
-int conv_h_eligible(const ConvArgs &A, int fuse, int64_t *nboxes) {
+// Is this fused layer (fuse 1, 2: the coupling forward, inverse; 3: logits out; 4, 5: the coupling's VJP) the split-fp16
+// kernel's?  The kernel has its own box, 2 x 2 x 2 lattice rows x one 32-site segment of the fastest axis: box, nbox, nboxes
+// (boxes per sample) and nitems are filled for a layer that is taken, also where it then has too many items.
+PlanVerdict plan_h(ConvArgs &A, int fuse, int64_t B, size_t *lds) {
   using namespace h;
-  if (!option(NF_OPT_SPLIT16) || !fuse) return 0;
-  if (A.cin != 8 || A.cout < 1 || A.cout > C || NF_DBG(A, 15) || NF_STAMPS(A)) return 0;
-  if (fuse != 3 && (A.P.m < 2 || A.P.m > M || A.cout != 3 * A.P.m - 2 || A.P.fx || A.P.fy)) return 0;
+  if (!option(NF_OPT_SPLIT16) || !fuse) return kPlanNotMine;
+  if (A.cin != 8 || A.cout < 1 || A.cout > C || NF_DBG(A, 15) || NF_STAMPS(A)) return kPlanNotMine;
+  if (fuse != 3 && (A.P.m < 2 || A.P.m > M || A.cout != 3 * A.P.m - 2 || A.P.fx || A.P.fy)) return kPlanNotMine;
   for (int mu = 0; mu < 4; ++mu)
-    if (A.k[mu] != 3) return 0;
-  if (A.L[3] < 32 || (A.L[3] & 15)) return 0;                // whole or half segments
-  if (A.L[3] != 32 && !A.in_split16) return 0;               // fp32 planes are staged by the whole-row fallback only
-  if (A.in_split16 && A.V * 32 >= (int64_t(1) << 32)) return 0;       // the mover's row offsets inside a sample are 32-bit
-  for (int mu = 0; mu < 3; ++mu)
-    if (A.L[mu] < 2 || (A.L[mu] & 1)) return 0;             // even extents: whole boxes, row parity independent of the box
-  if (nboxes) *nboxes = int64_t(A.L[0] / 2) * (A.L[1] / 2) * (A.L[2] / 2) * ((A.L[3] / 2 + 15) / 16);
-  return 1;
-}
-
-// 1 = launched (dry: would launch), 0 = not this kernel's layer, < 0 error.  A0 is nf_conv.hip's planned argument block.
-int launch_conv_h(const ConvArgs &A0, int64_t B, int fuse, hipStream_t stream, bool dry) {
-  using namespace h;
-  int64_t nboxes = 0;
-  if (!conv_h_eligible(A0, fuse, &nboxes)) return 0;
-  if (dry) return 1;
-  ConvArgs A = A0;
-  const bool segm = A.L[3] != 32;
+    if (A.k[mu] != 3) return kPlanNotMine;
+  if (!split16_lattice_ok(A.L)) return kPlanNotMine;
+  if (A.L[3] != 32 && !A.in_split16) return kPlanNotMine;    // fp32 planes are staged by the whole-row fallback only
+  if (A.in_split16 && A.V * 32 >= (int64_t(1) << 32)) return kPlanNotMine;       // the mover's row offsets inside a sample are 32-bit
   A.box[0] = A.box[1] = A.box[2] = 2; A.box[3] = SEGW;
   for (int mu = 0; mu < 3; ++mu) A.nbox[mu] = A.L[mu] / 2;
   A.nbox[3] = (A.L[3] / 2 + 15) / 16;
+  const int64_t nboxes = int64_t(A.nbox[0]) * A.nbox[1] * A.nbox[2] * A.nbox[3];
   A.nitems = B * nboxes;
   A.nboxes = int(nboxes);
-  if (A.nitems >= (int64_t(1) << 31) - 4096) return -2;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-    ncu = prop.multiProcessorCount;
-  }
-  int64_t grid = ncu;
-  if (grid > A.nitems) grid = A.nitems;
-  grid = (grid + 7) & ~int64_t(7);
+  if (lds) *lds = size_t(A.L[3] != 32 ? lds_bytes<true>() : lds_bytes<false>());
+  return A.nitems >= (int64_t(1) << 31) - 4096 ? kPlanTooManyItems : kPlanTaken;
+}
+
+// A: a block plan_h took.  1 = launched, < 0 = the runtime refused.
+int launch_conv_h(const ConvArgs &A, int fuse, hipStream_t stream) {
+  using namespace h;
+  const bool segm = A.L[3] != 32;
+  const int64_t grid = persistent_grid(1, A.nitems, true);
+  if (grid <= 0) return -1;
   auto go = [&](auto kern, int lds) {
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;
     hipLaunchKernelGGL(kern, dim3(unsigned(grid)), dim3(256), lds, stream, A);
@@ -904,21 +890,20 @@ static int last_logits_split16(const void *in, int in_split16, const void *wspli
   NF_REQUIRE(B >= 0, "nf_conv_last_logits_split16: negative batch");
   if (B == 0) return NF_OK;
   ConvArgs A{};
-  A.V = 1;
-  for (int mu = 0; mu < 4; ++mu) { A.L[mu] = lattice[mu]; A.k[mu] = 3; A.V *= lattice[mu]; }
+  set_lattice_k3(A, lattice);
   A.in = in; A.wfrag = wsplit; A.bias = bias; A.out = logits;
   A.cin = 8; A.cout = cout;
   A.parity = active_parity & 1;
   A.in_split16 = in_split16 ? 1 : 0;
   A.gscale_bits = static_cast<const unsigned *>(absmax_bits);
   A.accumulate = accumulate ? 1 : 0;
-  const int pr = launch_conv_h(A, B, 3, stream, false);
-  if (pr == 0) {
+  const PlanVerdict v = plan_h(A, 3, B, nullptr);
+  if (v == kPlanNotMine) {
     set_error("nf_conv_last_logits_split16: layer not supported (4-D lattice, even extents, fastest axis 32 + 16 n sites; fp32 planes need 32)");
     return NF_EINVAL;
   }
-  if (pr == -2) { set_error("nf_conv_last_logits_split16: batch x boxes >= 2^31 work items, split the batch"); return NF_EINVAL; }
-  if (pr != 1) { set_error("nf_conv_last_logits_split16: could not launch the kernel"); return NF_ELAUNCH; }
+  if (v == kPlanTooManyItems || launch_conv_h(A, 3, stream) != 1)
+    return conv_launch_error("nf_conv_last_logits_split16", "kernel", v == kPlanTooManyItems);
   return check_launch("conv split-fp16 logits kernel");
 }
 
@@ -932,16 +917,14 @@ static int rqs_train_args(ConvArgs &A, const char *who, const void *in, int in_s
   NF_REQUIRE(B >= 0, "%s: negative batch", who);
   NF_REQUIRE(!opts->fixed_knots_x && !opts->fixed_knots_y, "%s: fixed knots are not fused", who);
   NF_REQUIRE(opts->xhi > opts->xlo && opts->yhi > opts->ylo, "%s: empty xlim/ylim", who);
-  A.V = 1;
-  for (int mu = 0; mu < 4; ++mu) { A.L[mu] = lattice[mu]; A.k[mu] = 3; A.V *= lattice[mu]; }
+  set_lattice_k3(A, lattice);
   A.in = in; A.wfrag = wsplit; A.bias = bias;
   A.cin = 8; A.cout = cout;
   A.parity = active_parity & 1;
   A.in_split16 = in_split16 ? 1 : 0;
   A.gscale_bits = static_cast<const unsigned *>(absmax_bits);
   A.xact = static_cast<const float *>(x);
-  A.P.xlo = opts->xlo; A.P.xhi = opts->xhi; A.P.ylo = opts->ylo; A.P.yhi = opts->yhi;
-  A.P.fx = nullptr; A.P.fy = nullptr; A.P.m = opts->m; A.P.el = opts->extrap_left; A.P.er = opts->extrap_right;
+  A.P = rqs_params(opts);
   return NF_OK;
 }
 
@@ -960,16 +943,16 @@ extern "C" int nf_conv_rqs_split16_train(const void *in, int in_split16, const v
   A.yout = static_cast<float *>(y);
   A.partial = static_cast<double *>(workspace);
   const int fuse = inverse ? 2 : 1;
-  int64_t nboxes = 0;
-  if (!conv_h_eligible(A, fuse, &nboxes)) {
+  const PlanVerdict v = plan_h(A, fuse, B, nullptr);
+  const int64_t nboxes = A.nboxes;
+  if (v == kPlanNotMine) {
     set_error("nf_conv_rqs_split16_train: layer not supported (4-D lattice, even extents, fastest axis 32 + 16 n sites -- fp32 planes need 32 --, knots_len 2..16, cout = 3m-2)");
     return NF_EINVAL;
   }
   NF_REQUIRE(workspace && workspace_bytes >= size_t(B) * size_t(nboxes) * sizeof(double),
              "nf_conv_rqs_split16_train: workspace %zu B < %zu B needed", workspace_bytes, size_t(B) * size_t(nboxes) * sizeof(double));
-  const int pr = launch_conv_h(A, B, fuse, stream, false);
-  if (pr == -2) { set_error("nf_conv_rqs_split16_train: batch x boxes >= 2^31 work items, split the batch"); return NF_EINVAL; }
-  if (pr != 1) { set_error("nf_conv_rqs_split16_train: could not launch the kernel"); return NF_ELAUNCH; }
+  if (v == kPlanTooManyItems || launch_conv_h(A, fuse, stream) != 1)
+    return conv_launch_error("nf_conv_rqs_split16_train", "kernel", v == kPlanTooManyItems);
   const int rl = check_launch("conv split-fp16 training forward kernel");
   if (rl) return rl;
   return launch_finalize<float>(A.partial, nboxes, log0, logj, B, stream);
@@ -991,12 +974,12 @@ extern "C" int nf_conv_rqs_split16_vjp(const void *in, int in_split16, const voi
   A.out = grad_logits;
   A.yout = static_cast<float *>(grad_x);
   const int fuse = inverse ? 5 : 4;
-  if (!conv_h_eligible(A, fuse, nullptr)) {
+  const PlanVerdict v = plan_h(A, fuse, B, nullptr);
+  if (v == kPlanNotMine) {
     set_error("nf_conv_rqs_split16_vjp: layer not supported (4-D lattice, even extents, fastest axis 32 + 16 n sites -- fp32 planes need 32 --, knots_len 2..16, cout = 3m-2)");
     return NF_EINVAL;
   }
-  const int pr = launch_conv_h(A, B, fuse, stream, false);
-  if (pr == -2) { set_error("nf_conv_rqs_split16_vjp: batch x boxes >= 2^31 work items, split the batch"); return NF_EINVAL; }
-  if (pr != 1) { set_error("nf_conv_rqs_split16_vjp: could not launch the kernel"); return NF_ELAUNCH; }
+  if (v == kPlanTooManyItems || launch_conv_h(A, fuse, stream) != 1)
+    return conv_launch_error("nf_conv_rqs_split16_vjp", "kernel", v == kPlanTooManyItems);
   return check_launch("conv split-fp16 coupling VJP kernel");
 }

@@ -403,24 +403,20 @@ __global__ __launch_bounds__(kBlock, 2) void conv_pipe_kernel(ConvArgs A) {
   }
 }
 
-template <int MT, int NT, int K3, bool COMPACT, int FUSE, bool WIDE, bool HOT>
-static int launch_pipe_w(const ConvArgs &A, size_t lds, hipStream_t stream) {
-  const void *fn = reinterpret_cast<const void *>(&conv_pipe_kernel<MT, NT, K3, COMPACT, FUSE, WIDE, HOT>);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-    ncu = prop.multiProcessorCount;
-  }
+// Grid of a persistent kernel `fn` of kBlock lanes: as many workgroups per CU as fit with `lds` bytes each (one if the
+// runtime will not say), rounded to the XCDs; the LDS limit of the kernel is raised where needed.  <= 0: the runtime refused.
+static int64_t occupancy_grid(const void *fn, size_t lds, int64_t nitems) {
   if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) != hipSuccess) return -1;
   int blocks_per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, fn, kBlock, lds) != hipSuccess || blocks_per_cu < 1)
     blocks_per_cu = 1;
-  int64_t grid = int64_t(blocks_per_cu) * ncu;
-  if (grid > A.nitems) grid = A.nitems;
-  grid = (grid + 7) & ~int64_t(7);
+  return persistent_grid(blocks_per_cu, nitems, true);
+}
+
+template <int MT, int NT, int K3, bool COMPACT, int FUSE, bool WIDE, bool HOT>
+static int launch_pipe_w(const ConvArgs &A, size_t lds, hipStream_t stream) {
+  const int64_t grid = occupancy_grid(reinterpret_cast<const void *>(&conv_pipe_kernel<MT, NT, K3, COMPACT, FUSE, WIDE, HOT>), lds, A.nitems);
+  if (grid <= 0) return -1;
   hipLaunchKernelGGL((conv_pipe_kernel<MT, NT, K3, COMPACT, FUSE, WIDE, HOT>), dim3(unsigned(grid)), dim3(kBlock), lds, stream, A);
   return 1;
 }
@@ -434,14 +430,14 @@ static int launch_pipe_one(const ConvArgs &A, size_t lds, hipStream_t stream) {
                    : launch_pipe_w<MT, NT, K3, COMPACT, FUSE, false, false>(A, lds, stream);
 }
 
-// Returns 1 when the layer was launched here, 0 when it is not eligible (the caller falls back to
-// the one-box kernel), < 0 on error.  `A0` is the fully planned argument block of nf_conv.hip
-// (MT = 2 boxes); only the plane stride is re-planned (slack for masked stores).
-int launch_conv_pipe(const ConvArgs &A0, int64_t B, int64_t nboxes, int fuse, hipStream_t stream, bool dry) {
-  const int off = !option(NF_OPT_PIPE);
-  if (off) return 0;
+// Is the layer the persistent kernel's?  `A` is the fully planned argument block of nf_conv.hip, which plans MT = 2 boxes for
+// the layers that can come here; the plane stride (slack for masked stores), the channels per pass, the wide staging and the
+// item counts are re-planned.  A layer that is not taken keeps its one-box plan.
+PlanVerdict plan_pipe(ConvArgs &A0, int MT, int64_t B, int64_t nboxes, int fuse, size_t *lds_out) {
+  if (!option(NF_OPT_PIPE) || MT != 2) return kPlanNotMine;
   ConvArgs A = A0;
-  if (A.packed || A.k[3] != 3 || NF_DBG(A, 15) || NF_STAMPS(A)) return 0;    // cin % 4 != 0 (>= 8): channel planes zero-padded in LDS
+  A.nt0 = 0;
+  if (A.packed || A.k[3] != 3 || NF_DBG(A, 15) || NF_STAMPS(A)) return kPlanNotMine;    // cin % 4 != 0 (>= 8): channel planes zero-padded in LDS
   A.wide_no = 0; A.wide_llpr = 0;
   {
     static const int wide_off = NF_DIAG_ENV_INT("NF_CONV_PIPE_NARROW", 0);     // A/B knob
@@ -456,14 +452,14 @@ int launch_conv_pipe(const ConvArgs &A0, int64_t B, int64_t nboxes, int fuse, hi
       if (no <= 4) { A.wide_no = int(no); A.wide_llpr = llpr; }
     }
   }
-  if (!A.wide_no && A.hal[3] > 64) return 0;
-  if (A.nt_total - A.nt0 > 3 || A.nt0 != 0) return 0;
+  if (!A.wide_no && A.hal[3] > 64) return kPlanNotMine;
+  if (A.nt_total - A.nt0 > 3 || A.nt0 != 0) return kPlanNotMine;
   const int nrows = A.k[0] * A.k[1] * A.k[2];
-  if (nrows < 2) return 0;
+  if (nrows < 2) return kPlanNotMine;
   for (int mu = 0; mu < 4; ++mu) {
     const int r = A.k[mu] >> 1;
-    if (r > A.L[mu] || A.nbox[mu] * A.box[mu] + r - 1 >= 2 * A.L[mu]) return 0;    // wrap1's range
-    if (A.hal[mu] > 255) return 0;
+    if (r > A.L[mu] || A.nbox[mu] * A.box[mu] + r - 1 >= 2 * A.L[mu]) return kPlanNotMine;    // wrap1's range
+    if (A.hal[mu] > 255) return kPlanNotMine;
   }
   int64_t halvol = 1, rows = 1;
   for (int mu = 0; mu < 4; ++mu) halvol *= A.hal[mu];
@@ -473,14 +469,19 @@ int launch_conv_pipe(const ConvArgs &A0, int64_t B, int64_t nboxes, int fuse, hi
   A.S = S;
   A.cchunk = 4;
   A.nitems = B * nboxes;
-  if (!dry && A.nitems >= (int64_t(1) << 31) - 4096) return -2;
+  if (A.nitems >= (int64_t(1) << 31) - 4096) return kPlanTooManyItems;
   A.nboxes = int(nboxes);
   const size_t lds = size_t(2) * 4 * S * sizeof(float);
-  if (rows > 256) return 0;                                 // one lane per row group of a wave (v_readlane)
-  if (lds > 160 * 1024) return 0;
-  if (fuse && size_t(48) * ((kBlock / kWave) * 2 * 16 + 4) * sizeof(float) > size_t(4) * S * sizeof(float)) return 0;
-  if (A.sh2 && size_t(8) * (2 * (kBlock / kWave) * 2 * 16 + 8) > size_t(4) * S) return 0;   // epilogue scratch = one buffer
-  if (dry) return 1;
+  if (rows > 256) return kPlanNotMine;                      // one lane per row group of a wave (v_readlane)
+  if (lds > 160 * 1024) return kPlanNotMine;
+  if (fuse && size_t(48) * ((kBlock / kWave) * 2 * 16 + 4) * sizeof(float) > size_t(4) * S * sizeof(float)) return kPlanNotMine;
+  if (A.sh2 && size_t(8) * (2 * (kBlock / kWave) * 2 * 16 + 8) > size_t(4) * S) return kPlanNotMine;   // epilogue scratch = one buffer
+  A0 = A;
+  *lds_out = lds;
+  return kPlanTaken;
+}
+
+int launch_conv_pipe(const ConvArgs &A, int fuse, size_t lds, hipStream_t stream) {
   const int n = A.nt_total;
   if (fuse) {
     if (n == 3) return fuse == 1 ? launch_pipe_one<2, 3, 3, true, 1>(A, lds, stream) : launch_pipe_one<2, 3, 3, true, 2>(A, lds, stream);
@@ -829,40 +830,25 @@ __global__ __launch_bounds__(kBlock, 2) void conv_c1_kernel(ConvArgs A) {
 
 template <int MT, int NROWS>
 static int launch_c1(const ConvArgs &A, size_t lds, hipStream_t stream) {
-  const void *fn = reinterpret_cast<const void *>(&conv_c1_kernel<MT, NROWS>);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-    ncu = prop.multiProcessorCount;
-  }
-  if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) != hipSuccess) return -1;
-  int blocks_per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, fn, kBlock, lds) != hipSuccess || blocks_per_cu < 1)
-    blocks_per_cu = 1;
-  int64_t grid = int64_t(blocks_per_cu) * ncu;
-  if (grid > A.nitems) grid = A.nitems;
-  grid = (grid + 7) & ~int64_t(7);
+  const int64_t grid = occupancy_grid(reinterpret_cast<const void *>(&conv_c1_kernel<MT, NROWS>), lds, A.nitems);
+  if (grid <= 0) return -1;
   hipLaunchKernelGGL((conv_c1_kernel<MT, NROWS>), dim3(unsigned(grid)), dim3(kBlock), lds, stream, A);
   return 1;
 }
 
-// 1 = launched, 0 = not this kernel's layer, < 0 = error.  `MT` is the box size nf_conv.hip planned (2 or 4).
-int launch_conv_c1(const ConvArgs &A0, int MT, int64_t B, int64_t nboxes, hipStream_t stream) {
-  const int off = !option(NF_OPT_PIPE);
-  if (off) return 0;
+// Is the layer K5c's?  `MT` is the box size nf_conv.hip planned (2 or 4); plane stride, wide staging and item counts are re-planned.
+PlanVerdict plan_c1(ConvArgs &A0, int MT, int64_t B, int64_t nboxes, size_t *lds_out) {
+  if (!option(NF_OPT_PIPE)) return kPlanNotMine;
   ConvArgs A = A0;
-  if (A.cin != 1 || !A.sh2 || A.k[3] != 3 || NF_DBG(A, 15) || NF_STAMPS(A) || A.compact) return 0;
-  if (A.out_split16 && A.cout != 8) return 0;
+  if (A.cin != 1 || !A.sh2 || A.k[3] != 3 || NF_DBG(A, 15) || NF_STAMPS(A) || A.compact) return kPlanNotMine;
+  if (A.out_split16 && A.cout != 8) return kPlanNotMine;
   const int nrows = A.k[0] * A.k[1] * A.k[2];
-  if (nrows != 27 && nrows != 9 && nrows != 3) return 0;
+  if (nrows != 27 && nrows != 9 && nrows != 3) return kPlanNotMine;
   const int L3 = A.L[3];
-  if (!(A.nbox[3] == 1 && A.box[3] == L3 && (L3 == 8 || L3 == 16 || L3 == 32 || L3 == 64))) return 0;
+  if (!(A.nbox[3] == 1 && A.box[3] == L3 && (L3 == 8 || L3 == 16 || L3 == 32 || L3 == 64))) return kPlanNotMine;
   for (int mu = 0; mu < 4; ++mu) {
     const int r = A.k[mu] >> 1;
-    if (r > A.L[mu] || A.nbox[mu] * A.box[mu] + r - 1 >= 2 * A.L[mu] || A.hal[mu] > 255) return 0;
+    if (r > A.L[mu] || A.nbox[mu] * A.box[mu] + r - 1 >= 2 * A.L[mu] || A.hal[mu] > 255) return kPlanNotMine;
   }
   int64_t halvol = 1, rows = 1;
   for (int mu = 0; mu < 4; ++mu) halvol *= A.hal[mu];
@@ -871,15 +857,22 @@ int launch_conv_c1(const ConvArgs &A0, int MT, int64_t B, int64_t nboxes, hipStr
   while ((4 << llpr) < L3) ++llpr;
   const int rpi = 64 >> llpr;
   const int64_t no = (rows + rpi * 4 - 1) / (rpi * 4);
-  if (no > 4) return 0;
+  if (no > 4) return kPlanNotMine;
   A.wide_no = int(no); A.wide_llpr = llpr;
   A.S = (int(halvol) + kSlack + 3) & ~3;
   A.nitems = B * nboxes;
   A.nboxes = int(nboxes);
-  if (A.nitems >= (int64_t(1) << 31) - 4096) return -2;
+  if (A.nitems >= (int64_t(1) << 31) - 4096) return kPlanTooManyItems;
   // three input planes + the output transpose (two of them for the split16 output: item m-1 leaves while item m multiplies)
   const size_t lds = (size_t(3) * A.S + size_t(A.out_split16 ? 2 : 1) * 8 * (2 * (kBlock / kWave) * MT * 16 + 8)) * sizeof(float);
-  if (lds > 160 * 1024) return 0;
+  if (lds > 160 * 1024) return kPlanNotMine;
+  A0 = A;
+  *lds_out = lds;
+  return kPlanTaken;
+}
+
+int launch_conv_c1(const ConvArgs &A, int MT, size_t lds, hipStream_t stream) {
+  const int nrows = A.k[0] * A.k[1] * A.k[2];
   if (MT == 4) return nrows == 27 ? launch_c1<4, 27>(A, lds, stream) : (nrows == 9 ? launch_c1<4, 9>(A, lds, stream) : launch_c1<4, 3>(A, lds, stream));
   return nrows == 27 ? launch_c1<2, 27>(A, lds, stream) : (nrows == 9 ? launch_c1<2, 9>(A, lds, stream) : launch_c1<2, 3>(A, lds, stream));
 }

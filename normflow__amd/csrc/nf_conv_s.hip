@@ -441,18 +441,10 @@ extern "C" int nf_small_lattice_coupling(int kind, const void *x_frozen, const v
   A.B = B; A.L0 = ndim == 3 ? lattice[0] : 1; A.L1 = lattice[ndim - 2]; A.flat = ndim == 2 ? 1 : 0;
   A.parity = active_parity & 1; A.cout = cout; A.act1 = act1; A.act2 = act2;
   if (kind == 0) {
-    A.P.xlo = opts->xlo; A.P.xhi = opts->xhi; A.P.ylo = opts->ylo; A.P.yhi = opts->yhi;
-    A.P.fx = nullptr; A.P.fy = nullptr; A.P.m = opts->m; A.P.el = opts->extrap_left; A.P.er = opts->extrap_right;
+    A.P = rqs_params(opts);
   }
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { set_error("%s: no device properties", who); return NF_ELAUNCH; }
-    ncu = prop.multiProcessorCount;
-  }
-  const int64_t grid = B < ncu ? B : ncu;
+  const int64_t grid = persistent_grid(1, B, false);         // min(B, CUs): a workgroup walks over samples
+  if (grid <= 0) { set_error("%s: no device properties", who); return NF_ELAUNCH; }
   const int lds = int(s3::lds_bytes(A.L0, A.L1));
   auto go = [&](auto kern) {
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;

@@ -470,7 +470,7 @@ extern "C" int nf_conv_wgrad_split16_supported(const int32_t *lattice, const int
   if (!lattice || !ksize) return 0;
   for (int mu = 0; mu < 4; ++mu)
     if (ksize[mu] != 3 || lattice[mu] < 1) return 0;
-  if (lattice[3] < 32 || (lattice[3] & 15)) return 0;       // segments of 32 sites, the last one 32 or 16
+  if (!split16_axis_ok(lattice[3])) return 0;               // segments of 32 sites, the last one 32 or 16
   if (cin != 1 && cin != 8) return 0;
   return cout >= 1 && cout <= 48;
 }

@@ -14,6 +14,10 @@ constexpr int kMaxBlocksX = 65535 * 16;
 void set_error(const char *fmt, ...);
 int check_launch(const char *what);
 int option(int which);      // nf_set_option / nf_get_option (nf_common.hip)
+int cu_count();             // compute units of the current device (asked once per device id); 0 if it cannot be asked
+// Workgroups of a persistent launch: blocks_per_cu on every CU, no more than there are items, optionally rounded up to a
+// multiple of 8 (one share per XCD; the surplus workgroups find no item and leave).  0 if the device cannot be asked.
+int64_t persistent_grid(int blocks_per_cu, int64_t n_items, bool round_to_8);
 
 #define NF_REQUIRE(cond, ...)                \
   do {                                       \
