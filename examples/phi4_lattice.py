@@ -9,6 +9,8 @@ DistConvertor_), or a stack of RQ-spline couplings, assembled from the same name
     python examples/phi4_lattice.py --lat 8,8 --ladder    no fit: a ladder of kappas across the transition sampled by
                                                            model.hmc.ladder, chi, U4 and tau_int(m) per rung, without and
                                                            with replica exchange
+    python examples/phi4_lattice.py --lat 8,8 --ladder --cluster    the same, and once more with a cluster sweep of every
+                                                           chain at its rung's coupling before every step
     python examples/phi4_lattice.py --lat 16,16 --hmc     after the fit: <phi^2> from model.mcmc next to model.hmc, then
                                                           chi, the Binder cumulant, xi_2 and tau_int(m) of both
     python examples/phi4_lattice.py --lat 8,8 --hmc --cluster    the same, and model.hmc once more with a cluster sweep of
@@ -91,19 +93,20 @@ def compare_with_hmc(model, n_chains=64, rows=128, cluster=False):
         print("model.hmc, cluster_every=1   " + observables(model, y, n_chains, rows // 4))
 
 
-def ladder_scan(lat, m_sq, lambd, kappas, replicas=32, steps=600):
+def ladder_scan(lat, m_sq, lambd, kappas, replicas=32, steps=600, cluster=False):
     """A coupling ladder across the transition in ONE launch per step: chi, the Binder cumulant and tau_int(m) per rung
     from model.hmc.ladder(...).measure (nothing stored), without and with replica exchange between neighbouring rungs.
-    The first quarter of every run is dropped as thermalisation."""
+    `cluster`: a third run with exchanges and a Swendsen-Wang sweep of every chain, at the hopping coefficient of the rung
+    it holds, before every step (cluster_every=1).  The first quarter of every run is dropped as thermalisation."""
     from normflow__amd.action import ScalarPhi4Ladder
     ladder = ScalarPhi4Ladder(kappa=kappas, m_sq=m_sq, lambd=lambd)
     model = nf.Model(net_=None, prior=NormalPrior(shape=lat), action=ladder.rung(0))
     K, C = len(ladder), len(ladder) * replicas
-    for every in (0, 1):
+    for every, sweeps in ((0, 0), (1, 0)) + (((1, 1),) if cluster else ()):
         sampler = model.hmc.ladder(ladder)
-        ms = sampler.measure(steps * C, n_chains=C, n_md=10, dt=0.1, exchange_every=every)
+        ms = sampler.measure(steps * C, n_chains=C, n_md=10, dt=0.1, exchange_every=every, cluster_every=sweeps)
         rates = sampler.history.exchange_rate[-1]
-        print("exchange_every = %d   HMC accept rate %.3f%s" % (every, sampler.history.accept_rate[-1],
+        print("exchange_every = %d, cluster_every = %d   HMC accept rate %.3f%s" % (every, sweeps, sampler.history.accept_rate[-1],
               "" if not every else "   exchange rates " + " ".join("%.2f" % r for r in rates)))
         for k in range(K):
             e = Ensemble(ms[k], n_chains=replicas, drop=steps // 4)
@@ -129,14 +132,15 @@ def main():
     ap.add_argument("--hmc", action="store_true",
                     help="after the fit, print <phi^2> from model.hmc (hybrid Monte Carlo on the action) next to model.mcmc")
     ap.add_argument("--cluster", action="store_true",
-                    help="with --hmc: model.hmc once more with cluster_every=1, tau_int(m) with and without cluster sweeps")
+                    help="with --hmc: model.hmc once more with cluster_every=1, tau_int(m) with and without cluster sweeps; "
+                         "with --ladder: the ladder once more with exchanges and cluster_every=1")
     ap.add_argument("--ladder", action="store_true",
                     help="no fit: a ladder of 6 kappas from --kappa down to 0.4 of it in one HMC launch per step, chi, U4 and "
                          "tau_int(m) per rung without and with replica exchange")
     a = ap.parse_args()
     lat = tuple(int(n) for n in a.lat.split(","))
     if a.ladder:
-        ladder_scan(lat, a.m_sq, a.lambd, [a.kappa * (1 - 0.12 * k) for k in range(6)])
+        ladder_scan(lat, a.m_sq, a.lambd, [a.kappa * (1 - 0.12 * k) for k in range(6)], cluster=a.cluster)
         return
     model = nf.Model(net_=build_net(lat, a.kind, a.layers, a.knots, a.transform), prior=NormalPrior(shape=lat),
                      action=ScalarPhi4Action(kappa=a.kappa, m_sq=a.m_sq, lambd=a.lambd))

@@ -882,6 +882,13 @@ int nf_phi4_ladder_exchange(const double *rows, int64_t row_stride, const double
  * NF_EINVAL: NULL phi / stats / lattice, an unsupported lattice or dtype, C out of range.
  * nf_phi4_cluster_plan / nf_phi4_cluster_supported: pure host; the lane map is nf_phi4_hmc's.
  *
+ * nf_phi4_cluster_ladder / nf_phi4_cluster_tiled_ladder: the two sweeps on a coupling ladder, argument for argument with
+ * (coef (K, 3) double, K, rung (C) int32, clamped into 0 .. K - 1) of nf_phi4_hmc_ladder in place of w0: a chain on rung
+ * k gets nf_phi4_cluster's bits at w0_k = coef[3 k].  phi and labels_out stay at c; stats is written at the RUNG-ORDERED
+ * row (c / K) K + rung[c], like dh_out of the ladder HMC kernels (rows collide unless rung is a permutation of
+ * 0 .. K - 1 within every set of K chains).  Planners, workspace, launches and Philox indices are the plain ones.
+ * NF_EINVAL: whatever the plain entry point refuses, a NULL coef or rung, K < 1, C not a multiple of K.
+ *
  * nf_phi4_cluster_draws: the draws of the sweep at (seed, offset), element-wise, for any lattice with V < 2^31 and C in
  * 1 .. 65535: u_out (C, V, 4) double = the uniforms of step 2 (all four words, whatever the extents), flip_out (C, V)
  * uint8 = the bit of step 4 for every site index taken as a label.  A sweep composed from other pieces walks the kernel's
@@ -895,6 +902,9 @@ int nf_phi4_cluster_supported(const int32_t *lattice, int dtype);
 int nf_phi4_cluster_plan(const int32_t *lattice, int dtype, nf_cluster_plan *out);
 int nf_phi4_cluster(void *phi, int32_t *stats, int32_t *labels_out, int64_t C, const int32_t *lattice, double w0,
                     uint64_t seed, uint64_t offset, int dtype, void *stream);
+int nf_phi4_cluster_ladder(void *phi, int32_t *stats, int32_t *labels_out, int64_t C, const int32_t *lattice,
+                           const double *coef, int K, const int32_t *rung, uint64_t seed, uint64_t offset, int dtype,
+                           void *stream);
 int nf_phi4_cluster_draws(double *u_out, uint8_t *flip_out, int64_t C, const int32_t *lattice, uint64_t seed,
                           uint64_t offset, void *stream);
 
@@ -937,6 +947,9 @@ size_t nf_phi4_cluster_tiled_workspace(int64_t C, const int32_t *lattice, int64_
 int nf_phi4_cluster_tiled(void *phi, int32_t *stats, int32_t *labels_out, int64_t C, const int32_t *lattice, double w0,
                           uint64_t seed, uint64_t offset, int dtype, int64_t tile_sites, void *workspace,
                           size_t workspace_bytes, void *stream);
+int nf_phi4_cluster_tiled_ladder(void *phi, int32_t *stats, int32_t *labels_out, int64_t C, const int32_t *lattice,
+                                 const double *coef, int K, const int32_t *rung, uint64_t seed, uint64_t offset, int dtype,
+                                 int64_t tile_sites, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- what the samplers' rows measure (nf_measure.hip; MI355X-side extension): every sufficient statistic of N
  * configurations in one pass.  cfgs (N, V) of dtype NF_F32 / NF_F64 on lattice[4] (leading extents 1 for d < 4);

@@ -114,6 +114,9 @@ PROTOTYPES = {
     "nf_phi4_cluster_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I64]),
     "nf_phi4_cluster_tiled": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _D, C.c_uint64, C.c_uint64, _I, _I64, _P, _SZ,
                                    _P]),
+    "nf_phi4_cluster_ladder": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, C.c_uint64, C.c_uint64, _I, _P]),
+    "nf_phi4_cluster_tiled_ladder": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, C.c_uint64, C.c_uint64, _I,
+                                          _I64, _P, _SZ, _P]),
     "nf_lattice_measure_supported": (_I, [C.POINTER(C.c_int32), _I]),
     "nf_lattice_measure_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
     "nf_lattice_measure_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
@@ -2283,6 +2286,48 @@ def phi4_cluster_tiled(phi, w0, position=None, want_labels=False, tile_sites=0, 
                                         _dtype_code(phi), ts, _ptr(workspace), workspace.numel(), _stream()),
            "nf_phi4_cluster_tiled")
     return dict(stats=stats, labels=labels)
+
+
+# ========================================================================= the two sweeps on a coupling ladder
+def _phi4_cluster_ladder_call(what, phi, coef, rung, position, want_labels, generator, tiled=None):
+    """The body of `phi4_cluster_ladder` and `phi4_cluster_tiled_ladder` (`what`; the entry point is nf_<what>): the
+    checks, the outputs, the 2 Philox positions, the call and the dict.  `tiled` = (tile_sites, workspace) or None."""
+    _require_device(phi)
+    if not phi.is_contiguous():
+        raise NormflowHipError(f"{what} needs contiguous phi (C, *L)")
+    Cn, lat, dev = phi.shape[0], tuple(phi.shape[1:]), phi.device
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"{what}: lattices of 1 to 4 axes, got {lat}")
+    ladder = _ladder_tensors(what, coef, rung, Cn, dev)[1]
+    tail = ()
+    if tiled is not None:
+        ts, workspace = _tile_sites(tiled[0]), tiled[1]
+        if workspace is None:
+            need = load().nf_phi4_cluster_tiled_workspace(Cn, _lat4(lat), ts)
+            workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+        tail = (ts, _ptr(workspace), workspace.numel())
+    stats = torch.empty((Cn, 4), dtype=torch.int32, device=dev)
+    labels = torch.empty((Cn,) + lat, dtype=torch.int32, device=dev) if want_labels else None
+    seed, offset = position if position is not None else _philox_positions(dev, 2, generator)
+    _check(getattr(load(), "nf_" + what)(_ptr(phi), _ptr(stats), _ptr(labels), Cn, _lat4(lat), *ladder, seed, offset,
+                                         _dtype_code(phi), *tail, _stream()), "nf_" + what)
+    return dict(stats=stats, labels=labels)
+
+
+def phi4_cluster_ladder(phi, coef, rung, position=None, want_labels=False, generator=None):
+    """nf_phi4_cluster_ladder: `phi4_cluster` with a hopping coefficient per chain.  coef (K, 3) float64 holds (w0, w2, w4)
+    per rung, of which the sweep reads w0; rung (C) int32 is the rung of every chain, C a multiple of K.  A chain on rung k
+    gets `phi4_cluster`'s bits at w0_k.  The same dict and the same 2 Philox positions; phi and labels stay at the chain's
+    index, stats (C, 4) is RUNG-ORDERED: the row of chain c is (c // K) K + rung[c]."""
+    return _phi4_cluster_ladder_call("phi4_cluster_ladder", phi, coef, rung, position, want_labels, generator)
+
+
+def phi4_cluster_tiled_ladder(phi, coef, rung, position=None, want_labels=False, tile_sites=0, workspace=None,
+                              generator=None):
+    """nf_phi4_cluster_tiled_ladder: `phi4_cluster_tiled` with a hopping coefficient per chain, as `phi4_cluster_ladder`;
+    `tile_sites` and `workspace` as `phi4_cluster_tiled` takes them."""
+    return _phi4_cluster_ladder_call("phi4_cluster_tiled_ladder", phi, coef, rung, position, want_labels, generator,
+                                     tiled=(tile_sites, workspace))
 
 
 # ========================================================================= observables of sampler rows (nf_measure.hip)

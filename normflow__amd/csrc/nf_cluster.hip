@@ -21,6 +21,11 @@
 // Then the labels go to registers, the label array is reused for the clusters' sizes (integer ds_add), and every site takes
 // its cluster's flip bit and, where set, stores phi back with the sign bit flipped: plain vector stores, nothing else of
 // phi is written.  Integer atomics on LDS only: the same inputs give the same bits.
+// nf_phi4_cluster_ladder is the same kernel compiled with LADDER, as nf_hmc.hip's: the workgroup of chain c takes w0 from
+// row rung[c] of the ladder's table, once, into scalar registers, and writes its stats at the rung-ordered row
+// (c / K) K + rung[c]; phi, the labels and the Philox indices stay at c.  A chain on rung k has nf_phi4_cluster's bits at w0_k.
+#include <type_traits>
+
 #include "nf_sampler_core.h"
 
 namespace nf {
@@ -67,8 +72,19 @@ struct ClusterArgs {
   PhiloxPos bond_pos, flip_pos;
 };
 
-template <typename T, int NS>
-__global__ __launch_bounds__(kClMaxLanes) void phi4_cluster_kernel(ClusterArgs A) {
+// What LADDER adds (nf_phi4_cluster_ladder): the table of the K rungs' coefficients and the rung every chain holds, as
+// nf_hmc.hip's HmcLadderArgs; w0 is unused
+struct ClusterLadderArgs : ClusterArgs {
+  const double *coef;   // (K, 3): row k starts with the w0 of rung k
+  const int32_t *rung;  // (C): the rung of chain c, clamped into 0 .. K - 1 by the kernel
+  int K;
+};
+
+template <bool LADDER>
+using ClusterKernelArgs = std::conditional_t<LADDER, ClusterLadderArgs, ClusterArgs>;
+
+template <typename T, int NS, bool LADDER>
+__global__ __launch_bounds__(kClMaxLanes) void phi4_cluster_kernel(ClusterKernelArgs<LADDER> A) {
   extern __shared__ __align__(16) unsigned char cl_lds[];
   volatile int *s_flag = reinterpret_cast<volatile int *>(cl_lds);     // [2]: did round r (mod 2) see a link with two labels
   int *s_sum = reinterpret_cast<int *>(cl_lds) + 2;                   // clusters, sites flipped, the largest cluster
@@ -82,6 +98,15 @@ __global__ __launch_bounds__(kClMaxLanes) void phi4_cluster_kernel(ClusterArgs A
   // the step to the forward neighbour along mu from a site at the end of its axis; 0 for an axis of extent 1 (no link)
   const int wrap[4] = {-st[0] * (A.L[0] - 1), -st[1] * (A.L[1] - 1), -st[2] * (A.L[2] - 1), -st[3] * (A.L[3] - 1)};
   auto fwd = [&](int x, uint32_t b, int mu) { return x + ((b >> (4 + mu)) & 1u ? wrap[mu] : st[mu]); };
+  // LADDER: the chain's w0 is that of row rung[c] of the table, read once into scalar registers, and its stats row is the
+  // rung-ordered (c / K) K + rung[c]; phi, the labels and the Philox indices stay at c
+  double lw0 = 0.0;
+  int64_t oc = c;
+  if constexpr (LADDER) {
+    const int r = min(max(int(A.rung[c]), 0), A.K - 1);
+    lw0 = uniform_scalar(A.coef[3 * int64_t(r)]);
+    oc = c / A.K * A.K + r;
+  }
 
   // ---- bonds: one Philox call per site, word mu for the link (x, mu); phi(x) stays in a register for the flip
   T phi[NS];
@@ -107,7 +132,7 @@ __global__ __launch_bounds__(kClMaxLanes) void phi4_cluster_kernel(ClusterArgs A
         if (A.L[mu] > 1) {
           if (xs[mu] == A.L[mu] - 1) b |= 16u << mu;
           const T q = gphi[fwd(x, b, mu)];
-          if (cluster_bond(A.w0, double(p), double(q), philox_u32_mid(w[mu]))) b |= 1u << mu;
+          if (cluster_bond(LADDER ? lw0 : A.w0, double(p), double(q), philox_u32_mid(w[mu]))) b |= 1u << mu;
         }
       }
       lab[x] = x;
@@ -213,7 +238,7 @@ __global__ __launch_bounds__(kClMaxLanes) void phi4_cluster_kernel(ClusterArgs A
   }
   __syncthreads();
   if (tid == 0) {
-    int32_t *row = A.stats + 4 * c;
+    int32_t *row = A.stats + 4 * oc;
     row[0] = settled ? s_sum[0] : 0;
     row[1] = settled ? s_sum[1] : 0;
     row[2] = settled ? s_sum[2] : 0;
@@ -221,32 +246,56 @@ __global__ __launch_bounds__(kClMaxLanes) void phi4_cluster_kernel(ClusterArgs A
   }
 }
 
-template <typename T, int NS>
-static int launch_cluster(const ClusterArgs &A, int64_t C, const ClusterPlan &p, hipStream_t s) {
-  auto kern = phi4_cluster_kernel<T, NS>;
+template <typename T, int NS, bool LADDER>
+static int launch_cluster(const char *what, const ClusterKernelArgs<LADDER> &A, int64_t C, const ClusterPlan &p, hipStream_t s) {
+  auto kern = phi4_cluster_kernel<T, NS, LADDER>;
   if (p.lds > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                           int(p.lds)) != hipSuccess) {
     (void)hipGetLastError();
-    set_error("nf_phi4_cluster: cannot raise the dynamic LDS limit to %zu B", p.lds);
+    set_error("%s: cannot raise the dynamic LDS limit to %zu B", what, p.lds);
     return NF_ELAUNCH;
   }
   hipLaunchKernelGGL(kern, dim3(unsigned(C)), dim3(unsigned(p.nt)), p.lds, s, A);
-  return check_launch("nf_phi4_cluster");
+  return check_launch(what);
 }
 
-template <typename T>
-static int dispatch_cluster(const ClusterArgs &A, int64_t C, const ClusterPlan &p, hipStream_t s) {
+template <typename T, bool LADDER>
+static int dispatch_cluster(const char *what, const ClusterKernelArgs<LADDER> &A, int64_t C, const ClusterPlan &p, hipStream_t s) {
   switch (p.ns) {
-    case 1: return launch_cluster<T, 1>(A, C, p, s);
-    case 2: return launch_cluster<T, 2>(A, C, p, s);
-    case 4: return launch_cluster<T, 4>(A, C, p, s);
-    case 8: return launch_cluster<T, 8>(A, C, p, s);
+    case 1: return launch_cluster<T, 1, LADDER>(what, A, C, p, s);
+    case 2: return launch_cluster<T, 2, LADDER>(what, A, C, p, s);
+    case 4: return launch_cluster<T, 4, LADDER>(what, A, C, p, s);
+    case 8: return launch_cluster<T, 8, LADDER>(what, A, C, p, s);
     case 16:
-      if constexpr (sizeof(T) == 4) return launch_cluster<T, 16>(A, C, p, s);     // 8-byte fields end at 8 sites per lane
+      if constexpr (sizeof(T) == 4) return launch_cluster<T, 16, LADDER>(what, A, C, p, s);     // 8-byte fields end at 8 sites per lane
   }
-  set_error("nf_phi4_cluster: no kernel for %d sites per lane", p.ns);
+  set_error("%s: no kernel for %d sites per lane", what, p.ns);
   return NF_EINVAL;
+}
+
+// nf_phi4_cluster (coef == NULL, not a ladder call) and nf_phi4_cluster_ladder (ladder: w0 unused)
+static int cluster_entry(const char *what, bool ladder, void *phi, int32_t *stats, int32_t *labels_out, int64_t C,
+                         const int32_t *lattice, double w0, const double *coef, int K, const int32_t *rung, uint64_t seed,
+                         uint64_t offset, int dtype, void *stream) {
+  NF_REQUIRE(phi && stats, "%s: phi or stats is NULL", what);
+  NF_REQUIRE(C >= 1 && C <= 65535, "%s: C (%lld) must be in 1 .. 65535", what, (long long)C);
+  ClusterPlan p;
+  int rc = cluster_plan(what, lattice, dtype, p);
+  if (!rc && ladder) rc = hmc_ladder_checks(what, coef, K, rung, C);
+  if (rc) return rc;
+  ClusterLadderArgs A{};
+  A.phi = phi; A.stats = stats; A.labels = labels_out;
+  A.V = int(p.V);
+  for (int mu = 0; mu < 4; ++mu) A.L[mu] = p.L[mu];
+  A.lab_bytes = int(p.lab_bytes);
+  A.w0 = w0;
+  A.bond_pos = philox_pos(seed, NF_PHILOX_CLUSTER_DOMAIN, offset);
+  A.flip_pos = philox_pos_after(A.bond_pos, 1);
+  A.coef = coef; A.rung = rung; A.K = K;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (ladder) return dtype == NF_F32 ? dispatch_cluster<float, true>(what, A, C, p, s) : dispatch_cluster<double, true>(what, A, C, p, s);
+  return dtype == NF_F32 ? dispatch_cluster<float, false>(what, A, C, p, s) : dispatch_cluster<double, false>(what, A, C, p, s);
 }
 
 // The sweep's draws, element-wise: u (n, 4) = the bond uniforms of index i, flip (n) = the flip bit of index i as a label
@@ -284,22 +333,15 @@ extern "C" int nf_phi4_cluster_plan(const int32_t *lattice, int dtype, nf_cluste
 
 extern "C" int nf_phi4_cluster(void *phi, int32_t *stats, int32_t *labels_out, int64_t C, const int32_t *lattice, double w0,
                                uint64_t seed, uint64_t offset, int dtype, void *stream) {
-  const char *what = "nf_phi4_cluster";
-  NF_REQUIRE(phi && stats, "%s: phi or stats is NULL", what);
-  NF_REQUIRE(C >= 1 && C <= 65535, "%s: C (%lld) must be in 1 .. 65535", what, (long long)C);
-  ClusterPlan p;
-  const int rc = cluster_plan(what, lattice, dtype, p);
-  if (rc) return rc;
-  ClusterArgs A{};
-  A.phi = phi; A.stats = stats; A.labels = labels_out;
-  A.V = int(p.V);
-  for (int mu = 0; mu < 4; ++mu) A.L[mu] = p.L[mu];
-  A.lab_bytes = int(p.lab_bytes);
-  A.w0 = w0;
-  A.bond_pos = philox_pos(seed, NF_PHILOX_CLUSTER_DOMAIN, offset);
-  A.flip_pos = philox_pos_after(A.bond_pos, 1);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return dtype == NF_F32 ? dispatch_cluster<float>(A, C, p, s) : dispatch_cluster<double>(A, C, p, s);
+  return cluster_entry("nf_phi4_cluster", false, phi, stats, labels_out, C, lattice, w0, nullptr, 0, nullptr, seed, offset,
+                       dtype, stream);
+}
+
+extern "C" int nf_phi4_cluster_ladder(void *phi, int32_t *stats, int32_t *labels_out, int64_t C, const int32_t *lattice,
+                                      const double *coef, int K, const int32_t *rung, uint64_t seed, uint64_t offset,
+                                      int dtype, void *stream) {
+  return cluster_entry("nf_phi4_cluster_ladder", true, phi, stats, labels_out, C, lattice, 0.0, coef, K, rung, seed, offset,
+                       dtype, stream);
 }
 
 extern "C" int nf_phi4_cluster_draws(double *u_out, uint8_t *flip_out, int64_t C, const int32_t *lattice, uint64_t seed,

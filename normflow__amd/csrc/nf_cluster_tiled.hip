@@ -35,6 +35,10 @@
 // rounds that a tile of the chain took stay in the workspace's flags, for whoever wants to look.
 // Workspace, per call: labels (C, V) int32 | sizes (C, V) int32 | flags (C, 2) int32 (bound hit, most local rounds) | bond
 // bytes (C, V).  Integer atomics only: the same inputs give the same bits.
+// nf_phi4_cluster_tiled_ladder compiles phases 1 and 4 a second time with LADDER: phase 1 takes w0 from row rung[c] of the
+// ladder's table, and both address the stats row (c / K) K + rung[c]; everything else, the launches included, is the same.
+#include <type_traits>
+
 #include "nf_sampler_core.h"
 #include "nf_cluster_union.h"
 
@@ -104,6 +108,22 @@ struct ClusterTiledArgs {
   PhiloxPos bond_pos, flip_pos;
 };
 
+// What LADDER adds (nf_phi4_cluster_tiled_ladder), as nf_cluster.hip's ClusterLadderArgs; w0 is unused.  Phase 1 takes w0
+// from row rung[c] of the table and phases 1 and 4 address the chain's stats row by the rung; phases 2 and 3 are the plain
+// kernels.  `rung` is not written between the launches of a call, so every workgroup of a chain reads the same rung.
+struct ClusterTiledLadderArgs : ClusterTiledArgs {
+  const double *coef;   // (K, 3): row k starts with the w0 of rung k
+  const int32_t *rung;  // (C): the rung of chain c, clamped into 0 .. K - 1 by the kernels
+  int K;
+};
+
+template <bool LADDER>
+using ClusterTiledKernelArgs = std::conditional_t<LADDER, ClusterTiledLadderArgs, ClusterTiledArgs>;
+
+// The rung of chain c, clamped, and its rung-ordered stats row (c / K) K + rung
+__device__ __forceinline__ int ladder_rung(const ClusterTiledLadderArgs &A, int64_t c) { return min(max(int(A.rung[c]), 0), A.K - 1); }
+__device__ __forceinline__ int64_t ladder_row(const ClusterTiledLadderArgs &A, int64_t c) { return c / A.K * A.K + ladder_rung(A, c); }
+
 // The label array in HBM as nf_cluster_union.h sees it
 struct DeviceAtomics {
   typedef int cell;
@@ -131,8 +151,8 @@ struct Steps {
 };
 
 // ---------------------------------------------------------------- phase 1: bonds and the labels of the tile's local links
-template <typename T>
-__global__ __launch_bounds__(kCtMaxLanes) void cluster_tiled_local_kernel(ClusterTiledArgs A) {
+template <typename T, bool LADDER>
+__global__ __launch_bounds__(kCtMaxLanes) void cluster_tiled_local_kernel(ClusterTiledKernelArgs<LADDER> A) {
   extern __shared__ __align__(16) unsigned char ct_lds[];
   volatile int *s_flag = reinterpret_cast<volatile int *>(ct_lds);     // [2]: did round r (mod 2) see a link with two labels
   int *lab = reinterpret_cast<int *>(ct_lds + kCtScratchBytes);        // slot s holds the site t0 + s
@@ -144,6 +164,13 @@ __global__ __launch_bounds__(kCtMaxLanes) void cluster_tiled_local_kernel(Cluste
   const uint64_t i0 = uint64_t(c) * uint64_t(V);
   const T *__restrict__ gphi = static_cast<const T *>(A.phi) + c * int64_t(V);
   const Steps S(A.L);
+  // LADDER: the w0 of the chain's rung, read once into scalar registers, and the rung-ordered stats row
+  double lw0 = 0.0;
+  int64_t oc = c;
+  if constexpr (LADDER) {
+    lw0 = uniform_scalar(A.coef[3 * int64_t(ladder_rung(A, c))]);
+    oc = ladder_row(A, c);
+  }
 
   if (tid < 2) s_flag[tid] = 0;
   for (int s = tid; s < n; s += NT) {
@@ -163,7 +190,7 @@ __global__ __launch_bounds__(kCtMaxLanes) void cluster_tiled_local_kernel(Cluste
       if (A.L[mu] > 1) {
         if (xs[mu] == A.L[mu] - 1) b |= 16u << mu;
         const T q = gphi[S.fwd(x, b, mu)];
-        if (cluster_bond(A.w0, double(p), double(q), philox_u32_mid(w[mu]))) b |= 1u << mu;
+        if (cluster_bond(LADDER ? lw0 : A.w0, double(p), double(q), philox_u32_mid(w[mu]))) b |= 1u << mu;
       }
     }
     lab[s] = s;
@@ -225,7 +252,7 @@ __global__ __launch_bounds__(kCtMaxLanes) void cluster_tiled_local_kernel(Cluste
     if (!settled) atomicOr(&A.flags[2 * c], 1);
     atomicMax(&A.flags[2 * c + 1], rounds);
     if (blockIdx.x == 0) {
-      int32_t *row = A.stats + 4 * c;
+      int32_t *row = A.stats + 4 * oc;
       row[0] = 0; row[1] = 0; row[2] = 0; row[3] = 0;
     }
   }
@@ -300,8 +327,8 @@ __global__ __launch_bounds__(kCtLanes) void cluster_tiled_flatten_kernel(Cluster
 }
 
 // ---------------------------------------------------------------- phase 4: flips and stats
-template <typename T>
-__global__ __launch_bounds__(kCtLanes) void cluster_tiled_flip_kernel(ClusterTiledArgs A) {
+template <typename T, bool LADDER>
+__global__ __launch_bounds__(kCtLanes) void cluster_tiled_flip_kernel(ClusterTiledKernelArgs<LADDER> A) {
   __shared__ int s_sum[3];
   const int tid = threadIdx.x, V = A.V;
   const int64_t c = blockIdx.y;
@@ -338,7 +365,9 @@ __global__ __launch_bounds__(kCtLanes) void cluster_tiled_flip_kernel(ClusterTil
   }
   __syncthreads();
   if (tid == 0) {
-    int32_t *row = A.stats + 4 * c;
+    int64_t oc = c;
+    if constexpr (LADDER) oc = ladder_row(A, c);
+    int32_t *row = A.stats + 4 * oc;
     if (!bad) {
       if (s_sum[0]) atomicAdd(&row[0], s_sum[0]);
       if (s_sum[1]) atomicAdd(&row[1], s_sum[1]);
@@ -348,10 +377,10 @@ __global__ __launch_bounds__(kCtLanes) void cluster_tiled_flip_kernel(ClusterTil
   }
 }
 
-template <typename T>
-static int launch_cluster_tiled(const ClusterTiledArgs &A, int64_t C, const ClusterTiledPlan &p, hipStream_t s) {
-  const char *what = "nf_phi4_cluster_tiled";
-  auto local = cluster_tiled_local_kernel<T>;
+template <typename T, bool LADDER>
+static int launch_cluster_tiled(const char *what, const ClusterTiledKernelArgs<LADDER> &A, int64_t C, const ClusterTiledPlan &p,
+                                hipStream_t s) {
+  auto local = cluster_tiled_local_kernel<T, LADDER>;
   // once per instantiation and for the largest tile there is: nothing is set per sweep, or inside a stream capture that
   // is not the first call
   static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void *>(local),
@@ -371,14 +400,54 @@ static int launch_cluster_tiled(const ClusterTiledArgs &A, int64_t C, const Clus
   int rc = check_launch(what);
   if (rc) return rc;
   if (p.tiles > 1) {
-    hipLaunchKernelGGL(cluster_tiled_merge_kernel, sites, dim3(kCtLanes), 0, s, A);
+    hipLaunchKernelGGL(cluster_tiled_merge_kernel, sites, dim3(kCtLanes), 0, s, static_cast<const ClusterTiledArgs &>(A));
     if ((rc = check_launch(what))) return rc;
   }
   const dim3 runs(unsigned((p.V + kCtBlockSites - 1) / kCtBlockSites), unsigned(C));
-  hipLaunchKernelGGL(cluster_tiled_flatten_kernel, runs, dim3(kCtLanes), 0, s, A);
+  hipLaunchKernelGGL(cluster_tiled_flatten_kernel, runs, dim3(kCtLanes), 0, s, static_cast<const ClusterTiledArgs &>(A));
   if ((rc = check_launch(what))) return rc;
-  hipLaunchKernelGGL(cluster_tiled_flip_kernel<T>, runs, dim3(kCtLanes), 0, s, A);
+  hipLaunchKernelGGL((cluster_tiled_flip_kernel<T, LADDER>), runs, dim3(kCtLanes), 0, s, A);
   return check_launch(what);
+}
+
+// nf_phi4_cluster_tiled (not a ladder call: coef, K and rung unused) and nf_phi4_cluster_tiled_ladder (ladder: w0 unused)
+static int cluster_tiled_entry(const char *what, bool ladder, void *phi, int32_t *stats, int32_t *labels_out, int64_t C,
+                               const int32_t *lattice, double w0, const double *coef, int K, const int32_t *rung, uint64_t seed,
+                               uint64_t offset, int dtype, int64_t tile_sites, void *workspace, size_t workspace_bytes,
+                               void *stream) {
+  NF_REQUIRE(phi && stats, "%s: phi or stats is NULL", what);
+  NF_REQUIRE(C >= 1 && C <= 65535, "%s: C (%lld) must be in 1 .. 65535", what, (long long)C);
+  ClusterTiledPlan p;
+  int rc = cluster_tiled_plan(what, lattice, dtype, tile_sites, p);
+  if (!rc && ladder) rc = hmc_ladder_checks(what, coef, K, rung, C);
+  if (rc) return rc;
+  const size_t need = cluster_tiled_workspace(C, p.V);
+  NF_REQUIRE(workspace != nullptr, "%s: workspace is NULL (%zu B needed)", what, need);
+  NF_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu B is too small, %zu B needed", what, workspace_bytes, need);
+  NF_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % kCtAlign == 0, "%s: workspace is not aligned to %zu B", what, kCtAlign);
+  const size_t n = size_t(C) * size_t(p.V);
+  ClusterTiledLadderArgs A{};
+  A.phi = phi; A.stats = stats; A.labels_out = labels_out;
+  A.lab = static_cast<int *>(workspace);
+  A.size = A.lab + n;
+  A.flags = A.size + n;
+  A.bnd = reinterpret_cast<uint8_t *>(A.flags + 2 * size_t(C));
+  A.V = int(p.V);
+  A.ts = p.ts;
+  A.tiles = int(p.tiles);
+  for (int mu = 0; mu < 4; ++mu) A.L[mu] = p.L[mu];
+  A.lab_bytes = int(p.lab_bytes);
+  A.w0 = w0;
+  A.bond_pos = philox_pos(seed, NF_PHILOX_CLUSTER_DOMAIN, offset);
+  A.flip_pos = philox_pos_after(A.bond_pos, 1);
+  A.coef = coef; A.rung = rung; A.K = K;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (ladder) {
+    return dtype == NF_F32 ? launch_cluster_tiled<float, true>(what, A, C, p, s)
+                           : launch_cluster_tiled<double, true>(what, A, C, p, s);
+  }
+  return dtype == NF_F32 ? launch_cluster_tiled<float, false>(what, A, C, p, s)
+                         : launch_cluster_tiled<double, false>(what, A, C, p, s);
 }
 
 }  // namespace nf
@@ -411,31 +480,14 @@ extern "C" size_t nf_phi4_cluster_tiled_workspace(int64_t C, const int32_t *latt
 extern "C" int nf_phi4_cluster_tiled(void *phi, int32_t *stats, int32_t *labels_out, int64_t C, const int32_t *lattice,
                                      double w0, uint64_t seed, uint64_t offset, int dtype, int64_t tile_sites, void *workspace,
                                      size_t workspace_bytes, void *stream) {
-  const char *what = "nf_phi4_cluster_tiled";
-  NF_REQUIRE(phi && stats, "%s: phi or stats is NULL", what);
-  NF_REQUIRE(C >= 1 && C <= 65535, "%s: C (%lld) must be in 1 .. 65535", what, (long long)C);
-  ClusterTiledPlan p;
-  const int rc = cluster_tiled_plan(what, lattice, dtype, tile_sites, p);
-  if (rc) return rc;
-  const size_t need = cluster_tiled_workspace(C, p.V);
-  NF_REQUIRE(workspace != nullptr, "%s: workspace is NULL (%zu B needed)", what, need);
-  NF_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu B is too small, %zu B needed", what, workspace_bytes, need);
-  NF_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % kCtAlign == 0, "%s: workspace is not aligned to %zu B", what, kCtAlign);
-  const size_t n = size_t(C) * size_t(p.V);
-  ClusterTiledArgs A{};
-  A.phi = phi; A.stats = stats; A.labels_out = labels_out;
-  A.lab = static_cast<int *>(workspace);
-  A.size = A.lab + n;
-  A.flags = A.size + n;
-  A.bnd = reinterpret_cast<uint8_t *>(A.flags + 2 * size_t(C));
-  A.V = int(p.V);
-  A.ts = p.ts;
-  A.tiles = int(p.tiles);
-  for (int mu = 0; mu < 4; ++mu) A.L[mu] = p.L[mu];
-  A.lab_bytes = int(p.lab_bytes);
-  A.w0 = w0;
-  A.bond_pos = philox_pos(seed, NF_PHILOX_CLUSTER_DOMAIN, offset);
-  A.flip_pos = philox_pos_after(A.bond_pos, 1);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return dtype == NF_F32 ? launch_cluster_tiled<float>(A, C, p, s) : launch_cluster_tiled<double>(A, C, p, s);
+  return cluster_tiled_entry("nf_phi4_cluster_tiled", false, phi, stats, labels_out, C, lattice, w0, nullptr, 0, nullptr, seed,
+                             offset, dtype, tile_sites, workspace, workspace_bytes, stream);
+}
+
+extern "C" int nf_phi4_cluster_tiled_ladder(void *phi, int32_t *stats, int32_t *labels_out, int64_t C, const int32_t *lattice,
+                                            const double *coef, int K, const int32_t *rung, uint64_t seed, uint64_t offset,
+                                            int dtype, int64_t tile_sites, void *workspace, size_t workspace_bytes,
+                                            void *stream) {
+  return cluster_tiled_entry("nf_phi4_cluster_tiled_ladder", true, phi, stats, labels_out, C, lattice, 0.0, coef, K, rung,
+                             seed, offset, dtype, tile_sites, workspace, workspace_bytes, stream);
 }

@@ -109,14 +109,6 @@ struct HmcLadderArgs : HmcMeasureArgs {
 template <bool MEASURE, bool LADDER>
 using HmcKernelArgs = std::conditional_t<LADDER, HmcLadderArgs, std::conditional_t<MEASURE, HmcMeasureArgs, HmcArgs>>;
 
-// A value every lane of the workgroup holds, moved into scalar registers: the ladder's coefficients come from memory, not
-// from the kernel's arguments, and must not cost a vector register each.
-__device__ __forceinline__ double hmc_uniform(double v) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(b)), hi = __builtin_amdgcn_readfirstlane(uint32_t(b >> 32));
-  return __builtin_bit_cast(double, uint64_t(hi) << 32 | lo);
-}
-
 // Sum of (a, b) over the workgroup, valid in every lane and the same bits in every lane: lane partials -> shuffle tree ->
 // one slot per wave -> the waves added in order.  `slot` alternates between calls, so a slot is overwritten only after a
 // barrier that follows its last read.
@@ -172,9 +164,9 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcKernelArgs<MEASURE, 
   if constexpr (LADDER) {
     const int r = min(max(int(A.rung[c]), 0), A.K - 1);
     const double *row = A.coef + 3 * int64_t(r);
-    lw0 = V > 1 ? hmc_uniform(row[0]) : 0.0;             // a lattice of one site: the site is read as its own neighbour
-    lw2 = hmc_uniform(row[1]);
-    lw4 = hmc_uniform(row[2]);
+    lw0 = V > 1 ? uniform_scalar(row[0]) : 0.0;             // a lattice of one site: the site is read as its own neighbour
+    lw2 = uniform_scalar(row[1]);
+    lw4 = uniform_scalar(row[2]);
     oc = c / A.K * A.K + r;
   }
   const T w0 = T(LADDER ? lw0 : A.w0), w2x2 = T(2) * T(LADDER ? lw2 : A.w2), w4x4 = T(4) * T(LADDER ? lw4 : A.w4), dt = T(A.dt),

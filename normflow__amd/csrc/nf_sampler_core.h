@@ -146,6 +146,14 @@ __device__ __forceinline__ double phi4_site_energy(double p, double nb_back, dou
   return __builtin_fma(__builtin_fma(w4, p2, w2), p2, -(w0 * p) * nb_back);
 }
 
+// A value every lane of the workgroup holds, moved into scalar registers: a ladder's coefficients come from memory, not
+// from the kernel's arguments, and must not cost a vector register each.
+__device__ __forceinline__ double uniform_scalar(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(b)), hi = __builtin_amdgcn_readfirstlane(uint32_t(b >> 32));
+  return __builtin_bit_cast(double, uint64_t(hi) << 32 | lo);
+}
+
 // ---------------------------------------------------------------- host side
 // The call of nf_phi4_hmc and nf_phi4_hmc_tiled, and the checks the two entry points share.
 struct HmcCall {

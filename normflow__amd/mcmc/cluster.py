@@ -21,6 +21,7 @@ def cluster_sweep(phi, w0, u, flip):
       u     (C, V, 4) float64 in (0, 1): word mu of site x decides the link (x, mu), mu counted on the lattice padded
             with leading extents 1 to four axes;
       flip  (C, V) bool or uint8: entry rho decides the cluster whose label -- its smallest site index -- is rho.
+      w0    a float, or a (C,) float64 tensor with the hopping coefficient of every chain (a coupling ladder);
     Bonds: t = (w0 phi(x)) phi(x + mu) in double, active iff t > 0 and u < -expm1(-2 t); an axis of extent 1 has no link.
     Labels: labels = min(labels, where(bond, rolled labels)) in both directions of every axis, then labels[labels]
     (pointer jumping: it lowers a label to another label of the same cluster), until a round changes nothing; at most V
@@ -37,6 +38,10 @@ def cluster_sweep(phi, w0, u, flip):
     dev = phi.device
     u = u.reshape((C,) + lat + (4,))
     f = phi.double()
+    if isinstance(w0, torch.Tensor):
+        if w0.dtype != torch.float64 or tuple(w0.shape) != (C,):
+            raise ValueError(f"cluster_sweep: a tensor w0 is ({C},) float64, one per chain, got {tuple(w0.shape)} {w0.dtype}")
+        w0 = w0.reshape((C,) + (1,) * len(lat))
     labels = torch.arange(V, dtype=torch.int64, device=dev).reshape(lat).expand((C,) + lat).contiguous()
     own = labels.clone()
     bonds = []

@@ -227,25 +227,32 @@ class HMCSampler:
             f"HMCSampler.cluster(path={path!r}): nf_phi4_cluster{'_tiled' if path == 'tiled' else ''} does not apply to a "
             f"{type(self._model.action).__name__} and a {phi.device} tensor of shape {lat} and {phi.dtype}")
 
-    def _sweep(self, phi, position=None, want_labels=False, path=None, workspace=None):
-        """(the swept copy of phi, stats[, labels]) by the path `_sweep_path` names: a kernel, or composed -- on the device
-        with the kernel's draws from the same two positions, on CPU tensors with torch's CPU generator.  `workspace`: the
-        tiled kernel's, when the caller keeps one for several sweeps."""
+    def _sweep_couplings(self, phi):
+        """What a sweep of the chains phi takes after them: (w0,); the ladder's sampler gives (coef, rung)."""
         action = self._model.action
         if not hasattr(action, 'get_coef'):
             raise TypeError("cluster sweeps need the hopping coefficient of a phi^4 action (get_coef), got a "
                             f"{type(action).__name__}")
+        return (float(action.get_coef(phi.ndim - 1)[0]),)
+
+    def _sweep(self, phi, position=None, want_labels=False, path=None, workspace=None, couplings=None):
+        """(the swept copy of phi, stats[, labels]) by the path `_sweep_path` names: a kernel, or composed -- on the device
+        with the kernel's draws from the same two positions, on CPU tensors with torch's CPU generator.  `workspace`: the
+        tiled kernel's, when the caller keeps one for several sweeps.  `couplings`: `_sweep_couplings(phi)` unless given;
+        the pair (coef, rung) goes to the ladder kernels as it is and to the composed sweep as coef[rung, 0]."""
+        couplings = self._sweep_couplings(phi) if couplings is None else couplings
+        ladder = len(couplings) == 2
         lat = tuple(phi.shape[1:])
-        w0 = float(action.get_coef(len(lat))[0])
         path = self._sweep_path(phi, path)
         if path != 'composed':
             new = phi.clone().contiguous()
-            if path == 'kernel':
-                r = _hip.phi4_cluster(new, w0, position=position, want_labels=want_labels)
-            else:
-                r = _hip.phi4_cluster_tiled(new, w0, position=position, want_labels=want_labels, workspace=workspace)
+            kernel = getattr(_hip, 'phi4_cluster' + ('_tiled' if path == 'tiled' else '') + ('_ladder' if ladder else ''))
+            kw = dict(workspace=workspace) if path == 'tiled' else {}
+            r = kernel(new, *couplings, position=position, want_labels=want_labels, **kw)
             return (new, r['stats'], r['labels']) if want_labels else (new, r['stats'])
         from .cluster import cluster_sweep
+        # a chain's rung clamped into the table, as the kernels clamp it
+        w0 = couplings[0][couplings[1].long().clamp(0, couplings[0].shape[0] - 1), 0] if ladder else couplings[0]
         C, V = phi.shape[0], phi[0].numel()
         if phi.is_cuda:
             u, flip = _hip.phi4_cluster_draws(C, lat, phi.device, position=position)

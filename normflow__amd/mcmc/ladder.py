@@ -109,7 +109,18 @@ class LadderHMCSampler(HMCSampler):
     order: 2 per trajectory and 1 per sweep.  Nothing is read back from the device inside the loop; the one read per call
     fills `history` (accept_rate, exp_mdh, dh_rms and exchange_rate: K - 1 rates accepted / tried, nan where a pair was
     never tried).  `last` holds dh and accept (trajectories, C), rung-ordered, and swapped (sweeps, R, K - 1); `_ref`
-    holds the chains' phi (C, *L), action (C) and rung (C) int32, indexed by chain."""
+    holds the chains' phi (C, *L), action (C) and rung (C) int32, indexed by chain.
+    cluster_every = Ec (sample, sample_, measure; 0 = none, the sampler as it was): one Swendsen-Wang sweep of all chains,
+    each under the hopping coefficient of the rung it holds, BEFORE every recorded step s with s % Ec == 0 (s counted
+    across calls; `start` resets it).  The exchange sweep stays AFTER every E-th step and spans end at whichever boundary
+    comes first; where both fall between the same two steps the exchange comes first and the cluster sweep uses the new
+    rungs.  The path is `HMCSampler._sweep_path`'s: nf_phi4_cluster_ladder, nf_phi4_cluster_tiled_ladder (one workspace
+    per call), or the composed `cluster_sweep` with coef[rung, 0] (its draws from nf_phi4_cluster_draws on the device,
+    from torch's CPU generator on CPU tensors; on the composed HMC path S is recomputed under the chains' rungs after a
+    sweep).  Philox positions in call order: 2 per trajectory, 1 per exchange, 2 per cluster sweep.  `last['cluster']`
+    holds the sweeps' stats (sweeps, C, 4) int32 on the device, rung-ordered.  When measuring on the fused path the
+    exchange still decides by the rows of the span's last launch: they are always taken after the last cluster sweep,
+    because sweeps precede spans.  `cluster(phi, rung)` is the bare sweep."""
 
     def __init__(self, model, ladder):
         if len(ladder) < 1:
@@ -170,13 +181,43 @@ class LadderHMCSampler(HMCSampler):
         self._steps = self._sweeps = 0
         return super().start(phi)
 
+    @torch.no_grad()
+    def cluster(self, phi, rung=None, position=None, path=None):
+        """ONE Swendsen-Wang sweep of the chains phi (C, *L), C a multiple of K, chain c under the hopping coefficient of
+        rung[c] ((C) integers; None: the identity state c % K); phi and the stored chains are left alone.  Returns
+        dict(phi, labels, stats) as `HMCSampler.cluster`, phi and labels by chain and stats (C, 4) RUNG-ORDERED: the row of
+        chain c is (c // K) K + rung[c].  `position` and `path` as in `HMCSampler.cluster`; 'kernel' and 'tiled' are
+        nf_phi4_cluster_ladder and nf_phi4_cluster_tiled_ladder."""
+        K, C = len(self._ladder), phi.shape[0]
+        if C < K or C % K != 0:
+            raise ValueError(f"cluster: the {C} chains are not a positive multiple of the K = {K} rungs")
+        rung = torch.arange(C, device=phi.device) % K if rung is None else torch.as_tensor(rung, device=phi.device)
+        if tuple(rung.shape) != (C,):
+            raise ValueError(f"cluster: rung must be ({C},), one rung per chain, got {tuple(rung.shape)}")
+        coef = self._ladder.coef_table(tuple(phi.shape[1:]), phi.device)
+        new, stats, labels = self._sweep(phi.detach(), (coef, rung.to(torch.int32).contiguous()), position=position,
+                                         want_labels=True, path=path)
+        return dict(phi=new, labels=labels, stats=stats)
+
+    def _sweep(self, phi, couplings, position=None, want_labels=False, path=None, workspace=None):
+        """HMCSampler's with `couplings` = (coef, rung) and the stats rung-ordered on every path: the ladder kernels write
+        them so, the composed sweep's are laid out by the column (c // K) K + rung[c] here."""
+        coef, rung = couplings
+        out = super()._sweep(phi, position=position, want_labels=want_labels, path=path, workspace=workspace,
+                             couplings=couplings)
+        if self._sweep_path(phi, path) != 'composed':
+            return out
+        K = coef.shape[0]
+        col = (torch.arange(phi.shape[0], device=phi.device) // K) * K + rung.long().clamp(0, K - 1)
+        return (out[0], torch.empty_like(out[1]).index_copy_(0, col, out[1])) + tuple(out[2:])
+
     def trajectory(self, *args, **kwargs):
         raise NotImplementedError("LadderHMCSampler has no single-trajectory entry: use _hip.phi4_hmc_ladder or "
                                   "model.hmc.trajectory with the rung's action")
 
     # ---- which path: HMCSampler's `_choose`, on the proxy model (whose action is a phi^4 action)
     def _advance(self, batch_size, n_chains=None, n_md=10, dt=0.1, n_skip=0, exchange_every=1, path=None, want_rows=True,
-                 want_stats=False):
+                 want_stats=False, cluster_every=0):
         """batch_size // C recorded steps.  Returns (the rung-ordered rows or None, the rung-ordered measure rows
         (steps, C, n_out) or None)."""
         K = len(self._ladder)
@@ -184,6 +225,7 @@ class LadderHMCSampler(HMCSampler):
         if C < 1 or C % K != 0:
             raise ValueError(f"n_chains ({C}) must be a positive multiple of the K = {K} rungs")
         C, n_md, every, E = self._checked(batch_size, C, n_md, n_skip, exchange_every, 'exchange_every')
+        Ec = self._checked(batch_size, C, n_md, n_skip, cluster_every, 'cluster_every')[3]
         self._restart(C)
         phi, S, rung = self._ref['sample'].clone(), self._ref['action'], self._ref['rung'].clone()
         path = self._choose(phi, path)
@@ -194,11 +236,20 @@ class LadderHMCSampler(HMCSampler):
         out = torch.empty((rows, C) + lat, dtype=phi.dtype, device=dev) if want_rows else None
         stats = _RungStats(rows, C, lat, dev) if want_stats else None
         ws = self._tiled_workspace(phi) if path == 'tiled' else None
-        dhs, accs, swaps, parities = [], [], [], []
+        sweep_ws = None
+        if Ec and self._sweep_path(phi) == 'tiled':      # one workspace for all sweeps of the call
+            need = _hip.cluster_tiled_workspace(C, lat)
+            sweep_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        dhs, accs, swaps, parities, sweeps = [], [], [], [], []
         r0 = 0
         while r0 < rows:
-            g = self._span(self._steps, rows - r0, E)
             self._ref['rung'] = rung                     # what the composed path's action reads
+            if Ec and self._steps % Ec == 0:             # after the exchange that fell between the same two steps
+                phi, st = self._sweep(phi, (coef, rung), workspace=sweep_ws)
+                sweeps.append(st)
+                if path == 'composed':
+                    S = self._model.action(phi.double()).double()
+            g = self._span(self._steps, self._span(self._steps, rows - r0, E), Ec)
             col = base + rung.long()                     # the rung-ordered column of every chain
             if stats is not None:
                 stats.col = col
@@ -226,6 +277,9 @@ class LadderHMCSampler(HMCSampler):
         swapped = torch.stack(swaps) if swaps else torch.zeros((0, C // K, K - 1), dtype=torch.uint8, device=dev)
         accepted = self._finish(dhs, accs, extra=swapped.double().sum(dim=(0, 1)))    # the accepted swaps per pair
         self.last['swapped'] = swapped
+        if Ec:
+            self.last['cluster'] = (torch.stack(sweeps) if sweeps else
+                                    torch.empty((0, C, 4), dtype=torch.int32, device=dev))
         tried = [sum(1 for p in parities if p == k % 2) * (C // K) for k in range(K - 1)]
         self.history.exchange_rate.append([n / t if t else float('nan') for n, t in zip(accepted, tried)])
         y = None if out is None else out.reshape((batch_size,) + lat)
