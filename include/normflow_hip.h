@@ -951,6 +951,56 @@ int nf_phi4_cluster_tiled_ladder(void *phi, int32_t *stats, int32_t *labels_out,
                                  const double *coef, int K, const int32_t *rung, uint64_t seed, uint64_t offset, int dtype,
                                  int64_t tile_sites, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- cluster-improved estimators from the labels of a sweep (nf_cluster_moments.hip; MI355X-side extension).  Every
+ * cluster's sign is an independent coin, so the average of an even observable over all 2^Nc sign assignments follows
+ * from per-cluster sums.  The rule, stated once:
+ * Inputs.  A chain phi (V) of dtype NF_F32 / NF_F64; its labels (V) int32, ANY keys in 0 .. V - 1: sites with equal keys
+ * are one cluster (the sweeps give the smallest site index); lattice[4] with leading extents 1 for d < 4; x is the
+ * row-major site index and x_mu its coordinate along axis mu.
+ * Fixed point.  q(w) = llrint(w 2^32), round half to even, of a double w.  Integer sums make a per-cluster sum
+ * independent of the order of its terms: integer atomics only, no floating-point atomic anywhere.  A site is IN RANGE iff
+ * |phi(x)| < 2^min(16, 30 - ceil(log2 V)); NaN and +-inf are not.  No int64 sum can overflow under it.
+ * Per-cluster sums, all int64:
+ *   A_C      = sum_{x in C} q(phi(x))
+ *   R_{C,mu} = sum_{x in C} q(phi(x) tw[off_mu + x_mu][0]),  I_{C,mu} likewise with [1], for every axis mu
+ * phi is cast to double and multiplied ONCE: that product is the only rounding before q.  tw is the caller's table of
+ * (lattice[0] + lattice[1] + lattice[2] + lattice[3], 2) doubles, off_mu = sum_{nu < mu} lattice[nu]; entry t of axis mu
+ * is meant to be (cos, sin)(2 pi t / L_mu), but the kernel uses whatever numbers it is given.
+ * Outputs.
+ *   out         (C, 6) double: sum_C a^2, sum_C a^4 and, per axis mu = 0 .. 3, sum_C r^2 + sum_C i^2, where
+ *               a = (double)A_C 2^-32 and r, i likewise from R and I.  Each of the sums over the V slots (a^2, a^4, and r^2
+ *               and i^2 of every axis, separately) is taken in a fixed order: lane l of the workgroup takes the slots
+ *               l, l + lanes, ... with explicit fma (acc = fma(a, a, acc); acc4 = fma(a a, a a, acc4)), then a shuffle
+ *               tree per wave, then the waves in order; out[2 + mu] = (sum r^2) + (sum i^2).  A row's bits depend on the
+ *               chain, its labels, the lattice and the dtype alone.  An axis of extent 1 repeats column 0.
+ *   status      (C) int32: 0 for a good chain; 1 if any site is out of range or any label lies outside 0 .. V - 1.  Such a
+ *               chain has its out row all NaN and its moments row all 0; no slot outside the chain's own is touched, and
+ *               the label check comes before any indexed access: a bad label is a refused input, never an
+ *               out-of-bounds access.
+ *   moments_out (C, V) int64 or NULL: A_C at slot = label, 0 elsewhere.
+ * With M_C = A_C 2^-32 and the signs averaged: <(sum phi)^2> = sum M_C^2; <(sum phi)^4> = 3 (sum M_C^2)^2 - 2 sum M_C^4;
+ * <|sum_x phi e^{i p x_mu}|^2> = sum_C |M~_C(p)|^2.  All three are sign-invariant (q(-w) = -q(w)): a flipped cluster gives
+ * the same bits, so they may be taken from the field before or after the flip.
+ *
+ * nf_cluster_moments: one workgroup per chain with nf_phi4_cluster's lane map, for the lattices nf_phi4_cluster_supported
+ * takes (V sizeof <= 64 KiB).  phi and the labels are read once into registers; the int64 slots live in LDS (8 V bytes per
+ * quantity) and are filled by 64-bit integer LDS adds.  The 1 + 2 d quantities (d = axes of extent > 1) go in `passes`
+ * passes of `per_pass` quantities that reuse the slot arrays: as many per pass as the 160 KiB of LDS hold behind 2 KiB of
+ * reduction slots.  Same-address contention (one cluster holding most of the lattice) is met in the lane: consecutive
+ * sites of a lane with one label are added in a register and issue ONE atomic.  Integer sums: bit-exact either way.
+ * C is 1 .. 65535.  No allocation, no host synchronisation: the call can be captured into a HIP graph.
+ * NF_EINVAL: NULL phi / labels / out / status / lattice / tw, an unsupported lattice or dtype, C out of range.
+ * nf_cluster_moments_plan / nf_cluster_moments_supported: pure host. */
+typedef struct nf_moments_plan {
+  int32_t sites_per_lane, lanes;
+  int32_t quantities, passes, per_pass;
+  int64_t lds_bytes;
+} nf_moments_plan;
+int nf_cluster_moments_supported(const int32_t *lattice, int dtype);
+int nf_cluster_moments_plan(const int32_t *lattice, int dtype, nf_moments_plan *out);
+int nf_cluster_moments(const void *phi, const int32_t *labels, double *out, int32_t *status, int64_t *moments_out,
+                       int64_t C, const int32_t *lattice, const double *tw, int dtype, void *stream);
+
 /* ---- what the samplers' rows measure (nf_measure.hip; MI355X-side extension): every sufficient statistic of N
  * configurations in one pass.  cfgs (N, V) of dtype NF_F32 / NF_F64 on lattice[4] (leading extents 1 for d < 4);
  * out (N, n_out) DOUBLE, n_out = 7 + lattice[0] + lattice[1] + lattice[2] + lattice[3], per row

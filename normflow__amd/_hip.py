@@ -6,6 +6,7 @@ HIP device, the call raises.  PyTorch is used for device memory, the current
 stream and autograd bookkeeping only.
 """
 import ctypes as C
+import math
 import os
 import threading
 import weakref
@@ -114,6 +115,9 @@ PROTOTYPES = {
     "nf_phi4_cluster_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I64]),
     "nf_phi4_cluster_tiled": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _D, C.c_uint64, C.c_uint64, _I, _I64, _P, _SZ,
                                    _P]),
+    "nf_cluster_moments_supported": (_I, [C.POINTER(C.c_int32), _I]),
+    "nf_cluster_moments_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
+    "nf_cluster_moments": (_I, [_P, _P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P]),
     "nf_phi4_cluster_ladder": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_phi4_cluster_tiled_ladder": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, C.c_uint64, C.c_uint64, _I,
                                           _I64, _P, _SZ, _P]),
@@ -2328,6 +2332,78 @@ def phi4_cluster_tiled_ladder(phi, coef, rung, position=None, want_labels=False,
     `tile_sites` and `workspace` as `phi4_cluster_tiled` takes them."""
     return _phi4_cluster_ladder_call("phi4_cluster_tiled_ladder", phi, coef, rung, position, want_labels, generator,
                                      tiled=(tile_sites, workspace))
+
+
+# ========================================================================= cluster-improved estimators (nf_cluster_moments.hip)
+class MomentsPlan(C.Structure):
+    """nf_moments_plan (include/normflow_hip.h)."""
+    _fields_ = [("sites_per_lane", C.c_int32), ("lanes", C.c_int32), ("quantities", C.c_int32), ("passes", C.c_int32),
+                ("per_pass", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
+def cluster_moments_supported(lat, dtype):
+    """True if nf_cluster_moments takes chains on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own
+    planner, pure host code."""
+    return _planner_supported("nf_cluster_moments_supported", lat, dtype)
+
+
+def cluster_moments_plan(lat, dtype):
+    """What nf_cluster_moments will do on the lattice `lat` in `dtype`: dict(sites_per_lane, lanes (of a chain's
+    workgroup), quantities (1 + 2 x the axes of extent > 1), passes, per_pass (quantities per pass), lds_bytes).  Pure
+    host code."""
+    out = _planner_plan("cluster_moments_plan", "nf_cluster_moments_plan", lat, dtype, MomentsPlan())
+    return {name: getattr(out, name) for name, _ in MomentsPlan._fields_}
+
+
+def cluster_moments_limit(V):
+    """The range of the improved estimators' fixed point: a site is in range iff |phi| < 2^min(16, 30 - ceil(log2 V))."""
+    return 2.0 ** min(16, 30 - (int(V) - 1).bit_length())
+
+
+_TWIDDLES = {}
+
+
+def twiddle_table(lat, device=None):
+    """The table tw (sum of the four padded extents, 2) float64 of nf_cluster_moments for the lattice `lat` (1 to 4 axes):
+    rows off_mu + t = (cos, sin)(2 pi t / L_mu), computed once on the host (math.cos / math.sin of the double
+    2 pi t / L_mu) and cached per (lattice, device), so that every path uses the same numbers bit for bit."""
+    lat = tuple(int(n) for n in lat)
+    key = (lat, None if device is None else str(torch.device(device)))
+    if key not in _TWIDDLES:
+        if device is not None:
+            _TWIDDLES[key] = twiddle_table(lat).to(device)
+        else:
+            rows = [(math.cos(2.0 * math.pi * t / n), math.sin(2.0 * math.pi * t / n))
+                    for n in (1,) * (4 - len(lat)) + lat for t in range(n)]
+            _TWIDDLES[key] = torch.tensor(rows, dtype=torch.float64, device='cpu')
+    return _TWIDDLES[key]
+
+
+def cluster_moments(phi, labels, want_moments=False):
+    """nf_cluster_moments: the sign-averaged sums of the C chains phi (C, *L) under the cluster decomposition labels
+    (C, *L) int32 (any keys in 0 .. V - 1; the sweeps' labels are), in ONE launch with no slab loop (C <= 65535, as the
+    sweeps).  Returns dict(out (C, 2 + d) float64 = sum_C M_C^2, sum_C M_C^4 and per axis of `L` sum_C |M~_C(p_min)|^2, with
+    M_C = the cluster's sum of phi; status (C) int32, 1 = refused (a site out of range or a label outside 0 .. V - 1: the
+    out row is NaN, the moments row 0); moments (C, *L) int64 = the clusters' fixed-point sums A_C = M_C 2^32 at slot =
+    label, or None).  The rule is stated in include/normflow_hip.h.
+    Graph capture: the launch itself neither allocates nor synchronises, but the FIRST call for a (lattice, device) copies
+    the twiddle table to the device.  Call `twiddle_table(lat, device)` (or this function once) before capturing."""
+    _require_device(phi, labels)
+    lat = tuple(phi.shape[1:])
+    if not phi.is_contiguous() or not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"cluster_moments needs contiguous phi (C, *L) with 1 to 4 lattice axes, got {tuple(phi.shape)}")
+    if labels.shape != phi.shape or labels.dtype != torch.int32 or not labels.is_contiguous() or labels.device != phi.device:
+        raise NormflowHipError(f"cluster_moments: labels must be a contiguous int32 tensor {tuple(phi.shape)} on {phi.device}, "
+                               f"got {tuple(labels.shape)} {labels.dtype} on {labels.device}")
+    Cn, dev = phi.shape[0], phi.device
+    out = torch.empty((Cn, 6), dtype=torch.float64, device=dev)
+    status = torch.empty((Cn,), dtype=torch.int32, device=dev)
+    moments = torch.empty((Cn,) + lat, dtype=torch.int64, device=dev) if want_moments else None
+    tw = twiddle_table(lat, dev)
+    _check(load().nf_cluster_moments(_ptr(phi), _ptr(labels), _ptr(out), _ptr(status), _ptr(moments), Cn, _lat4(lat),
+                                     _ptr(tw), _dtype_code(phi), _stream()), "nf_cluster_moments")
+    pad = 4 - len(lat)
+    return dict(out=torch.cat([out[:, :2], out[:, 2 + pad:]], dim=1), status=status, moments=moments)
 
 
 # ========================================================================= observables of sampler rows (nf_measure.hip)

@@ -2,7 +2,7 @@
 of include/normflow_hip.h (section "cluster updates") on any device.  `HMCSampler(cluster_every=E)` uses it for CPU
 tensors and for the device lattices that neither nf_phi4_cluster nor, by TILED_CLASSES, nf_phi4_cluster_tiled is routed
 to; on the device its `u` and `flip` come from nf_phi4_cluster_draws at the positions the kernels would use, so that it
-walks the kernels' chain."""
+walks the kernels' chain.  `cluster_moments` is the composed path of the cluster-improved estimators (nf_cluster_moments)."""
 import torch
 
 PATHS = (None, 'kernel', 'tiled', 'composed')
@@ -76,3 +76,51 @@ def cluster_sweep(phi, w0, u, flip):
     stats = torch.stack([(labels == own).reshape(C, V).sum(dim=1), flips.sum(dim=1), sizes.max(dim=1).values,
                          torch.full((C,), rounds, dtype=torch.int64, device=dev)], dim=1).to(torch.int32)
     return out, labels.to(torch.int32), stats
+
+
+def cluster_moments(phi, labels, want_moments=False):
+    """The rule of nf_cluster_moments (include/normflow_hip.h, "cluster-improved estimators") from torch ops, on any
+    device and any lattice of 1 to 4 axes with V < 2^31, fp32 / fp64: the dict of `_hip.cluster_moments`, out (C, 2 + d)
+    float64, status (C) int32, moments (C, *L) int64 or None.
+      q(w) = torch.round(w 2^32) (half to even) as int64; the clusters' sums by scatter_add_ on int64, which is exact on
+      every device, so the moments are the kernel's bit for bit; the sums of squares by `sum` in double, which agree with
+      the kernel's within rounding.
+    A chain with a site out of range (|phi| >= 2^min(16, 30 - ceil(log2 V)), NaN, inf) or a label outside 0 .. V - 1 is
+    refused: status 1, a NaN row, a zero moments row; its values never reach an index.  Nothing is read back from the
+    device."""
+    from .. import _hip
+    C, lat = phi.shape[0], tuple(phi.shape[1:])
+    if not 1 <= len(lat) <= 4:
+        raise ValueError(f"cluster_moments: lattices of 1 to 4 axes, got {lat}")
+    if labels.shape != phi.shape:
+        raise ValueError(f"cluster_moments: labels {tuple(labels.shape)} do not match phi {tuple(phi.shape)}")
+    V = 1
+    for n in lat:
+        V *= n
+    dev = phi.device
+    x = phi.double().reshape(C, V)
+    lab = labels.reshape(C, V).long()
+    bad = (~(x.abs() < _hip.cluster_moments_limit(V)) | (lab < 0) | (lab >= V)).any(dim=1)
+    x = torch.where(bad.unsqueeze(1), torch.zeros_like(x), x)
+    lab = torch.where(bad.unsqueeze(1), torch.zeros_like(lab), lab)
+    q = lambda w: torch.round(w * 2.0 ** 32).to(torch.int64)
+    slots = lambda w: torch.zeros((C, V), dtype=torch.int64, device=dev).scatter_add_(1, lab, q(w))
+    squares = lambda s: (s.double() * 2.0 ** -32).square().sum(dim=1)
+    A = slots(x)
+    a2 = (A.double() * 2.0 ** -32).square()
+    cols = [a2.sum(dim=1), a2.square().sum(dim=1)]
+    tw = _hip.twiddle_table(lat, dev)
+    site = torch.arange(V, device=dev)
+    off, stride = 4 - len(lat), V
+    for n in lat:
+        stride //= n
+        if n == 1:
+            cols.append(cols[0])
+        else:
+            t = tw[off + (site // stride) % n]              # (V, 2)
+            cols.append(squares(slots(x * t[:, 0])) + squares(slots(x * t[:, 1])))
+        off += n
+    out = torch.stack(cols, dim=1)
+    out = torch.where(bad.unsqueeze(1), torch.full_like(out, float('nan')), out)
+    moments = A.reshape((C,) + lat) if want_moments else None
+    return dict(out=out, status=bad.to(torch.int32), moments=moments)

@@ -76,7 +76,8 @@ class HMCSampler:
         return y, (-self._model.action(y)).to(y.dtype)
 
     @torch.no_grad()
-    def measure(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, return_rows=False, cluster_every=0):
+    def measure(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, return_rows=False, cluster_every=0,
+                improved=False):
         """The `Measurement` of the rows that `sample(batch_size, ...)` would return from the same chain and generator
         state, WITHOUT storing them: every recorded state is measured where it is and only its 7 + sum L sums are kept.
         The rows are in the samplers' layout (`Ensemble(m, n_chains=C)` takes it as is), the action is attached when the
@@ -87,14 +88,36 @@ class HMCSampler:
           tiled     per recorded step nf_phi4_hmc_tiled on the chains in place, then the measure kernel that
                     `observables.route` names for them, writing into that step's rows;
           composed  the same with the composed trajectory.
-        return_rows=True: (Measurement, y), y as `sample` returns it."""
+        return_rows=True: (Measurement, y), y as `sample` returns it.
+        improved=True (or 'kernel' / 'composed' to force a path of `observables.measure_improved`): every cluster sweep
+        of the call asks for its labels and the cluster-improved row of all chains is taken right after it; the
+        Measurement then carries `.improved`, an `ImprovedMeasurement` of sweeps x C rows, row s C + c = sweep s of chain
+        c (`ImprovedEnsemble(m.improved, n_chains=C)` takes it as is).  It needs cluster_every >= 1 (ValueError) and
+        changes nothing else: the Measurement, the chains, `last`, `history` and the generator are those of the call
+        without it bit for bit, and there is still one device-to-host read (the statuses stay on the device)."""
+        ipath = self._improved_path(improved, cluster_every)
         y, stats = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=return_rows, want_stats=True,
-                                 cluster_every=cluster_every)
+                                 cluster_every=cluster_every, improved=ipath)
         action = self._model.action
         m = stats.measurement(action if hasattr(action, 'get_coef') else None)
+        if ipath is not False:
+            m.improved = stats.improved
         return (m, y) if return_rows else m
 
-    def _advance(self, batch_size, n_chains, n_md, dt, n_skip, path, want_rows, want_stats, cluster_every=0):
+    @staticmethod
+    def _improved_path(improved, cluster_every):
+        """False (no improved rows), or the `path` of `observables.measure_improved`: None, 'kernel' or 'composed'."""
+        if improved is False or improved is None:
+            return False
+        if improved is not True and improved not in ('kernel', 'composed'):
+            raise ValueError(f"improved must be False, True, 'kernel' or 'composed', got {improved!r}")
+        if int(cluster_every) < 1:
+            raise ValueError("improved estimators are taken from the labels of the cluster sweeps: improved needs "
+                             f"cluster_every >= 1, got {cluster_every}")
+        return None if improved is True else improved
+
+    def _advance(self, batch_size, n_chains, n_md, dt, n_skip, path, want_rows, want_stats, cluster_every=0,
+                 improved=False):
         """batch_size // n_chains recorded steps of the chains: (the rows (batch_size, *L) or None, the `_Stats` of the
         recorded states or None); the chains, `last` and `history` updated.  cluster_every = E >= 1: the recorded steps
         are run in spans that end before the next step s (counted across calls) with s % E == 0, with one cluster sweep
@@ -113,10 +136,16 @@ class HMCSampler:
             sweep_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=phi.device)
         if path != 'composed':
             phi = phi.clone()                                     # the kernels run in place
-        dhs, accs, sweeps, r0 = [], [], [], 0
+        if improved is not False:
+            from ..lib.observables import ImprovedMeasurement, measure_improved
+        dhs, accs, sweeps, parts, r0 = [], [], [], [], 0
         while r0 < rows:
             if E and (self._steps + r0) % E == 0:
-                phi, st = self._sweep(phi, workspace=sweep_ws)
+                if improved is False:
+                    phi, st = self._sweep(phi, workspace=sweep_ws)
+                else:                                                 # the same sweep, its labels kept
+                    phi, st, labels = self._sweep(phi, workspace=sweep_ws, want_labels=True)
+                    parts.append(measure_improved(phi, labels, path=improved))
                 sweeps.append(st)
                 if path == 'composed':
                     S = self._model.action(phi.double()).double()
@@ -133,6 +162,8 @@ class HMCSampler:
         if E:
             self.last['cluster'] = (torch.stack(sweeps) if sweeps else
                                     torch.empty((0, phi.shape[0], 4), dtype=torch.int32, device=phi.device))
+        if improved is not False:                 # only `measure` asks, so there are stats to carry the rows
+            stats.improved = ImprovedMeasurement.cat(parts, tuple(phi.shape[1:]), phi.device)
         y = None if out is None else out.reshape((batch_size,) + tuple(phi.shape[1:]))
         return y, stats
 
@@ -417,6 +448,7 @@ class _Stats:
         self.lattice = tuple(phi.shape[1:])
         self.path = observables.route(phi)
         self.kernel = None
+        self.improved = None            # the call's ImprovedMeasurement, where `measure(improved=...)` asked for one
         if self.path != 'composed':
             self.kernel = _hip.lattice_measure if self.path == 'kernel' else _hip.lattice_measure_tiled
             self.out = torch.empty((rows, phi.shape[0], _hip.measure_n_out(self.lattice)), dtype=torch.float64, device=phi.device)

@@ -149,8 +149,14 @@ class LadderHMCSampler(HMCSampler):
         return y, (-self._ladder.action(y, rung)).to(y.dtype)
 
     @torch.no_grad()
-    def measure(self, batch_size=1, return_rows=False, **kwargs):
-        y, stats = self._advance(batch_size, want_rows=return_rows, want_stats=True, **kwargs)
+    def measure(self, batch_size=1, return_rows=False, improved=False, **kwargs):
+        """The list of K `Measurement`s.  improved=True / 'kernel' / 'composed' as in `HMCSampler.measure`: entry k then
+        carries `.improved`, the `ImprovedMeasurement` of rung k's sweeps x R rows (the kernel does not know the
+        couplings: a sweep's C rows are taken by chain and laid out rung-ordered, row (c // K) K + rung[c] with the rungs
+        in force at that sweep, like `last['cluster']`)."""
+        ipath = self._improved_path(improved, kwargs.get('cluster_every', 0))
+        y, rung_stats = self._advance(batch_size, want_rows=return_rows, want_stats=True, improved=ipath, **kwargs)
+        stats = rung_stats.out
         from ..lib import observables as ob
         K = len(self._ladder)
         lat = tuple(self._ref['sample'].shape[1:])
@@ -158,6 +164,10 @@ class LadderHMCSampler(HMCSampler):
         for k in range(K):
             rows = stats[:, k::K].flatten(0, 1)                    # (steps R, n_out): step-major, the samplers' layout
             ms.append(ob.Measurement(*ob._split(rows, lat), lat, self._ladder.rung(k)))
+            if ipath is not False:
+                im, C = rung_stats.improved, self._ref['sample'].shape[0]
+                pick = lambda t: t.reshape((-1, C) + tuple(t.shape[1:]))[:, k::K].flatten(0, 1)    # (sweeps R, ...)
+                ms[k].improved = ob.ImprovedMeasurement(pick(im.out), pick(im.status), lat)
         return (ms, y) if return_rows else ms
 
     def split(self, y):
@@ -217,9 +227,9 @@ class LadderHMCSampler(HMCSampler):
 
     # ---- which path: HMCSampler's `_choose`, on the proxy model (whose action is a phi^4 action)
     def _advance(self, batch_size, n_chains=None, n_md=10, dt=0.1, n_skip=0, exchange_every=1, path=None, want_rows=True,
-                 want_stats=False, cluster_every=0):
-        """batch_size // C recorded steps.  Returns (the rung-ordered rows or None, the rung-ordered measure rows
-        (steps, C, n_out) or None)."""
+                 want_stats=False, cluster_every=0, improved=False):
+        """batch_size // C recorded steps.  Returns (the rung-ordered rows or None, the `_RungStats` with the rung-ordered
+        measure rows `out` (steps, C, n_out) or None)."""
         K = len(self._ladder)
         C = int(K if n_chains is None else n_chains)
         if C < 1 or C % K != 0:
@@ -240,12 +250,18 @@ class LadderHMCSampler(HMCSampler):
         if Ec and self._sweep_path(phi) == 'tiled':      # one workspace for all sweeps of the call
             need = _hip.cluster_tiled_workspace(C, lat)
             sweep_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        dhs, accs, swaps, parities, sweeps = [], [], [], [], []
+        if improved is not False:
+            from ..lib.observables import ImprovedMeasurement, measure_improved
+        dhs, accs, swaps, parities, sweeps, parts = [], [], [], [], [], []
         r0 = 0
         while r0 < rows:
             self._ref['rung'] = rung                     # what the composed path's action reads
             if Ec and self._steps % Ec == 0:             # after the exchange that fell between the same two steps
-                phi, st = self._sweep(phi, (coef, rung), workspace=sweep_ws)
+                if improved is False:
+                    phi, st = self._sweep(phi, (coef, rung), workspace=sweep_ws)
+                else:                                    # the same sweep, its labels kept; the rows rung-ordered
+                    phi, st, labels = self._sweep(phi, (coef, rung), workspace=sweep_ws, want_labels=True)
+                    parts.append(measure_improved(phi, labels, path=improved).rows(base + rung.long()))
                 sweeps.append(st)
                 if path == 'composed':
                     S = self._model.action(phi.double()).double()
@@ -280,10 +296,12 @@ class LadderHMCSampler(HMCSampler):
         if Ec:
             self.last['cluster'] = (torch.stack(sweeps) if sweeps else
                                     torch.empty((0, C, 4), dtype=torch.int32, device=dev))
+        if improved is not False:                 # only `measure` asks, so there are stats to carry the rows
+            stats.improved = ImprovedMeasurement.cat(parts, lat, dev)
         tried = [sum(1 for p in parities if p == k % 2) * (C // K) for k in range(K - 1)]
         self.history.exchange_rate.append([n / t if t else float('nan') for n, t in zip(accepted, tried)])
         y = None if out is None else out.reshape((batch_size,) + lat)
-        return y, None if stats is None else stats.out
+        return y, stats
 
     def _run_composed(self, phi, S, rows, every, n_md, dt, sink, dhs, accs, col):
         """HMCSampler's, with the chains updated in place and dH and the accept flags rung-ordered.  Returns S."""
@@ -305,6 +323,7 @@ class _RungStats:
     def __init__(self, rows, C, lat, device):
         self.out = torch.empty((rows, C, _hip.measure_n_out(lat)), dtype=torch.float64, device=device)
         self.col = self.chain_rows = None
+        self.improved = None            # the call's rung-ordered ImprovedMeasurement, where `measure(improved=...)` asked
 
     def put(self, r, phi):
         """Step r: the chains as they lie."""

@@ -18,7 +18,13 @@
       of the active-or-not forward links that cross tiles; and the tiled sweep against nf_phi4_cluster at 16^3 x 1024,
       where both apply.  The ratios and the verdict are those of the library's default tile.
 
-    python tools/cluster_bench.py [--reps 5] [--inner 20] [--steps 1500] [--skip-tau] [--tiled]
+  --improved: instead of (a) .. (c), the cluster-improved estimators: the bare nf_cluster_moments against nf_phi4_cluster of the same build on the same thermalised
+      chains and against the composed path (`mcmc.cluster.cluster_moments`) on the device; 16^2 x 512 and 16^3 x 1024, fp32
+      and fp64, at kappa = 0.67 (one giant cluster) and kappa = 0.25 (many small ones): the two contention regimes;
+      `hmc.measure(cluster_every=1, improved=True)` against `improved=False`; and the variance of (sum phi)^2 and of
+      |phi~(p_min)|^2 over that of their improved forms on (8, 8) x 32 chains (`--steps` recorded steps after 200).
+
+    python tools/cluster_bench.py [--reps 5] [--inner 20] [--steps 1500] [--skip-tau] [--tiled | --improved]
 Prints one JSON line per shape and dtype and one for (c)."""
 import argparse
 import json
@@ -196,6 +202,93 @@ def tiled(lattice, C, dtype, reps, inner, both=False):
                 tiles=int(stats[:, 3].max().item()), local_rounds=local_rounds, other_rounds=other_rounds)
 
 
+def improved(lattice, C, dtype, kappa, reps, inner):
+    """nf_cluster_moments on thermalised chains at `kappa`, against the sweep and the composed path, timed alternately."""
+    from normflow__amd.mcmc.cluster import cluster_moments
+    prior = NormalPrior(loc=torch.zeros(lattice, dtype=dtype, device=DEV), scale=torch.ones(lattice, dtype=dtype, device=DEV))
+    model = nf.Model(net_=None, prior=prior, action=ScalarPhi4Action(**dict(COUPLINGS, kappa=kappa)))
+    s = model.hmc
+    torch.manual_seed(0)
+    s.start(n_chains=C)
+    with torch.no_grad():
+        s.measure(30 * C, n_chains=C, n_md=N_MD, dt=DT, cluster_every=1)             # thermalise, sweeps included; no rows
+        phi = s._ref['sample'].clone()
+        w0 = float(model.action.get_coef(len(lattice))[0])
+        r = _hip.phi4_cluster(phi.clone(), w0, position=(1, 0), want_labels=True)
+        labels, stats = r['labels'], r['stats'].double()
+        work = phi.clone()
+
+        def moments():
+            for _ in range(inner):
+                _hip.cluster_moments(phi, labels)
+
+        def sweep():
+            for _ in range(inner):
+                _hip.phi4_cluster(work, w0)
+
+        composed = lambda: cluster_moments(phi, labels)
+        for _ in range(2):
+            moments(); sweep(); composed()
+        torch.cuda.synchronize()
+        k, c = _hip.cluster_moments(phi, labels, want_moments=True), cluster_moments(phi, labels, want_moments=True)
+        same = bool(torch.equal(k['moments'], c['moments']) and torch.equal(k['status'], c['status']))
+        rel = ((k['out'] - c['out']).abs() / c['out'].abs()).max().item()
+        tm, ts, tc = [], [], []
+        for _ in range(reps):
+            tm.append(_ms(moments) / inner)
+            ts.append(_ms(sweep) / inner)
+            tc.append(_ms(composed))
+        # the sampler: one recorded step of one trajectory with a sweep, with and without the improved row
+        kw = dict(n_chains=C, n_md=N_MD, dt=DT, cluster_every=1)
+        plain = lambda: s.measure(4 * C, **kw)
+        with_improved = lambda: s.measure(4 * C, improved=True, **kw)
+        plain(); with_improved()
+        tp, ti = [], []
+        for _ in range(reps):
+            tp.append(_ms(plain) / 4)
+            ti.append(_ms(with_improved) / 4)
+    mm, ms, mc, mp, mi = (statistics.median(t) for t in (tm, ts, tc, tp, ti))
+    spread = max((max(t) - min(t)) / statistics.median(t) for t in (tm, tc))
+    margin = max(0.10, spread)
+    rnd = lambda t: [round(min(t), 4), round(max(t), 4)]
+    return dict(lattice=list(lattice), chains=C, dtype=str(dtype).replace("torch.", ""), kappa=kappa, launches_per_timing=inner,
+                moments_ms=round(mm, 4), moments_ms_spread=rnd(tm),
+                sweep_ms=round(ms, 4), sweep_ms_spread=rnd(ts), moments_over_sweep=round(mm / ms, 3),
+                composed_ms=round(mc, 3), composed_ms_spread=rnd(tc), composed_over_kernel=round(mc / mm, 1),
+                margin=round(margin, 3), kernel_wins=bool(mc / mm > 1 + margin), same_moments_as_composed=same,
+                max_rel_diff_of_the_doubles=rel, plan=_hip.cluster_moments_plan(lattice, dtype),
+                step_ms=round(mp, 4), step_ms_spread=rnd(tp), step_improved_ms=round(mi, 4), step_improved_ms_spread=rnd(ti),
+                improved_over_plain_step=round(mi / mp, 3),
+                mean_clusters=round(stats[:, 0].mean().item(), 1), mean_largest_fraction=round(stats[:, 2].mean().item() / phi[0].numel(), 4))
+
+
+def variance_ratios(steps):
+    """Row variance of (sum phi)^2 over that of sum_C M_C^2, and of |phi~(p_min)|^2 over that of sum_C |M~_C(p_min)|^2, with
+    the means both ways: (8, 8), 32 chains, fp64, `steps` recorded steps after 200, a sweep before every step."""
+    from normflow__amd.lib.observables import ImprovedEnsemble
+    lattice, C, drop = (8, 8), 32, 200
+    out = dict(lattice=list(lattice), chains=C, steps=steps, m_sq=COUPLINGS['m_sq'], lambd=COUPLINGS['lambd'], rows={})
+    for kappa in (0.67, 0.45, 0.35, 0.25):
+        prior = NormalPrior(loc=torch.zeros(lattice, dtype=torch.float64, device=DEV), scale=torch.ones(lattice, dtype=torch.float64, device=DEV))
+        model = nf.Model(net_=None, prior=prior, action=ScalarPhi4Action(**dict(COUPLINGS, kappa=kappa)))
+        s = model.hmc
+        torch.manual_seed(3)
+        s.start(n_chains=C)
+        with torch.no_grad():
+            m = s.measure((drop + steps) * C, n_chains=C, n_md=N_MD, dt=DT, cluster_every=1, improved=True)
+        im = m.improved
+        plain2, imp2 = (m.sum_phi ** 2)[drop * C:], im.sum_m2[drop * C:]
+        plainp, impp = (m.propagator()[:, 1] * 64)[drop * C:], im.prop1.mean(dim=1)[drop * C:]
+        e, ie = Ensemble(m, n_chains=C, drop=drop), ImprovedEnsemble(im, n_chains=C, drop=drop)
+        r4 = lambda v: [round(float(x), 4) for x in v]
+        out['rows'][str(kappa)] = dict(
+            var_ratio_m2=round((plain2.var() / imp2.var()).item(), 2), var_ratio_prop1=round((plainp.var() / impp.var()).item(), 2),
+            chi_plain=r4([64 * x for x in e.mean('m2')]), chi_improved=r4(ie.susceptibility()),
+            binder_plain=r4(e.binder()), binder_improved=r4(ie.binder()), xi2_plain=r4(e.xi2()), xi2_improved=r4(ie.xi2()),
+            refused_rows=int(im.status.sum().item()))
+    return out
+
+
 def tunnelling(steps):
     lattice, C = (8, 8), 32
     out = dict(lattice=list(lattice), chains=C, steps=steps, **COUPLINGS)
@@ -224,7 +317,16 @@ def main():
     ap.add_argument("--steps", type=int, default=1500, help="recorded steps of the tau_int run (and of its thermalisation)")
     ap.add_argument("--skip-tau", action="store_true")
     ap.add_argument("--tiled", action="store_true", help="nf_phi4_cluster_tiled on the lattices beyond nf_phi4_cluster")
+    ap.add_argument("--improved", action="store_true", help="nf_cluster_moments and the improved estimators")
     a = ap.parse_args()
+    if a.improved:
+        for lattice, C in SHAPES:
+            for dtype in (torch.float32, torch.float64):
+                for kappa in (0.67, 0.25):
+                    print(json.dumps(improved(lattice, C, dtype, kappa, a.reps, a.inner)), flush=True)
+        if not a.skip_tau:
+            print(json.dumps(variance_ratios(a.steps)), flush=True)
+        return
     if a.tiled:
         for dtype in (torch.float32, torch.float64):
             print(json.dumps(tiled((16, 16, 16), 1024, dtype, a.reps, a.inner, both=True)), flush=True)
