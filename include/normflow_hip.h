@@ -1001,6 +1001,56 @@ int nf_cluster_moments_plan(const int32_t *lattice, int dtype, nf_moments_plan *
 int nf_cluster_moments(const void *phi, const int32_t *labels, double *out, int32_t *status, int64_t *moments_out,
                        int64_t C, const int32_t *lattice, const double *tw, int dtype, void *stream);
 
+/* ---- the same estimators with the chains, the labels and the int64 slots in HBM (nf_cluster_moments_tiled.hip): for
+ * lattices beyond nf_cluster_moments' class (32^3, 16^4, 32^4, 48^4, ...).  The "cluster-improved estimators" rule above
+ * holds word for word: the fixed point q, the range test, the sums A, R, I per cluster in int64, the caller's twiddle
+ * table, status, the NaN row and the zero moments row of a refused chain, moments_out.  The clusters' integer sums are
+ * exact whatever the grouping, so moments_out and status are nf_cluster_moments' and the composed path's bit for bit.
+ * The ONE new part is the order of the sums of squares over the V slots, because one workgroup no longer sees them all:
+ *   - a chain's slots are cut into BLOCKS, runs of block_sites consecutive slot indices (the last may be short);
+ *   - within a block, lane l of 256 takes the slots first + l, first + l + 256, ... with the explicit fma forms above,
+ *     then the shuffle tree per wave, then the 4 waves in order: the block's partial;
+ *   - a last kernel adds the blocks' partials with one wave per (chain, column): lane l takes the blocks l, l + 64, ... in
+ *     order, then the shuffle tree (nf_lattice_measure_tiled's rule for its bricks);
+ *   - out[2 + mu] = (sum r^2) + (sum i^2); an axis of extent 1 repeats column 0.
+ * A row's bits depend on the chain, its labels, the lattice, the dtype and block_sites alone: not on C, not on the row's
+ * place in the batch, not on per_pass, not on the schedule.
+ * Any lattice of extents >= 1 with V < 2^31, NF_F32 / NF_F64, C in 1 .. 65535.  block_sites = 0 is the default (4096, 16
+ * sites per lane); any value from 1 upwards is legal and a value above V means V; blocks x 256 must stay below 2^32.  The
+ * 1 + 2 d quantities go in passes of per_pass quantities that reuse the slot arrays; per_pass = 0 means all in one pass.
+ * Launches, in a line on `stream` after one memset of the flags: CHECK (range and label test of every site, before
+ * anything is indexed by a label; a failing block sets the chain's flag, and every later kernel leaves a refused chain's
+ * slots alone); per pass a memset of the pass's slot arrays, SCATTER (every site's q to the slot of its label by 64-bit
+ * integer atomic adds without a return value) and SQUARES (the blocks' partials; quantity 0 also writes the moments_out
+ * row, zeros for a refused chain); FINISH (the partials in block order, the row or NaNs, status): 2 + 2 passes kernels.
+ * No floating-point atomic, no allocation, no host synchronisation: the call can be captured into a HIP graph.
+ * Same-address contention is met on chip (nf_cluster_table.h): a lane adds up its consecutive sites that share a label,
+ * then claims the label's entry of a direct-mapped table in LDS, H = 512 entries of an int32 key (-1: free) and one int64
+ * sum per quantity of the pass, entry h = label & (H - 1), by a compare-and-swap of the key; a lane that finds the entry
+ * its label's adds there (LDS integer adds), a lane that finds another label's sends its run straight to HBM; after a
+ * barrier every claimed entry sends ONE global add per non-zero sum.  Labels k, k + H, k + 2 H share an entry.  Hit, miss
+ * and flush order cannot change a bit.
+ *   workspace   nf_cluster_moments_tiled_workspace bytes, 16-byte aligned, owned by the caller, need not be initialised:
+ *               4 C bytes of flags rounded up to 16, per_pass C V 8 bytes of slots, C blocks 10 doubles of partials.
+ * nf_cluster_moments_tiled_plan (pure host): blocks per chain, the block_sites in force, quantities, per_pass (in force),
+ * passes, table entries (H), kernel launches, and the LDS bytes of the scatter kernel.  _supported (pure host): 1 or 0
+ * with the reason in nf_last_error_string.  _workspace (pure host): the bytes, 0 for a case the planner refuses or C
+ * outside 1 .. 65535.
+ * NF_EINVAL: whatever nf_cluster_moments refuses other than the lattice's class, 2^31 sites or more, block_sites < 0 or so
+ * small that blocks x 256 reaches 2^32, per_pass outside 0 .. quantities, a NULL, short or misaligned workspace. */
+typedef struct nf_moments_tiled_plan {
+  int64_t blocks;
+  int32_t block_sites, quantities, per_pass, passes, table_entries, launches;
+  int64_t lds_bytes;
+} nf_moments_tiled_plan;
+int nf_cluster_moments_tiled_supported(const int32_t *lattice, int dtype, int64_t block_sites);
+int nf_cluster_moments_tiled_plan(const int32_t *lattice, int dtype, int64_t block_sites, int per_pass,
+                                  nf_moments_tiled_plan *out);
+size_t nf_cluster_moments_tiled_workspace(int64_t C, const int32_t *lattice, int64_t block_sites, int per_pass);
+int nf_cluster_moments_tiled(const void *phi, const int32_t *labels, double *out, int32_t *status, int64_t *moments_out,
+                             int64_t C, const int32_t *lattice, const double *tw, int dtype, int64_t block_sites,
+                             int per_pass, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- what the samplers' rows measure (nf_measure.hip; MI355X-side extension): every sufficient statistic of N
  * configurations in one pass.  cfgs (N, V) of dtype NF_F32 / NF_F64 on lattice[4] (leading extents 1 for d < 4);
  * out (N, n_out) DOUBLE, n_out = 7 + lattice[0] + lattice[1] + lattice[2] + lattice[3], per row

@@ -118,6 +118,10 @@ PROTOTYPES = {
     "nf_cluster_moments_supported": (_I, [C.POINTER(C.c_int32), _I]),
     "nf_cluster_moments_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
     "nf_cluster_moments": (_I, [_P, _P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P]),
+    "nf_cluster_moments_tiled_supported": (_I, [C.POINTER(C.c_int32), _I, _I64]),
+    "nf_cluster_moments_tiled_plan": (_I, [C.POINTER(C.c_int32), _I, _I64, _I, _P]),
+    "nf_cluster_moments_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I64, _I]),
+    "nf_cluster_moments_tiled": (_I, [_P, _P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _I64, _I, _P, _SZ, _P]),
     "nf_phi4_cluster_ladder": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_phi4_cluster_tiled_ladder": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, C.c_uint64, C.c_uint64, _I,
                                           _I64, _P, _SZ, _P]),
@@ -2402,6 +2406,100 @@ def cluster_moments(phi, labels, want_moments=False):
     tw = twiddle_table(lat, dev)
     _check(load().nf_cluster_moments(_ptr(phi), _ptr(labels), _ptr(out), _ptr(status), _ptr(moments), Cn, _lat4(lat),
                                      _ptr(tw), _dtype_code(phi), _stream()), "nf_cluster_moments")
+    pad = 4 - len(lat)
+    return dict(out=torch.cat([out[:, :2], out[:, 2 + pad:]], dim=1), status=status, moments=moments)
+
+
+# ========================================================================= the same, slots in HBM (nf_cluster_moments_tiled.hip)
+class MomentsTiledPlan(C.Structure):
+    """nf_moments_tiled_plan (include/normflow_hip.h)."""
+    _fields_ = [("blocks", C.c_int64), ("block_sites", C.c_int32), ("quantities", C.c_int32), ("per_pass", C.c_int32),
+                ("passes", C.c_int32), ("table_entries", C.c_int32), ("launches", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
+def _block_sites(block_sites):
+    """None / 0: the library's default block."""
+    b = 0 if block_sites is None else int(block_sites)
+    if b < 0:
+        raise NormflowHipError(f"block_sites must be None or >= 0, got {block_sites}")
+    return b
+
+
+def _dtype_code_of(dtype):
+    return NF_F32 if dtype == torch.float32 else NF_F64 if dtype == torch.float64 else NF_F16
+
+
+def cluster_moments_tiled_supported(lat, dtype, block_sites=0):
+    """True if nf_cluster_moments_tiled takes chains on the lattice `lat` (1 to 4 extents) in `dtype` with blocks of
+    `block_sites` sites (0: the default): the launcher's own planner, pure host code."""
+    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
+        return False
+    return bool(load().nf_cluster_moments_tiled_supported(_lat4(lat), _dtype_code_of(dtype), _block_sites(block_sites)))
+
+
+def cluster_moments_tiled_plan(lat, dtype, block_sites=0, per_pass=0):
+    """What nf_cluster_moments_tiled will do on the lattice `lat` in `dtype`: dict(blocks (per chain), block_sites (in
+    force), quantities, per_pass (in force; 0 asks for all), passes, table_entries (H: labels k and k + H share an
+    entry), launches (kernels: 2 + 2 passes), lds_bytes).  Pure host code."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"cluster_moments_tiled_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
+    out = MomentsTiledPlan()
+    _check(load().nf_cluster_moments_tiled_plan(_lat4(lat), _dtype_code_of(dtype), _block_sites(block_sites),
+                                                int(per_pass or 0), C.byref(out)), "nf_cluster_moments_tiled_plan")
+    return {name: getattr(out, name) for name, _ in MomentsTiledPlan._fields_}
+
+
+def cluster_moments_tiled_workspace(Cn, lat, block_sites=0, per_pass=0):
+    """nf_cluster_moments_tiled_workspace: the bytes of the workspace of a call on Cn chains on `lat`; pure host code."""
+    return int(load().nf_cluster_moments_tiled_workspace(int(Cn), _lat4(tuple(lat)), _block_sites(block_sites),
+                                                         int(per_pass or 0)))
+
+
+def moments_max_workspace():
+    """The footprint that `cluster_moments_tiled(per_pass=None)` stays under: NF_MOMENTS_MAX_WORKSPACE bytes, 1 GiB unless
+    the environment says otherwise.  A footprint policy, not a tuned number."""
+    return int(os.environ.get("NF_MOMENTS_MAX_WORKSPACE", 1 << 30))
+
+
+def cluster_moments_tiled_per_pass(Cn, lat, block_sites=0):
+    """The `per_pass` that `cluster_moments_tiled(per_pass=None)` takes: the largest whose workspace stays under
+    `moments_max_workspace()`, and at least 1.  The workspace is linear in per_pass, so two planner calls give it."""
+    one = cluster_moments_tiled_workspace(Cn, lat, block_sites, 1)
+    step = cluster_moments_tiled_workspace(Cn, lat, block_sites, 2) - one if _sites(lat) > 1 else 0
+    nq = 1 + 2 * sum(1 for n in lat if n > 1)
+    if one == 0 or step <= 0:
+        return 1
+    return int(max(1, min(nq, 1 + (moments_max_workspace() - one) // step)))
+
+
+def cluster_moments_tiled(phi, labels, want_moments=False, block_sites=0, per_pass=None, workspace=None):
+    """nf_cluster_moments_tiled: `cluster_moments` for chains that live in HBM, any lattice of 1 to 4 axes with fewer than
+    2^31 sites; the same dict.  status and moments are `cluster_moments`' bit for bit, out differs in the order of the sums
+    of squares alone (blocks of `block_sites` slots, 0: the default; include/normflow_hip.h).  The 1 + 2 d quantities go in
+    passes of `per_pass` (None: `cluster_moments_tiled_per_pass`; it changes the footprint and the launches, never a bit).
+    2 + 2 passes launches and 1 + passes memsets on the current stream.  The workspace comes from torch's caching
+    allocator per call (stream-aware and graph-pool safe), or is `workspace`: a uint8 tensor of at least
+    nf_cluster_moments_tiled_workspace bytes.  Graph capture: as `cluster_moments`, call `twiddle_table(lat, device)` first."""
+    _require_device(phi, labels)
+    lat = tuple(phi.shape[1:])
+    if not phi.is_contiguous() or not 1 <= len(lat) <= 4:
+        raise NormflowHipError("cluster_moments_tiled needs contiguous phi (C, *L) with 1 to 4 lattice axes, got "
+                               f"{tuple(phi.shape)}")
+    if labels.shape != phi.shape or labels.dtype != torch.int32 or not labels.is_contiguous() or labels.device != phi.device:
+        raise NormflowHipError(f"cluster_moments_tiled: labels must be a contiguous int32 tensor {tuple(phi.shape)} on "
+                               f"{phi.device}, got {tuple(labels.shape)} {labels.dtype} on {labels.device}")
+    Cn, dev, bs = phi.shape[0], phi.device, _block_sites(block_sites)
+    pp = cluster_moments_tiled_per_pass(Cn, lat, bs) if per_pass is None else int(per_pass)
+    if workspace is None:
+        need = load().nf_cluster_moments_tiled_workspace(Cn, _lat4(lat), bs, pp)
+        workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    out = torch.empty((Cn, 6), dtype=torch.float64, device=dev)
+    status = torch.empty((Cn,), dtype=torch.int32, device=dev)
+    moments = torch.empty((Cn,) + lat, dtype=torch.int64, device=dev) if want_moments else None
+    tw = twiddle_table(lat, dev)
+    _check(load().nf_cluster_moments_tiled(_ptr(phi), _ptr(labels), _ptr(out), _ptr(status), _ptr(moments), Cn, _lat4(lat),
+                                           _ptr(tw), _dtype_code(phi), bs, pp, _ptr(workspace), workspace.numel(),
+                                           _stream()), "nf_cluster_moments_tiled")
     pad = 4 - len(lat)
     return dict(out=torch.cat([out[:, :2], out[:, 2 + pad:]], dim=1), status=status, moments=moments)
 

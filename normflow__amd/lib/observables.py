@@ -282,7 +282,7 @@ class Ensemble:
 
 
 # ---------------------------------------------------------------- cluster-improved estimators
-IMPROVED_PATHS = (None, 'kernel', 'composed')
+IMPROVED_PATHS = (None, 'kernel', 'composed', 'hbm')
 
 
 def improved_kernel_applies(cfgs):
@@ -306,15 +306,19 @@ def measure_improved(cfgs, labels, path=None):
     `hmc.cluster(phi)['labels']`, with the field before or after the flip) -> `ImprovedMeasurement`: the averages over
     all 2^Nc assignments of the clusters' signs, in closed form from the clusters' sums M_C (include/normflow_hip.h,
     "cluster-improved estimators").  path=None: what `route_improved` says; 'kernel' (nf_cluster_moments; raises where it
-    cannot run) or 'composed' (`mcmc.cluster.cluster_moments`: torch ops, any device) force one."""
+    cannot run), 'composed' (`mcmc.cluster.cluster_moments`: torch ops, any device) or 'hbm' (nf_cluster_moments_tiled:
+    the slots in HBM, any lattice on the device; raises on CPU tensors) force one.  `route_improved` never says 'hbm':
+    the path is opt-in until the routing is redone from measured classes."""
     if path not in IMPROVED_PATHS:
-        raise ValueError(f"path must be None, 'kernel' or 'composed', got {path!r}")
+        raise ValueError(f"path must be None, 'kernel', 'composed' or 'hbm', got {path!r}")
     if not 1 <= cfgs.ndim - 1 <= 4:
         raise ValueError(f"measure_improved: configurations (N, *L) with 1 to 4 lattice axes, got {tuple(cfgs.shape)}")
     if path is None:
         path = route_improved(cfgs)
     if path == 'kernel':
         r = _hip.cluster_moments(cfgs.contiguous(), labels.contiguous())
+    elif path == 'hbm':
+        r = _hip.cluster_moments_tiled(cfgs.contiguous(), labels.contiguous())
     else:
         from ..mcmc.cluster import cluster_moments
         r = cluster_moments(cfgs, labels)

@@ -89,7 +89,8 @@ class HMCSampler:
                     `observables.route` names for them, writing into that step's rows;
           composed  the same with the composed trajectory.
         return_rows=True: (Measurement, y), y as `sample` returns it.
-        improved=True (or 'kernel' / 'composed' to force a path of `observables.measure_improved`): every cluster sweep
+        improved=True (or 'kernel' / 'composed' / 'hbm' to force a path of `observables.measure_improved`; 'hbm' is
+        nf_cluster_moments_tiled, for the lattices beyond one CU's LDS, and opt-in): every cluster sweep
         of the call asks for its labels and the cluster-improved row of all chains is taken right after it; the
         Measurement then carries `.improved`, an `ImprovedMeasurement` of sweeps x C rows, row s C + c = sweep s of chain
         c (`ImprovedEnsemble(m.improved, n_chains=C)` takes it as is).  It needs cluster_every >= 1 (ValueError) and
@@ -106,11 +107,11 @@ class HMCSampler:
 
     @staticmethod
     def _improved_path(improved, cluster_every):
-        """False (no improved rows), or the `path` of `observables.measure_improved`: None, 'kernel' or 'composed'."""
+        """False (no improved rows), or the `path` of `observables.measure_improved`: None, 'kernel', 'composed' or 'hbm'."""
         if improved is False or improved is None:
             return False
-        if improved is not True and improved not in ('kernel', 'composed'):
-            raise ValueError(f"improved must be False, True, 'kernel' or 'composed', got {improved!r}")
+        if improved is not True and improved not in ('kernel', 'composed', 'hbm'):
+            raise ValueError(f"improved must be False, True, 'kernel', 'composed' or 'hbm', got {improved!r}")
         if int(cluster_every) < 1:
             raise ValueError("improved estimators are taken from the labels of the cluster sweeps: improved needs "
                              f"cluster_every >= 1, got {cluster_every}")

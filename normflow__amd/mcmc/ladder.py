@@ -150,7 +150,7 @@ class LadderHMCSampler(HMCSampler):
 
     @torch.no_grad()
     def measure(self, batch_size=1, return_rows=False, improved=False, **kwargs):
-        """The list of K `Measurement`s.  improved=True / 'kernel' / 'composed' as in `HMCSampler.measure`: entry k then
+        """The list of K `Measurement`s.  improved=True / 'kernel' / 'composed' / 'hbm' as in `HMCSampler.measure`: entry k then
         carries `.improved`, the `ImprovedMeasurement` of rung k's sweeps x R rows (the kernel does not know the
         couplings: a sweep's C rows are taken by chain and laid out rung-ordered, row (c // K) K + rung[c] with the rungs
         in force at that sweep, like `last['cluster']`)."""
