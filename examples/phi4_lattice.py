@@ -13,6 +13,8 @@ DistConvertor_), or a stack of RQ-spline couplings, assembled from the same name
                                                            chain at its rung's coupling before every step
     python examples/phi4_lattice.py --lat 16,16 --hmc     after the fit: <phi^2> from model.mcmc next to model.hmc, then
                                                           chi, the Binder cumulant, xi_2 and tau_int(m) of both
+    python examples/phi4_lattice.py --lat 16,16 --hmc --integrator omelyan    the same with model.hmc on the second-order
+                                                           minimum-norm integrator (or omf4) instead of leapfrog
     python examples/phi4_lattice.py --lat 8,8 --hmc --cluster    the same, and model.hmc once more with a cluster sweep of
                                                           the signs before every step: tau_int(m) with and without sweeps
     python examples/phi4_lattice.py --lat 8,8 --hmc --cluster --improved    the same, and chi = V <m^2>, U4 and xi_2 of that
@@ -89,27 +91,35 @@ def both_ways(m, n_chains, drop):
     return "\n".join(lines)
 
 
-def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False):
+# trajectories of length 1 at about the same cost in force evaluations: n_md of each integrator, dt = 1 / n_md
+INTEGRATOR_N_MD = dict(leapfrog=10, omelyan=5, omf4=2)
+
+
+def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False, integrator='leapfrog'):
     """<phi^2> of the trained flow + Metropolis next to hybrid Monte Carlo on the action itself (exact up to its own
     statistical error; the first quarter of every chain is dropped as thermalisation), then the observables of both.
     `cluster`: also model.hmc with a Swendsen-Wang sweep of the signs before every recorded step (cluster_every=1), so
-    that tau_int(m) stands next to the one without sweeps."""
+    that tau_int(m) stands next to the one without sweeps.  `integrator`: model.hmc's integration scheme, at 10 force
+    evaluations per trajectory of length 1 whichever it is."""
+    n_md = INTEGRATOR_N_MD[integrator]
+    hmc = dict(n_chains=n_chains, n_md=n_md, dt=1.0 / n_md, integrator=integrator)
     y = model.mcmc.sample(n_chains * rows, n_chains=n_chains)
     print("<phi^2>  model.mcmc  %.5f +- %.5f   (accept rate %.3f)" % (*phi2(y, n_chains, rows // 4), model.mcmc.history.accept_rate[-1]))
     obs = observables(model, y, n_chains, rows // 4)
-    y = model.hmc.sample(n_chains * rows, n_chains=n_chains, n_md=10, dt=0.1)
-    print("<phi^2>  model.hmc   %.5f +- %.5f   (accept rate %.3f)" % (*phi2(y, n_chains, rows // 4), model.hmc.history.accept_rate[-1]))
+    y = model.hmc.sample(n_chains * rows, **hmc)
+    print("<phi^2>  model.hmc   %.5f +- %.5f   (%s, n_md = %d: accept rate %.3f, rms dH %.3g)"
+          % (*phi2(y, n_chains, rows // 4), integrator, n_md, model.hmc.history.accept_rate[-1], model.hmc.history.dh_rms[-1]))
     print("model.mcmc  " + obs)
     print("model.hmc   " + observables(model, y, n_chains, rows // 4))
     if cluster:
         model.hmc.start(n_chains=n_chains)
-        y = model.hmc.sample(n_chains * rows, n_chains=n_chains, n_md=10, dt=0.1, cluster_every=1)
+        y = model.hmc.sample(n_chains * rows, cluster_every=1, **hmc)
         big = model.hmc.last['cluster'][..., 2].double().mean().item() / model.prior.nvar
         print("<phi^2>  model.hmc, cluster_every=1   %.5f +- %.5f   (accept rate %.3f, mean largest cluster %.2f of the lattice)"
               % (*phi2(y, n_chains, rows // 4), model.hmc.history.accept_rate[-1], big))
         print("model.hmc, cluster_every=1   " + observables(model, y, n_chains, rows // 4))
         if improved:
-            m = model.hmc.measure(n_chains * rows, n_chains=n_chains, n_md=10, dt=0.1, cluster_every=1, improved=True)
+            m = model.hmc.measure(n_chains * rows, cluster_every=1, improved=True, **hmc)
             print("model.hmc, cluster_every=1, the next %d steps both ways (sweeps and steps coincide: drop = 0)" % rows)
             print(both_ways(m, n_chains, 0))
 
@@ -152,6 +162,9 @@ def main():
                     help="how the spectral block filters: torch.fft, or the LDS-resident Hartley kernel (lattices up to 64 KiB per sample)")
     ap.add_argument("--hmc", action="store_true",
                     help="after the fit, print <phi^2> from model.hmc (hybrid Monte Carlo on the action) next to model.mcmc")
+    ap.add_argument("--integrator", choices=sorted(INTEGRATOR_N_MD), default="leapfrog",
+                    help="with --hmc: model.hmc's integration scheme (leapfrog, the second-order minimum-norm scheme, or the "
+                         "fourth-order one), each at 10 force evaluations per trajectory of length 1")
     ap.add_argument("--cluster", action="store_true",
                     help="with --hmc: model.hmc once more with cluster_every=1, tau_int(m) with and without cluster sweeps; "
                          "with --ladder: the ladder once more with exchanges and cluster_every=1")
@@ -175,7 +188,7 @@ def main():
         model.fit(**kw)
         nf.backward_sanitychecker(model)
         if a.hmc:
-            compare_with_hmc(model, cluster=a.cluster, improved=a.improved)
+            compare_with_hmc(model, cluster=a.cluster, improved=a.improved, integrator=a.integrator)
 
 
 if __name__ == "__main__":

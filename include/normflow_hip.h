@@ -844,6 +844,68 @@ int nf_phi4_ladder_exchange(const double *rows, int64_t row_stride, const double
                             double *action, uint8_t *swapped, int64_t C, int parity, uint64_t seed, uint64_t offset,
                             void *stream);
 
+/* ---- integration schemes of the five HMC launchers above (nf_hmc.hip, nf_hmc_tiled.hip; MI355X-side extension).  A
+ * scheme is s stages (1 <= s <= NF_HMC_MAX_STAGES) of drift weights a_1 .. a_s and kick weights b_1 .. b_s; a trajectory is
+ *   pi -= (b_s / 2) dt F(phi)
+ *   k = 1 .. n_md, j = 1 .. s:  phi += a_j dt pi;  pi -= b_j dt F(phi)     (b_s / 2 instead of b_s when k = n_md and j = s)
+ * that is n_md s force evaluations (and one more at the start).  A scheme is valid when every weight is finite, sum a =
+ * sum b = 1 within 1e-12, and the sequence is symmetric within 1e-12: a_j = a_{s+1-j}, and b_j = b_{s-j} for j < s (the
+ * trajectory then reads the same backwards: it is reversible, and of even order).
+ * nf_hmc_scheme_check (pure host code): NF_OK, or NF_EINVAL with the broken condition in nf_last_error_string.
+ * nf_hmc_scheme_named (pure host code): the library's own schemes, stated here and nowhere else:
+ *   NF_HMC_LEAPFROG  s = 1: a = (1), b = (1)
+ *   NF_HMC_OMELYAN2  s = 2: the second-order minimum-norm scheme of Omelyan, Mryglod and Folk (Comput. Phys. Commun. 151
+ *                    (2003) 272, "2MN"), lambda = 0.1931833275037836: a = (1/2, 1/2), b = (1 - 2 lambda, 2 lambda)
+ *   NF_HMC_OMF4      s = 5: their fourth-order scheme with five force evaluations per step ("OMF4" in openQCD), r1 = 0.08398315262876693, r2 = 0.2539785108410595, r3 = 0.6822365335719091,
+ *                    r4 = -0.03230286765269967: a = (r2, r4, 1 - 2 (r2 + r4), r4, r2),
+ *                    b = (r3, 1/2 - r1 - r3, 1/2 - r1 - r3, r3, 2 r1)
+ * The _scheme form of a launcher takes its arguments and `scheme` (NULL: leapfrog), checks the scheme before anything
+ * else, and runs the same kernels: the update lengths they are handed are the doubles a_j dt, b_j dt and 0.5 b_s dt formed
+ * on the host and cast to dtype by the kernel, so the fused and the tiled kernels still agree bit for bit in fp64, and
+ * leapfrog through a _scheme entry is the launcher without it bit for bit (which calls the same code with NULL).  Random
+ * numbers: two Philox positions per trajectory whatever s.  The fused kernel keeps the lengths in its by-value
+ * arguments (scalar registers and scalar loads); the tiled call issues n_md s step launches, the buffers alternating with
+ * the launch, the energies of the end written by the last one; neither needs more LDS, registers per site or workspace.
+ * The work caps count force evaluations: n_md s stands where n_md stands above,
+ *   (n_md s n_traj + NF_HMC_MEASURE_MD_STEPS measured) max(V, 256) ceil(C / 1024) <= NF_HMC_MAX_WORK
+ *   (n_md s + 2) n_traj <= NF_HMC_TILED_MAX_LAUNCHES. */
+#define NF_HMC_MAX_STAGES 8
+#define NF_HMC_LEAPFROG 0
+#define NF_HMC_OMELYAN2 1
+#define NF_HMC_OMF4 2
+typedef struct nf_hmc_scheme {
+  int32_t stages;
+  double a[NF_HMC_MAX_STAGES];
+  double b[NF_HMC_MAX_STAGES];
+} nf_hmc_scheme;
+int nf_hmc_scheme_check(const nf_hmc_scheme *scheme);
+int nf_hmc_scheme_named(int which, nf_hmc_scheme *out);
+int nf_phi4_hmc_scheme(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out, uint8_t *accept_out,
+                       void *record, int record_every, int64_t C, const int32_t *lattice, double w0, double w2, double w4,
+                       int n_md, double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset, int dtype,
+                       void *stream, const nf_hmc_scheme *scheme);
+int nf_phi4_hmc_measure_scheme(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                               uint8_t *accept_out, void *record, double *measure_out, int record_every, int64_t C,
+                               const int32_t *lattice, double w0, double w2, double w4, int n_md, double dt, int n_traj,
+                               int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream,
+                               const nf_hmc_scheme *scheme);
+int nf_phi4_hmc_ladder_scheme(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                              uint8_t *accept_out, void *record, double *measure_out, int record_every, int64_t C,
+                              const int32_t *lattice, const double *coef, int K, const int32_t *rung, int n_md, double dt,
+                              int n_traj, int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream,
+                              const nf_hmc_scheme *scheme);
+int nf_phi4_hmc_tiled_scheme(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                             uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
+                             double w0, double w2, double w4, int n_md, double dt, int n_traj, int force_accept,
+                             uint64_t seed, uint64_t offset, void *workspace, size_t workspace_bytes, int dtype,
+                             void *stream, const nf_hmc_scheme *scheme);
+int nf_phi4_hmc_tiled_ladder_scheme(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                                    uint8_t *accept_out, void *record, int record_every, int64_t C,
+                                    const int32_t *lattice, const double *coef, int K, const int32_t *rung, int n_md,
+                                    double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset,
+                                    void *workspace, size_t workspace_bytes, int dtype, void *stream,
+                                    const nf_hmc_scheme *scheme);
+
 /* ---- cluster updates of phi^4 chains (nf_cluster.hip; MI355X-side extension): one Swendsen-Wang sweep of the embedded
  * Ising signs (Brower-Tamayo: phi = s |phi|).  A sweep is never rejected, leaves sum phi^2 and sum phi^4 alone and
  * flips every cluster half of the time.  The sweep, stated once:

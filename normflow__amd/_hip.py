@@ -106,6 +106,8 @@ PROTOTYPES = {
     "nf_phi4_hmc_tiled_ladder": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, C.POINTER(C.c_int32), _P, _I, _P, _I, _D, _I,
                                       _I, C.c_uint64, C.c_uint64, _P, _SZ, _I, _P]),
     "nf_phi4_ladder_exchange": (_I, [_P, _I64, _P, _I, _P, _P, _P, _I64, _I, C.c_uint64, C.c_uint64, _P]),
+    "nf_hmc_scheme_check": (_I, [_P]),
+    "nf_hmc_scheme_named": (_I, [_I, _P]),
     "nf_phi4_cluster_supported": (_I, [C.POINTER(C.c_int32), _I]),
     "nf_phi4_cluster_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
     "nf_phi4_cluster": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _D, C.c_uint64, C.c_uint64, _I, _P]),
@@ -172,6 +174,11 @@ PROTOTYPES = {
     "nf_conv_fwd": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I, _I, _I, _I,
                          _I, _P]),
 }
+
+# the _scheme form of the five HMC launchers: the launcher's arguments and `const nf_hmc_scheme *scheme`
+for _name in ("nf_phi4_hmc", "nf_phi4_hmc_measure", "nf_phi4_hmc_ladder", "nf_phi4_hmc_tiled", "nf_phi4_hmc_tiled_ladder"):
+    PROTOTYPES[_name + "_scheme"] = (_I, PROTOTYPES[_name][1] + [_P])
+del _name
 
 _lib = None
 _lock = threading.Lock()
@@ -1916,12 +1923,73 @@ def metropolis_select(y, ref_sample, accept, keep, n_chains):
 
 
 # ========================================================================= hybrid Monte Carlo, phi^4 (nf_hmc.hip)
-HMC_MAX_WORK = 1 << 26        # NF_HMC_MAX_WORK: the cap on n_md * n_traj * max(V, 256) * ceil(C / 1024) of one launch
+HMC_MAX_WORK = 1 << 26        # NF_HMC_MAX_WORK: the cap on n_md * s * n_traj * max(V, 256) * ceil(C / 1024) of one launch
+HMC_MAX_STAGES = 8            # NF_HMC_MAX_STAGES
+HMC_SCHEMES = {'leapfrog': 0, 'omelyan': 1, 'omf4': 2}      # NF_HMC_LEAPFROG, NF_HMC_OMELYAN2, NF_HMC_OMF4
+
+
+class HmcScheme(C.Structure):
+    """nf_hmc_scheme (include/normflow_hip.h, "integration schemes"): `stages`, the drift weights `a` and the kick weights
+    `b` as tuples, and `name` (one of HMC_SCHEMES, or None for a scheme given by its weights)."""
+    _fields_ = [("stages", C.c_int32), ("_a", C.c_double * HMC_MAX_STAGES), ("_b", C.c_double * HMC_MAX_STAGES)]
+    name = None
+
+    @property
+    def a(self):
+        return tuple(self._a[:self.stages])
+
+    @property
+    def b(self):
+        return tuple(self._b[:self.stages])
+
+    def label(self):
+        """What the samplers record in `last['integrator']`: the name, or the pair of weight tuples."""
+        return self.name if self.name is not None else (self.a, self.b)
+
+    def __repr__(self):
+        return f"HmcScheme({self.name!r}, a={self.a}, b={self.b})"
+
+
+class _NullScheme:
+    """`scheme=NULL_SCHEME`: call the _scheme entry point with a NULL scheme (the library's leapfrog)."""
+    stages = 1
+
+
+NULL_SCHEME = _NullScheme()
+
+
+def hmc_scheme(which):
+    """A validated `HmcScheme`: 'leapfrog', 'omelyan' (the second-order minimum-norm scheme, 2 stages) or 'omf4' (the
+    fourth-order one, 5 stages) as the LIBRARY states them (nf_hmc_scheme_named), or a pair (a, b) of sequences of drift
+    and kick weights, checked by nf_hmc_scheme_check, which names the broken condition.  An `HmcScheme` is returned as it
+    is.  Pure host code."""
+    if isinstance(which, HmcScheme):
+        return which
+    out = HmcScheme()
+    if isinstance(which, str):
+        if which not in HMC_SCHEMES:
+            raise ValueError(f"integrator must be one of {sorted(HMC_SCHEMES)} or a pair (a, b) of weights, got {which!r}")
+        _check(load().nf_hmc_scheme_named(HMC_SCHEMES[which], C.byref(out)), "nf_hmc_scheme_named")
+        out.name = which
+        return out
+    try:
+        a, b = which
+        a, b = [float(x) for x in a], [float(x) for x in b]
+    except (TypeError, ValueError):
+        raise ValueError(f"integrator must be one of {sorted(HMC_SCHEMES)} or a pair (a, b) of weights, got {which!r}") from None
+    if len(a) != len(b):
+        raise NormflowHipError(f"hmc_scheme: {len(a)} drift weights and {len(b)} kick weights: one of each per stage")
+    out.stages = len(a)
+    for j in range(min(len(a), HMC_MAX_STAGES)):          # more stages than the struct holds: refused below by their count
+        out._a[j], out._b[j] = a[j], b[j]
+    _check(load().nf_hmc_scheme_check(C.byref(out)), "nf_hmc_scheme_check")
+    return out
 
 
 def hmc_fused_budget(V, Cn):
-    """The MD steps (n_md * n_traj, and NF_HMC_MEASURE_MD_STEPS per measured trajectory) that one launch of nf_phi4_hmc and
-    its measuring and ladder forms may hold for Cn chains of V sites: hmc_entry's rule (nf_hmc.hip)."""
+    """The force evaluations (n_md * s * n_traj, s the stages of the scheme, and NF_HMC_MEASURE_MD_STEPS per measured
+    trajectory) that one launch of nf_phi4_hmc and its measuring and ladder forms may hold for Cn chains of V sites:
+    hmc_entry's rule (nf_hmc.hip)."""
     return HMC_MAX_WORK // (max(int(V), 256) * ((int(Cn) + 1023) // 1024))
 
 
@@ -2008,12 +2076,13 @@ def _ladder_tensors(what, coef, rung, Cn, dev):
 
 
 def _phi4_hmc_call(what, phi, w0, w2, w4, n_md, dt, *, n_traj, record_every, pi_in, want_pi, force_accept, position,
-                   generator, workspace=None, record=True, ladder=None, measure=False):
+                   generator, workspace=None, record=True, ladder=None, measure=False, scheme=None):
     """The body of `phi4_hmc` and `phi4_hmc_tiled` (`what`; the library's entry point is nf_<what>; "phi4_hmc_measure" is
     `phi4_hmc(measure=True)`) and of their ladder forms ("phi4_hmc_ladder", "phi4_hmc_tiled_ladder": `ladder` = (coef,
     rung) replaces the three scalars): the argument checks, the output tensors, the Philox positions, the call and the
     dict.  Only the tiled kernels have a workspace; only the measuring entry points have `measure` (the fused ladder
-    where asked: `measure`), and rows only where `record`."""
+    where asked: `measure`), and rows only where `record`.  `scheme`: None calls nf_<what> (leapfrog, the call as it
+    always was); an `HmcScheme` (or what `hmc_scheme` takes) or NULL_SCHEME calls nf_<what>_scheme."""
     tiled = what in ("phi4_hmc_tiled", "phi4_hmc_tiled_ladder")
     has_measure_arg = what in ("phi4_hmc_measure", "phi4_hmc_ladder")
     measures = what == "phi4_hmc_measure" or (what == "phi4_hmc_ladder" and measure)
@@ -2042,13 +2111,18 @@ def _phi4_hmc_call(what, phi, w0, w2, w4, n_md, dt, *, n_traj, record_every, pi_
         workspace = torch.empty(max(hmc_tiled_workspace(Cn, lat, phi.dtype), 256), dtype=torch.uint8, device=dev)
     ws = (_ptr(workspace), workspace.numel()) if tiled else ()
     couplings = (float(w0), float(w2), float(w4)) if ladder is None else _ladder_tensors(what, *ladder, Cn, dev)[1]
+    symbol, tail = "nf_" + what, ()
+    if scheme is not None:
+        if scheme is not NULL_SCHEME:
+            scheme = hmc_scheme(scheme)
+        symbol, tail = symbol + "_scheme", (None if scheme is NULL_SCHEME else C.byref(scheme),)
     seed, offset = position if position is not None else _philox_positions(dev, 2 * max(n_traj, 1), generator)
-    _check(getattr(load(), "nf_" + what)(_ptr(phi), _ptr(action), _ptr(pi_in), _ptr(pi_out), _ptr(dh), _ptr(accept),
+    _check(getattr(load(), symbol)(_ptr(phi), _ptr(action), _ptr(pi_in), _ptr(pi_out), _ptr(dh), _ptr(accept),
                                          _ptr(record), *((_ptr(measure),) if has_measure_arg else ()),
                                          1 if record_every is None else int(record_every), Cn, _lat4(lat),
                                          *couplings, int(n_md), float(dt), n_traj,
-                                         int(bool(force_accept)), seed, offset, *ws, _dtype_code(phi), _stream()),
-           "nf_" + what)
+                                         int(bool(force_accept)), seed, offset, *ws, _dtype_code(phi), _stream(), *tail),
+           symbol)
     out = dict(action=action, dh=dh, accept=accept, record=record, pi=pi_out)
     if measures:
         out['measure'] = measure
@@ -2056,7 +2130,7 @@ def _phi4_hmc_call(what, phi, w0, w2, w4, n_md, dt, *, n_traj, record_every, pi_
 
 
 def phi4_hmc(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in=None, want_pi=False, force_accept=False,
-             position=None, generator=None, measure=False, record=True):
+             position=None, generator=None, measure=False, record=True, scheme=None):
     """nf_phi4_hmc: n_traj HMC trajectories of the C chains phi (C, *L), in place, in ONE launch.  (w0, w2, w4) are the
     kernel's coefficients (a user axis of extent 1 already folded into w2).  Returns a dict with action (C) float64 of
     the final states, dh (n_traj, C) float64, accept (n_traj, C) uint8, record (n_traj // record_every, C, *L) or None,
@@ -2064,18 +2138,21 @@ def phi4_hmc(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in=None,
     `position` = (seed, offset) and leaves the generator alone.
     measure=True: nf_phi4_hmc_measure -- the dict gains measure (n_traj // record_every, C, n_out) float64, the rows that
     `lattice_measure` gives for the recorded states, taken inside the launch; with record=False no rows are allocated
-    (record is None)."""
+    (record is None).
+    scheme: None = leapfrog by nf_phi4_hmc[_measure]; an `HmcScheme`, a name or a pair of weights (`hmc_scheme`) runs
+    nf_phi4_hmc[_measure]_scheme: n_md steps of the scheme's s stages, n_md * s force evaluations per trajectory."""
     return _phi4_hmc_call("phi4_hmc_measure" if measure else "phi4_hmc", phi, w0, w2, w4, n_md, dt, n_traj=n_traj,
                           record_every=record_every, pi_in=pi_in, want_pi=want_pi, force_accept=force_accept,
-                          position=position, generator=generator, record=record)
+                          position=position, generator=generator, record=record, scheme=scheme)
 
 
 # ========================================================================= the same, chains in HBM (nf_hmc_tiled.hip)
-HMC_TILED_MAX_LAUNCHES = 65536      # NF_HMC_TILED_MAX_LAUNCHES: the cap on (n_md + 2) * n_traj of one call
+HMC_TILED_MAX_LAUNCHES = 65536      # NF_HMC_TILED_MAX_LAUNCHES: the cap on (n_md * s + 2) * n_traj of one call
 
 
 def hmc_tiled_budget(n_md):
-    """The trajectories that one call of nf_phi4_hmc_tiled and its ladder form may hold."""
+    """The trajectories that one call of nf_phi4_hmc_tiled and its ladder form may hold; `n_md` counts the force
+    evaluations of a trajectory: n_md * s for a scheme of s stages."""
     return HMC_TILED_MAX_LAUNCHES // (int(n_md) + 2)
 
 
@@ -2109,14 +2186,14 @@ def hmc_tiled_plan(lat, dtype):
 
 
 def phi4_hmc_tiled(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in=None, want_pi=False, force_accept=False,
-                   position=None, generator=None, workspace=None):
+                   position=None, generator=None, workspace=None, scheme=None):
     """nf_phi4_hmc_tiled: `phi4_hmc` for chains that live in HBM, any lattice of 1 to 4 axes; the same arguments, the same
-    Philox positions and the same dict.  (n_md + 2) * n_traj launches on the current stream.  The workspace comes from
+    Philox positions and the same dict.  (n_md * s + 2) * n_traj launches on the current stream (s = 1 without `scheme`).  The workspace comes from
     torch's caching allocator per call (stream-aware and graph-pool safe, like `_workspace`), or is `workspace`: a uint8
     tensor of at least nf_phi4_hmc_tiled_workspace bytes."""
     return _phi4_hmc_call("phi4_hmc_tiled", phi, w0, w2, w4, n_md, dt, n_traj=n_traj, record_every=record_every,
                           pi_in=pi_in, want_pi=want_pi, force_accept=force_accept, position=position, generator=generator,
-                          workspace=workspace)
+                          workspace=workspace, scheme=scheme)
 
 
 # ========================================================================= coupling ladders (nf_hmc.hip, nf_hmc_tiled.hip, nf_ladder.hip)
@@ -2124,22 +2201,22 @@ LADDER_MAX_K = 1024           # the rungs nf_phi4_ladder_exchange takes
 
 
 def phi4_hmc_ladder(phi, coef, rung, n_md, dt, n_traj=1, record_every=None, pi_in=None, want_pi=False, force_accept=False,
-                    position=None, generator=None, measure=False, record=True):
+                    position=None, generator=None, measure=False, record=True, scheme=None):
     """nf_phi4_hmc_ladder: `phi4_hmc` with per-chain couplings.  coef (K, 3) float64 holds (w0, w2, w4) per rung (a user
     axis of extent 1 folded into w2), rung (C) int32 the rung of every chain; chain c is in replica set c // K.  The dict
     is `phi4_hmc`'s, with dh, accept, record and measure RUNG-ORDERED (column (c // K) K + rung[c]) and action, pi per
     chain.  The same Philox positions."""
     return _phi4_hmc_call("phi4_hmc_ladder", phi, None, None, None, n_md, dt, n_traj=n_traj, record_every=record_every,
                           pi_in=pi_in, want_pi=want_pi, force_accept=force_accept, position=position, generator=generator,
-                          record=record, ladder=(coef, rung), measure=measure)
+                          record=record, ladder=(coef, rung), measure=measure, scheme=scheme)
 
 
 def phi4_hmc_tiled_ladder(phi, coef, rung, n_md, dt, n_traj=1, record_every=None, pi_in=None, want_pi=False,
-                          force_accept=False, position=None, generator=None, workspace=None):
+                          force_accept=False, position=None, generator=None, workspace=None, scheme=None):
     """nf_phi4_hmc_tiled_ladder: `phi4_hmc_tiled` with per-chain couplings, as `phi4_hmc_ladder`."""
     return _phi4_hmc_call("phi4_hmc_tiled_ladder", phi, None, None, None, n_md, dt, n_traj=n_traj,
                           record_every=record_every, pi_in=pi_in, want_pi=want_pi, force_accept=force_accept,
-                          position=position, generator=generator, workspace=workspace, ladder=(coef, rung))
+                          position=position, generator=generator, workspace=workspace, ladder=(coef, rung), scheme=scheme)
 
 
 def ladder_exchange(rows, coef, rung, parity, action=None, position=None, generator=None):

@@ -20,6 +20,10 @@
 // its time series (dH, accept flag, record row, measure row) at the rung-ordered column (c / K) K + rung[c]; its state, its
 // momenta and its Philox draws stay at c.  From there on it is the code above: a chain on rung k has nf_phi4_hmc's bits
 // at rung k's coefficients.  The exchange sweep that permutes `rung` between launches is nf_ladder.hip.
+// Integration schemes (the _scheme entry points; include/normflow_hip.h): the MD loop runs n_md s stages "phi += a_j dt pi
+// | barrier | image <- phi | barrier | pi -= b_j dt F(image)" with the lengths a_j dt, b_j dt and (b_s / 2) dt formed on the
+// host (HmcSteps, nf_sampler_core.h) and carried in the by-value arguments; leapfrog is s = 1 through the same loop, and
+// its lengths dt and dt / 2 are the bits they always were.
 #include <type_traits>
 
 #include "nf_measure_core.h"
@@ -85,10 +89,11 @@ struct HmcArgs {
   void *record;
   int64_t C, V;
   int L[4];
-  double w0, w2, w4, dt;
+  double w0, w2, w4;
   int n_md, n_traj, record_every, force;
   uint32_t k0n, k1n, k0a, k1a;   // keys of the normal and of the accept stream
   uint64_t offset;
+  HmcSteps steps;                // the scheme's update lengths (nf_sampler_core.h): uniform, read by scalar loads
 };
 
 // What MEASURE adds to the kernel's arguments; the kernels without it take HmcArgs as before.
@@ -144,8 +149,17 @@ __device__ __noinline__ void hmc_measure_image(int e0, int e1, int e2, int e3, i
   measure_image<T, false>(img, nullptr, nullptr, E, E, off, 0, -1, tl, nt, 0, 0, mred, msp, dst, live);
 }
 
+// The waves per SIMD that the light instantiations are compiled for -- float with one or two sites per lane and no
+// measure code (7 and 6), and the 256-lane double kernel with the measure and the ladder code (4): what they had before
+// the MD loop took its lengths from memory.  Left alone the register allocator spends a dozen registers more on them (on
+// the unrolled reads of the wave sums, not on the loop), and a CU holds fewer chains of up to 2048 sites.  1: no request.
+template <typename T, int NS, int LANES, bool MEASURE, bool LADDER>
+constexpr int kHmcMinWaves = sizeof(T) == 4 ? (MEASURE || NS > 2 ? 1 : NS == 1 ? 7 : 6)
+                                            : (LANES == 256 && MEASURE && LADDER ? 4 : 1);
+
 template <typename T, int NS, int D, int LANES, bool MEASURE, bool LADDER>
-__global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcKernelArgs<MEASURE, LADDER> A) {
+__global__ __launch_bounds__(LANES, (kHmcMinWaves<T, NS, LANES, MEASURE, LADDER>))
+void phi4_hmc_kernel(HmcKernelArgs<MEASURE, LADDER> A) {
   extern __shared__ __align__(16) unsigned char hmc_lds[];
   double *red = reinterpret_cast<double *>(hmc_lds);                       // 2 slots x 16 waves x 2 doubles = 512 B
   int *s_ok = reinterpret_cast<int *>(hmc_lds + 512);
@@ -169,8 +183,7 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcKernelArgs<MEASURE, 
     lw4 = uniform_scalar(row[2]);
     oc = c / A.K * A.K + r;
   }
-  const T w0 = T(LADDER ? lw0 : A.w0), w2x2 = T(2) * T(LADDER ? lw2 : A.w2), w4x4 = T(4) * T(LADDER ? lw4 : A.w4), dt = T(A.dt),
-          hdt = T(0.5) * T(A.dt);
+  const T w0 = T(LADDER ? lw0 : A.w0), w2x2 = T(2) * T(LADDER ? lw2 : A.w2), w4x4 = T(4) * T(LADDER ? lw4 : A.w4);
   const int s3 = 1, s2 = A.L[3], s1 = A.L[3] * A.L[2], s0 = A.L[3] * A.L[2] * A.L[1];
   const int st[4] = {s0, s1, s2, s3};
   // A.L holds the D axes of extent > 1 (HmcPlan): axes 4 - D .. 3 have neighbours, the others are not looked at
@@ -217,6 +230,23 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcKernelArgs<MEASURE, 
   auto back = [&](int i, uint32_t f, int mu) { return i + ((f >> (2 * mu)) & 1u ? st[mu] * (A.L[mu] - 1) : -st[mu]); };
   auto fwd = [&](int i, uint32_t f, int mu) { return i + ((f >> (2 * mu + 1)) & 1u ? -st[mu] * (A.L[mu] - 1) : st[mu]); };
 
+  // The scheme's lengths where the stage is a loop variable: read from the kernel's argument segment itself, in the
+  // constant address space, so that a uniform index makes scalar loads.  (Indexing the by-value copy `A` with a variable
+  // would make the compiler keep both arrays in vector registers.)  The kernel has one argument, at offset 0, and
+  // HmcArgs is the first base of every argument struct.
+  using KernArgByte = const __attribute__((address_space(4))) unsigned char;
+  using KernArgDouble = const __attribute__((address_space(4))) double;
+  KernArgDouble *lens = reinterpret_cast<KernArgDouble *>((KernArgByte *)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                         offsetof(HmcArgs, steps) + offsetof(HmcSteps, drift));
+  static_assert(offsetof(HmcSteps, kick) == offsetof(HmcSteps, drift) + NF_HMC_MAX_STAGES * sizeof(double),
+                "kick follows drift");
+  // An update length of the scheme, cast to the field type: uniform, and kept in scalar registers
+  auto length = [&](double v) {
+    if constexpr (sizeof(T) == 4)
+      return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, float(v))));
+    else
+      return v;
+  };
   // pi -= step * F(phi), the neighbours from the image (which holds phi)
   auto kick = [&](T step) {
     const int tv = fresh();
@@ -289,15 +319,29 @@ __global__ __launch_bounds__(LANES) void phi4_hmc_kernel(HmcKernelArgs<MEASURE, 
     double k0, e0;
     energy(k0, e0);
     hmc_sum2(k0, e0, red, slot);
-    // ---- leapfrog
+    // ---- the molecular dynamics: n_md steps of the scheme's stages, one force evaluation (two barriers) per stage; the
+    // loop's bounds and lengths are uniform, so every barrier below is met by the whole workgroup
+    const T hdt = length(A.steps.kick_half);
     kick(hdt);
-    for (int k = 1; k <= A.n_md; ++k) {
+    {
+      // one flat loop over the n_md s force evaluations, its body straight-line code; the two lengths of a stage are
+      // two scalar loads at a uniform index (leapfrog: always the same two), asked for one stage ahead so that they
+      // arrive behind the barriers of the stage before
+      const int evals = A.n_md * A.steps.stages;
+      double da = lens[0], db = lens[NF_HMC_MAX_STAGES];
+      for (int n = 1, j = 0; n <= evals; ++n) {
+        j = j + 1 == A.steps.stages ? 0 : j + 1;
+        const double na = lens[j], nb = lens[NF_HMC_MAX_STAGES + j];
+        const T ta = length(da);
 #pragma unroll
-      for (int j = 0; j < NS; ++j) phi[j] += dt * pi[j];
-      __syncthreads();                                   // every lane has read the old image
-      put_image();
-      __syncthreads();
-      kick(k == A.n_md ? hdt : dt);
+        for (int q = 0; q < NS; ++q) phi[q] += ta * pi[q];
+        __syncthreads();                                 // every lane has read the old image
+        put_image();
+        __syncthreads();
+        kick(n == evals ? hdt : length(db));
+        da = na;
+        db = nb;
+      }
     }
     double k1, e1;
     energy(k1, e1);
@@ -431,36 +475,41 @@ static int hmc_entry(const char *what, bool ladder, bool measures, double *measu
                      const void *pi_in, void *pi_out, double *dh_out, uint8_t *accept_out, void *record, int record_every,
                      int64_t C, const int32_t *lattice, double w0, double w2, double w4, const double *coef, int K,
                      const int32_t *rung, int n_md, double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset,
-                     int dtype, void *stream) {
+                     int dtype, void *stream, const nf_hmc_scheme *scheme) {
+  HmcSteps steps;
+  int rc = hmc_steps(what, scheme, dt, steps);           // the scheme first: a bad one is refused before anything else
+  if (rc) return rc;
   const HmcCall Kc{phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C, n_md, n_traj,
                    force_accept != 0, seed, offset};     // for the shared checks only: HmcArgs below keeps its kernel layout
   HmcPlan p;
-  int rc = hmc_call_checks(what, Kc);
+  rc = hmc_call_checks(what, Kc);
   if (!rc && ladder) rc = hmc_ladder_checks(what, coef, K, rung, C);
   if (!rc) rc = hmc_plan(what, lattice, dtype, p);
   if (rc) return rc;
   NF_REQUIRE(ladder || !measures || measure_out != nullptr, "%s: measure_out is NULL", what);
   // an MD step costs two barriers however few the sites: below 256 sites the steps, not the sites, set the time; and the
   // chains beyond the resident ones wait for a free CU: the time grows with every further 1024 chains
+  // the caps count force evaluations: n_md s of them per trajectory, s the stages of the scheme (1: leapfrog)
   const int64_t per_step = (p.V > 256 ? p.V : 256) * ((C + 1023) / 1024);
+  const int64_t evals = int64_t(n_md) * steps.stages;
   if (!measures) {
-    const int64_t work = int64_t(n_md) * int64_t(n_traj) * per_step;
+    const int64_t work = evals * int64_t(n_traj) * per_step;
     NF_REQUIRE(work <= NF_HMC_MAX_WORK,
-               "%s: n_md n_traj max(V, 256) ceil(C / 1024) = %lld exceeds NF_HMC_MAX_WORK (%lld): split the run into "
-               "several launches", what, (long long)work, (long long)NF_HMC_MAX_WORK);
+               "%s: n_md s n_traj max(V, 256) ceil(C / 1024) = %lld (s = %d stages) exceeds NF_HMC_MAX_WORK (%lld): split "
+               "the run into several launches", what, (long long)work, steps.stages, (long long)NF_HMC_MAX_WORK);
   } else {
-    const int64_t work = (int64_t(n_md) * int64_t(n_traj) + int64_t(NF_HMC_MEASURE_MD_STEPS) * (n_traj / record_every)) * per_step;
+    const int64_t work = (evals * int64_t(n_traj) + int64_t(NF_HMC_MEASURE_MD_STEPS) * (n_traj / record_every)) * per_step;
     NF_REQUIRE(work <= NF_HMC_MAX_WORK,
-               "%s: (n_md n_traj + NF_HMC_MEASURE_MD_STEPS (n_traj / record_every)) max(V, 256) "
-               "ceil(C / 1024) = %lld exceeds NF_HMC_MAX_WORK (%lld): split the run into several launches", what,
-               (long long)work, (long long)NF_HMC_MAX_WORK);
+               "%s: (n_md s n_traj + NF_HMC_MEASURE_MD_STEPS (n_traj / record_every)) max(V, 256) "
+               "ceil(C / 1024) = %lld (s = %d stages) exceeds NF_HMC_MAX_WORK (%lld): split the run into several launches",
+               what, (long long)work, steps.stages, (long long)NF_HMC_MAX_WORK);
   }
   HmcLadderArgs A{};
   A.phi = phi; A.action_out = action_out; A.pi_in = pi_in; A.pi_out = pi_out; A.dh_out = dh_out; A.accept_out = accept_out;
   A.record = record; A.C = C; A.V = p.V;
   for (int mu = 0; mu < 4; ++mu) A.L[mu] = p.L[mu];
   A.w0 = p.V > 1 ? w0 : 0.0;     // the one site of a lattice of one site is read as its own neighbour: weight 0
-  A.w2 = w2; A.w4 = w4; A.dt = dt;
+  A.w2 = w2; A.w4 = w4; A.steps = steps;
   A.n_md = n_md; A.n_traj = n_traj; A.record_every = record_every; A.force = force_accept != 0;
   // the keys of the two streams; the kernel adds 2 t (+ 1) to the offset itself
   const PhiloxPos kn = philox_pos(seed, NF_PHILOX_KEY_DOMAIN, offset), ka = philox_pos(seed, NF_PHILOX_ACCEPT_DOMAIN, offset);
@@ -513,7 +562,7 @@ extern "C" int nf_phi4_hmc(void *phi, double *action_out, const void *pi_in, voi
                            uint64_t seed, uint64_t offset, int dtype, void *stream) {
   return hmc_entry("nf_phi4_hmc", false, false, nullptr, phi, action_out, pi_in, pi_out, dh_out, accept_out, record,
                    record_every, C, lattice, w0, w2, w4, nullptr, 0, nullptr, n_md, dt, n_traj, force_accept, seed, offset,
-                   dtype, stream);
+                   dtype, stream, nullptr);
 }
 
 extern "C" int nf_phi4_hmc_measure(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
@@ -522,7 +571,7 @@ extern "C" int nf_phi4_hmc_measure(void *phi, double *action_out, const void *pi
                                    int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream) {
   return hmc_entry("nf_phi4_hmc_measure", false, true, measure_out, phi, action_out, pi_in, pi_out, dh_out, accept_out,
                    record, record_every, C, lattice, w0, w2, w4, nullptr, 0, nullptr, n_md, dt, n_traj, force_accept, seed,
-                   offset, dtype, stream);
+                   offset, dtype, stream, nullptr);
 }
 
 extern "C" int nf_phi4_hmc_ladder(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
@@ -531,5 +580,70 @@ extern "C" int nf_phi4_hmc_ladder(void *phi, double *action_out, const void *pi_
                                   int n_traj, int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream) {
   return hmc_entry("nf_phi4_hmc_ladder", true, measure_out != nullptr, measure_out, phi, action_out, pi_in, pi_out, dh_out,
                    accept_out, record, record_every, C, lattice, 0.0, 0.0, 0.0, coef, K, rung, n_md, dt, n_traj,
-                   force_accept, seed, offset, dtype, stream);
+                   force_accept, seed, offset, dtype, stream, nullptr);
+}
+
+// The same launchers with an integration scheme (NULL: leapfrog, the launchers above).
+extern "C" int nf_phi4_hmc_scheme(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                           uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
+                           double w0, double w2, double w4, int n_md, double dt, int n_traj, int force_accept,
+                           uint64_t seed, uint64_t offset, int dtype, void *stream, const nf_hmc_scheme *scheme) {
+  return hmc_entry("nf_phi4_hmc_scheme", false, false, nullptr, phi, action_out, pi_in, pi_out, dh_out, accept_out, record,
+                   record_every, C, lattice, w0, w2, w4, nullptr, 0, nullptr, n_md, dt, n_traj, force_accept, seed, offset,
+                   dtype, stream, scheme);
+}
+
+extern "C" int nf_phi4_hmc_measure_scheme(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                                   uint8_t *accept_out, void *record, double *measure_out, int record_every, int64_t C,
+                                   const int32_t *lattice, double w0, double w2, double w4, int n_md, double dt, int n_traj,
+                                   int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream, const nf_hmc_scheme *scheme) {
+  return hmc_entry("nf_phi4_hmc_measure_scheme", false, true, measure_out, phi, action_out, pi_in, pi_out, dh_out, accept_out,
+                   record, record_every, C, lattice, w0, w2, w4, nullptr, 0, nullptr, n_md, dt, n_traj, force_accept, seed,
+                   offset, dtype, stream, scheme);
+}
+
+extern "C" int nf_phi4_hmc_ladder_scheme(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                                  uint8_t *accept_out, void *record, double *measure_out, int record_every, int64_t C,
+                                  const int32_t *lattice, const double *coef, int K, const int32_t *rung, int n_md, double dt,
+                                  int n_traj, int force_accept, uint64_t seed, uint64_t offset, int dtype, void *stream, const nf_hmc_scheme *scheme) {
+  return hmc_entry("nf_phi4_hmc_ladder_scheme", true, measure_out != nullptr, measure_out, phi, action_out, pi_in, pi_out, dh_out,
+                   accept_out, record, record_every, C, lattice, 0.0, 0.0, 0.0, coef, K, rung, n_md, dt, n_traj,
+                   force_accept, seed, offset, dtype, stream, scheme);
+}
+
+extern "C" int nf_hmc_scheme_check(const nf_hmc_scheme *scheme) { return hmc_scheme_checks("nf_hmc_scheme_check", scheme); }
+
+extern "C" int nf_hmc_scheme_named(int which, nf_hmc_scheme *out) {
+  NF_REQUIRE(out != nullptr, "nf_hmc_scheme_named: out is NULL");
+  nf_hmc_scheme sc{};
+  switch (which) {
+    case NF_HMC_LEAPFROG:
+      sc.stages = 1;
+      sc.a[0] = sc.b[0] = 1.0;
+      break;
+    case NF_HMC_OMELYAN2: {
+      const double lambda = 0.1931833275037836;
+      sc.stages = 2;
+      sc.a[0] = sc.a[1] = 0.5;
+      sc.b[0] = 1.0 - 2.0 * lambda;
+      sc.b[1] = 2.0 * lambda;
+      break;
+    }
+    case NF_HMC_OMF4: {
+      const double r1 = 0.08398315262876693, r2 = 0.2539785108410595, r3 = 0.6822365335719091, r4 = -0.03230286765269967;
+      sc.stages = 5;
+      sc.a[0] = sc.a[4] = r2;
+      sc.a[1] = sc.a[3] = r4;
+      sc.a[2] = 1.0 - 2.0 * (r2 + r4);
+      sc.b[0] = sc.b[3] = r3;
+      sc.b[1] = sc.b[2] = 0.5 - r1 - r3;
+      sc.b[4] = 2.0 * r1;
+      break;
+    }
+    default:
+      set_error("nf_hmc_scheme_named: no scheme %d (NF_HMC_LEAPFROG, NF_HMC_OMELYAN2, NF_HMC_OMF4)", which);
+      return NF_EINVAL;
+  }
+  *out = sc;
+  return NF_OK;
 }

@@ -28,6 +28,9 @@
 // nf_phi4_hmc_tiled_ladder: the same kernels compiled with LADDER.  begin and step take the coefficients of the chain
 // their workgroup works on from row rung[c] of a table; commit writes dH, the accept flag and the record row at the
 // rung-ordered column (c / K) K + rung[c].  The same launches, the same workspace, the same plan.
+// Integration schemes (the _scheme entry points; include/normflow_hip.h): the step kernel always took its drift length
+// (dt) and its kick length (eps) per launch, so a scheme of s stages is n_md s step launches with the lengths a_j dt and
+// b_j dt of HmcSteps (nf_sampler_core.h), begin kicking by (b_s / 2) dt and the last launch likewise; leapfrog is s = 1.
 #include <type_traits>
 
 #include "nf_sampler_core.h"
@@ -519,7 +522,7 @@ static int raise_lds(const TiledPlan &p) {
 }
 
 template <typename T, int VEC, typename Args>
-static int run_tiled(const HmcCall &K, unsigned char *ws, Args A, const TiledPlan &p, hipStream_t s) {
+static int run_tiled(const HmcCall &K, const HmcSteps &st, unsigned char *ws, Args A, const TiledPlan &p, hipStream_t s) {
   constexpr bool LADDER = kTiledLadder<Args>;
   int rc = raise_lds<T, VEC, LADDER>(p);
   if (rc) return rc;
@@ -527,24 +530,28 @@ static int run_tiled(const HmcCall &K, unsigned char *ws, Args A, const TiledPla
   double *part = reinterpret_cast<double *>(ws);
   unsigned char *base = ws + round256(size_t(K.C) * size_t(p.tiles) * 4 * sizeof(double));
   void *fphi[2] = {base, base + field}, *fpi[2] = {base + 2 * field, base + 3 * field};
-  const double dt = A.dt;
   A.part = part;
+  const int evals = K.n_md * st.stages;                // step launches of a trajectory: one per force evaluation
   const int64_t per_chain = (p.V + kTiledLanes * 8 - 1) / (kTiledLanes * 8);
   const unsigned cblocks = unsigned(per_chain < 1024 ? per_chain : 1024);
   for (int t = 0; t < K.n_traj; ++t) {
     A.pos = philox_pos(K.seed, NF_PHILOX_KEY_DOMAIN, K.offset + 2 * uint64_t(t));
     A.phi_src = K.phi; A.pi_src = K.pi_in; A.phi_dst = nullptr; A.pi_dst = fpi[0];
-    A.eps = 0.5 * dt;
+    A.dt = 0.0;                                        // begin moves no site
+    A.eps = st.kick_half;
     if ((rc = launch_tiled_step<T, VEC>(0, A, p, K.C, s))) return rc;
     const void *src = K.phi;
-    for (int k = 1; k <= K.n_md; ++k) {
+    // launch k of the n_md s: stage (k - 1) % s of the scheme, the buffers alternating with k, the last launch with
+    // the half kick and the energies of the end
+    for (int k = 1, j = 0; k <= evals; ++k, j = j + 1 == st.stages ? 0 : j + 1) {
       A.phi_src = src; A.pi_src = fpi[(k - 1) & 1]; A.phi_dst = fphi[(k - 1) & 1]; A.pi_dst = fpi[k & 1];
-      A.eps = k == K.n_md ? 0.5 * dt : dt;
-      if ((rc = launch_tiled_step<T, VEC>(k == K.n_md ? 2 : 1, A, p, K.C, s))) return rc;
+      A.dt = st.drift[j];
+      A.eps = k == evals ? st.kick_half : st.kick[j];
+      if ((rc = launch_tiled_step<T, VEC>(k == evals ? 2 : 1, A, p, K.C, s))) return rc;
       src = A.phi_dst;
     }
     std::conditional_t<LADDER, CommitLadderArgs, CommitArgs> Q{};
-    Q.phi = K.phi; Q.prop = src; Q.pi_fin = fpi[K.n_md & 1];
+    Q.phi = K.phi; Q.prop = src; Q.pi_fin = fpi[evals & 1];
     const bool due = K.record && (t + 1) % K.record_every == 0;
     Q.record = due ? static_cast<T *>(K.record) + int64_t((t + 1) / K.record_every - 1) * K.C * p.V : nullptr;
     Q.pi_out = t + 1 == K.n_traj ? K.pi_out : nullptr;
@@ -612,21 +619,24 @@ static int tiled_entry(const char *what, bool ladder, void *phi, double *action_
                        double *dh_out, uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
                        double w0, double w2, double w4, const double *coef, int Kr, const int32_t *rung, int n_md, double dt,
                        int n_traj, int force_accept, uint64_t seed, uint64_t offset, void *workspace, size_t workspace_bytes,
-                       int dtype, void *stream) {
+                       int dtype, void *stream, const nf_hmc_scheme *scheme) {
+  HmcSteps st;
+  int rc = hmc_steps(what, scheme, dt, st);              // the scheme first: a bad one is refused before anything else
+  if (rc) return rc;
   const HmcCall K{phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C, n_md, n_traj,
                   force_accept != 0, seed, offset};
   TiledPlan p;
-  int rc = hmc_call_checks(what, K);
+  rc = hmc_call_checks(what, K);
   if (!rc && ladder) rc = hmc_ladder_checks(what, coef, Kr, rung, C);
   if (!rc) rc = tiled_plan(what, lattice, dtype, p);
   if (rc) return rc;
   NF_REQUIRE(int64_t(p.tiles) * C <= kTiledMaxGroups,
              "%s: %d tiles x %lld chains exceed the %lld workgroups of one launch: run the chains in several "
              "calls", what, p.tiles, (long long)C, (long long)kTiledMaxGroups);
-  const int64_t launches = (int64_t(n_md) + 2) * int64_t(n_traj);
+  const int64_t launches = (int64_t(n_md) * st.stages + 2) * int64_t(n_traj);
   NF_REQUIRE(launches <= NF_HMC_TILED_MAX_LAUNCHES,
-             "%s: (n_md + 2) n_traj = %lld launches exceed NF_HMC_TILED_MAX_LAUNCHES (%d): split the run into "
-             "several calls", what, (long long)launches, NF_HMC_TILED_MAX_LAUNCHES);
+             "%s: (n_md s + 2) n_traj = %lld launches (s = %d stages) exceed NF_HMC_TILED_MAX_LAUNCHES (%d): split the run "
+             "into several calls", what, (long long)launches, st.stages, NF_HMC_TILED_MAX_LAUNCHES);
   const size_t elem = dtype == NF_F32 ? 4 : 8;
   const size_t need = tiled_workspace(C, p, elem);
   NF_REQUIRE(workspace != nullptr && workspace_bytes >= need, "%s: workspace %zu B < %zu B needed", what,
@@ -639,7 +649,7 @@ static int tiled_entry(const char *what, bool ladder, void *phi, double *action_
     A.n[a] = p.n[a];
   }
   A.ring = p.ring; A.tiles = p.tiles;
-  A.w0 = w0; A.w2 = w2; A.w4 = w4; A.dt = dt;
+  A.w0 = w0; A.w2 = w2; A.w4 = w4;
   A.coef = coef; A.rung = rung; A.K = Kr;
   // 16-byte accesses need every row to start on 16 bytes: the lattice's fastest extent a multiple of 16 / sizeof (the
   // plan's vec) and the caller's fields aligned; the workspace's fields are, when the workspace is
@@ -650,12 +660,12 @@ static int tiled_entry(const char *what, bool ladder, void *phi, double *action_
   hipStream_t s = static_cast<hipStream_t>(stream);
   unsigned char *ws = static_cast<unsigned char *>(workspace);
   if (ladder) {
-    if (dtype == NF_F32) return wide ? run_tiled<float, 4>(K, ws, A, p, s) : run_tiled<float, 1>(K, ws, A, p, s);
-    return wide ? run_tiled<double, 2>(K, ws, A, p, s) : run_tiled<double, 1>(K, ws, A, p, s);
+    if (dtype == NF_F32) return wide ? run_tiled<float, 4>(K, st, ws, A, p, s) : run_tiled<float, 1>(K, st, ws, A, p, s);
+    return wide ? run_tiled<double, 2>(K, st, ws, A, p, s) : run_tiled<double, 1>(K, st, ws, A, p, s);
   }
   const TiledArgs &B = A;
-  if (dtype == NF_F32) return wide ? run_tiled<float, 4>(K, ws, B, p, s) : run_tiled<float, 1>(K, ws, B, p, s);
-  return wide ? run_tiled<double, 2>(K, ws, B, p, s) : run_tiled<double, 1>(K, ws, B, p, s);
+  if (dtype == NF_F32) return wide ? run_tiled<float, 4>(K, st, ws, B, p, s) : run_tiled<float, 1>(K, st, ws, B, p, s);
+  return wide ? run_tiled<double, 2>(K, st, ws, B, p, s) : run_tiled<double, 1>(K, st, ws, B, p, s);
 }
 
 extern "C" int nf_phi4_hmc_tiled(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
@@ -665,7 +675,7 @@ extern "C" int nf_phi4_hmc_tiled(void *phi, double *action_out, const void *pi_i
                                  void *stream) {
   return tiled_entry("nf_phi4_hmc_tiled", false, phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C,
                      lattice, w0, w2, w4, nullptr, 0, nullptr, n_md, dt, n_traj, force_accept, seed, offset, workspace,
-                     workspace_bytes, dtype, stream);
+                     workspace_bytes, dtype, stream, nullptr);
 }
 
 extern "C" int nf_phi4_hmc_tiled_ladder(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
@@ -675,5 +685,26 @@ extern "C" int nf_phi4_hmc_tiled_ladder(void *phi, double *action_out, const voi
                                         void *workspace, size_t workspace_bytes, int dtype, void *stream) {
   return tiled_entry("nf_phi4_hmc_tiled_ladder", true, phi, action_out, pi_in, pi_out, dh_out, accept_out, record,
                      record_every, C, lattice, 0.0, 0.0, 0.0, coef, K, rung, n_md, dt, n_traj, force_accept, seed, offset,
-                     workspace, workspace_bytes, dtype, stream);
+                     workspace, workspace_bytes, dtype, stream, nullptr);
+}
+
+// The same launchers with an integration scheme (NULL: leapfrog, the launchers above).
+extern "C" int nf_phi4_hmc_tiled_scheme(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                                 uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice,
+                                 double w0, double w2, double w4, int n_md, double dt, int n_traj, int force_accept,
+                                 uint64_t seed, uint64_t offset, void *workspace, size_t workspace_bytes, int dtype,
+                                 void *stream, const nf_hmc_scheme *scheme) {
+  return tiled_entry("nf_phi4_hmc_tiled_scheme", false, phi, action_out, pi_in, pi_out, dh_out, accept_out, record, record_every, C,
+                     lattice, w0, w2, w4, nullptr, 0, nullptr, n_md, dt, n_traj, force_accept, seed, offset, workspace,
+                     workspace_bytes, dtype, stream, scheme);
+}
+
+extern "C" int nf_phi4_hmc_tiled_ladder_scheme(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                                        uint8_t *accept_out, void *record, int record_every, int64_t C,
+                                        const int32_t *lattice, const double *coef, int K, const int32_t *rung, int n_md,
+                                        double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset,
+                                        void *workspace, size_t workspace_bytes, int dtype, void *stream, const nf_hmc_scheme *scheme) {
+  return tiled_entry("nf_phi4_hmc_tiled_ladder_scheme", true, phi, action_out, pi_in, pi_out, dh_out, accept_out, record,
+                     record_every, C, lattice, 0.0, 0.0, 0.0, coef, K, rung, n_md, dt, n_traj, force_accept, seed, offset,
+                     workspace, workspace_bytes, dtype, stream, scheme);
 }

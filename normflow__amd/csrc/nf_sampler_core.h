@@ -1,8 +1,10 @@
 // nf_sampler_core.h -- what nf_normal_sample (nf_endpoints.hip), nf_mcmc.hip, nf_hmc.hip and nf_hmc_tiled.hip share,
 // stated ONCE: Philox4x32-10, a stream position, the normal draw of a group and the accept uniform (the counter layouts
 // of include/normflow_hip.h), the HMC accept rule, the replica-exchange rule of the coupling ladders, the draws and the
-// bond test of the cluster sweep (nf_cluster.hip), the phi^4 site terms and the entry checks of the HMC kernels.
+// bond test of the cluster sweep (nf_cluster.hip), the phi^4 site terms, the entry checks of the HMC kernels and the update lengths of their integration schemes.
 #pragma once
+#include <cmath>
+
 #include "nf_internal.h"
 
 namespace nf {
@@ -175,6 +177,59 @@ inline int hmc_call_checks(const char *what, const HmcCall &K) {
   NF_REQUIRE(K.n_md >= 1 && K.n_traj >= 1 && K.record_every >= 1,
              "%s: n_md (%d), n_traj (%d) and record_every (%d) must be >= 1", what, K.n_md, K.n_traj, K.record_every);
   NF_REQUIRE(!K.pi_in || K.n_traj == 1, "%s: pi_in replaces the momenta of ONE trajectory (n_traj = %d)", what, K.n_traj);
+  return NF_OK;
+}
+
+// The validity conditions of an integration scheme (include/normflow_hip.h, "integration schemes"), in the order the
+// header states them; the message names the broken one.
+inline int hmc_scheme_checks(const char *what, const nf_hmc_scheme *sc) {
+  NF_REQUIRE(sc != nullptr, "%s: scheme is NULL", what);
+  const int s = sc->stages;
+  NF_REQUIRE(s >= 1 && s <= NF_HMC_MAX_STAGES, "%s: scheme: stages (%d) must be in 1 .. %d", what, s, NF_HMC_MAX_STAGES);
+  double sa = 0.0, sb = 0.0;
+  for (int j = 0; j < s; ++j) {
+    NF_REQUIRE(std::isfinite(sc->a[j]) && std::isfinite(sc->b[j]), "%s: scheme: weight %d (a = %g, b = %g) is not finite",
+               what, j + 1, sc->a[j], sc->b[j]);
+    sa += sc->a[j];
+    sb += sc->b[j];
+  }
+  NF_REQUIRE(std::fabs(sa - 1.0) <= 1e-12, "%s: scheme: the drift weights sum to %.17g, not to 1 (sum a)", what, sa);
+  NF_REQUIRE(std::fabs(sb - 1.0) <= 1e-12, "%s: scheme: the kick weights sum to %.17g, not to 1 (sum b)", what, sb);
+  for (int j = 0; j < s; ++j)
+    NF_REQUIRE(std::fabs(sc->a[j] - sc->a[s - 1 - j]) <= 1e-12,
+               "%s: scheme: the drift weights are not symmetric (a_%d = %.17g, a_%d = %.17g)", what, j + 1, sc->a[j], s - j,
+               sc->a[s - 1 - j]);
+  for (int j = 0; j + 1 < s; ++j)
+    NF_REQUIRE(std::fabs(sc->b[j] - sc->b[s - 2 - j]) <= 1e-12,
+               "%s: scheme: the kick weights are not symmetric (b_%d = %.17g, b_%d = %.17g)", what, j + 1, sc->b[j],
+               s - 1 - j, sc->b[s - 2 - j]);
+  return NF_OK;
+}
+
+// The lengths of a trajectory's updates as the kernels take them: the doubles a_j dt, b_j dt and (b_s / 2) dt, formed here
+// and nowhere else (the kernels cast them to the field type), so that the fused and the tiled kernels move by the same
+// bits.  Leapfrog: 1 dt and 0.5 dt are exact, the lengths the kernels always took.
+struct HmcSteps {
+  int stages;
+  double drift[NF_HMC_MAX_STAGES], kick[NF_HMC_MAX_STAGES], kick_half;
+};
+// `sc` NULL: leapfrog.
+inline int hmc_steps(const char *what, const nf_hmc_scheme *sc, double dt, HmcSteps &st) {
+  st = HmcSteps{};
+  if (sc == nullptr) {
+    st.stages = 1;
+    st.drift[0] = st.kick[0] = dt;
+    st.kick_half = 0.5 * dt;
+    return NF_OK;
+  }
+  const int rc = hmc_scheme_checks(what, sc);
+  if (rc) return rc;
+  st.stages = sc->stages;
+  for (int j = 0; j < sc->stages; ++j) {
+    st.drift[j] = sc->a[j] * dt;
+    st.kick[j] = sc->b[j] * dt;
+  }
+  st.kick_half = 0.5 * sc->b[sc->stages - 1] * dt;
   return NF_OK;
 }
 

@@ -7,6 +7,12 @@ One definition, three implementations.  For C independent chains, per trajectory
     pi -= (dt / 2) F(phi);  k = 1 .. n_md: phi += dt pi, pi -= (dt, or dt / 2 when k = n_md) F(phi)
     H1 likewise;  accept iff log u < -(H1 - H0), u in (0, 1];  a rejected chain keeps its phi bit for bit.
 The energies are taken in double whatever the field dtype.
+That is leapfrog, the default `integrator`.  In general an integrator is a scheme of s stages of drift weights a and kick
+weights b (include/normflow_hip.h, "integration schemes"; `_hip.hmc_scheme`): 'leapfrog', 'omelyan' (second-order
+minimum norm, s = 2), 'omf4' (fourth order, s = 5) or a pair (a, b), and a trajectory is
+    pi -= (b_s / 2) dt F(phi);  k = 1 .. n_md, j = 1 .. s: phi += a_j dt pi, pi -= b_j dt F(phi)
+    (b_s / 2 instead of b_s at the very end)
+with n_md s force evaluations, the same two random draws and no more memory, on all three implementations.
   * fused:    nf_phi4_hmc (nf_hmc.hip), a whole run of trajectories of a chain in one launch with the chain resident in a
               CU -- ScalarPhi4Action on a HIP device, lattices nf_phi4_hmc_supported takes;
   * tiled:    nf_phi4_hmc_tiled (nf_hmc_tiled.hip), the chains in HBM and many workgroups per chain, n_md + 2 launches per
@@ -36,7 +42,7 @@ class HMCHistory:
 
 
 class HMCSampler:
-    """`sample(batch_size, n_chains=C, n_md=10, dt=0.1, n_skip=0, path=None)` -> (batch_size, *L): row r is recorded
+    """`sample(batch_size, n_chains=C, n_md=10, dt=0.1, n_skip=0, path=None, integrator='leapfrog')` -> (batch_size, *L): row r is recorded
     trajectory r // C of chain r % C (the layout of the other samplers), with n_skip unrecorded trajectories before every
     recorded one.  `_ref` keeps the chains' phi (C, *L) and S (C) float64; the next call continues them, `start()` sets
     them.  `path`: None = the fused kernel where it applies, else the tiled kernels where they apply (they beat the composed path on
@@ -69,15 +75,18 @@ class HMCSampler:
         return self.sample_(batch_size=batch_size, **kwargs)[0]
 
     @torch.no_grad()
-    def sample_(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, cluster_every=0):
-        """(y, logp): batch_size // n_chains recorded trajectories of every chain and logp = -S(y) in the field dtype."""
+    def sample_(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, cluster_every=0,
+                integrator='leapfrog'):
+        """(y, logp): batch_size // n_chains recorded trajectories of every chain and logp = -S(y) in the field dtype.
+        `integrator`: 'leapfrog', 'omelyan', 'omf4', a pair (a, b) of weights or an `_hip.HmcScheme`; anything but
+        leapfrog is recorded in `last['integrator']` (the name, or the pair of weight tuples)."""
         y, _ = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=True, want_stats=False,
-                             cluster_every=cluster_every)
+                             cluster_every=cluster_every, integrator=integrator)
         return y, (-self._model.action(y)).to(y.dtype)
 
     @torch.no_grad()
     def measure(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, return_rows=False, cluster_every=0,
-                improved=False):
+                improved=False, integrator='leapfrog'):
         """The `Measurement` of the rows that `sample(batch_size, ...)` would return from the same chain and generator
         state, WITHOUT storing them: every recorded state is measured where it is and only its 7 + sum L sums are kept.
         The rows are in the samplers' layout (`Ensemble(m, n_chains=C)` takes it as is), the action is attached when the
@@ -98,7 +107,7 @@ class HMCSampler:
         without it bit for bit, and there is still one device-to-host read (the statuses stay on the device)."""
         ipath = self._improved_path(improved, cluster_every)
         y, stats = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=return_rows, want_stats=True,
-                                 cluster_every=cluster_every, improved=ipath)
+                                 cluster_every=cluster_every, improved=ipath, integrator=integrator)
         action = self._model.action
         m = stats.measurement(action if hasattr(action, 'get_coef') else None)
         if ipath is not False:
@@ -117,13 +126,19 @@ class HMCSampler:
                              f"cluster_every >= 1, got {cluster_every}")
         return None if improved is True else improved
 
+    @staticmethod
+    def _scheme(integrator):
+        """None for leapfrog by its name (the samplers then make the calls they always made), else the `_hip.HmcScheme`."""
+        return None if isinstance(integrator, str) and integrator == 'leapfrog' else _hip.hmc_scheme(integrator)
+
     def _advance(self, batch_size, n_chains, n_md, dt, n_skip, path, want_rows, want_stats, cluster_every=0,
-                 improved=False):
+                 improved=False, integrator='leapfrog'):
         """batch_size // n_chains recorded steps of the chains: (the rows (batch_size, *L) or None, the `_Stats` of the
         recorded states or None); the chains, `last` and `history` updated.  cluster_every = E >= 1: the recorded steps
         are run in spans that end before the next step s (counted across calls) with s % E == 0, with one cluster sweep
         of all chains in front of each such step; the span's launches are those of a call of that many steps."""
         n_chains, n_md, every, E = self._checked(batch_size, n_chains, n_md, n_skip, cluster_every, 'cluster_every')
+        scheme = self._scheme(integrator)
         self._restart(n_chains)
         phi, S = self._ref['sample'], self._ref['action']
         path = self._choose(phi, path)
@@ -153,13 +168,13 @@ class HMCSampler:
             k = self._span(self._steps + r0, rows - r0, E)
             sink = _Span(out, stats, r0)
             if path == 'composed':
-                phi, S = self._run_composed(phi, S, k, every, n_md, dt, sink, dhs, accs)
+                phi, S = self._run_composed(phi, S, k, every, n_md, dt, sink, dhs, accs, scheme)
             else:
-                S = self._run(path, phi, self._coef(phi.shape[1:]), k, every, n_md, dt, ws, sink, dhs, accs)
+                S = self._run(path, phi, self._coef(phi.shape[1:]), k, every, n_md, dt, ws, sink, dhs, accs, scheme)
             r0 += k
         self._steps += rows
         self._ref.update(sample=phi, action=S)
-        self._finish(dhs, accs)
+        self._finish(dhs, accs, scheme=scheme)
         if E:
             self.last['cluster'] = (torch.stack(sweeps) if sweeps else
                                     torch.empty((0, phi.shape[0], 4), dtype=torch.int32, device=phi.device))
@@ -199,11 +214,14 @@ class HMCSampler:
         need = _hip.hmc_tiled_workspace(phi.shape[0], tuple(phi.shape[1:]), phi.dtype)
         return torch.empty(max(need, 256), dtype=torch.uint8, device=phi.device)
 
-    def _finish(self, dhs, accs, extra=None):
+    def _finish(self, dhs, accs, extra=None, scheme=None):
         """`last` = the call's dH and accept flags (trajectories, C), left on the device, and `history`'s three entries,
-        by the call's ONE device-to-host read; the float64 vector `extra` rides in it and comes back as a list."""
+        by the call's ONE device-to-host read; the float64 vector `extra` rides in it and comes back as a list.  A
+        `scheme` (an integrator other than leapfrog) is recorded as `last['integrator']`."""
         dh, acc = (dhs[0], accs[0]) if len(dhs) == 1 else (torch.cat(dhs), torch.cat(accs))
         self.last = dict(dh=dh, accept=acc)
+        if scheme is not None:
+            self.last['integrator'] = scheme.label()
         got = torch.stack([acc.double().mean(), torch.exp(-dh).mean(), dh.square().mean().sqrt()])
         got = (got if extra is None else torch.cat([got, extra])).cpu().tolist()
         for key, val in zip(HMCHistory._KEYS, got):
@@ -295,17 +313,21 @@ class HMCSampler:
         return (new, stats, labels) if want_labels else (new, stats)
 
     @torch.no_grad()
-    def trajectory(self, phi, n_md=10, dt=0.1, pi=None, force_accept=False, path=None, position=None):
+    def trajectory(self, phi, n_md=10, dt=0.1, pi=None, force_accept=False, path=None, position=None,
+                   integrator='leapfrog'):
         """ONE trajectory of the chains phi (C, *L), which are left alone; the stored chains are not touched.  Returns
         dict(phi = the states after the decision, pi = the momenta at the end of the trajectory, dh (C) float64,
         accept (C) uint8, action (C) float64 = S of the returned states).  `pi` replaces the drawn momenta.  `position`
-        = (seed, offset) fixes the Philox position of a device run instead of taking it from torch's CUDA generator."""
+        = (seed, offset) fixes the Philox position of a device run instead of taking it from torch's CUDA generator.
+        `integrator` as in `sample_`."""
         phi = phi.detach().clone().contiguous()
         path = self._choose(phi, path)
+        scheme = self._scheme(integrator)
         if path != 'composed':
             kernel = _hip.phi4_hmc if path == 'fused' else _hip.phi4_hmc_tiled
+            kw = {} if scheme is None else dict(scheme=scheme)
             r = kernel(phi, *self._coef(phi.shape[1:]), n_md, dt, n_traj=1, pi_in=pi, want_pi=True,
-                       force_accept=force_accept, position=position)
+                       force_accept=force_accept, position=position, **kw)
             return dict(phi=phi, pi=r['pi'], dh=r['dh'][0], accept=r['accept'][0], action=r['action'])
         gen = None
         if position is not None:
@@ -313,7 +335,8 @@ class HMCSampler:
             gen.manual_seed(position[0])
             gen.set_offset(4 * position[1])
         S0 = self._model.action(phi.double()).double()
-        phi, S, dh, acc, pi = self._trajectory_composed(phi, S0, n_md, dt, pi=pi, force_accept=force_accept, generator=gen)
+        phi, S, dh, acc, pi = self._trajectory_composed(phi, S0, n_md, dt, pi=pi, force_accept=force_accept, generator=gen,
+                                                        scheme=scheme)
         return dict(phi=phi, pi=pi, dh=dh, accept=acc, action=S)
 
     def ladder(self, ladder):
@@ -367,21 +390,25 @@ class HMCSampler:
         return float(w0), float(w2 - own * w0), float(w4)
 
     # ---- fused and tiled
-    def _run(self, path, phi, couplings, rows, every, n_md, dt, ws, sink, dhs, accs):
+    def _run(self, path, phi, couplings, rows, every, n_md, dt, ws, sink, dhs, accs, scheme=None):
         """`rows` recorded steps of the chains phi, IN PLACE, by the kernel of `path`, in the launches that `schedule`
         (mcmc/schedule.py) cuts them into under the kernel's work cap (`_hip.hmc_fused_budget`, `_hip.hmc_tiled_budget`).
         `couplings`: (w0, w2, w4), or the ladder kernels' (coef, rung).  Rows and statistics go to `sink` (a `_Span`), dH
-        and the accept flags of every launch to the lists.  Returns S (C) of the chains."""
+        and the accept flags of every launch to the lists.  Returns S (C) of the chains.  `scheme` (None: leapfrog, and
+        the calls as they always were): the caps count force evaluations, so the budget and the schedule are fed
+        n_md * s, and every launch gets the scheme."""
         tiled, ladder = path == 'tiled', len(couplings) == 2
         kernel = getattr(_hip, 'phi4_hmc' + ('_tiled' if tiled else '') + ('_ladder' if ladder else ''))
-        budget = _hip.hmc_tiled_budget(n_md) if tiled else _hip.hmc_fused_budget(phi[0].numel(), phi.shape[0])
-        for a in schedule(rows, every, n_md, budget, tiled=tiled, ladder=ladder, stats=sink.stats is not None,
+        evals = n_md * (1 if scheme is None else scheme.stages)
+        extra = {} if scheme is None else dict(scheme=scheme)
+        budget = _hip.hmc_tiled_budget(evals) if tiled else _hip.hmc_fused_budget(phi[0].numel(), phi.shape[0])
+        for a in schedule(rows, every, evals, budget, tiled=tiled, ladder=ladder, stats=sink.stats is not None,
                           want_rows=sink.out is not None, measure_cost=_hip.HMC_MEASURE_MD_STEPS):
             if isinstance(a, Take):
                 sink.take(a.row, phi, a.copy)
                 continue
             kw = dict(workspace=ws) if tiled else dict(measure=a.measure, record=a.record)
-            r = kernel(phi, *couplings, n_md, dt, n_traj=a.n_traj, record_every=a.record_every, **kw)
+            r = kernel(phi, *couplings, n_md, dt, n_traj=a.n_traj, record_every=a.record_every, **kw, **extra)
             dhs.append(r['dh']); accs.append(r['accept'])
             sink.launch(a.row0, r)
         return r['action']
@@ -396,7 +423,11 @@ class HMCSampler:
     def _energy(self, phi, pi):
         return 0.5 * pi.double().square().flatten(1).sum(dim=1) + self._model.action(phi.double()).double()
 
-    def _trajectory_composed(self, phi, S0, n_md, dt, pi=None, force_accept=False, generator=None):
+    def _trajectory_composed(self, phi, S0, n_md, dt, pi=None, force_accept=False, generator=None, scheme=None):
+        """One trajectory by the definition at the top of the module; the update lengths are the doubles a_j dt, b_j dt
+        and 0.5 b_s dt, as the kernels are handed them (leapfrog: dt and 0.5 dt)."""
+        a, b = ((1.0,), (1.0,)) if scheme is None else (scheme.a, scheme.b)
+        s, half = len(a), 0.5 * b[-1] * dt
         C, shape = phi.shape[0], tuple(phi.shape[1:])
         on_device = phi.is_cuda
         if pi is None:
@@ -408,10 +439,11 @@ class HMCSampler:
             _hip._philox_position(phi.device, generator)      # handed-in momenta still take the position of the draw
         H0 = 0.5 * pi.double().square().flatten(1).sum(dim=1) + S0
         new = phi
-        pi = pi - (0.5 * dt) * self._force(new)
+        pi = pi - half * self._force(new)
         for k in range(1, n_md + 1):
-            new = new + dt * pi
-            pi = pi - (dt if k < n_md else 0.5 * dt) * self._force(new)
+            for j in range(s):
+                new = new + (a[j] * dt) * pi
+                pi = pi - (half if k == n_md and j == s - 1 else b[j] * dt) * self._force(new)
         S1 = self._model.action(new.double()).double()
         dh = 0.5 * pi.double().square().flatten(1).sum(dim=1) + S1 - H0
         if on_device:
@@ -429,9 +461,9 @@ class HMCSampler:
             acc = ok.to(torch.uint8)
         return new, torch.where(ok, S1, S0), dh, acc, pi
 
-    def _run_composed(self, phi, S, rows, every, n_md, dt, sink, dhs, accs):
+    def _run_composed(self, phi, S, rows, every, n_md, dt, sink, dhs, accs, scheme=None):
         for t in range(rows * every):
-            phi, S, dh, acc, _ = self._trajectory_composed(phi, S, n_md, dt)
+            phi, S, dh, acc, _ = self._trajectory_composed(phi, S, n_md, dt, scheme=scheme)
             dhs.append(dh.unsqueeze(0)); accs.append(acc.unsqueeze(0))
             if (t + 1) % every == 0:
                 sink.take((t + 1) // every - 1, phi)

@@ -93,7 +93,8 @@ class _LadderModel:
 
 
 class LadderHMCSampler(HMCSampler):
-    """`sample(batch_size, n_chains=C, n_md=10, dt=0.1, n_skip=0, exchange_every=1, path=None)` -> (batch_size, *L),
+    """`sample(batch_size, n_chains=C, n_md=10, dt=0.1, n_skip=0, exchange_every=1, path=None, integrator='leapfrog')`
+    -> (batch_size, *L) (`integrator` as in HMCSampler, on sample, sample_ and measure alike),
     RUNG-ORDERED: row r is recorded step r // C, column r % C = set K + rung.  C must be a multiple of K = len(ladder)
     and batch_size of C.  `split(y)` -> (K, batch_size / K, *L): entry k is rung k's rows in the samplers' layout for
     n_chains = R = C / K.  `measure(...)` takes the same arguments and returns a list of K `Measurement`s, entry k that of
@@ -222,12 +223,12 @@ class LadderHMCSampler(HMCSampler):
         return (out[0], torch.empty_like(out[1]).index_copy_(0, col, out[1])) + tuple(out[2:])
 
     def trajectory(self, *args, **kwargs):
-        raise NotImplementedError("LadderHMCSampler has no single-trajectory entry: use _hip.phi4_hmc_ladder or "
-                                  "model.hmc.trajectory with the rung's action")
+        raise NotImplementedError("LadderHMCSampler has no single-trajectory entry: use _hip.phi4_hmc_ladder(scheme=...) "
+                                  "or model.hmc.trajectory(integrator=...) with the rung's action")
 
     # ---- which path: HMCSampler's `_choose`, on the proxy model (whose action is a phi^4 action)
     def _advance(self, batch_size, n_chains=None, n_md=10, dt=0.1, n_skip=0, exchange_every=1, path=None, want_rows=True,
-                 want_stats=False, cluster_every=0, improved=False):
+                 want_stats=False, cluster_every=0, improved=False, integrator='leapfrog'):
         """batch_size // C recorded steps.  Returns (the rung-ordered rows or None, the `_RungStats` with the rung-ordered
         measure rows `out` (steps, C, n_out) or None)."""
         K = len(self._ladder)
@@ -236,6 +237,7 @@ class LadderHMCSampler(HMCSampler):
             raise ValueError(f"n_chains ({C}) must be a positive multiple of the K = {K} rungs")
         C, n_md, every, E = self._checked(batch_size, C, n_md, n_skip, exchange_every, 'exchange_every')
         Ec = self._checked(batch_size, C, n_md, n_skip, cluster_every, 'cluster_every')[3]
+        scheme = self._scheme(integrator)
         self._restart(C)
         phi, S, rung = self._ref['sample'].clone(), self._ref['action'], self._ref['rung'].clone()
         path = self._choose(phi, path)
@@ -271,9 +273,9 @@ class LadderHMCSampler(HMCSampler):
                 stats.col = col
             sink = _Span(out, stats, r0, col)
             if path == 'composed':
-                S = self._run_composed(phi, S, g, every, n_md, dt, sink, dhs, accs, col)
+                S = self._run_composed(phi, S, g, every, n_md, dt, sink, dhs, accs, col, scheme)
             else:
-                S = self._run(path, phi, (coef, rung), g, every, n_md, dt, ws, sink, dhs, accs)
+                S = self._run(path, phi, (coef, rung), g, every, n_md, dt, ws, sink, dhs, accs, scheme)
             r0 += g
             self._steps += g
             if E and self._steps % E == 0 and K > 1:
@@ -291,7 +293,7 @@ class LadderHMCSampler(HMCSampler):
                 self._sweeps += 1
         self._ref.update(sample=phi, action=S, rung=rung)
         swapped = torch.stack(swaps) if swaps else torch.zeros((0, C // K, K - 1), dtype=torch.uint8, device=dev)
-        accepted = self._finish(dhs, accs, extra=swapped.double().sum(dim=(0, 1)))    # the accepted swaps per pair
+        accepted = self._finish(dhs, accs, extra=swapped.double().sum(dim=(0, 1)), scheme=scheme)    # the accepted swaps per pair
         self.last['swapped'] = swapped
         if Ec:
             self.last['cluster'] = (torch.stack(sweeps) if sweeps else
@@ -303,10 +305,10 @@ class LadderHMCSampler(HMCSampler):
         y = None if out is None else out.reshape((batch_size,) + lat)
         return y, stats
 
-    def _run_composed(self, phi, S, rows, every, n_md, dt, sink, dhs, accs, col):
+    def _run_composed(self, phi, S, rows, every, n_md, dt, sink, dhs, accs, col, scheme=None):
         """HMCSampler's, with the chains updated in place and dH and the accept flags rung-ordered.  Returns S."""
         for t in range(rows * every):
-            phi_new, S, dh, acc, _ = self._trajectory_composed(phi, S, n_md, dt)
+            phi_new, S, dh, acc, _ = self._trajectory_composed(phi, S, n_md, dt, scheme=scheme)
             phi.copy_(phi_new)
             dhs.append(torch.empty_like(dh).index_copy_(0, col, dh).unsqueeze(0))
             accs.append(torch.empty_like(acc).index_copy_(0, col, acc).unsqueeze(0))

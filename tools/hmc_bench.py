@@ -21,7 +21,15 @@ times `hmc.measure(...)` (the observables taken as the chain runs, no rows store
 (the rows stored, then measured) instead: 16^2 x 512 and 16^3 x 1024 chains in fp32 and fp64 (fused, `--traj` recorded
 trajectories per call) and 32^4 x 16 chains in fp32 (tiled, `--composed-traj` per call).  Per shape: trajectories per
 second of both (medians of `--reps` alternating calls, with the spread) and the rise of torch.cuda.max_memory_allocated
-over one call of each."""
+over one call of each.
+
+    python tools/hmc_bench.py --integrator NAME [NAME ...] [--reps 5] [--traj 20] [--shapes small|large|all]
+what the integration schemes ('leapfrog', 'omelyan', 'omf4') buy: on chains thermalised at the couplings above, at
+trajectory length tau = n_md dt = 1, fp32, 16^3 x 1024 chains on the fused path (`--shapes small`) and 32^4 x 16 on the
+tiled path (`--shapes large`), per scheme over a small scan of n_md: the bare call's time per force evaluation (a
+trajectory of a scheme of s stages is n_md s of them), the acceptance and the rms dH of `--traj` trajectories from the
+same start and Philox position; then the fewest force evaluations per trajectory in the scan that reach an acceptance of
+0.8, and the trajectories per second there.  The configurations are timed alternately, `--reps` times each; medians."""
 import argparse
 import json
 import os
@@ -167,6 +175,59 @@ def measure_streaming(lattice, C, dtype, reps, n_traj):
                 accept_rate=round(s.history.accept_rate[-1], 3))
 
 
+INTEGRATOR_SHAPES = {'small': ((16, 16, 16), 1024, 'fused'), 'large': ((32, 32, 32, 32), 16, 'tiled')}
+INTEGRATOR_SCAN = {1: (6, 8, 10, 12, 16, 24, 32, 48), 2: (3, 4, 5, 6, 8, 12, 16, 24), 5: (1, 2, 3, 4, 6)}      # n_md, by stages
+
+
+def measure_integrators(names, lattice, C, path, reps, n_traj):
+    dtype = torch.float32
+    prior = NormalPrior(loc=torch.zeros(lattice, dtype=dtype, device=DEV), scale=torch.ones(lattice, dtype=dtype, device=DEV))
+    model = nf.Model(net_=None, prior=prior, action=ScalarPhi4Action(kappa=0.67, m_sq=-2.68, lambd=0.5))
+    s = model.hmc
+    torch.manual_seed(0)
+    s.start(n_chains=C)
+    coef = s._coef(lattice)
+    kernel = _hip.phi4_hmc if path == 'fused' else _hip.phi4_hmc_tiled
+    ws = dict(workspace=s._tiled_workspace(s._ref['sample'])) if path == 'tiled' else {}
+    with torch.no_grad():
+        s.sample(40 * C, n_chains=C, n_md=16, dt=1.0 / 16, path=path)           # thermalise: 40 trajectories of tau = 1
+        start = s._ref['sample'].clone()
+        configs = []
+        for name in names:
+            scheme = _hip.hmc_scheme(name)
+            for n_md in INTEGRATOR_SCAN.get(scheme.stages, INTEGRATOR_SCAN[2]):
+                kw = dict(ws) if name == 'leapfrog' else dict(ws, scheme=scheme)      # leapfrog: the entry point as it always was
+                configs.append(dict(name=name, stages=scheme.stages, n_md=n_md, times=[], run=(
+                    lambda n_md=n_md, kw=kw: kernel(start.clone(), *coef, n_md, 1.0 / n_md, n_traj=n_traj, position=(1, 0), **kw))))
+        for c in configs:                           # warm-up, and the statistics: every configuration from the same start
+            r = c['run']()
+            c['accept'] = r['accept'].float().mean().item()
+            c['dh_rms'] = r['dh'].double().square().mean().sqrt().item()
+        torch.cuda.synchronize()
+        for _ in range(reps):                       # alternate them, so that a drift of the machine hits all
+            for c in configs:
+                c['times'].append(_ms(c['run']))
+    V = prior.nvar
+    out = dict(lattice=list(lattice), chains=C, dtype="float32", path=path, tau=1.0, traj_per_call=n_traj, schemes={})
+    for name in names:
+        rows, best = [], None
+        for c in (c for c in configs if c['name'] == name):
+            ms = statistics.median(c['times'])
+            evals = c['n_md'] * c['stages']
+            row = dict(n_md=c['n_md'], force_evals=evals, us_per_force_eval=round(ms * 1e3 / (n_traj * evals), 3),
+                       ns_per_force_eval_site=round(ms * 1e6 / (n_traj * evals * C * V), 5),
+                       ms_spread=[round(min(c['times']), 3), round(max(c['times']), 3)], ms_per_call=round(ms, 3),
+                       accept=round(c['accept'], 3), dh_rms=float(f"{c['dh_rms']:.3e}"),
+                       traj_per_s=round(C * n_traj / ms * 1e3, 1))
+            rows.append(row)
+            if row['accept'] >= 0.8 and (best is None or evals < best['force_evals']):
+                best = row
+        out['schemes'][name] = dict(scan=rows, fewest_force_evals_at_accept_0p8=None if best is None else best['force_evals'],
+                                    n_md_there=None if best is None else best['n_md'],
+                                    traj_per_s_there=None if best is None else best['traj_per_s'])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -174,7 +235,15 @@ def main():
     ap.add_argument("--composed-traj", type=int, default=5, help="trajectories per composed call")
     ap.add_argument("--shapes", choices=("all", "small", "large"), default="all")
     ap.add_argument("--measure", action="store_true", help="hmc.measure against measure(hmc.sample()) (module docstring)")
+    ap.add_argument("--integrator", nargs="+", metavar="NAME", choices=sorted(_hip.HMC_SCHEMES),
+                    help="what the integration schemes buy at tau = 1 (module docstring)")
     a = ap.parse_args()
+    if a.integrator:
+        for key in ('small', 'large'):
+            if a.shapes in ('all', key):
+                lattice, C, path = INTEGRATOR_SHAPES[key]
+                print(json.dumps(measure_integrators(a.integrator, lattice, C, path, a.reps, min(a.traj, 20))), flush=True)
+        return
     if a.measure:
         for lattice, C, dtype in MEASURE_SHAPES:
             n = a.traj if _hip.hmc_supported(lattice, dtype) else a.composed_traj
