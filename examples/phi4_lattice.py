@@ -20,6 +20,7 @@ DistConvertor_), or a stack of RQ-spline couplings, assembled from the same name
     python examples/phi4_lattice.py --lat 8,8 --hmc --cluster --improved    the same, and chi = V <m^2>, U4 and xi_2 of that
                                                           run both ways: from the one sign assignment the sweeps left, and
                                                           averaged over all of them (the cluster-improved estimators)
+    python examples/phi4_lattice.py --lat 8,8 --hmc --cluster --improved --correlator    that, and G(t) and m_eff(t) both ways
 """
 import argparse
 import os
@@ -91,11 +92,26 @@ def both_ways(m, n_chains, drop):
     return "\n".join(lines)
 
 
+def correlators(m, n_chains, drop):
+    """G(t) and m_eff(t) along axis 0 of a measurement whose `.improved` carries the full spectrum (momenta='all'): from
+    the sign assignment the sweeps left and averaged over all sign assignments, with their errors."""
+    e, ie = Ensemble(m, n_chains=n_chains, drop=drop), ImprovedEnsemble(m.improved, n_chains=n_chains, drop=drop)
+    (g, ge), (ig, ige) = e.correlator(axis=0), ie.correlator(axis=0)
+    (ms, mse), (ims, imse) = e.effective_mass(axis=0), ie.effective_mass(axis=0)
+    lines = ["   t   G(t)                    improved G(t)           m_eff(t)                improved m_eff(t)"]
+    for t in range(len(g) // 2 + 1):
+        mass = ("%-23s %s" % (fmt_val_err(ms[t - 1].item(), mse[t - 1].item()), fmt_val_err(ims[t - 1].item(), imse[t - 1].item()))
+                if 1 <= t <= len(ms) else "")
+        lines.append("  %2d   %-23s %-23s %s" % (t, fmt_val_err(g[t].item(), ge[t].item()), fmt_val_err(ig[t].item(), ige[t].item()),
+                                                 mass))
+    return "\n".join(lines)
+
+
 # trajectories of length 1 at about the same cost in force evaluations: n_md of each integrator, dt = 1 / n_md
 INTEGRATOR_N_MD = dict(leapfrog=10, omelyan=5, omf4=2)
 
 
-def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False, integrator='leapfrog'):
+def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False, integrator='leapfrog', correlator=False):
     """<phi^2> of the trained flow + Metropolis next to hybrid Monte Carlo on the action itself (exact up to its own
     statistical error; the first quarter of every chain is dropped as thermalisation), then the observables of both.
     `cluster`: also model.hmc with a Swendsen-Wang sweep of the signs before every recorded step (cluster_every=1), so
@@ -119,9 +135,11 @@ def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False
               % (*phi2(y, n_chains, rows // 4), model.hmc.history.accept_rate[-1], big))
         print("model.hmc, cluster_every=1   " + observables(model, y, n_chains, rows // 4))
         if improved:
-            m = model.hmc.measure(n_chains * rows, cluster_every=1, improved=True, **hmc)
+            m = model.hmc.measure(n_chains * rows, cluster_every=1, improved=True, momenta='all' if correlator else None, **hmc)
             print("model.hmc, cluster_every=1, the next %d steps both ways (sweeps and steps coincide: drop = 0)" % rows)
             print(both_ways(m, n_chains, 0))
+            if correlator:
+                print(correlators(m, n_chains, 0))
 
 
 def ladder_scan(lat, m_sq, lambd, kappas, replicas=32, steps=600, cluster=False):
@@ -170,6 +188,9 @@ def main():
                          "with --ladder: the ladder once more with exchanges and cluster_every=1")
     ap.add_argument("--improved", action="store_true",
                     help="with --hmc --cluster: chi = V<m^2>, U4 and xi_2 also from the cluster-improved estimators")
+    ap.add_argument("--correlator", action="store_true",
+                    help="with --hmc --cluster --improved: the time-slice correlator G(t) and the effective mass along axis 0, "
+                         "plain and cluster-improved (the sweeps' spectrum at all momenta)")
     ap.add_argument("--ladder", action="store_true",
                     help="no fit: a ladder of 6 kappas from --kappa down to 0.4 of it in one HMC launch per step, chi, U4 and "
                          "tau_int(m) per rung without and with replica exchange")
@@ -188,7 +209,7 @@ def main():
         model.fit(**kw)
         nf.backward_sanitychecker(model)
         if a.hmc:
-            compare_with_hmc(model, cluster=a.cluster, improved=a.improved, integrator=a.integrator)
+            compare_with_hmc(model, cluster=a.cluster, improved=a.improved, integrator=a.integrator, correlator=a.correlator)
 
 
 if __name__ == "__main__":

@@ -1113,6 +1113,48 @@ int nf_cluster_moments_tiled(const void *phi, const int32_t *labels, double *out
                              int64_t C, const int32_t *lattice, const double *tw, int dtype, int64_t block_sites,
                              int per_pass, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- cluster spectrum (nf_cluster_spectrum.hip; MI355X-side extension): the "cluster-improved estimators" above at every
+ * on-axis momentum, the input of the improved propagator and time-slice correlator.  It extends that rule and changes
+ * nothing of it: the fixed point q, the range test, the refusal (status 1, a NaN row), the int64 sums, the caller's table
+ * tw and the order of a sum of squares over the V slots (lane l takes the slots l, l + lanes, ... with explicit fma, then
+ * the wave shuffle tree, then the waves in order) hold word for word.  What is new:
+ * Momenta.  kmax >= 0 is the caller's.  K_mu = 0 for an axis of extent 1; otherwise K_mu = floor(L_mu / 2) if kmax = 0
+ * ("all"), else min(kmax, floor(L_mu / 2)).
+ * Per-cluster sums, all int64, for every axis mu in order and every k = 1 .. K_mu:
+ *   R_{C,mu,k} = sum_{x in C} q(phi(x) tw[off_mu + (k x_mu mod L_mu)][0]),  I_{C,mu,k} likewise with [1],
+ * and A_C as above.  The table is the one of nf_cluster_moments: no new table, every path gets the same twiddles bit for
+ * bit, and k = 1 is that rule's quantity.  At the Nyquist momentum (2 k = L_mu) I is LEFT OUT: the table's sine there is
+ * at most 1.3e-16 in magnitude, q of it times any in-range phi is 0, and the column has the same bits as with it.
+ * The quantities, in order: A, then per axis in order and per k ascending R, I (R alone at Nyquist):
+ *   Q = 1 + sum_mu (2 K_mu - [2 K_mu = L_mu]).
+ * Outputs.
+ *   out     (C, 2 + sum_mu K_mu) double: sum_C a^2, sum_C a^4, then per axis in order and per k ascending
+ *           (sum_C r^2) + (sum_C i^2), at Nyquist sum_C r^2 alone; NO column for an axis of extent 1.  Every sum of
+ *           squares is taken in the order above, so columns 0 and 1 and every k = 1 column are nf_cluster_moments' bits.
+ *           A row's bits depend on the chain, its labels, the lattice, the dtype and kmax alone.
+ *   status  (C) int32, as above; a refused chain's out row is all NaN.
+ * With the signs averaged, P_mu(k) = sum_C |sum_{x in C} phi(x) e^{2 pi i k x_mu / L_mu}|^2 is the column of (mu, k),
+ * P_mu(0) = column 0 and P_mu(L - k) = P_mu(k); sum_s <S_mu(s) S_mu(s + t)> = (1 / L_mu) sum_k P_mu(k) cos(2 pi k t / L_mu).
+ *
+ * nf_cluster_spectrum: the lattices and the structure of nf_cluster_moments (one workgroup per chain, nf_phi4_cluster's
+ * lane map, phi and labels read once into registers, the checks before any indexed access, int64 slot arrays in dynamic
+ * LDS filled by 64-bit integer LDS adds, a lane's run of same-label sites as ONE atomic, passes that reuse the arrays).
+ * A quantity's axis, k and component follow inside the kernel from wave-uniform integer arithmetic on its index and four
+ * per-axis prefix counts: nothing in registers is indexed dynamically.  The reduction region is 4 KiB whatever Q: a
+ * pass's wave sums are added in wave order at the end of the pass and its columns written then; a sum r^2 whose sum i^2
+ * falls into the next pass is carried.  per_pass = min(Q, 16, (160 KiB - 4 KiB) / 8 V), passes = ceil(Q / per_pass),
+ * lds_bytes = 4096 + per_pass 8 V.  C is 1 .. 65535.  No allocation, no host synchronisation: graph-capturable.
+ * NF_EINVAL: whatever nf_cluster_moments refuses, and kmax < 0.
+ * nf_cluster_spectrum_plan / _supported: pure host; plan.kmax[mu] = K_mu of the padded axes, columns = 2 + sum K_mu. */
+typedef struct nf_spectrum_plan {
+  int32_t sites_per_lane, lanes, kmax[4], columns, quantities, passes, per_pass;
+  int64_t lds_bytes;
+} nf_spectrum_plan;
+int nf_cluster_spectrum_supported(const int32_t *lattice, int dtype, int kmax);
+int nf_cluster_spectrum_plan(const int32_t *lattice, int dtype, int kmax, nf_spectrum_plan *out);
+int nf_cluster_spectrum(const void *phi, const int32_t *labels, double *out, int32_t *status, int64_t C,
+                        const int32_t *lattice, int kmax, const double *tw, int dtype, void *stream);
+
 /* ---- what the samplers' rows measure (nf_measure.hip; MI355X-side extension): every sufficient statistic of N
  * configurations in one pass.  cfgs (N, V) of dtype NF_F32 / NF_F64 on lattice[4] (leading extents 1 for d < 4);
  * out (N, n_out) DOUBLE, n_out = 7 + lattice[0] + lattice[1] + lattice[2] + lattice[3], per row

@@ -120,6 +120,9 @@ PROTOTYPES = {
     "nf_cluster_moments_supported": (_I, [C.POINTER(C.c_int32), _I]),
     "nf_cluster_moments_plan": (_I, [C.POINTER(C.c_int32), _I, _P]),
     "nf_cluster_moments": (_I, [_P, _P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P]),
+    "nf_cluster_spectrum_supported": (_I, [C.POINTER(C.c_int32), _I, _I]),
+    "nf_cluster_spectrum_plan": (_I, [C.POINTER(C.c_int32), _I, _I, _P]),
+    "nf_cluster_spectrum": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _I, _P, _I, _P]),
     "nf_cluster_moments_tiled_supported": (_I, [C.POINTER(C.c_int32), _I, _I64]),
     "nf_cluster_moments_tiled_plan": (_I, [C.POINTER(C.c_int32), _I, _I64, _I, _P]),
     "nf_cluster_moments_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I64, _I]),
@@ -2485,6 +2488,76 @@ def cluster_moments(phi, labels, want_moments=False):
                                      _ptr(tw), _dtype_code(phi), _stream()), "nf_cluster_moments")
     pad = 4 - len(lat)
     return dict(out=torch.cat([out[:, :2], out[:, 2 + pad:]], dim=1), status=status, moments=moments)
+
+
+# ========================================================================= cluster spectrum (nf_cluster_spectrum.hip)
+class SpectrumPlan(C.Structure):
+    """nf_spectrum_plan (include/normflow_hip.h)."""
+    _fields_ = [("sites_per_lane", C.c_int32), ("lanes", C.c_int32), ("kmax", C.c_int32 * 4), ("columns", C.c_int32),
+                ("quantities", C.c_int32), ("passes", C.c_int32), ("per_pass", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
+def spectrum_kmax(momenta):
+    """`momenta` ('all' or an int >= 1) as the library's kmax: 0 means all."""
+    if isinstance(momenta, str):
+        if momenta != 'all':
+            raise NormflowHipError(f"momenta must be 'all' or an int >= 1, got {momenta!r}")
+        return 0
+    if isinstance(momenta, bool) or not isinstance(momenta, int) or momenta < 1:
+        raise NormflowHipError(f"momenta must be 'all' or an int >= 1, got {momenta!r}")
+    return int(momenta)
+
+
+def spectrum_momenta(lat, momenta='all'):
+    """K_mu of the axes of `lat` under `momenta`: 0 for an axis of extent 1, else floor(L / 2) or min(momenta, floor(L / 2))."""
+    kmax = spectrum_kmax(momenta)
+    return tuple(0 if n == 1 else (n // 2 if kmax == 0 else min(kmax, n // 2)) for n in lat)
+
+
+def cluster_spectrum_supported(lat, dtype, momenta='all'):
+    """True if nf_cluster_spectrum takes chains on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own
+    planner, pure host code."""
+    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
+        return False
+    return bool(load().nf_cluster_spectrum_supported(_lat4(lat), _dtype_code_of(dtype), spectrum_kmax(momenta)))
+
+
+def cluster_spectrum_plan(lat, dtype, momenta='all'):
+    """What nf_cluster_spectrum will do on the lattice `lat` in `dtype`: dict(sites_per_lane, lanes, kmax (K_mu of the
+    four padded axes), columns, quantities, passes, per_pass, lds_bytes).  Pure host code."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"cluster_spectrum_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
+    out = SpectrumPlan()
+    _check(load().nf_cluster_spectrum_plan(_lat4(lat), _dtype_code_of(dtype), spectrum_kmax(momenta), C.byref(out)),
+           "nf_cluster_spectrum_plan")
+    d = {name: getattr(out, name) for name, _ in SpectrumPlan._fields_}
+    d['kmax'] = tuple(out.kmax)
+    return d
+
+
+def cluster_spectrum(phi, labels, momenta='all'):
+    """nf_cluster_spectrum: `cluster_moments` at every on-axis momentum k = 1 .. K_mu, in ONE launch (C <= 65535).  Returns
+    dict(out (C, 2 + sum K_mu) float64 = sum_C M_C^2, sum_C M_C^4, then per axis of `L` and per k ascending
+    sum_C |M~_C(2 pi k / L_mu)|^2 (no column for an axis of extent 1); status (C) int32, 1 = refused (the out row is NaN);
+    momenta = (K_mu of the axes of `L`)).  `momenta` is 'all' (K_mu = L_mu // 2) or an int >= 1 (K_mu = min of the two).
+    The rule is stated in include/normflow_hip.h, "cluster spectrum".  Graph capture: as `cluster_moments`, call
+    `twiddle_table(lat, device)` first."""
+    _require_device(phi, labels)
+    lat = tuple(phi.shape[1:])
+    if not phi.is_contiguous() or not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"cluster_spectrum needs contiguous phi (C, *L) with 1 to 4 lattice axes, got {tuple(phi.shape)}")
+    if labels.shape != phi.shape or labels.dtype != torch.int32 or not labels.is_contiguous() or labels.device != phi.device:
+        raise NormflowHipError(f"cluster_spectrum: labels must be a contiguous int32 tensor {tuple(phi.shape)} on {phi.device}, "
+                               f"got {tuple(labels.shape)} {labels.dtype} on {labels.device}")
+    kmax = spectrum_kmax(momenta)
+    K = spectrum_momenta(lat, momenta)
+    Cn, dev = phi.shape[0], phi.device
+    out = torch.empty((Cn, 2 + sum(K)), dtype=torch.float64, device=dev)
+    status = torch.empty((Cn,), dtype=torch.int32, device=dev)
+    tw = twiddle_table(lat, dev)
+    _check(load().nf_cluster_spectrum(_ptr(phi), _ptr(labels), _ptr(out), _ptr(status), Cn, _lat4(lat), kmax, _ptr(tw),
+                                      _dtype_code(phi), _stream()), "nf_cluster_spectrum")
+    return dict(out=out, status=status, momenta=K)
 
 
 # ========================================================================= the same, slots in HBM (nf_cluster_moments_tiled.hip)

@@ -13,7 +13,8 @@ and the on-axis momentum-space propagator |sum_t e^{ipt} S_mu(t)|^2 / V at p = 2
 
 `measure_improved(cfgs, labels)` gives the cluster-improved forms of (sum phi)^2, (sum phi)^4 and the propagator at
 p_min from the labels of a Swendsen-Wang sweep (`ImprovedMeasurement`, `ImprovedEnsemble`; nf_cluster_moments on the
-device).
+device).  With `momenta='all'` it also carries the cluster spectrum (nf_cluster_spectrum), from which the improved
+propagator at every on-axis momentum and the improved time-slice correlator follow.
 
 `Ensemble` reads the rows as (steps, chains) -- row r = step r // C of chain r % C, the layout of model.mcmc,
 model.blocked_mcmc and model.hmc -- and gives every estimate as (value, error): leave-one-chain-out jackknife for
@@ -301,18 +302,39 @@ def route_improved(cfgs):
 
 
 @torch.no_grad()
-def measure_improved(cfgs, labels, path=None):
+def measure_improved(cfgs, labels, path=None, momenta=None):
     """(N, *L) configurations and the (N, *L) int32 labels of their cluster decompositions (a Swendsen-Wang sweep's:
     `hmc.cluster(phi)['labels']`, with the field before or after the flip) -> `ImprovedMeasurement`: the averages over
     all 2^Nc assignments of the clusters' signs, in closed form from the clusters' sums M_C (include/normflow_hip.h,
     "cluster-improved estimators").  path=None: what `route_improved` says; 'kernel' (nf_cluster_moments; raises where it
     cannot run), 'composed' (`mcmc.cluster.cluster_moments`: torch ops, any device) or 'hbm' (nf_cluster_moments_tiled:
     the slots in HBM, any lattice on the device; raises on CPU tensors) force one.  `route_improved` never says 'hbm':
-    the path is opt-in until the routing is redone from measured classes."""
+    the path is opt-in until the routing is redone from measured classes.
+    momenta='all' or an int >= 1: the measurement also carries the spectrum, sum_C |M~_C(2 pi k / L_mu)|^2 at
+    k = 1 .. K_mu of every axis (include/normflow_hip.h, "cluster spectrum"), from which `propagator` and `correlator`
+    follow where momenta='all'.  path=None / 'kernel' then run nf_cluster_spectrum where `improved_kernel_applies`
+    (path=None elsewhere: composed), 'composed' is `mcmc.cluster.cluster_spectrum`, and 'hbm' raises ValueError: there is
+    no tiled spectrum kernel, lattices beyond one CU take the composed path.  `out` is that of the call without momenta
+    bit for bit on the same path (its columns are columns of the spectrum's row)."""
     if path not in IMPROVED_PATHS:
         raise ValueError(f"path must be None, 'kernel', 'composed' or 'hbm', got {path!r}")
     if not 1 <= cfgs.ndim - 1 <= 4:
         raise ValueError(f"measure_improved: configurations (N, *L) with 1 to 4 lattice axes, got {tuple(cfgs.shape)}")
+    lat = tuple(cfgs.shape[1:])
+    if momenta is not None:
+        if path == 'hbm':
+            raise ValueError("measure_improved: no spectrum on path 'hbm' (nf_cluster_moments_tiled has no spectrum form): "
+                             "use path='composed' for lattices beyond one CU")
+        if momenta != 'all' and (isinstance(momenta, bool) or not isinstance(momenta, int) or momenta < 1):
+            raise ValueError(f"momenta must be None, 'all' or an int >= 1, got {momenta!r}")
+        if path is None:
+            path = 'kernel' if improved_kernel_applies(cfgs) else 'composed'
+        if path == 'kernel':
+            r = _hip.cluster_spectrum(cfgs.contiguous(), labels.contiguous(), momenta)
+        else:
+            from ..mcmc.cluster import cluster_spectrum
+            r = cluster_spectrum(cfgs, labels, momenta)
+        return ImprovedMeasurement.from_spectrum(r['out'], r['status'], lat, r['momenta'])
     if path is None:
         path = route_improved(cfgs)
     if path == 'kernel':
@@ -322,7 +344,7 @@ def measure_improved(cfgs, labels, path=None):
     else:
         from ..mcmc.cluster import cluster_moments
         r = cluster_moments(cfgs, labels)
-    return ImprovedMeasurement(r['out'], r['status'], tuple(cfgs.shape[1:]))
+    return ImprovedMeasurement(r['out'], r['status'], lat)
 
 
 class ImprovedMeasurement:
@@ -330,13 +352,32 @@ class ImprovedMeasurement:
     sum_C |sum_{x in C} phi(x) e^{i p x_mu}|^2 at p = 2 pi / L_mu per axis (an axis of extent 1 repeats sum_m2); status (N)
     int32, 1 = a refused row (all NaN); lattice, volume.  With the clusters' signs averaged,
         <(sum phi)^2> = sum M_C^2,   <(sum phi)^4> = 3 (sum M_C^2)^2 - 2 sum M_C^4,   <|phi~(p)|^2> = sum_C |M~_C(p)|^2,
-    and all three are invariant under the flips: the field before or after the sweep gives the same bits."""
+    and all three are invariant under the flips: the field before or after the sweep gives the same bits.
+    `spectrum` (None, or a list of d tensors (N, K_mu)): the last of the three at p = 2 pi k / L_mu, k = 1 .. K_mu, and
+    `momenta` the K_mu; `propagator` and `correlator` need the full spectrum, K_mu = L_mu // 2 (momenta='all')."""
 
-    def __init__(self, out, status, lattice):
+    def __init__(self, out, status, lattice, spectrum=None, momenta=None):
         self.out = out                        # (N, 2 + d): the three below side by side
         self.sum_m2, self.sum_m4c, self.prop1, self.status = out[:, 0], out[:, 1], out[:, 2:], status
         self.lattice = tuple(lattice)
         self.volume = math.prod(self.lattice)
+        self.spectrum = None if spectrum is None else list(spectrum)
+        if self.spectrum is not None:
+            momenta = tuple(int(t.shape[1]) for t in self.spectrum) if momenta is None else tuple(int(k) for k in momenta)
+            if len(self.spectrum) != len(self.lattice) or momenta != tuple(int(t.shape[1]) for t in self.spectrum):
+                raise ValueError(f"spectrum: one (N, K_mu) tensor per axis of {self.lattice} with K = {momenta}")
+        self.momenta = momenta if self.spectrum is not None else None
+
+    @classmethod
+    def from_spectrum(cls, row, status, lattice, momenta):
+        """From the (N, 2 + sum K_mu) rows of the cluster spectrum: `out` takes columns 0 and 1 and the k = 1 column of
+        every axis (column 0 for an axis of extent 1), which are `cluster_moments`' bits."""
+        at, parts, cols = 2, [], [0, 1]
+        for K in momenta:
+            parts.append(row[:, at:at + K])
+            cols.append(at if K else 0)
+            at += K
+        return cls(torch.stack([row[:, c] for c in cols], dim=1), status, lattice, parts, momenta)    # slices: no index tensor
 
     def __len__(self):
         return self.sum_m2.shape[0]
@@ -344,17 +385,28 @@ class ImprovedMeasurement:
     _axes = Measurement._axes
 
     @classmethod
-    def cat(cls, parts, lattice, device):
-        """The rows of `parts` (ImprovedMeasurements of one lattice) one after the other; none: an empty one on `device`."""
+    def cat(cls, parts, lattice, device, momenta=None):
+        """The rows of `parts` (ImprovedMeasurements of one lattice) one after the other; none: an empty one on `device`
+        (with the empty spectrum of `momenta`, the K_mu, where given)."""
         if not parts:
+            spec = None if momenta is None else [torch.empty((0, K), dtype=torch.float64, device=device) for K in momenta]
             return cls(torch.empty((0, 2 + len(lattice)), dtype=torch.float64, device=device),
-                       torch.empty((0,), dtype=torch.int32, device=device), lattice)
-        return cls(torch.cat([p.out for p in parts]), torch.cat([p.status for p in parts]), lattice)
+                       torch.empty((0,), dtype=torch.int32, device=device), lattice, spec, momenta)
+        spec = None
+        if parts[0].spectrum is not None:
+            spec = [torch.cat([p.spectrum[mu] for p in parts]) for mu in range(len(lattice))]
+        return cls(torch.cat([p.out for p in parts]), torch.cat([p.status for p in parts]), lattice, spec, parts[0].momenta)
 
     def rows(self, col):
         """The same rows laid out by `col`: row i goes to row col[i] (the ladder's rung order)."""
+        spec = None if self.spectrum is None else [torch.empty_like(t).index_copy_(0, col, t) for t in self.spectrum]
         return type(self)(torch.empty_like(self.out).index_copy_(0, col, self.out),
-                          torch.empty_like(self.status).index_copy_(0, col, self.status), self.lattice)
+                          torch.empty_like(self.status).index_copy_(0, col, self.status), self.lattice, spec, self.momenta)
+
+    def pick(self, fn):
+        """The measurement of the rows that `fn` picks from every (N, ...) tensor (the ladder's rows of one rung)."""
+        spec = None if self.spectrum is None else [fn(t) for t in self.spectrum]
+        return type(self)(fn(self.out), fn(self.status), self.lattice, spec, self.momenta)
 
     def m2(self):
         """<m^2>_signs = sum M_C^2 / V^2."""
@@ -373,6 +425,38 @@ class ImprovedMeasurement:
         (of equal extents, as in `Measurement`)."""
         axes = self._axes(axis)
         return self.prop1[:, axes].sum(dim=1) / (len(axes) * self.volume)
+
+    def has_spectrum(self):
+        """True where the measurement carries the spectrum at all momenta, K_mu = L_mu // 2 of every axis."""
+        return self.spectrum is not None and all(K == (n // 2 if n > 1 else 0) for K, n in zip(self.momenta, self.lattice))
+
+    def _power(self, mu):
+        """(N, L) P_mu(k) = sum_C |M~_C(2 pi k / L)|^2, k = 0 .. L - 1: P(0) = sum M_C^2 and P(L - k) = P(k)."""
+        if not self.has_spectrum():
+            raise ValueError("the propagator and the correlator need the spectrum at all momenta: measure with momenta='all'"
+                             + ("" if self.spectrum is None else f" (this one has K = {self.momenta} on {self.lattice})"))
+        L, half = self.lattice[mu], self.spectrum[mu]
+        k = torch.arange(L, device=half.device)
+        fold = torch.minimum(k, L - k)                              # 0 .. L // 2
+        return torch.cat([self.sum_m2.unsqueeze(1), half], dim=1)[:, fold]
+
+    def propagator(self, axis=None):
+        """(N, L) the improved `Measurement.propagator`: P_mu(k) / V at p = 2 pi k / L, k = 0 .. L - 1."""
+        axes = self._axes(axis)
+        return sum(self._power(mu) for mu in axes) / (len(axes) * self.volume)
+
+    def correlator(self, axis=None):
+        """(N, L) the improved `Measurement.correlator`: G_mu(t) = (1 / V^2) sum_k P_mu(k) cos(2 pi k t / L) in float64;
+        axis=None: the mean over the axes."""
+        axes = self._axes(axis)
+        out = 0
+        for mu in axes:
+            P = self._power(mu)
+            L = self.lattice[mu]
+            k = torch.arange(L, dtype=torch.float64, device=P.device)
+            cos = torch.cos(2.0 * math.pi * ((k[:, None] * k[None, :]) % L) / L)
+            out = out + P @ cos / self.volume ** 2
+        return out / len(axes)
 
 
 class ImprovedEnsemble(Ensemble):
@@ -414,7 +498,29 @@ class ImprovedEnsemble(Ensemble):
             return torch.where(r >= 0, r.clamp(min=0).sqrt(), torch.full_like(r, float('nan'))) / (2 * math.sin(math.pi / L))
         return self.estimate(p, xi, binsize)
 
-    def _unsupported(self, *args, **kwargs):
-        raise NotImplementedError("an ImprovedEnsemble has m2, m4, susceptibility, binder, propagator1, xi2 and tau_int")
+    def _spectral(self, what):
+        if self.m.spectrum is None:
+            raise NotImplementedError(f"an ImprovedEnsemble has {what} only on a measurement with a spectrum (measure with "
+                                      "momenta='all'); without one it has m2, m4, susceptibility, binder, propagator1, xi2 "
+                                      "and tau_int")
 
-    correlator = propagator = effective_mass = _corr = _unsupported
+    def _corr(self, axis, connected):
+        self._spectral('a correlator')
+        if connected:
+            raise ValueError("connected=True: the sign-averaged <m> is 0, the improved correlator is its own connected part")
+        return self.series(self.m.correlator(axis)), (lambda a: a)
+
+    def correlator(self, axis=None, connected=False, binsize=1):
+        """<G_mu(t)> improved, t = 0 .. L - 1 (`ImprovedMeasurement.correlator`); connected=True raises ValueError."""
+        p, fn = self._corr(axis, connected)
+        return self.estimate(p, fn, binsize)
+
+    def propagator(self, axis=None, binsize=1):
+        """<sum_C |M~_C(p)|^2> / V at p = 2 pi k / L, k = 0 .. L - 1."""
+        self._spectral('a propagator')
+        return self.estimate(self.series(self.m.propagator(axis)), binsize=binsize)
+
+    def effective_mass(self, axis=None, connected=False, binsize=1):
+        """`Ensemble.effective_mass`'s formula on the improved correlator."""
+        self._spectral('an effective mass')
+        return Ensemble.effective_mass(self, axis, connected, binsize)

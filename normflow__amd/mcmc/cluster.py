@@ -124,3 +124,46 @@ def cluster_moments(phi, labels, want_moments=False):
     out = torch.where(bad.unsqueeze(1), torch.full_like(out, float('nan')), out)
     moments = A.reshape((C,) + lat) if want_moments else None
     return dict(out=out, status=bad.to(torch.int32), moments=moments)
+
+
+def cluster_spectrum(phi, labels, momenta='all'):
+    """The rule of nf_cluster_spectrum (include/normflow_hip.h, "cluster spectrum") from torch ops, on any device and any
+    lattice of 1 to 4 axes with V < 2^31, fp32 / fp64: the dict of `_hip.cluster_spectrum`, out (C, 2 + sum K_mu) float64,
+    status (C) int32, momenta (K_mu of the axes).  q, the int64 scatter_add_ and the `sum` in double are those of
+    `cluster_moments`, on the same twiddle table: columns 0 and 1 and every k = 1 column are its bits.  The sine
+    quantity at the Nyquist momentum is left out, as in the kernel.  Nothing is read back from the device."""
+    from .. import _hip
+    C, lat = phi.shape[0], tuple(phi.shape[1:])
+    if not 1 <= len(lat) <= 4:
+        raise ValueError(f"cluster_spectrum: lattices of 1 to 4 axes, got {lat}")
+    if labels.shape != phi.shape:
+        raise ValueError(f"cluster_spectrum: labels {tuple(labels.shape)} do not match phi {tuple(phi.shape)}")
+    K = _hip.spectrum_momenta(lat, momenta)
+    V = 1
+    for n in lat:
+        V *= n
+    dev = phi.device
+    x = phi.double().reshape(C, V)
+    lab = labels.reshape(C, V).long()
+    bad = (~(x.abs() < _hip.cluster_moments_limit(V)) | (lab < 0) | (lab >= V)).any(dim=1)
+    x = torch.where(bad.unsqueeze(1), torch.zeros_like(x), x)
+    lab = torch.where(bad.unsqueeze(1), torch.zeros_like(lab), lab)
+    q = lambda w: torch.round(w * 2.0 ** 32).to(torch.int64)
+    slots = lambda w: torch.zeros((C, V), dtype=torch.int64, device=dev).scatter_add_(1, lab, q(w))
+    squares = lambda s: (s.double() * 2.0 ** -32).square().sum(dim=1)
+    a2 = (slots(x).double() * 2.0 ** -32).square()
+    cols = [a2.sum(dim=1), a2.square().sum(dim=1)]
+    tw = _hip.twiddle_table(lat, dev)
+    site = torch.arange(V, device=dev)
+    off, stride = 4 - len(lat), V
+    for n, Kmu in zip(lat, K):
+        stride //= n
+        xm = (site // stride) % n
+        for k in range(1, Kmu + 1):
+            t = tw[off + (k * xm) % n]                      # (V, 2)
+            col = squares(slots(x * t[:, 0]))
+            cols.append(col if 2 * k == n else col + squares(slots(x * t[:, 1])))
+        off += n
+    out = torch.stack(cols, dim=1)
+    out = torch.where(bad.unsqueeze(1), torch.full_like(out, float('nan')), out)
+    return dict(out=out, status=bad.to(torch.int32), momenta=K)

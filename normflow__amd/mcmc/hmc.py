@@ -86,7 +86,7 @@ class HMCSampler:
 
     @torch.no_grad()
     def measure(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, return_rows=False, cluster_every=0,
-                improved=False, integrator='leapfrog'):
+                improved=False, integrator='leapfrog', momenta=None):
         """The `Measurement` of the rows that `sample(batch_size, ...)` would return from the same chain and generator
         state, WITHOUT storing them: every recorded state is measured where it is and only its 7 + sum L sums are kept.
         The rows are in the samplers' layout (`Ensemble(m, n_chains=C)` takes it as is), the action is attached when the
@@ -104,10 +104,15 @@ class HMCSampler:
         Measurement then carries `.improved`, an `ImprovedMeasurement` of sweeps x C rows, row s C + c = sweep s of chain
         c (`ImprovedEnsemble(m.improved, n_chains=C)` takes it as is).  It needs cluster_every >= 1 (ValueError) and
         changes nothing else: the Measurement, the chains, `last`, `history` and the generator are those of the call
-        without it bit for bit, and there is still one device-to-host read (the statuses stay on the device)."""
+        without it bit for bit, and there is still one device-to-host read (the statuses stay on the device).
+        momenta='all' or an int >= 1 (with improved; ValueError without): `.improved` also carries the cluster spectrum
+        (`observables.measure_improved(..., momenta=...)`), from which the improved propagator and time-slice correlator
+        follow; it changes nothing else of the call, bit for bit, `improved.out` included."""
         ipath = self._improved_path(improved, cluster_every)
+        if momenta is not None and ipath is False:
+            raise ValueError("momenta asks for the spectrum of the improved estimators: it needs improved=True (or a path)")
         y, stats = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=return_rows, want_stats=True,
-                                 cluster_every=cluster_every, improved=ipath, integrator=integrator)
+                                 cluster_every=cluster_every, improved=ipath, integrator=integrator, momenta=momenta)
         action = self._model.action
         m = stats.measurement(action if hasattr(action, 'get_coef') else None)
         if ipath is not False:
@@ -132,7 +137,7 @@ class HMCSampler:
         return None if isinstance(integrator, str) and integrator == 'leapfrog' else _hip.hmc_scheme(integrator)
 
     def _advance(self, batch_size, n_chains, n_md, dt, n_skip, path, want_rows, want_stats, cluster_every=0,
-                 improved=False, integrator='leapfrog'):
+                 improved=False, integrator='leapfrog', momenta=None):
         """batch_size // n_chains recorded steps of the chains: (the rows (batch_size, *L) or None, the `_Stats` of the
         recorded states or None); the chains, `last` and `history` updated.  cluster_every = E >= 1: the recorded steps
         are run in spans that end before the next step s (counted across calls) with s % E == 0, with one cluster sweep
@@ -161,7 +166,7 @@ class HMCSampler:
                     phi, st = self._sweep(phi, workspace=sweep_ws)
                 else:                                                 # the same sweep, its labels kept
                     phi, st, labels = self._sweep(phi, workspace=sweep_ws, want_labels=True)
-                    parts.append(measure_improved(phi, labels, path=improved))
+                    parts.append(measure_improved(phi, labels, path=improved, momenta=momenta))
                 sweeps.append(st)
                 if path == 'composed':
                     S = self._model.action(phi.double()).double()
@@ -179,7 +184,8 @@ class HMCSampler:
             self.last['cluster'] = (torch.stack(sweeps) if sweeps else
                                     torch.empty((0, phi.shape[0], 4), dtype=torch.int32, device=phi.device))
         if improved is not False:                 # only `measure` asks, so there are stats to carry the rows
-            stats.improved = ImprovedMeasurement.cat(parts, tuple(phi.shape[1:]), phi.device)
+            K = None if momenta is None else _hip.spectrum_momenta(tuple(phi.shape[1:]), momenta)
+            stats.improved = ImprovedMeasurement.cat(parts, tuple(phi.shape[1:]), phi.device, K)
         y = None if out is None else out.reshape((batch_size,) + tuple(phi.shape[1:]))
         return y, stats
 

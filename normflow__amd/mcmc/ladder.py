@@ -150,13 +150,17 @@ class LadderHMCSampler(HMCSampler):
         return y, (-self._ladder.action(y, rung)).to(y.dtype)
 
     @torch.no_grad()
-    def measure(self, batch_size=1, return_rows=False, improved=False, **kwargs):
+    def measure(self, batch_size=1, return_rows=False, improved=False, momenta=None, **kwargs):
         """The list of K `Measurement`s.  improved=True / 'kernel' / 'composed' / 'hbm' as in `HMCSampler.measure`: entry k then
         carries `.improved`, the `ImprovedMeasurement` of rung k's sweeps x R rows (the kernel does not know the
         couplings: a sweep's C rows are taken by chain and laid out rung-ordered, row (c // K) K + rung[c] with the rungs
-        in force at that sweep, like `last['cluster']`)."""
+        in force at that sweep, like `last['cluster']`).  momenta='all' or an int >= 1 as in `HMCSampler.measure`: the
+        spectrum rides along, rung-ordered like the rest."""
         ipath = self._improved_path(improved, kwargs.get('cluster_every', 0))
-        y, rung_stats = self._advance(batch_size, want_rows=return_rows, want_stats=True, improved=ipath, **kwargs)
+        if momenta is not None and ipath is False:
+            raise ValueError("momenta asks for the spectrum of the improved estimators: it needs improved=True (or a path)")
+        y, rung_stats = self._advance(batch_size, want_rows=return_rows, want_stats=True, improved=ipath, momenta=momenta,
+                                      **kwargs)
         stats = rung_stats.out
         from ..lib import observables as ob
         K = len(self._ladder)
@@ -168,7 +172,7 @@ class LadderHMCSampler(HMCSampler):
             if ipath is not False:
                 im, C = rung_stats.improved, self._ref['sample'].shape[0]
                 pick = lambda t: t.reshape((-1, C) + tuple(t.shape[1:]))[:, k::K].flatten(0, 1)    # (sweeps R, ...)
-                ms[k].improved = ob.ImprovedMeasurement(pick(im.out), pick(im.status), lat)
+                ms[k].improved = im.pick(pick)
         return (ms, y) if return_rows else ms
 
     def split(self, y):
@@ -228,7 +232,7 @@ class LadderHMCSampler(HMCSampler):
 
     # ---- which path: HMCSampler's `_choose`, on the proxy model (whose action is a phi^4 action)
     def _advance(self, batch_size, n_chains=None, n_md=10, dt=0.1, n_skip=0, exchange_every=1, path=None, want_rows=True,
-                 want_stats=False, cluster_every=0, improved=False, integrator='leapfrog'):
+                 want_stats=False, cluster_every=0, improved=False, integrator='leapfrog', momenta=None):
         """batch_size // C recorded steps.  Returns (the rung-ordered rows or None, the `_RungStats` with the rung-ordered
         measure rows `out` (steps, C, n_out) or None)."""
         K = len(self._ladder)
@@ -263,7 +267,7 @@ class LadderHMCSampler(HMCSampler):
                     phi, st = self._sweep(phi, (coef, rung), workspace=sweep_ws)
                 else:                                    # the same sweep, its labels kept; the rows rung-ordered
                     phi, st, labels = self._sweep(phi, (coef, rung), workspace=sweep_ws, want_labels=True)
-                    parts.append(measure_improved(phi, labels, path=improved).rows(base + rung.long()))
+                    parts.append(measure_improved(phi, labels, path=improved, momenta=momenta).rows(base + rung.long()))
                 sweeps.append(st)
                 if path == 'composed':
                     S = self._model.action(phi.double()).double()
@@ -299,7 +303,8 @@ class LadderHMCSampler(HMCSampler):
             self.last['cluster'] = (torch.stack(sweeps) if sweeps else
                                     torch.empty((0, C, 4), dtype=torch.int32, device=dev))
         if improved is not False:                 # only `measure` asks, so there are stats to carry the rows
-            stats.improved = ImprovedMeasurement.cat(parts, lat, dev)
+            stats.improved = ImprovedMeasurement.cat(parts, lat, dev,
+                                                     None if momenta is None else _hip.spectrum_momenta(lat, momenta))
         tried = [sum(1 for p in parities if p == k % 2) * (C // K) for k in range(K - 1)]
         self.history.exchange_rate.append([n / t if t else float('nan') for n, t in zip(accepted, tried)])
         y = None if out is None else out.reshape((batch_size,) + lat)

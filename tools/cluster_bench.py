@@ -32,7 +32,15 @@
       path.  `--shapes 0,1` picks shapes by index (0 is 16^3 x 1024).  The ratios and the verdict are those of the default
       block.
 
-    python tools/cluster_bench.py [--reps 5] [--inner 20] [--steps 1500] [--skip-tau] [--tiled | --improved | --improved-tiled]
+  --spectrum: instead of (a) .. (c), nf_cluster_spectrum on thermalised chains of 16^2 x 512 and 16^3 x 1024, fp32 and
+      fp64, at kappa = 0.67 and 0.25, with momenta 1, 2, 4 and all: the bare call against nf_cluster_moments (momenta 1
+      must be within the margin of it), against the composed path (`mcmc.cluster.cluster_spectrum`) on the device, and
+      against one sweep plus one trajectory (n_md = 10); medians of alternating timings with [min, max], the margin the
+      larger of 10 % and the run's spread.  Then the row variance of sum_s S(s) S(s + t) over that of its improved form on
+      (8, 8) x 32 chains at kappa = 0.25 and 0.45, fp64 (`--steps` recorded steps after 100).
+
+    python tools/cluster_bench.py [--reps 5] [--inner 20] [--steps 1500] [--skip-tau]
+                                  [--tiled | --improved | --improved-tiled | --spectrum]
 Prints one JSON line per shape and dtype and one for (c)."""
 import argparse
 import json
@@ -270,6 +278,93 @@ def improved(lattice, C, dtype, kappa, reps, inner):
                 mean_clusters=round(stats[:, 0].mean().item(), 1), mean_largest_fraction=round(stats[:, 2].mean().item() / phi[0].numel(), 4))
 
 
+def spectrum(lattice, C, dtype, kappa, reps, inner):
+    """nf_cluster_spectrum at momenta 1, 2, 4 and all on thermalised chains at `kappa`, against nf_cluster_moments, the
+    composed path and one sweep plus one trajectory, timed alternately."""
+    from normflow__amd.mcmc.cluster import cluster_spectrum
+    prior = NormalPrior(loc=torch.zeros(lattice, dtype=dtype, device=DEV), scale=torch.ones(lattice, dtype=dtype, device=DEV))
+    model = nf.Model(net_=None, prior=prior, action=ScalarPhi4Action(**dict(COUPLINGS, kappa=kappa)))
+    s = model.hmc
+    torch.manual_seed(0)
+    s.start(n_chains=C)
+    rnd = lambda t: [round(min(t), 4), round(max(t), 4)]
+    rel_spread = lambda t: (max(t) - min(t)) / statistics.median(t)
+    out = dict(lattice=list(lattice), chains=C, dtype=str(dtype).replace("torch.", ""), kappa=kappa, launches_per_timing=inner,
+               momenta={})
+    with torch.no_grad():
+        s.measure(30 * C, n_chains=C, n_md=N_MD, dt=DT, cluster_every=1)             # thermalise, sweeps included; no rows
+        phi = s._ref['sample'].clone()
+        coef, w0 = s._coef(lattice), float(model.action.get_coef(len(lattice))[0])
+        labels = _hip.phi4_cluster(phi.clone(), w0, position=(1, 0), want_labels=True)['labels']
+        work = phi.clone()
+
+        def moments():
+            for _ in range(inner):
+                _hip.cluster_moments(phi, labels)
+
+        def step():                                                  # one sweep and one trajectory, in place on a copy
+            for _ in range(inner):
+                _hip.phi4_cluster(work, w0)
+                _hip.phi4_hmc(work, *coef, N_MD, DT, n_traj=1)
+
+        for momenta in (1, 2, 4, 'all'):
+            def kernel():
+                for _ in range(inner):
+                    _hip.cluster_spectrum(phi, labels, momenta)
+
+            composed = lambda: cluster_spectrum(phi, labels, momenta)
+            for _ in range(2):
+                kernel(); moments(); step(); composed()
+            torch.cuda.synchronize()
+            k, c = _hip.cluster_spectrum(phi, labels, momenta), composed()
+            rel = ((k['out'] - c['out']).abs() / c['out'].abs()).max().item()
+            tk, tm, ts, tc = [], [], [], []
+            for _ in range(reps):
+                tk.append(_ms(kernel) / inner)
+                tm.append(_ms(moments) / inner)
+                ts.append(_ms(step) / inner)
+                tc.append(_ms(composed))
+            mk, mm, mst, mc = (statistics.median(t) for t in (tk, tm, ts, tc))
+            margin = max(0.10, rel_spread(tk), rel_spread(tm), rel_spread(tc))
+            plan = _hip.cluster_spectrum_plan(lattice, dtype, momenta)
+            out['momenta'][str(momenta)] = dict(
+                spectrum_ms=round(mk, 4), spectrum_ms_spread=rnd(tk), moments_ms=round(mm, 4), moments_ms_spread=rnd(tm),
+                spectrum_over_moments=round(mk / mm, 3), composed_ms=round(mc, 3), composed_ms_spread=rnd(tc),
+                composed_over_kernel=round(mc / mk, 1), sweep_plus_trajectory_ms=round(mst, 4),
+                sweep_plus_trajectory_ms_spread=rnd(ts), spectrum_over_step=round(mk / mst, 3), margin=round(margin, 3),
+                kernel_wins=bool(mc / mk > 1 + margin), quantities=plan['quantities'], passes=plan['passes'],
+                us_per_quantity=round(1000 * mk / plan['quantities'], 2), max_rel_diff_of_the_doubles=rel,
+                same_status=bool(torch.equal(k['status'], c['status'])))
+        one = out['momenta']['1']
+        out['momenta_1_within_margin_of_moments'] = bool(one['spectrum_over_moments'] <= 1 + one['margin'])
+    return out
+
+
+def correlator_variance_ratios(steps):
+    """Row variance of sum_s S(s) S(s + t) over that of its improved form, t = 0 .. L / 2, and the jackknife errors of
+    G(L / 2) both ways: (8, 8), 32 chains, fp64, `steps` recorded steps after 100, a sweep before every step."""
+    from normflow__amd.lib.observables import ImprovedEnsemble
+    lattice, C, drop = (8, 8), 32, 100
+    out = dict(lattice=list(lattice), chains=C, steps=steps, m_sq=COUPLINGS['m_sq'], lambd=COUPLINGS['lambd'], rows={})
+    for kappa in (0.25, 0.45):
+        prior = NormalPrior(loc=torch.zeros(lattice, dtype=torch.float64, device=DEV), scale=torch.ones(lattice, dtype=torch.float64, device=DEV))
+        model = nf.Model(net_=None, prior=prior, action=ScalarPhi4Action(**dict(COUPLINGS, kappa=kappa)))
+        s = model.hmc
+        torch.manual_seed(1)
+        s.start(n_chains=C)
+        with torch.no_grad():
+            m = s.measure((drop + steps) * C, n_chains=C, n_md=N_MD, dt=DT, cluster_every=1, improved=True, momenta='all')
+        plain, imp = m.correlator(axis=0)[drop * C:], m.improved.correlator(axis=0)[drop * C:]
+        (g, ge), (ig, ige) = (Ensemble(m, n_chains=C, drop=drop).correlator(axis=0),
+                              ImprovedEnsemble(m.improved, n_chains=C, drop=drop).correlator(axis=0))
+        out['rows'][str(kappa)] = dict(
+            var_ratio_t=[round((plain[:, t].var() / imp[:, t].var()).item(), 2) for t in range(5)],
+            G_plain=[round(float(x), 6) for x in g[:5]], G_plain_err=[round(float(x), 6) for x in ge[:5]],
+            G_improved=[round(float(x), 6) for x in ig[:5]], G_improved_err=[round(float(x), 6) for x in ige[:5]],
+            refused_rows=int(m.improved.status.sum().item()))
+    return out
+
+
 BLOCKS = (2048, 4096, 8192)
 
 
@@ -432,8 +527,17 @@ def main():
     ap.add_argument("--tiled", action="store_true", help="nf_phi4_cluster_tiled on the lattices beyond nf_phi4_cluster")
     ap.add_argument("--improved", action="store_true", help="nf_cluster_moments and the improved estimators")
     ap.add_argument("--improved-tiled", action="store_true", help="nf_cluster_moments_tiled on the lattices beyond nf_cluster_moments")
+    ap.add_argument("--spectrum", action="store_true", help="nf_cluster_spectrum and the improved correlator")
     ap.add_argument("--shapes", default="", help="--improved-tiled: comma-separated indices into 16^3 x 1024 and the four tiled shapes")
     a = ap.parse_args()
+    if a.spectrum:
+        for lattice, C in SHAPES:
+            for dtype in (torch.float32, torch.float64):
+                for kappa in (0.67, 0.25):
+                    print(json.dumps(spectrum(lattice, C, dtype, kappa, a.reps, a.inner)), flush=True)
+        if not a.skip_tau:
+            print(json.dumps(correlator_variance_ratios(a.steps)), flush=True)
+        return
     if a.improved_tiled:
         shapes = [((16, 16, 16), 1024, True)] + [(lat, C, False) for lat, C in TILED_SHAPES]
         picked = [int(i) for i in a.shapes.split(",") if i != ""] or range(len(shapes))
