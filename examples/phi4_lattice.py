@@ -111,7 +111,8 @@ def correlators(m, n_chains, drop):
 INTEGRATOR_N_MD = dict(leapfrog=10, omelyan=5, omf4=2)
 
 
-def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False, integrator='leapfrog', correlator=False):
+def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False, integrator='leapfrog', correlator=False,
+                     spectrum_path=None):
     """<phi^2> of the trained flow + Metropolis next to hybrid Monte Carlo on the action itself (exact up to its own
     statistical error; the first quarter of every chain is dropped as thermalisation), then the observables of both.
     `cluster`: also model.hmc with a Swendsen-Wang sweep of the signs before every recorded step (cluster_every=1), so
@@ -135,7 +136,8 @@ def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False
               % (*phi2(y, n_chains, rows // 4), model.hmc.history.accept_rate[-1], big))
         print("model.hmc, cluster_every=1   " + observables(model, y, n_chains, rows // 4))
         if improved:
-            m = model.hmc.measure(n_chains * rows, cluster_every=1, improved=True, momenta='all' if correlator else None, **hmc)
+            m = model.hmc.measure(n_chains * rows, cluster_every=1, improved=True, momenta='all' if correlator else None,
+                                  spectrum_path=spectrum_path if correlator else None, **hmc)
             print("model.hmc, cluster_every=1, the next %d steps both ways (sweeps and steps coincide: drop = 0)" % rows)
             print(both_ways(m, n_chains, 0))
             if correlator:
@@ -191,6 +193,9 @@ def main():
     ap.add_argument("--correlator", action="store_true",
                     help="with --hmc --cluster --improved: the time-slice correlator G(t) and the effective mass along axis 0, "
                          "plain and cluster-improved (the sweeps' spectrum at all momenta)")
+    ap.add_argument("--spectrum-path", choices=("hbm",), default=None,
+                    help="with --correlator: take the sweeps' spectrum with nf_cluster_spectrum_tiled (the slots in HBM), the "
+                         "kernel for lattices beyond one CU's LDS; default: the one-CU kernel where it applies, else torch ops")
     ap.add_argument("--ladder", action="store_true",
                     help="no fit: a ladder of 6 kappas from --kappa down to 0.4 of it in one HMC launch per step, chi, U4 and "
                          "tau_int(m) per rung without and with replica exchange")
@@ -209,7 +214,8 @@ def main():
         model.fit(**kw)
         nf.backward_sanitychecker(model)
         if a.hmc:
-            compare_with_hmc(model, cluster=a.cluster, improved=a.improved, integrator=a.integrator, correlator=a.correlator)
+            compare_with_hmc(model, cluster=a.cluster, improved=a.improved, integrator=a.integrator, correlator=a.correlator,
+                             spectrum_path=a.spectrum_path)
 
 
 if __name__ == "__main__":

@@ -1155,6 +1155,64 @@ int nf_cluster_spectrum_plan(const int32_t *lattice, int dtype, int kmax, nf_spe
 int nf_cluster_spectrum(const void *phi, const int32_t *labels, double *out, int32_t *status, int64_t C,
                         const int32_t *lattice, int kmax, const double *tw, int dtype, void *stream);
 
+/* ---- the cluster spectrum with the chains, the labels and the int64 slots in HBM (nf_cluster_spectrum_tiled.hip): for
+ * lattices beyond nf_cluster_spectrum's class (32^3, 16^4, 32^4, 48^4, ...).  The "cluster spectrum" rule above holds word
+ * for word: the momenta K_mu from kmax; the quantities and their order (A, then per axis in order and per k ascending R,
+ * I; R alone at Nyquist); Q = 1 + sum_mu (2 K_mu - [2 K_mu = L_mu]); the fixed point q, the range test, the caller's
+ * twiddle table with index off_mu + (k x_mu mod L_mu); the refusal (status 1, a NaN row); the columns (C, 2 + sum_mu K_mu),
+ * with no column for an axis of extent 1.
+ * The ONE new part is the order of each sum of squares over the V slots, and it is nf_cluster_moments_tiled's:
+ *   - a chain's slots are cut into BLOCKS, runs of block_sites consecutive slot indices (the last may be short);
+ *   - within a block, lane l of 256 takes the slots first + l, first + l + 256, ... with the explicit fma forms above,
+ *     then the shuffle tree per wave, then the 4 waves in order: the block's partial;
+ *   - a last kernel adds the blocks' partials with one wave per (chain, sum): lane l takes the blocks l, l + 64, ... in
+ *     order, then the shuffle tree;
+ *   - a column is (sum r^2) + (sum i^2), formed after both sums are complete; at Nyquist sum r^2 alone.
+ * Consequences:
+ *   - a row's bits depend on the chain, its labels, the lattice, the dtype and block_sites alone: not on C, not on the
+ *     row's place in the batch, not on per_pass, not on the workspace's former content, not on the schedule;
+ *   - a column's bits do not depend on kmax: the columns at kmax = m are the corresponding columns at kmax = 0;
+ *   - columns 0 and 1 and every k = 1 column are nf_cluster_moments_tiled's bits at the same block_sites, and status is
+ *     its status;
+ *   - where one block holds the chain and nf_cluster_spectrum runs 256 lanes (a (16, 16) lattice is such a case), the row
+ *     is nf_cluster_spectrum's bit for bit.
+ * Any lattice of extents >= 1 with V < 2^31, NF_F32 / NF_F64, C in 1 .. 65535.  block_sites as in
+ * nf_cluster_moments_tiled: 0 is the default (4096), a value above V means V, blocks x 256 must stay below 2^32.  The Q
+ * quantities go in passes of per_pass CONSECUTIVE quantities that reuse the slot arrays; per_pass = 0 means min(Q, 16) and
+ * the legal values are 0 .. min(Q, 16): 16 is nf_cluster_spectrum's cap per pass and keeps a lane's run sums in registers.
+ * Q <= 1024: a lattice and kmax with more quantities is refused (give a smaller kmax > 0); the cap bounds the launches and
+ * the partials.
+ * Launches, in a line on `stream` after one memset of the flags: CHECK (range and label test of every site, before
+ * anything is indexed by a label; a failing block sets the chain's flag, and every later kernel leaves a refused chain's
+ * slots alone); per pass a memset of the pass's slot arrays, SCATTER (a site is read once per pass and all quantities of
+ * the pass are taken from it; x_mu is taken once per axis of the pass; a lane adds up its consecutive sites that share a
+ * label and sends the run through the claim-add-flush table of nf_cluster_moments_tiled, H = 512 entries with one int64
+ * sum per quantity of the pass in dynamic LDS, 512 (4 + 8 per_pass) bytes; one global 64-bit integer add without a return
+ * value per claimed (label, quantity)) and SQUARES (the blocks' partials); FINISH (the partials in block order, the row or
+ * NaNs, status): 2 + 2 passes kernels and 1 + passes memsets.  No floating-point atomic, no allocation, no host
+ * synchronisation: the call can be captured into a HIP graph.
+ *   workspace   nf_cluster_spectrum_tiled_workspace bytes, 16-byte aligned, owned by the caller, need not be initialised:
+ *               4 C bytes of flags rounded up to 16, per_pass C V 8 bytes of slots, C (Q + 1) blocks doubles of partials
+ *               (a^2, a^4 and one sum per further quantity).
+ * nf_cluster_spectrum_tiled_plan (pure host): blocks per chain, the block_sites in force, kmax[mu] = K_mu of the padded
+ * axes, columns, quantities, per_pass (in force), passes, table entries (H), kernel launches, and the LDS bytes of the
+ * scatter kernel.  _supported (pure host, per_pass = 0): 1 or 0 with the reason in nf_last_error_string.  _workspace (pure
+ * host): the bytes, 0 for a case the planner refuses or C outside 1 .. 65535.
+ * NF_EINVAL, all checked before anything is launched: whatever nf_cluster_moments_tiled refuses, kmax < 0, per_pass
+ * outside 0 .. min(Q, 16), Q > 1024. */
+typedef struct nf_spectrum_tiled_plan {
+  int64_t blocks;
+  int32_t block_sites, kmax[4], columns, quantities, per_pass, passes, table_entries, launches;
+  int64_t lds_bytes;
+} nf_spectrum_tiled_plan;
+int nf_cluster_spectrum_tiled_supported(const int32_t *lattice, int dtype, int kmax, int64_t block_sites);
+int nf_cluster_spectrum_tiled_plan(const int32_t *lattice, int dtype, int kmax, int64_t block_sites, int per_pass,
+                                   nf_spectrum_tiled_plan *out);
+size_t nf_cluster_spectrum_tiled_workspace(int64_t C, const int32_t *lattice, int kmax, int64_t block_sites, int per_pass);
+int nf_cluster_spectrum_tiled(const void *phi, const int32_t *labels, double *out, int32_t *status, int64_t C,
+                              const int32_t *lattice, int kmax, const double *tw, int dtype, int64_t block_sites,
+                              int per_pass, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- what the samplers' rows measure (nf_measure.hip; MI355X-side extension): every sufficient statistic of N
  * configurations in one pass.  cfgs (N, V) of dtype NF_F32 / NF_F64 on lattice[4] (leading extents 1 for d < 4);
  * out (N, n_out) DOUBLE, n_out = 7 + lattice[0] + lattice[1] + lattice[2] + lattice[3], per row

@@ -127,6 +127,10 @@ PROTOTYPES = {
     "nf_cluster_moments_tiled_plan": (_I, [C.POINTER(C.c_int32), _I, _I64, _I, _P]),
     "nf_cluster_moments_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I64, _I]),
     "nf_cluster_moments_tiled": (_I, [_P, _P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _I64, _I, _P, _SZ, _P]),
+    "nf_cluster_spectrum_tiled_supported": (_I, [C.POINTER(C.c_int32), _I, _I, _I64]),
+    "nf_cluster_spectrum_tiled_plan": (_I, [C.POINTER(C.c_int32), _I, _I, _I64, _I, _P]),
+    "nf_cluster_spectrum_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I, _I64, _I]),
+    "nf_cluster_spectrum_tiled": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _I, _P, _I, _I64, _I, _P, _SZ, _P]),
     "nf_phi4_cluster_ladder": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_phi4_cluster_tiled_ladder": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, C.c_uint64, C.c_uint64, _I,
                                           _I64, _P, _SZ, _P]),
@@ -2652,6 +2656,96 @@ def cluster_moments_tiled(phi, labels, want_moments=False, block_sites=0, per_pa
                                            _stream()), "nf_cluster_moments_tiled")
     pad = 4 - len(lat)
     return dict(out=torch.cat([out[:, :2], out[:, 2 + pad:]], dim=1), status=status, moments=moments)
+
+
+# ========================================================================= the spectrum, slots in HBM (nf_cluster_spectrum_tiled.hip)
+SPECTRUM_TILED_MAX_PASS = 16            # quantities per pass: nf_cluster_spectrum's cap
+
+
+class SpectrumTiledPlan(C.Structure):
+    """nf_spectrum_tiled_plan (include/normflow_hip.h)."""
+    _fields_ = [("blocks", C.c_int64), ("block_sites", C.c_int32), ("kmax", C.c_int32 * 4), ("columns", C.c_int32),
+                ("quantities", C.c_int32), ("per_pass", C.c_int32), ("passes", C.c_int32), ("table_entries", C.c_int32),
+                ("launches", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
+def cluster_spectrum_tiled_supported(lat, dtype, momenta='all', block_sites=0):
+    """True if nf_cluster_spectrum_tiled takes chains on the lattice `lat` (1 to 4 extents) in `dtype` at `momenta` with
+    blocks of `block_sites` sites (0: the default): the launcher's own planner, pure host code."""
+    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
+        return False
+    return bool(load().nf_cluster_spectrum_tiled_supported(_lat4(lat), _dtype_code_of(dtype), spectrum_kmax(momenta),
+                                                           _block_sites(block_sites)))
+
+
+def cluster_spectrum_tiled_plan(lat, dtype, momenta='all', block_sites=0, per_pass=0):
+    """What nf_cluster_spectrum_tiled will do on the lattice `lat` in `dtype`: dict(blocks (per chain), block_sites (in
+    force), kmax (K_mu of the four padded axes), columns, quantities, per_pass (in force; 0 asks for min(Q, 16)), passes,
+    table_entries (H), launches (kernels: 2 + 2 passes), lds_bytes (of the scatter kernel)).  Pure host code."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"cluster_spectrum_tiled_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
+    out = SpectrumTiledPlan()
+    _check(load().nf_cluster_spectrum_tiled_plan(_lat4(lat), _dtype_code_of(dtype), spectrum_kmax(momenta),
+                                                 _block_sites(block_sites), int(per_pass or 0), C.byref(out)),
+           "nf_cluster_spectrum_tiled_plan")
+    d = {name: getattr(out, name) for name, _ in SpectrumTiledPlan._fields_}
+    d['kmax'] = tuple(out.kmax)
+    return d
+
+
+def cluster_spectrum_tiled_workspace(Cn, lat, momenta='all', block_sites=0, per_pass=0):
+    """nf_cluster_spectrum_tiled_workspace: the bytes of the workspace of a call on Cn chains on `lat`; pure host code."""
+    return int(load().nf_cluster_spectrum_tiled_workspace(int(Cn), _lat4(tuple(lat)), spectrum_kmax(momenta),
+                                                          _block_sites(block_sites), int(per_pass or 0)))
+
+
+def cluster_spectrum_tiled_per_pass(Cn, lat, momenta='all', block_sites=0):
+    """The `per_pass` that `cluster_spectrum_tiled(per_pass=None)` takes: the largest value <= min(Q, 16) whose workspace
+    stays under `moments_max_workspace()`, and at least 1.  The workspace is linear in per_pass, so two planner calls
+    give it."""
+    lat = tuple(lat)
+    K = spectrum_momenta(lat, momenta)
+    cap = min(SPECTRUM_TILED_MAX_PASS, 1 + sum(2 * k - (1 if k and 2 * k == n else 0) for k, n in zip(K, lat)))
+    one = cluster_spectrum_tiled_workspace(Cn, lat, momenta, block_sites, 1)
+    if one == 0 or cap < 2:
+        return 1
+    step = cluster_spectrum_tiled_workspace(Cn, lat, momenta, block_sites, 2) - one
+    if step <= 0:
+        return 1
+    return int(max(1, min(cap, 1 + (moments_max_workspace() - one) // step)))
+
+
+def cluster_spectrum_tiled(phi, labels, momenta='all', block_sites=0, per_pass=None, workspace=None):
+    """nf_cluster_spectrum_tiled: `cluster_spectrum` for chains that live in HBM, any lattice of 1 to 4 axes with fewer
+    than 2^31 sites; the same dict(out, status, momenta).  status is `cluster_spectrum`'s bit for bit, out differs in the
+    order of the sums of squares alone (blocks of `block_sites` slots, 0: the default; include/normflow_hip.h): columns 0
+    and 1 and the k = 1 columns are `cluster_moments_tiled`'s bits at the same `block_sites`.  The Q quantities go in passes
+    of `per_pass` <= 16 (None: `cluster_spectrum_tiled_per_pass`; it changes the footprint and the launches, never a bit).
+    2 + 2 passes launches and 1 + passes memsets on the current stream.  The workspace comes from torch's caching
+    allocator per call (stream-aware and graph-pool safe), or is `workspace`: a uint8 tensor of at least
+    nf_cluster_spectrum_tiled_workspace bytes.  Graph capture: as `cluster_moments`, call `twiddle_table(lat, device)` first."""
+    _require_device(phi, labels)
+    lat = tuple(phi.shape[1:])
+    if not phi.is_contiguous() or not 1 <= len(lat) <= 4:
+        raise NormflowHipError("cluster_spectrum_tiled needs contiguous phi (C, *L) with 1 to 4 lattice axes, got "
+                               f"{tuple(phi.shape)}")
+    if labels.shape != phi.shape or labels.dtype != torch.int32 or not labels.is_contiguous() or labels.device != phi.device:
+        raise NormflowHipError(f"cluster_spectrum_tiled: labels must be a contiguous int32 tensor {tuple(phi.shape)} on "
+                               f"{phi.device}, got {tuple(labels.shape)} {labels.dtype} on {labels.device}")
+    kmax = spectrum_kmax(momenta)
+    K = spectrum_momenta(lat, momenta)
+    Cn, dev, bs = phi.shape[0], phi.device, _block_sites(block_sites)
+    pp = cluster_spectrum_tiled_per_pass(Cn, lat, momenta, bs) if per_pass is None else int(per_pass)
+    if workspace is None:
+        need = load().nf_cluster_spectrum_tiled_workspace(Cn, _lat4(lat), kmax, bs, pp)
+        workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    out = torch.empty((Cn, 2 + sum(K)), dtype=torch.float64, device=dev)
+    status = torch.empty((Cn,), dtype=torch.int32, device=dev)
+    tw = twiddle_table(lat, dev)
+    _check(load().nf_cluster_spectrum_tiled(_ptr(phi), _ptr(labels), _ptr(out), _ptr(status), Cn, _lat4(lat), kmax, _ptr(tw),
+                                            _dtype_code(phi), bs, pp, _ptr(workspace), workspace.numel(), _stream()),
+           "nf_cluster_spectrum_tiled")
+    return dict(out=out, status=status, momenta=K)
 
 
 # ========================================================================= observables of sampler rows (nf_measure.hip)

@@ -13,6 +13,7 @@
 //     owns quantity j, an R writes its column with the I that follows it in the pass, and an R that ends a pass leaves its
 //     sum in the carry slot for thread 0 of the next pass.
 #include "nf_internal.h"
+#include "nf_cluster_spectrum_core.h"
 
 namespace nf {
 namespace {
@@ -25,12 +26,9 @@ constexpr size_t kCsScratch = 4096;                 // kCsWaves x kCsCols double
 constexpr size_t kCsLdsBudget = 160 * 1024;
 static_assert((kCsWaves * kCsCols + kCsCols + 2) * sizeof(double) <= kCsScratch, "reduction region");
 
-struct CsPlan {
+struct CsPlan : CsLayout {        // K, stride, extent, off, the prefix counts, nq, ncols: nf_cluster_spectrum_core.h
   int64_t V;
-  int ns, nt, nq, ncols, per_pass, passes;
-  int K[4], stride[4], extent[4], off[4];
-  int qpre[4];                   // quantities (after A) in front of axis mu
-  int cpre[4];                   // columns (after the two of A) in front of axis mu
+  int ns, nt, per_pass, passes;
   size_t lds;
   double limit;                  // 2^min(16, 30 - ceil(log2 V))
 };
@@ -49,23 +47,7 @@ int cs_plan(const char *what, const int32_t *lattice, int dtype, int kmax, CsPla
   p.V = int64_t(lattice[0]) * lattice[1] * lattice[2] * lattice[3];
   p.ns = cp.sites_per_lane;
   p.nt = cp.lanes;
-  int stride = int(p.V), off = 0, nq = 0, nc = 0;
-  for (int mu = 0; mu < 4; ++mu) {
-    const int L = lattice[mu];
-    stride /= L;
-    const int K = L == 1 ? 0 : (kmax == 0 || kmax > L / 2 ? L / 2 : kmax);
-    p.K[mu] = K;
-    p.stride[mu] = stride;
-    p.extent[mu] = L;
-    p.off[mu] = off;
-    p.qpre[mu] = nq;
-    p.cpre[mu] = nc;
-    nq += 2 * K - (K > 0 && 2 * K == L ? 1 : 0);
-    nc += K;
-    off += L;
-  }
-  p.nq = 1 + nq;
-  p.ncols = 2 + nc;
+  cs_layout(lattice, kmax, p.V, p);
   size_t fit = (kCsLdsBudget - kCsScratch) / (size_t(p.V) * 8);      // >= 1: V <= 16384
   if (fit > size_t(kCsMaxPass)) fit = kCsMaxPass;
   p.per_pass = int(fit < size_t(p.nq) ? fit : size_t(p.nq));
@@ -88,26 +70,6 @@ struct CsArgs {
   int stride[4], extent[4], off[4], qpre[4], cpre[4];
   double limit;
 };
-
-// the descriptor of quantity qid >= 1, wave-uniform: the axis is the last whose prefix count is <= qid - 1 (an axis without
-// quantities shares its prefix with the next one that has some, and the comparisons step over it)
-struct CsQuantity {
-  int stride, extent, off, k, comp, col;
-};
-
-__device__ __forceinline__ CsQuantity cs_quantity(const CsArgs &A, int qid) {
-  const int r = qid - 1;
-  const int mu = (r >= A.qpre[1] ? 1 : 0) + (r >= A.qpre[2] ? 1 : 0) + (r >= A.qpre[3] ? 1 : 0);
-#define NF_CS_PICK(f) (mu == 1 ? A.f[1] : mu == 2 ? A.f[2] : mu == 3 ? A.f[3] : A.f[0])
-  CsQuantity d{NF_CS_PICK(stride), NF_CS_PICK(extent), NF_CS_PICK(off), 0, 0, NF_CS_PICK(cpre)};
-  const int pre = NF_CS_PICK(qpre);
-#undef NF_CS_PICK
-  const int local = r - pre;
-  d.k = (local >> 1) + 1;
-  d.comp = local & 1;
-  d.col += 2 + (local >> 1);
-  return d;
-}
 
 template <typename T, int NS>
 __global__ __launch_bounds__(kCsMaxLanes) void cluster_spectrum_kernel(CsArgs A) {

@@ -14,7 +14,8 @@ and the on-axis momentum-space propagator |sum_t e^{ipt} S_mu(t)|^2 / V at p = 2
 `measure_improved(cfgs, labels)` gives the cluster-improved forms of (sum phi)^2, (sum phi)^4 and the propagator at
 p_min from the labels of a Swendsen-Wang sweep (`ImprovedMeasurement`, `ImprovedEnsemble`; nf_cluster_moments on the
 device).  With `momenta='all'` it also carries the cluster spectrum (nf_cluster_spectrum), from which the improved
-propagator at every on-axis momentum and the improved time-slice correlator follow.
+propagator at every on-axis momentum and the improved time-slice correlator follow; `spectrum_path='hbm'` takes it with
+nf_cluster_spectrum_tiled, the kernel for lattices beyond one CU's LDS.
 
 `Ensemble` reads the rows as (steps, chains) -- row r = step r // C of chain r % C, the layout of model.mcmc,
 model.blocked_mcmc and model.hmc -- and gives every estimate as (value, error): leave-one-chain-out jackknife for
@@ -284,6 +285,7 @@ class Ensemble:
 
 # ---------------------------------------------------------------- cluster-improved estimators
 IMPROVED_PATHS = (None, 'kernel', 'composed', 'hbm')
+SPECTRUM_PATHS = (None, 'hbm')             # of `measure_improved(spectrum_path=...)`: 'hbm' is nf_cluster_spectrum_tiled
 
 
 def improved_kernel_applies(cfgs):
@@ -302,7 +304,7 @@ def route_improved(cfgs):
 
 
 @torch.no_grad()
-def measure_improved(cfgs, labels, path=None, momenta=None):
+def measure_improved(cfgs, labels, path=None, momenta=None, spectrum_path=None, workspace=None):
     """(N, *L) configurations and the (N, *L) int32 labels of their cluster decompositions (a Swendsen-Wang sweep's:
     `hmc.cluster(phi)['labels']`, with the field before or after the flip) -> `ImprovedMeasurement`: the averages over
     all 2^Nc assignments of the clusters' signs, in closed form from the clusters' sums M_C (include/normflow_hip.h,
@@ -314,19 +316,38 @@ def measure_improved(cfgs, labels, path=None, momenta=None):
     k = 1 .. K_mu of every axis (include/normflow_hip.h, "cluster spectrum"), from which `propagator` and `correlator`
     follow where momenta='all'.  path=None / 'kernel' then run nf_cluster_spectrum where `improved_kernel_applies`
     (path=None elsewhere: composed), 'composed' is `mcmc.cluster.cluster_spectrum`, and 'hbm' raises ValueError: there is
-    no tiled spectrum kernel, lattices beyond one CU take the composed path.  `out` is that of the call without momenta
-    bit for bit on the same path (its columns are columns of the spectrum's row)."""
+    no spectrum on that path key; the tiled spectrum kernel is reached through `spectrum_path`.  `out` is that of the call
+    without momenta bit for bit on the same path (its columns are columns of the spectrum's row).
+    spectrum_path='hbm' (opt-in; needs momenta, and path None or 'hbm'; ValueError otherwise): nf_cluster_spectrum_tiled,
+    the slots in HBM, any lattice on the device (raises on CPU tensors); `out` is then that of path='hbm' bit for bit.
+    `workspace`: a uint8 tensor for that kernel (`_hip.cluster_spectrum_tiled`), None: one per call; ValueError where it
+    is given without spectrum_path.  Without
+    spectrum_path every call does what it did: path=None beyond one CU stays on the composed path."""
     if path not in IMPROVED_PATHS:
         raise ValueError(f"path must be None, 'kernel', 'composed' or 'hbm', got {path!r}")
     if not 1 <= cfgs.ndim - 1 <= 4:
         raise ValueError(f"measure_improved: configurations (N, *L) with 1 to 4 lattice axes, got {tuple(cfgs.shape)}")
     lat = tuple(cfgs.shape[1:])
+    if spectrum_path not in SPECTRUM_PATHS:
+        raise ValueError(f"spectrum_path must be None or 'hbm', got {spectrum_path!r}")
+    if workspace is not None and spectrum_path is None:
+        raise ValueError("measure_improved: workspace is the workspace of spectrum_path='hbm' (nf_cluster_spectrum_tiled); "
+                         "no other path takes one")
+    if spectrum_path is not None:
+        if momenta is None:
+            raise ValueError("measure_improved: spectrum_path='hbm' is the path of the spectrum: it needs momenta")
+        if path not in (None, 'hbm'):
+            raise ValueError(f"measure_improved: spectrum_path='hbm' goes with path None or 'hbm', got path={path!r}")
     if momenta is not None:
-        if path == 'hbm':
+        if path == 'hbm' and spectrum_path is None:
             raise ValueError("measure_improved: no spectrum on path 'hbm' (nf_cluster_moments_tiled has no spectrum form): "
-                             "use path='composed' for lattices beyond one CU")
+                             "use spectrum_path='hbm' (nf_cluster_spectrum_tiled), or path='composed', for lattices beyond "
+                             "one CU")
         if momenta != 'all' and (isinstance(momenta, bool) or not isinstance(momenta, int) or momenta < 1):
             raise ValueError(f"momenta must be None, 'all' or an int >= 1, got {momenta!r}")
+        if spectrum_path == 'hbm':
+            r = _hip.cluster_spectrum_tiled(cfgs.contiguous(), labels.contiguous(), momenta, workspace=workspace)
+            return ImprovedMeasurement.from_spectrum(r['out'], r['status'], lat, r['momenta'])
         if path is None:
             path = 'kernel' if improved_kernel_applies(cfgs) else 'composed'
         if path == 'kernel':

@@ -86,7 +86,7 @@ class HMCSampler:
 
     @torch.no_grad()
     def measure(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, return_rows=False, cluster_every=0,
-                improved=False, integrator='leapfrog', momenta=None):
+                improved=False, integrator='leapfrog', momenta=None, spectrum_path=None):
         """The `Measurement` of the rows that `sample(batch_size, ...)` would return from the same chain and generator
         state, WITHOUT storing them: every recorded state is measured where it is and only its 7 + sum L sums are kept.
         The rows are in the samplers' layout (`Ensemble(m, n_chains=C)` takes it as is), the action is attached when the
@@ -107,12 +107,17 @@ class HMCSampler:
         without it bit for bit, and there is still one device-to-host read (the statuses stay on the device).
         momenta='all' or an int >= 1 (with improved; ValueError without): `.improved` also carries the cluster spectrum
         (`observables.measure_improved(..., momenta=...)`), from which the improved propagator and time-slice correlator
-        follow; it changes nothing else of the call, bit for bit, `improved.out` included."""
+        follow; it changes nothing else of the call, bit for bit, `improved.out` included.
+        spectrum_path='hbm' (with momenta; ValueError without; improved True or 'hbm'): the spectrum is
+        nf_cluster_spectrum_tiled's (`observables.measure_improved(..., spectrum_path='hbm')`), for the lattices beyond
+        one CU's LDS, with one workspace for all sweeps of the call."""
         ipath = self._improved_path(improved, cluster_every)
         if momenta is not None and ipath is False:
             raise ValueError("momenta asks for the spectrum of the improved estimators: it needs improved=True (or a path)")
+        self._spectrum_path(spectrum_path, momenta, ipath)
         y, stats = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=return_rows, want_stats=True,
-                                 cluster_every=cluster_every, improved=ipath, integrator=integrator, momenta=momenta)
+                                 cluster_every=cluster_every, improved=ipath, integrator=integrator, momenta=momenta,
+                                 spectrum_path=spectrum_path)
         action = self._model.action
         m = stats.measurement(action if hasattr(action, 'get_coef') else None)
         if ipath is not False:
@@ -132,12 +137,35 @@ class HMCSampler:
         return None if improved is True else improved
 
     @staticmethod
+    def _spectrum_path(spectrum_path, momenta, ipath):
+        """The checks of `measure(spectrum_path=...)`, before anything runs: those of `observables.measure_improved`."""
+        if spectrum_path is None:
+            return
+        if spectrum_path != 'hbm':
+            raise ValueError(f"spectrum_path must be None or 'hbm', got {spectrum_path!r}")
+        if momenta is None:
+            raise ValueError("spectrum_path='hbm' is the path of the spectrum of the improved estimators: it needs momenta")
+        if ipath not in (None, 'hbm'):
+            raise ValueError(f"spectrum_path='hbm' goes with improved=True or 'hbm', got improved={ipath!r}")
+
+    @staticmethod
+    def _spectrum_workspace(phi, momenta, spectrum_path):
+        """One workspace of nf_cluster_spectrum_tiled for all sweeps of a call, and the keywords that hand it on."""
+        if spectrum_path is None:
+            return {}
+        if not phi.is_cuda:
+            raise _hip.NormflowHipError("spectrum_path='hbm' is nf_cluster_spectrum_tiled: it needs chains on the device")
+        Cn, lat = phi.shape[0], tuple(phi.shape[1:])
+        need = _hip.cluster_spectrum_tiled_workspace(Cn, lat, momenta, 0, _hip.cluster_spectrum_tiled_per_pass(Cn, lat, momenta))
+        return dict(spectrum_path=spectrum_path, workspace=torch.empty(max(need, 256), dtype=torch.uint8, device=phi.device))
+
+    @staticmethod
     def _scheme(integrator):
         """None for leapfrog by its name (the samplers then make the calls they always made), else the `_hip.HmcScheme`."""
         return None if isinstance(integrator, str) and integrator == 'leapfrog' else _hip.hmc_scheme(integrator)
 
     def _advance(self, batch_size, n_chains, n_md, dt, n_skip, path, want_rows, want_stats, cluster_every=0,
-                 improved=False, integrator='leapfrog', momenta=None):
+                 improved=False, integrator='leapfrog', momenta=None, spectrum_path=None):
         """batch_size // n_chains recorded steps of the chains: (the rows (batch_size, *L) or None, the `_Stats` of the
         recorded states or None); the chains, `last` and `history` updated.  cluster_every = E >= 1: the recorded steps
         are run in spans that end before the next step s (counted across calls) with s % E == 0, with one cluster sweep
@@ -159,6 +187,7 @@ class HMCSampler:
             phi = phi.clone()                                     # the kernels run in place
         if improved is not False:
             from ..lib.observables import ImprovedMeasurement, measure_improved
+            spec = self._spectrum_workspace(phi, momenta, spectrum_path)      # one workspace for all sweeps of the call
         dhs, accs, sweeps, parts, r0 = [], [], [], [], 0
         while r0 < rows:
             if E and (self._steps + r0) % E == 0:
@@ -166,7 +195,7 @@ class HMCSampler:
                     phi, st = self._sweep(phi, workspace=sweep_ws)
                 else:                                                 # the same sweep, its labels kept
                     phi, st, labels = self._sweep(phi, workspace=sweep_ws, want_labels=True)
-                    parts.append(measure_improved(phi, labels, path=improved, momenta=momenta))
+                    parts.append(measure_improved(phi, labels, path=improved, momenta=momenta, **spec))
                 sweeps.append(st)
                 if path == 'composed':
                     S = self._model.action(phi.double()).double()

@@ -150,17 +150,18 @@ class LadderHMCSampler(HMCSampler):
         return y, (-self._ladder.action(y, rung)).to(y.dtype)
 
     @torch.no_grad()
-    def measure(self, batch_size=1, return_rows=False, improved=False, momenta=None, **kwargs):
+    def measure(self, batch_size=1, return_rows=False, improved=False, momenta=None, spectrum_path=None, **kwargs):
         """The list of K `Measurement`s.  improved=True / 'kernel' / 'composed' / 'hbm' as in `HMCSampler.measure`: entry k then
         carries `.improved`, the `ImprovedMeasurement` of rung k's sweeps x R rows (the kernel does not know the
         couplings: a sweep's C rows are taken by chain and laid out rung-ordered, row (c // K) K + rung[c] with the rungs
         in force at that sweep, like `last['cluster']`).  momenta='all' or an int >= 1 as in `HMCSampler.measure`: the
-        spectrum rides along, rung-ordered like the rest."""
+        spectrum rides along, rung-ordered like the rest.  spectrum_path='hbm' as in `HMCSampler.measure`."""
         ipath = self._improved_path(improved, kwargs.get('cluster_every', 0))
         if momenta is not None and ipath is False:
             raise ValueError("momenta asks for the spectrum of the improved estimators: it needs improved=True (or a path)")
+        self._spectrum_path(spectrum_path, momenta, ipath)
         y, rung_stats = self._advance(batch_size, want_rows=return_rows, want_stats=True, improved=ipath, momenta=momenta,
-                                      **kwargs)
+                                      spectrum_path=spectrum_path, **kwargs)
         stats = rung_stats.out
         from ..lib import observables as ob
         K = len(self._ladder)
@@ -232,7 +233,8 @@ class LadderHMCSampler(HMCSampler):
 
     # ---- which path: HMCSampler's `_choose`, on the proxy model (whose action is a phi^4 action)
     def _advance(self, batch_size, n_chains=None, n_md=10, dt=0.1, n_skip=0, exchange_every=1, path=None, want_rows=True,
-                 want_stats=False, cluster_every=0, improved=False, integrator='leapfrog', momenta=None):
+                 want_stats=False, cluster_every=0, improved=False, integrator='leapfrog', momenta=None,
+                 spectrum_path=None):
         """batch_size // C recorded steps.  Returns (the rung-ordered rows or None, the `_RungStats` with the rung-ordered
         measure rows `out` (steps, C, n_out) or None)."""
         K = len(self._ladder)
@@ -258,6 +260,7 @@ class LadderHMCSampler(HMCSampler):
             sweep_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
         if improved is not False:
             from ..lib.observables import ImprovedMeasurement, measure_improved
+            spec = self._spectrum_workspace(phi, momenta, spectrum_path)      # one workspace for all sweeps of the call
         dhs, accs, swaps, parities, sweeps, parts = [], [], [], [], [], []
         r0 = 0
         while r0 < rows:
@@ -267,7 +270,7 @@ class LadderHMCSampler(HMCSampler):
                     phi, st = self._sweep(phi, (coef, rung), workspace=sweep_ws)
                 else:                                    # the same sweep, its labels kept; the rows rung-ordered
                     phi, st, labels = self._sweep(phi, (coef, rung), workspace=sweep_ws, want_labels=True)
-                    parts.append(measure_improved(phi, labels, path=improved, momenta=momenta).rows(base + rung.long()))
+                    parts.append(measure_improved(phi, labels, path=improved, momenta=momenta, **spec).rows(base + rung.long()))
                 sweeps.append(st)
                 if path == 'composed':
                     S = self._model.action(phi.double()).double()
