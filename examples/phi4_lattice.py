@@ -15,6 +15,8 @@ DistConvertor_), or a stack of RQ-spline couplings, assembled from the same name
                                                           chi, the Binder cumulant, xi_2 and tau_int(m) of both
     python examples/phi4_lattice.py --lat 16,16 --hmc --integrator omelyan    the same with model.hmc on the second-order
                                                            minimum-norm integrator (or omf4) instead of leapfrog
+    python examples/phi4_lattice.py --lat 16,16 --hmc --fourier 0.25    the same, and model.hmc once more with the Fourier-
+                                                           accelerated kinetic term: acceptance, <phi^2>, chi, tau_int both ways
     python examples/phi4_lattice.py --lat 8,8 --hmc --cluster    the same, and model.hmc once more with a cluster sweep of
                                                           the signs before every step: tau_int(m) with and without sweeps
     python examples/phi4_lattice.py --lat 8,8 --hmc --cluster --improved    the same, and chi = V <m^2>, U4 and xi_2 of that
@@ -79,6 +81,12 @@ def observables(model, y, n_chains, drop):
         fmt_val_err(*e.susceptibility()), fmt_val_err(*e.binder()), fmt_val_err(*e.xi2(axis)), fmt_val_err(tau, tau_err), window)
 
 
+def tau_ints(model, y, n_chains, drop):
+    """tau_int of the magnetization and of phi^2 of sampler rows, with their errors."""
+    e = Ensemble(model.measure(y), n_chains=n_chains, drop=drop)
+    return ", ".join(fmt_val_err(*e.tau_int(name)[:2]) for name in ('magnetization', 'phi2'))
+
+
 def both_ways(m, n_chains, drop):
     """chi = V <m^2> (the symmetric definition: there is no improved <|m|>), U4 and xi_2 of a measurement that carries
     `.improved`, from the sign assignment the sweeps left and averaged over all sign assignments, with their errors."""
@@ -112,7 +120,7 @@ INTEGRATOR_N_MD = dict(leapfrog=10, omelyan=5, omf4=2)
 
 
 def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False, integrator='leapfrog', correlator=False,
-                     spectrum_path=None):
+                     spectrum_path=None, fourier=None):
     """<phi^2> of the trained flow + Metropolis next to hybrid Monte Carlo on the action itself (exact up to its own
     statistical error; the first quarter of every chain is dropped as thermalisation), then the observables of both.
     `cluster`: also model.hmc with a Swendsen-Wang sweep of the signs before every recorded step (cluster_every=1), so
@@ -128,6 +136,14 @@ def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False
           % (*phi2(y, n_chains, rows // 4), integrator, n_md, model.hmc.history.accept_rate[-1], model.hmc.history.dh_rms[-1]))
     print("model.mcmc  " + obs)
     print("model.hmc   " + observables(model, y, n_chains, rows // 4))
+    if fourier is not None:
+        plain_tau = tau_ints(model, y, n_chains, rows // 4)
+        model.hmc.start(n_chains=n_chains)
+        y = model.hmc.sample(n_chains * rows, fa_mass_sq=fourier, **hmc)
+        print("<phi^2>  model.hmc, fa_mass_sq=%g   %.5f +- %.5f   (accept rate %.3f, rms dH %.3g)"
+              % (fourier, *phi2(y, n_chains, rows // 4), model.hmc.history.accept_rate[-1], model.hmc.history.dh_rms[-1]))
+        print("model.hmc, fa_mass_sq=%g   " % fourier + observables(model, y, n_chains, rows // 4))
+        print("tau_int(m), tau_int(phi^2):   plain %s   accelerated %s" % (plain_tau, tau_ints(model, y, n_chains, rows // 4)))
     if cluster:
         model.hmc.start(n_chains=n_chains)
         y = model.hmc.sample(n_chains * rows, cluster_every=1, **hmc)
@@ -185,6 +201,9 @@ def main():
     ap.add_argument("--integrator", choices=sorted(INTEGRATOR_N_MD), default="leapfrog",
                     help="with --hmc: model.hmc's integration scheme (leapfrog, the second-order minimum-norm scheme, or the "
                          "fourth-order one), each at 10 force evaluations per trajectory of length 1")
+    ap.add_argument("--fourier", type=float, default=None, metavar="M2",
+                    help="with --hmc: model.hmc once more with the Fourier-accelerated kinetic term (fa_mass_sq=M2): acceptance, "
+                         "<phi^2>, chi and tau_int(m), tau_int(phi^2) with and without acceleration")
     ap.add_argument("--cluster", action="store_true",
                     help="with --hmc: model.hmc once more with cluster_every=1, tau_int(m) with and without cluster sweeps; "
                          "with --ladder: the ladder once more with exchanges and cluster_every=1")
@@ -214,7 +233,7 @@ def main():
         model.fit(**kw)
         nf.backward_sanitychecker(model)
         if a.hmc:
-            compare_with_hmc(model, cluster=a.cluster, improved=a.improved, integrator=a.integrator, correlator=a.correlator,
+            compare_with_hmc(model, cluster=a.cluster, improved=a.improved, integrator=a.integrator, correlator=a.correlator, fourier=a.fourier,
                              spectrum_path=a.spectrum_path)
 
 

@@ -906,6 +906,68 @@ int nf_phi4_hmc_tiled_ladder_scheme(void *phi, double *action_out, const void *p
                                     void *workspace, size_t workspace_bytes, int dtype, void *stream,
                                     const nf_hmc_scheme *scheme);
 
+/* ---- Fourier-accelerated hybrid Monte Carlo (nf_hmc_fa.hip; MI355X-side extension; Batrouni et al., Phys. Rev. D 32
+ * (1985) 2736).  nf_phi4_hmc's definition word for word -- the action, the force, the schemes, the Philox positions, the
+ * accept rule, the outputs -- with the kinetic term pi^T A pi / 2 in place of pi^2 / 2:
+ *   The per-axis table.  shat_mu(k) = 4 sin^2(pi k / L_mu) for k = 0 .. L_mu - 1, made by the host in double through
+ *     sinpi: ONE table of sum_mu L_mu doubles (nf_phi4_hmc_fa_table) that every path shares.  a(k) = 1 / (w0 sum_mu
+ *     shat_mu(k_mu) + M^2), M^2 = fa_mass_sq, the sum over the axes left to right, formed in double and cast to dtype;
+ *     a^(-1/2)(k) = sqrt(w0 sum_mu shat_mu(k_mu) + M^2) likewise.  Nothing is added for an axis of extent 1.
+ *   The operator.  A = T diag(a) T with T = H_{L_0} x .. x H_{L_3} the orthonormal separable Hartley transform,
+ *     H_N[k, n] = (cos(2 pi k n / N) + sin(2 pi k n / N)) / sqrt(N) (nf_spectral_core.h; a is even in every k_mu, so
+ *     T diag(a) T x = irfftn(rfftn(x) a)).  A^(-1/2) is the same with a^(-1/2).
+ *   One trajectory.  eta is drawn as nf_phi4_hmc draws its momenta, at (seed, offset + 2 t).
+ *     1. pi = A^(-1/2) eta                                       (pi_in, when given, replaces this step: it is pi, not eta)
+ *     2. H0 = sum pi (A pi) / 2 + S(phi)
+ *     3. pi -= (b_s / 2) dt F(phi)
+ *     4. k = 1 .. n_md, j = 1 .. s:  phi += a_j dt (A pi);  pi -= b_j dt F(phi)      (b_s / 2 at the very end)
+ *     5. H1 = sum pi (A pi) / 2 + S(phi)
+ *     6. accept = force_accept || log u < -(H1 - H0), u the uniform at (seed, offset + 2 t + 1)
+ *   The kinetic energy is taken from pi and A pi at both ends, never from eta: dH is a function of (phi, pi) through one
+ *   operator, and a reversed trajectory reproduces it.  The energies are summed in double in a fixed order, no atomics.
+ *   pi_out is pi (of the proposal, accepted or not).  A rejected chain keeps its phi bit for bit.  Two Philox positions
+ *   per trajectory, as before.  Cost: n_md s + 3 filters per trajectory (refresh, H0, one per drift, H1); a filter is two
+ *   transforms and one multiply.
+ * nf_phi4_hmc_fa: nf_phi4_hmc_scheme's arguments (scheme NULL: leapfrog) and fa_mass_sq.  One workgroup per chain runs all
+ * n_traj trajectories in ONE launch with nf_phi4_hmc's lane map; pi in registers, phi in LDS (the image that the force
+ * reads is the state), one transform buffer of V elements and the Hartley matrices (built once per launch; equal extents
+ * share one): dynamic LDS = 2 V sizeof(dtype) + matrices.  The table travels in the kernel's argument segment.  No
+ * allocation, no host synchronisation, capturable into a HIP graph, bitwise reproducible; n_traj trajectories in one
+ * launch equal n_traj launches of one; record / record_every as in nf_phi4_hmc.  There is no measuring form: record the
+ * rows and measure them with nf_lattice_measure.
+ * nf_phi4_hmc_fa_supported (pure host code, the launcher's planner): 1 iff dtype is NF_F32 / NF_F64, every extent is at
+ * most 64, V sizeof(dtype) <= 65536 and 2 V sizeof(dtype) + matrices <= 163840 (16^2, 64^2, 16^3, 8^4 in both, 24^3 in
+ * fp32; not 128^2) -- and V >= 8 (the reduction slots lie in the transform buffer) -- else 0 with the reason in
+ * nf_last_error_string.
+ * nf_phi4_hmc_fa_plan (pure host code): lanes and sites per lane, where phi and pi live (phi_in_lds, pi_in_lds: 1 = LDS,
+ * 0 = registers), lds_bytes, matrix_bytes and filters = n_md stages + 3; NF_EINVAL where _supported answers 0.
+ * nf_phi4_hmc_fa_table (pure host code): out[sum_mu lattice[mu]] = shat of the four extents one behind the other.
+ * NF_EINVAL, with the reason in the message: what nf_phi4_hmc_scheme refuses, fa_mass_sq <= 0 or not finite, w0 < 0, an
+ * unsupported lattice, or
+ *   (n_md s + NF_HMC_FA_MD_STEPS (n_md s + 3)) n_traj max(V, 256) ceil(C / 1024) > NF_HMC_MAX_WORK:
+ * a filter counts as NF_HMC_FA_MD_STEPS MD steps.  MEASURED on an MI355X (tools/hmc_fa_bench.py, the bare launch, leapfrog,
+ * n_md = 10, 20 trajectories, medians of 7 alternating timings): one accelerated force evaluation in MD steps of nf_phi4_hmc
+ * is 6.20 at 16^2 x 512 fp32, 6.30 in fp64, 6.25 at 16^3 x 1024 fp32, 6.57 in fp64; the largest, rounded up to a power of
+ * two, is 8.  (Counting LDS passes in the code had given the same: an MD step is 2 d + 2 accesses per site and 2 barriers,
+ * a filter 3 + 2 d (2 + ceil(L / 16)) accesses per site and 2 d + 2 barriers.) */
+#define NF_HMC_FA_MD_STEPS 8
+typedef struct nf_hmc_fa_plan {
+  int32_t sites_per_lane;
+  int32_t lanes;
+  int32_t phi_in_lds;
+  int32_t pi_in_lds;
+  int64_t lds_bytes;
+  int64_t matrix_bytes;
+  int64_t filters;
+} nf_hmc_fa_plan;
+int nf_phi4_hmc_fa_supported(const int32_t *lattice, int dtype);
+int nf_phi4_hmc_fa_plan(const int32_t *lattice, int dtype, int n_md, int stages, nf_hmc_fa_plan *out);
+int nf_phi4_hmc_fa_table(const int32_t *lattice, double *out);
+int nf_phi4_hmc_fa(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out, uint8_t *accept_out,
+                   void *record, int record_every, int64_t C, const int32_t *lattice, double w0, double w2, double w4,
+                   int n_md, double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset, int dtype,
+                   void *stream, const nf_hmc_scheme *scheme, double fa_mass_sq);
+
 /* ---- cluster updates of phi^4 chains (nf_cluster.hip; MI355X-side extension): one Swendsen-Wang sweep of the embedded
  * Ising signs (Brower-Tamayo: phi = s |phi|).  A sweep is never rejected, leaves sum phi^2 and sum phi^4 alone and
  * flips every cluster half of the time.  The sweep, stated once:

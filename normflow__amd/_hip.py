@@ -182,6 +182,14 @@ PROTOTYPES = {
                          _I, _P]),
 }
 
+PROTOTYPES.update({
+    "nf_phi4_hmc_fa_supported": (_I, [C.POINTER(C.c_int32), _I]),
+    "nf_phi4_hmc_fa_plan": (_I, [C.POINTER(C.c_int32), _I, _I, _I, _P]),
+    "nf_phi4_hmc_fa_table": (_I, [C.POINTER(C.c_int32), _P]),
+    # nf_phi4_hmc's arguments, `const nf_hmc_scheme *scheme` and `double fa_mass_sq`
+    "nf_phi4_hmc_fa": (_I, PROTOTYPES["nf_phi4_hmc"][1] + [_P, _D]),
+})
+
 # the _scheme form of the five HMC launchers: the launcher's arguments and `const nf_hmc_scheme *scheme`
 for _name in ("nf_phi4_hmc", "nf_phi4_hmc_measure", "nf_phi4_hmc_ladder", "nf_phi4_hmc_tiled", "nf_phi4_hmc_tiled_ladder"):
     PROTOTYPES[_name + "_scheme"] = (_I, PROTOTYPES[_name][1] + [_P])
@@ -2151,6 +2159,103 @@ def phi4_hmc(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in=None,
     return _phi4_hmc_call("phi4_hmc_measure" if measure else "phi4_hmc", phi, w0, w2, w4, n_md, dt, n_traj=n_traj,
                           record_every=record_every, pi_in=pi_in, want_pi=want_pi, force_accept=force_accept,
                           position=position, generator=generator, record=record, scheme=scheme)
+
+
+# ========================================================================= Fourier-accelerated HMC (nf_hmc_fa.hip)
+HMC_FA_MD_STEPS = 8           # NF_HMC_FA_MD_STEPS: the MD steps a filter counts as under the cap (measured: 6.2 to 6.6)
+
+
+class HmcFaPlan(C.Structure):
+    """nf_hmc_fa_plan (include/normflow_hip.h)."""
+    _fields_ = [("sites_per_lane", C.c_int32), ("lanes", C.c_int32), ("phi_in_lds", C.c_int32), ("pi_in_lds", C.c_int32),
+                ("lds_bytes", C.c_int64), ("matrix_bytes", C.c_int64), ("filters", C.c_int64)]
+
+
+def hmc_fa_supported(lat, dtype):
+    """True if nf_phi4_hmc_fa takes chains on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own planner,
+    pure host code; the reason of a refusal is in `last_error()`."""
+    return _planner_supported("nf_phi4_hmc_fa_supported", lat, dtype)
+
+
+def last_error():
+    """nf_last_error_string: the message of the library's last refusal."""
+    return load().nf_last_error_string().decode("utf-8", "replace")
+
+
+def hmc_fa_plan(lat, dtype, n_md=1, stages=1):
+    """What nf_phi4_hmc_fa will do on the lattice `lat` in `dtype` with n_md steps of a scheme of `stages` stages:
+    dict(sites_per_lane, lanes, phi ('lds' or 'registers'), pi (likewise), lds_bytes, matrix_bytes, filters (per
+    trajectory: n_md * stages + 3)).  Pure host code."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"hmc_fa_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
+    code = NF_F32 if dtype == torch.float32 else NF_F64 if dtype == torch.float64 else NF_F16
+    out = HmcFaPlan()
+    _check(load().nf_phi4_hmc_fa_plan(_lat4(lat), code, int(n_md), int(stages), C.byref(out)), "nf_phi4_hmc_fa_plan")
+    where = lambda flag: 'lds' if flag else 'registers'
+    return dict(sites_per_lane=out.sites_per_lane, lanes=out.lanes, phi=where(out.phi_in_lds), pi=where(out.pi_in_lds),
+                lds_bytes=out.lds_bytes, matrix_bytes=out.matrix_bytes, filters=out.filters)
+
+
+def hmc_fa_table(lat):
+    """nf_phi4_hmc_fa_table: the list of per-axis tensors shat_mu(k) = 4 sin^2(pi k / L_mu), k = 0 .. L_mu - 1, float64 on
+    the CPU, one per axis of `lat` -- the one table the kernel and the composed path share.  Pure host code."""
+    lat = tuple(int(n) for n in lat)
+    if not 1 <= len(lat) <= 4 or min(lat) < 1:
+        raise NormflowHipError(f"hmc_fa_table: lattices of 1 to 4 axes of extent >= 1, got {lat}")
+    pad = 4 - len(lat)
+    buf = (C.c_double * (pad + sum(lat)))()
+    _check(load().nf_phi4_hmc_fa_table(_lat4(lat), buf), "nf_phi4_hmc_fa_table")
+    flat = torch.tensor(list(buf)[pad:], dtype=torch.float64)
+    return list(torch.split(flat, list(lat)))
+
+
+def hmc_fa_denominator(lat, w0, fa_mass_sq):
+    """w0 sum_mu shat_mu(k_mu) + M^2 on the momentum lattice `lat`, float64 on the CPU, the axes summed left to right:
+    a(k) is its reciprocal and a^(-1/2)(k) its square root (include/normflow_hip.h)."""
+    table = hmc_fa_table(lat)
+    d = len(lat)
+    s = None
+    for mu, t in enumerate(table):
+        term = t.reshape((1,) * mu + (-1,) + (1,) * (d - 1 - mu))
+        s = term if s is None else s + term
+    return float(w0) * s.expand(tuple(lat)) + float(fa_mass_sq)
+
+
+def hmc_fa_cost(evals):
+    """The MD steps that a trajectory of `evals` = n_md * s force evaluations of nf_phi4_hmc_fa counts as under
+    NF_HMC_MAX_WORK: its force evaluations and NF_HMC_FA_MD_STEPS per filter, evals + 3 filters."""
+    return int(evals) + HMC_FA_MD_STEPS * (int(evals) + 3)
+
+
+def phi4_hmc_fa(phi, w0, w2, w4, n_md, dt, fa_mass_sq, n_traj=1, record_every=None, pi_in=None, want_pi=False,
+                force_accept=False, position=None, generator=None, record=True, scheme=None):
+    """nf_phi4_hmc_fa: `phi4_hmc` with the kinetic term pi^T A pi / 2, a(k) = 1 / (w0 khat^2 + fa_mass_sq) (include/
+    normflow_hip.h, "Fourier-accelerated hybrid Monte Carlo"); the same arguments and the same dict, `pi_in` and pi being
+    pi (not the drawn eta).  scheme: None = leapfrog, else what `hmc_scheme` takes."""
+    _require_device(phi, pi_in)
+    if not phi.is_contiguous() or (pi_in is not None and (not pi_in.is_contiguous() or pi_in.dtype != phi.dtype
+                                                            or pi_in.shape != phi.shape)):
+        raise NormflowHipError("phi4_hmc_fa needs contiguous phi (C, *L) and pi_in of its shape and dtype")
+    Cn, lat, dev = phi.shape[0], tuple(phi.shape[1:]), phi.device
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"phi4_hmc_fa: lattices of 1 to 4 axes, got {lat}")
+    n_traj = int(n_traj)
+    dh = torch.empty((max(n_traj, 0), Cn), dtype=torch.float64, device=dev)
+    accept = torch.empty((max(n_traj, 0), Cn), dtype=torch.uint8, device=dev)
+    action = torch.empty(Cn, dtype=torch.float64, device=dev)
+    rec = None
+    if record_every is not None and record:
+        rec = torch.empty((n_traj // int(record_every), Cn) + lat, dtype=phi.dtype, device=dev)
+    pi_out = torch.empty_like(phi) if want_pi else None
+    if scheme is not None and scheme is not NULL_SCHEME:
+        scheme = hmc_scheme(scheme)
+    sc = None if scheme is None or scheme is NULL_SCHEME else C.byref(scheme)
+    seed, offset = position if position is not None else _philox_positions(dev, 2 * max(n_traj, 1), generator)
+    _check(load().nf_phi4_hmc_fa(_ptr(phi), _ptr(action), _ptr(pi_in), _ptr(pi_out), _ptr(dh), _ptr(accept), _ptr(rec),
+                                 1 if record_every is None else int(record_every), Cn, _lat4(lat), float(w0), float(w2),
+                                 float(w4), int(n_md), float(dt), n_traj, int(bool(force_accept)), seed, offset,
+                                 _dtype_code(phi), _stream(), sc, float(fa_mass_sq)), "nf_phi4_hmc_fa")
+    return dict(action=action, dh=dh, accept=accept, record=rec, pi=pi_out)
 
 
 # ========================================================================= the same, chains in HBM (nf_hmc_tiled.hip)

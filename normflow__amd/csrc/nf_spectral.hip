@@ -23,21 +23,17 @@
 // banks), accumulators = all ceil(N / 16) output tiles of those lines, written back in place: a wave owns its lines, so a
 // pass needs one barrier, at its end.  Tiny lattices pack several samples (P V / N_max >= 64 lines: a full tile per wave)
 // up to 16 KiB; partial last packs and B = 1 run the same code with fewer lines.
-#include "nf_internal.h"
+#include "nf_spectral_core.h"
 
 namespace nf {
 
-constexpr int kSpecMaxAxis = 64;
 constexpr int kSpecLdsBytes = 160 * 1024;     // LDS of a CU
 constexpr int kSpecPackBytes = 16 * 1024;     // packs of small samples grow up to this
 constexpr int kSpecGroups = 1024;             // workgroups of the filter (4 per CU)
 constexpr int kSpecVjpGroups = 512;           // workgroups of the VJP: one partial gw_half each
 
-struct SpecPlan {
-  int n[4], stride[4];   // axis lengths (leading 1s) and element strides
-  int ldh[4], hoff[4];   // row stride and element offset of the axis' Hartley matrix in LDS (equal lengths share one)
-  int hsize;             // elements of all matrices
-  int V, Vh, nh;         // sites, entries of w_half, N_last / 2 + 1
+struct SpecPlan : HartleyAxes {   // the axes and their matrices (nf_spectral_core.h), V = sites
+  int Vh, nh;            // entries of w_half, N_last / 2 + 1
   int P;                 // samples per pack
   int vec;               // the field can move as 16-byte words
   int64_t B, packs;
@@ -52,6 +48,36 @@ struct SpecArgs {
   double *partial;
   int zero_replaced;
 };
+
+// Strides, matrix layout (row stride: the 16-tile padding, plus 16 where that keeps the four rows a wave reads in different
+// banks; equal lengths share one matrix), hsize and V from the lengths p.n.
+void spectral_axes(HartleyAxes &p, const int n[4]) {
+  int len[4];
+  for (int a = 0; a < 4; ++a) len[a] = n[a];      // n may be p.n itself
+  p.hsize = 0;
+  int V = 1;
+  for (int a = 3; a >= 0; --a) {
+    p.n[a] = len[a];
+    p.stride[a] = V;
+    V *= len[a];
+    p.ldh[a] = p.hoff[a] = 0;
+  }
+  p.V = V;
+  for (int a = 0; a < 4; ++a) {
+    if (p.n[a] == 1) continue;
+    int same = -1;
+    for (int c = 0; c < a; ++c)
+      if (p.n[c] == p.n[a]) same = c;
+    const int pad16 = (p.n[a] + 15) & ~15;
+    p.ldh[a] = pad16 % 32 == 16 ? pad16 : pad16 + 16;
+    if (same >= 0) {
+      p.hoff[a] = p.hoff[same];
+    } else {
+      p.hoff[a] = p.hsize;
+      p.hsize += pad16 * p.ldh[a];
+    }
+  }
+}
 
 static int make_plan(SpecPlan &p, const int32_t *lat, int ndim, int dtype, int for_vjp, int64_t B, const char *who) {
   NF_REQUIRE(lat != nullptr, "%s: NULL lattice", who);
@@ -70,30 +96,12 @@ static int make_plan(SpecPlan &p, const int32_t *lat, int ndim, int dtype, int f
     nmax = n > nmax ? n : nmax;
   }
   const int64_t esize = dtype == NF_F32 ? 4 : 8;
-  for (int a = 3, s = 1; a >= 0; --a) {
-    p.stride[a] = s;
-    s *= p.n[a];
-  }
-  for (int a = 0; a < 4; ++a) {
-    if (p.n[a] == 1) continue;
-    int same = -1;
-    for (int c = 0; c < a; ++c)
-      if (p.n[c] == p.n[a]) same = c;
-    const int pad16 = (p.n[a] + 15) & ~15;
-    p.ldh[a] = pad16 % 32 == 16 ? pad16 : pad16 + 16;
-    if (same >= 0) {
-      p.hoff[a] = p.hoff[same];
-    } else {
-      p.hoff[a] = p.hsize;
-      p.hsize += pad16 * p.ldh[a];
-    }
-  }
+  spectral_axes(p, p.n);
   const int64_t nbuf = for_vjp ? 2 : 1;
   NF_REQUIRE(nbuf * V * esize + p.hsize * esize <= kSpecLdsBytes,
              "%s: a sample of %lld sites (%lld B%s) and its Hartley matrices (%lld B) exceed the %d B of LDS; use "
              "transform='fft'", who, (long long)V, (long long)(nbuf * V * esize), for_vjp ? ", field and cotangent" : "",
              (long long)(p.hsize * esize), kSpecLdsBytes);
-  p.V = int(V);
   p.nh = p.n[3] / 2 + 1;
   p.Vh = p.V / p.n[3] * p.nh;
   p.B = B;
@@ -114,109 +122,6 @@ static int make_plan(SpecPlan &p, const int32_t *lat, int ndim, int dtype, int f
   p.lds = size_t(nbuf * p.P * V * esize + p.hsize * esize);
   p.vec = (V * esize) % 16 == 0;
   return NF_OK;
-}
-
-template <typename T> struct Mfma;
-template <> struct Mfma<float> {
-  typedef float acc_t __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ acc_t run(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) * 4 + r; }
-};
-template <> struct Mfma<double> {     // the f64 form has its own C/D map: row = lane / 16 + 4 reg
-  typedef double acc_t __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ acc_t run(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
-};
-
-// H[r][c] for r, c < N, zero in the padding; the angle is reduced exactly (r c mod N) and evaluated in double.
-template <typename T>
-__device__ void build_hartley(T *hm, const SpecPlan &p) {
-  for (int a = 0; a < 4; ++a) {
-    const int N = p.n[a];
-    if (N == 1) continue;
-    bool shared = false;
-    for (int c = 0; c < a; ++c) shared |= p.n[c] == N;
-    if (shared) continue;
-    const int ldh = p.ldh[a], rows = (N + 15) & ~15;
-    const double norm = 1.0 / ::sqrt(double(N));
-    T *h = hm + p.hoff[a];
-    for (int idx = threadIdx.x; idx < rows * ldh; idx += kBlock) {
-      const int r = idx / ldh, c = idx - r * ldh;
-      double v = 0.0;
-      if (r < N && c < N) {
-        double sn, cs;
-        ::sincospi(2.0 * double((r * c) % N) / double(N), &sn, &cs);
-        v = (cs + sn) * norm;
-      }
-      h[idx] = T(v);
-    }
-  }
-}
-
-// One axis pass, in place: every line l of the `lines` lines (element n at (l / S) N S + l % S + n S) becomes H line.
-// MT = ceil(N / 16) output tiles per line group; the k loop runs over 16 MT values of n in steps of JB quads whose LDS
-// loads are all issued before the first MFMA needs one (rows of H beyond N are zero).
-template <typename T, int MT>
-__device__ __forceinline__ void axis_pass(T *buf, const T *h, int ldh, int N, int S, int lines) {
-  using M = Mfma<T>;
-  constexpr int JB = MT <= 2 ? 4 : 2;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const int col = lane & 15, kq = lane >> 4;
-  const int NS = N * S;
-  const int groups = (lines + 15) >> 4;
-#pragma unroll 1
-  for (int g = wave; g < groups; g += kBlock / kWave) {
-    const int l = g * 16 + col;
-    const bool valid = l < lines;
-    const int q = l / S;
-    const int base = valid ? q * NS + (l - q * S) : 0;
-    typename M::acc_t acc[MT];
-#pragma unroll
-    for (int it = 0; it < MT; ++it) acc[it] = typename M::acc_t{0, 0, 0, 0};
-#pragma unroll 1
-    for (int k0 = 0; k0 < 4 * MT; k0 += JB) {
-      T b[JB], a[JB][MT];
-#pragma unroll
-      for (int j = 0; j < JB; ++j) {
-        const int n = 4 * (k0 + j) + kq;
-        b[j] = (valid && n < N) ? buf[base + n * S] : T(0);
-        const T *hrow = h + n * ldh + col;        // H is symmetric: A[i][n] = H[n][i], 16 consecutive i per row n
-#pragma unroll
-        for (int it = 0; it < MT; ++it) a[j][it] = hrow[16 * it];
-      }
-#pragma unroll
-      for (int j = 0; j < JB; ++j) {
-#pragma unroll
-        for (int it = 0; it < MT; ++it) acc[it] = M::run(a[j][it], b[j], acc[it]);
-      }
-    }
-#pragma unroll
-    for (int it = 0; it < MT; ++it) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = 16 * it + M::row(lane, r);
-        if (valid && i < N) buf[base + i * S] = acc[it][r];
-      }
-    }
-  }
-  __syncthreads();
-}
-
-template <typename T>
-__device__ __forceinline__ void transform(T *buf, const T *hm, const SpecPlan &p, int nv) {
-  for (int a = 0; a < 4; ++a) {
-    const int N = p.n[a], lines = nv * (p.V / (N > 0 ? N : 1));
-    const T *h = hm + p.hoff[a];
-    if (N <= 1) continue;
-    if (N <= 16) axis_pass<T, 1>(buf, h, p.ldh[a], N, p.stride[a], lines);
-    else if (N <= 32) axis_pass<T, 2>(buf, h, p.ldh[a], N, p.stride[a], lines);
-    else if (N <= 48) axis_pass<T, 3>(buf, h, p.ldh[a], N, p.stride[a], lines);
-    else axis_pass<T, 4>(buf, h, p.ldh[a], N, p.stride[a], lines);
-  }
 }
 
 template <typename T>
@@ -244,7 +149,7 @@ __global__ __launch_bounds__(kBlock, 4) void spectral_kernel(SpecArgs A) {
   const T *zero_new = static_cast<const T *>(A.zero_new);
   T *zero_old = static_cast<T *>(A.zero_old);
   const int V = p.V, n3 = p.n[3], nh = p.nh;
-  build_hartley(hm, p);
+  build_hartley(hm, p, kBlock);
   __syncthreads();
   for (int64_t pk = blockIdx.x; pk < p.packs; pk += gridDim.x) {
     const int64_t b0 = pk * p.P;
@@ -252,9 +157,9 @@ __global__ __launch_bounds__(kBlock, 4) void spectral_kernel(SpecArgs A) {
     copy_field(buf, static_cast<const T *>(VJP ? A.g : A.x) + b0 * V, ne, p.vec);
     if (VJP) copy_field(buf2, static_cast<const T *>(A.x) + b0 * V, ne, p.vec);
     __syncthreads();
-    transform(buf, hm, p, nv);
+    transform(buf, hm, p, nv, kBlock);
     if (VJP) {
-      transform(buf2, hm, p, nv);
+      transform(buf2, hm, p, nv, kBlock);
       double *part = A.partial + int64_t(blockIdx.x) * p.Vh;
       const bool first = pk == blockIdx.x;
       for (int kh = threadIdx.x; kh < p.Vh; kh += kBlock) {
@@ -287,7 +192,7 @@ __global__ __launch_bounds__(kBlock, 4) void spectral_kernel(SpecArgs A) {
       }
     }
     __syncthreads();
-    transform(buf, hm, p, nv);
+    transform(buf, hm, p, nv, kBlock);
     copy_field(static_cast<T *>(A.y) + b0 * V, buf, ne, p.vec);
     __syncthreads();                 // the next pack's load overwrites what this store reads
   }

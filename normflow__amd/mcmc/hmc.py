@@ -22,12 +22,23 @@ with n_md s force evaluations, the same two random draws and no more memory, on 
               autograd through `model.action`, torch ops for the updates, nf_block_accept for the decision and the
               restore) -- any lattice, any action object; on CPU tensors with torch's CPU generator.
 On the device all three draw from the same Philox positions of torch's CUDA generator (two per trajectory: momenta,
-uniform), so from the same seed they walk the same chain up to rounding."""
+uniform), so from the same seed they walk the same chain up to rounding.
+
+Fourier acceleration (`fa_mass_sq=M2` on sample, sample_, measure and trajectory; None = everything above, call for call):
+the kinetic term becomes pi^T A pi / 2 with A = T diag(a) T diagonal in momentum space, a(k) = 1 / (w0 khat^2 + M2), so
+that every mode of the quadratic part of the action turns at nearly the same rate (include/normflow_hip.h,
+"Fourier-accelerated hybrid Monte Carlo"):
+    pi = A^(-1/2) eta, eta ~ N(0, 1);  H = sum pi (A pi) / 2 + S(phi);  phi += a_j dt (A pi);  pi -= b_j dt F(phi)
+  * fa:       nf_phi4_hmc_fa (nf_hmc_fa.hip), the chain and the Hartley transform resident in a CU -- ScalarPhi4Action on
+              a HIP device, lattices nf_phi4_hmc_fa_supported takes;
+  * composed: the same rule from torch ops, the filter through torch.fft.rfftn / irfftn with a(k) from the shared table
+              (`_hip.hmc_fa_table`) -- everywhere else: CPU tensors, lattices beyond one CU, any action with a `get_coef`.
+There is no tiled accelerated kernel.  Cluster sweeps fall between launches and do not see the kinetic term."""
 import torch
 
 from .. import _hip
 from ..action.scalar_action import ScalarPhi4Action
-from .schedule import Take, schedule
+from .schedule import Take, schedule, schedule_fa
 
 
 class HMCHistory:
@@ -76,17 +87,19 @@ class HMCSampler:
 
     @torch.no_grad()
     def sample_(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, cluster_every=0,
-                integrator='leapfrog'):
+                integrator='leapfrog', fa_mass_sq=None):
         """(y, logp): batch_size // n_chains recorded trajectories of every chain and logp = -S(y) in the field dtype.
         `integrator`: 'leapfrog', 'omelyan', 'omf4', a pair (a, b) of weights or an `_hip.HmcScheme`; anything but
-        leapfrog is recorded in `last['integrator']` (the name, or the pair of weight tuples)."""
+        leapfrog is recorded in `last['integrator']` (the name, or the pair of weight tuples).
+        `fa_mass_sq`: None, or M^2 > 0 of the Fourier-accelerated kinetic term (module docstring), recorded in
+        `last['fa_mass_sq']`; `path` is then None, 'fa' or 'composed'."""
         y, _ = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=True, want_stats=False,
-                             cluster_every=cluster_every, integrator=integrator)
+                             cluster_every=cluster_every, integrator=integrator, **self._fa_kw(fa_mass_sq))
         return y, (-self._model.action(y)).to(y.dtype)
 
     @torch.no_grad()
     def measure(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, return_rows=False, cluster_every=0,
-                improved=False, integrator='leapfrog', momenta=None, spectrum_path=None):
+                improved=False, integrator='leapfrog', momenta=None, spectrum_path=None, fa_mass_sq=None):
         """The `Measurement` of the rows that `sample(batch_size, ...)` would return from the same chain and generator
         state, WITHOUT storing them: every recorded state is measured where it is and only its 7 + sum L sums are kept.
         The rows are in the samplers' layout (`Ensemble(m, n_chains=C)` takes it as is), the action is attached when the
@@ -110,14 +123,16 @@ class HMCSampler:
         follow; it changes nothing else of the call, bit for bit, `improved.out` included.
         spectrum_path='hbm' (with momenta; ValueError without; improved True or 'hbm'): the spectrum is
         nf_cluster_spectrum_tiled's (`observables.measure_improved(..., spectrum_path='hbm')`), for the lattices beyond
-        one CU's LDS, with one workspace for all sweeps of the call."""
+        one CU's LDS, with one workspace for all sweeps of the call.
+        fa_mass_sq (as in `sample_`): the accelerated kernel does not measure inside its launch; its launches record
+        the rows and they are measured afterwards by the kernel `observables.route` names, the same bits."""
         ipath = self._improved_path(improved, cluster_every)
         if momenta is not None and ipath is False:
             raise ValueError("momenta asks for the spectrum of the improved estimators: it needs improved=True (or a path)")
         self._spectrum_path(spectrum_path, momenta, ipath)
         y, stats = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=return_rows, want_stats=True,
                                  cluster_every=cluster_every, improved=ipath, integrator=integrator, momenta=momenta,
-                                 spectrum_path=spectrum_path)
+                                 spectrum_path=spectrum_path, **self._fa_kw(fa_mass_sq))
         action = self._model.action
         m = stats.measurement(action if hasattr(action, 'get_coef') else None)
         if ipath is not False:
@@ -160,12 +175,17 @@ class HMCSampler:
         return dict(spectrum_path=spectrum_path, workspace=torch.empty(max(need, 256), dtype=torch.uint8, device=phi.device))
 
     @staticmethod
+    def _fa_kw(fa_mass_sq):
+        """The keyword that hands fa_mass_sq on; none at all for None, so that the calls are the ones they always were."""
+        return {} if fa_mass_sq is None else dict(fa_mass_sq=fa_mass_sq)
+
+    @staticmethod
     def _scheme(integrator):
         """None for leapfrog by its name (the samplers then make the calls they always made), else the `_hip.HmcScheme`."""
         return None if isinstance(integrator, str) and integrator == 'leapfrog' else _hip.hmc_scheme(integrator)
 
     def _advance(self, batch_size, n_chains, n_md, dt, n_skip, path, want_rows, want_stats, cluster_every=0,
-                 improved=False, integrator='leapfrog', momenta=None, spectrum_path=None):
+                 improved=False, integrator='leapfrog', momenta=None, spectrum_path=None, fa_mass_sq=None):
         """batch_size // n_chains recorded steps of the chains: (the rows (batch_size, *L) or None, the `_Stats` of the
         recorded states or None); the chains, `last` and `history` updated.  cluster_every = E >= 1: the recorded steps
         are run in spans that end before the next step s (counted across calls) with s % E == 0, with one cluster sweep
@@ -174,7 +194,12 @@ class HMCSampler:
         scheme = self._scheme(integrator)
         self._restart(n_chains)
         phi, S = self._ref['sample'], self._ref['action']
-        path = self._choose(phi, path)
+        fa = None
+        if fa_mass_sq is None:
+            path = self._choose(phi, path)
+        else:
+            path = self._choose_fa(phi, path)
+            fa = _Fourier(phi, self._fa_w0(phi), fa_mass_sq)
         rows = batch_size // n_chains
         out = torch.empty((rows,) + tuple(phi.shape), dtype=phi.dtype, device=phi.device) if want_rows else None
         stats = _Stats(phi, rows) if want_stats else None
@@ -202,13 +227,18 @@ class HMCSampler:
             k = self._span(self._steps + r0, rows - r0, E)
             sink = _Span(out, stats, r0)
             if path == 'composed':
-                phi, S = self._run_composed(phi, S, k, every, n_md, dt, sink, dhs, accs, scheme)
+                phi, S = self._run_composed(phi, S, k, every, n_md, dt, sink, dhs, accs, scheme,
+                                            **({} if fa is None else dict(fa=fa)))
+            elif path == 'fa':
+                S = self._run_fa(phi, self._coef(phi.shape[1:]), fa.mass_sq, k, every, n_md, dt, sink, dhs, accs, scheme)
             else:
                 S = self._run(path, phi, self._coef(phi.shape[1:]), k, every, n_md, dt, ws, sink, dhs, accs, scheme)
             r0 += k
         self._steps += rows
         self._ref.update(sample=phi, action=S)
         self._finish(dhs, accs, scheme=scheme)
+        if fa is not None:
+            self.last['fa_mass_sq'] = fa.mass_sq
         if E:
             self.last['cluster'] = (torch.stack(sweeps) if sweeps else
                                     torch.empty((0, phi.shape[0], 4), dtype=torch.int32, device=phi.device))
@@ -349,15 +379,25 @@ class HMCSampler:
 
     @torch.no_grad()
     def trajectory(self, phi, n_md=10, dt=0.1, pi=None, force_accept=False, path=None, position=None,
-                   integrator='leapfrog'):
+                   integrator='leapfrog', fa_mass_sq=None):
         """ONE trajectory of the chains phi (C, *L), which are left alone; the stored chains are not touched.  Returns
         dict(phi = the states after the decision, pi = the momenta at the end of the trajectory, dh (C) float64,
         accept (C) uint8, action (C) float64 = S of the returned states).  `pi` replaces the drawn momenta.  `position`
         = (seed, offset) fixes the Philox position of a device run instead of taking it from torch's CUDA generator.
-        `integrator` as in `sample_`."""
+        `integrator` and `fa_mass_sq` as in `sample_`; with fa_mass_sq, `pi` (in and out) is pi, not the drawn eta."""
         phi = phi.detach().clone().contiguous()
-        path = self._choose(phi, path)
         scheme = self._scheme(integrator)
+        fa = None
+        if fa_mass_sq is None:
+            path = self._choose(phi, path)
+        else:
+            path = self._choose_fa(phi, path)
+            fa = _Fourier(phi, self._fa_w0(phi), fa_mass_sq)
+        if path == 'fa':
+            kw = {} if scheme is None else dict(scheme=scheme)
+            r = _hip.phi4_hmc_fa(phi, *self._coef(phi.shape[1:]), n_md, dt, fa.mass_sq, n_traj=1, pi_in=pi, want_pi=True,
+                                 force_accept=force_accept, position=position, **kw)
+            return dict(phi=phi, pi=r['pi'], dh=r['dh'][0], accept=r['accept'][0], action=r['action'])
         if path != 'composed':
             kernel = _hip.phi4_hmc if path == 'fused' else _hip.phi4_hmc_tiled
             kw = {} if scheme is None else dict(scheme=scheme)
@@ -371,7 +411,7 @@ class HMCSampler:
             gen.set_offset(4 * position[1])
         S0 = self._model.action(phi.double()).double()
         phi, S, dh, acc, pi = self._trajectory_composed(phi, S0, n_md, dt, pi=pi, force_accept=force_accept, generator=gen,
-                                                        scheme=scheme)
+                                                        scheme=scheme, **({} if fa is None else dict(fa=fa)))
         return dict(phi=phi, pi=pi, dh=dh, accept=acc, action=S)
 
     def ladder(self, ladder):
@@ -417,6 +457,42 @@ class HMCSampler:
                 f"{tuple(phi.shape[1:])} and {phi.dtype}")
         return 'tiled' if self._tiled_refusal(phi) is None else 'composed'
 
+    def _fa_w0(self, phi):
+        """The hopping coefficient that a(k) is built from."""
+        action = self._model.action
+        if not hasattr(action, 'get_coef'):
+            raise TypeError("Fourier acceleration builds a(k) from the hopping coefficient of a phi^4 action (get_coef), "
+                            f"got a {type(action).__name__}")
+        return float(action.get_coef(phi.ndim - 1)[0])
+
+    def _fa_refusal(self, phi):
+        """Why nf_phi4_hmc_fa does not take these chains, or None."""
+        if not isinstance(self._model.action, ScalarPhi4Action):
+            return f"the action is a {type(self._model.action).__name__}, not a ScalarPhi4Action"
+        if not phi.is_cuda:
+            return f"the chains are a {phi.device} tensor, not on a HIP device"
+        if not _hip.hmc_fa_supported(tuple(phi.shape[1:]), phi.dtype):
+            return (_hip.last_error() if phi.dtype in (torch.float32, torch.float64) and 1 <= phi.ndim - 1 <= 4
+                    else f"the chains are {phi.dtype} on {phi.ndim - 1} axes")
+        return None
+
+    def _choose_fa(self, phi, path):
+        """'fa' or 'composed', with fa_mass_sq: the kernel where nf_phi4_hmc_fa_supported holds on device tensors, the
+        composed path everywhere else.  There is no tiled accelerated kernel: lattices beyond one CU stay composed."""
+        if path in ('tiled', 'fused'):
+            raise ValueError(f"path={path!r} with fa_mass_sq: there is no {path} accelerated kernel (lattices beyond one CU "
+                             "run the composed path); path must be None, 'fa' or 'composed'")
+        if path not in (None, 'fa', 'composed'):
+            raise ValueError(f"path must be None, 'fa' or 'composed' with fa_mass_sq, got {path!r}")
+        if path == 'composed':
+            return path
+        why = self._fa_refusal(phi)
+        if why is None:
+            return 'fa'
+        if path == 'fa':
+            raise _hip.NormflowHipError(f"HMCSampler(path='fa'): nf_phi4_hmc_fa does not apply: {why}")
+        return 'composed'
+
     def _coef(self, lat):
         """(w0, w2, w4) as nf_phi4_hmc takes them: ScalarPhi4Action.action's rule for a user axis of extent 1 (it is its own
         neighbour: -w0 phi^2) folded into w2, as for nf_phi4_action."""
@@ -448,6 +524,29 @@ class HMCSampler:
             sink.launch(a.row0, r)
         return r['action']
 
+    # ---- Fourier-accelerated kernel
+    def _run_fa(self, phi, couplings, mass_sq, rows, every, n_md, dt, sink, dhs, accs, scheme=None):
+        """`_run` for nf_phi4_hmc_fa, by `schedule_fa`: the kernel does not measure, so where statistics are wanted its
+        launches record the rows and they are measured afterwards, row by row, as `model.measure` would."""
+        evals = n_md * (1 if scheme is None else scheme.stages)
+        extra = {} if scheme is None else dict(scheme=scheme)
+        budget = _hip.hmc_fused_budget(phi[0].numel(), phi.shape[0])
+        for a in schedule_fa(rows, every, _hip.hmc_fa_cost(evals), budget, want_rows=sink.out is not None,
+                             stats=sink.stats is not None):
+            if isinstance(a, Take):
+                sink.take(a.row, phi, a.copy)
+                continue
+            r = _hip.phi4_hmc_fa(phi, *couplings, n_md, dt, mass_sq, n_traj=a.n_traj, record_every=a.record_every,
+                                 record=a.record, **extra)
+            dhs.append(r['dh']); accs.append(r['accept'])
+            if r['record'] is not None:
+                if sink.out is not None:
+                    sink.launch(a.row0, r)
+                if sink.stats is not None:
+                    for i in range(r['record'].shape[0]):
+                        sink.put_stats(a.row0 + i, r['record'][i])
+        return r['action']
+
     # ---- composed
     def _force(self, phi):
         with torch.enable_grad():
@@ -458,9 +557,12 @@ class HMCSampler:
     def _energy(self, phi, pi):
         return 0.5 * pi.double().square().flatten(1).sum(dim=1) + self._model.action(phi.double()).double()
 
-    def _trajectory_composed(self, phi, S0, n_md, dt, pi=None, force_accept=False, generator=None, scheme=None):
+    def _trajectory_composed(self, phi, S0, n_md, dt, pi=None, force_accept=False, generator=None, scheme=None, fa=None):
         """One trajectory by the definition at the top of the module; the update lengths are the doubles a_j dt, b_j dt
-        and 0.5 b_s dt, as the kernels are handed them (leapfrog: dt and 0.5 dt)."""
+        and 0.5 b_s dt, as the kernels are handed them (leapfrog: dt and 0.5 dt).  `fa` (a `_Fourier`): the accelerated
+        rule -- the drawn eta becomes pi = A^(-1/2) eta, the kinetic energy is sum pi (A pi) / 2 and phi moves by A pi."""
+        kinetic = (lambda p: 0.5 * p.double().square().flatten(1).sum(dim=1)) if fa is None else fa.kinetic
+        velocity = (lambda p: p) if fa is None else fa.apply
         a, b = ((1.0,), (1.0,)) if scheme is None else (scheme.a, scheme.b)
         s, half = len(a), 0.5 * b[-1] * dt
         C, shape = phi.shape[0], tuple(phi.shape[1:])
@@ -470,17 +572,19 @@ class HMCSampler:
                 pi = _hip.normal_sample(None, None, C, shape, phi.dtype, phi.device, generator=generator)[0]
             else:
                 pi = torch.randn(phi.shape, dtype=phi.dtype, device=phi.device)
+            if fa is not None:
+                pi = fa.refresh(pi)
         elif on_device:
             _hip._philox_position(phi.device, generator)      # handed-in momenta still take the position of the draw
-        H0 = 0.5 * pi.double().square().flatten(1).sum(dim=1) + S0
+        H0 = kinetic(pi) + S0
         new = phi
         pi = pi - half * self._force(new)
         for k in range(1, n_md + 1):
             for j in range(s):
-                new = new + (a[j] * dt) * pi
+                new = new + (a[j] * dt) * velocity(pi)
                 pi = pi - (half if k == n_md and j == s - 1 else b[j] * dt) * self._force(new)
         S1 = self._model.action(new.double()).double()
-        dh = 0.5 * pi.double().square().flatten(1).sum(dim=1) + S1 - H0
+        dh = kinetic(pi) + S1 - H0
         if on_device:
             new = new.contiguous()
             acc = torch.empty(C, dtype=torch.uint8, device=phi.device)
@@ -496,13 +600,49 @@ class HMCSampler:
             acc = ok.to(torch.uint8)
         return new, torch.where(ok, S1, S0), dh, acc, pi
 
-    def _run_composed(self, phi, S, rows, every, n_md, dt, sink, dhs, accs, scheme=None):
+    def _run_composed(self, phi, S, rows, every, n_md, dt, sink, dhs, accs, scheme=None, **fa):
         for t in range(rows * every):
-            phi, S, dh, acc, _ = self._trajectory_composed(phi, S, n_md, dt, scheme=scheme)
+            phi, S, dh, acc, _ = self._trajectory_composed(phi, S, n_md, dt, scheme=scheme, **fa)
             dhs.append(dh.unsqueeze(0)); accs.append(acc.unsqueeze(0))
             if (t + 1) % every == 0:
                 sink.take((t + 1) // every - 1, phi)
         return phi, S
+
+
+class _Fourier:
+    """The kinetic operator of the accelerated rule on the lattice of the chains phi (C, *L), from torch ops: a(k) and
+    a^(-1/2)(k) from the shared table (`_hip.hmc_fa_denominator`), formed in double and cast to the field dtype, and the
+    filter T diag(d) T x = irfftn(rfftn(x) d) (d is even in every k_mu, so its half along the last axis is all rfftn
+    needs)."""
+
+    def __init__(self, phi, w0, mass_sq):
+        mass_sq = float(mass_sq)
+        if not mass_sq > 0.0 or mass_sq == float('inf'):
+            raise ValueError(f"fa_mass_sq must be a finite number > 0, got {mass_sq}")
+        if w0 < 0.0:
+            raise ValueError(f"Fourier acceleration needs a hopping coefficient w0 >= 0 (a(k) > 0), got {w0}")
+        self.mass_sq = mass_sq
+        self.lat = tuple(phi.shape[1:])
+        self.axes = tuple(range(1, phi.ndim))
+        den = _hip.hmc_fa_denominator(self.lat, w0, mass_sq)
+        nh = self.lat[-1] // 2 + 1
+        self.a = (1.0 / den)[..., :nh].to(phi.dtype).to(phi.device)
+        self.inv_sqrt_a = den.sqrt()[..., :nh].to(phi.dtype).to(phi.device)
+
+    def _filter(self, x, d):
+        return torch.fft.irfftn(torch.fft.rfftn(x, dim=self.axes) * d, s=self.lat, dim=self.axes)
+
+    def apply(self, pi):
+        """A pi."""
+        return self._filter(pi, self.a)
+
+    def refresh(self, eta):
+        """pi = A^(-1/2) eta."""
+        return self._filter(eta, self.inv_sqrt_a)
+
+    def kinetic(self, pi):
+        """sum pi (A pi) / 2 per chain, in double."""
+        return 0.5 * (pi.double() * self.apply(pi).double()).flatten(1).sum(dim=1)
 
 
 class _Stats:
@@ -562,6 +702,10 @@ class _Span:
             self.out[r0:r0 + r['record'].shape[0]] = r['record']
         if 'measure' in r:
             self.stats.put_rows(r0, r['measure'])
+
+    def put_stats(self, r, phi):
+        """Step r: the statistics of the recorded row phi (C, *L)."""
+        self.stats.put(r + self._first, phi)
 
     def take(self, r, phi, copy=True):
         """Step r from the chains as they lie: its statistics, and the row itself unless a launch recorded it."""

@@ -234,9 +234,12 @@ class LadderHMCSampler(HMCSampler):
     # ---- which path: HMCSampler's `_choose`, on the proxy model (whose action is a phi^4 action)
     def _advance(self, batch_size, n_chains=None, n_md=10, dt=0.1, n_skip=0, exchange_every=1, path=None, want_rows=True,
                  want_stats=False, cluster_every=0, improved=False, integrator='leapfrog', momenta=None,
-                 spectrum_path=None):
+                 spectrum_path=None, fa_mass_sq=None):
         """batch_size // C recorded steps.  Returns (the rung-ordered rows or None, the `_RungStats` with the rung-ordered
         measure rows `out` (steps, C, n_out) or None)."""
+        if fa_mass_sq is not None:
+            raise TypeError("model.hmc.ladder(...) does not take fa_mass_sq: a(k) = 1 / (w0 khat^2 + M^2) would depend on "
+                            "the rung a chain holds; Fourier acceleration runs on model.hmc with one action")
         K = len(self._ladder)
         C = int(K if n_chains is None else n_chains)
         if C < 1 or C % K != 0:

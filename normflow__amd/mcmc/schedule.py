@@ -59,3 +59,29 @@ def schedule(rows, every, n_md, budget, *, tiled, ladder, stats, want_rows, meas
             left -= k
         acts.append(Launch(last, last, True, want_rows, r, 1) if last else Take(r, copy=want_rows))
     return acts
+
+
+def schedule_fa(rows, every, cost, budget, *, want_rows, stats):
+    """The ordered actions of a span of `rows` recorded steps of the Fourier-accelerated kernel (nf_phi4_hmc_fa), an entry
+    of its own: `cost` is `_hip.hmc_fa_cost(n_md * s)`, the MD steps one trajectory counts as under the cap (its force
+    evaluations and NF_HMC_FA_MD_STEPS per filter), `budget` is `_hip.hmc_fused_budget`.  A launch holds per = max(1,
+    budget // cost) trajectories, fit = per // every whole recorded steps.  The kernel does not measure: with `stats` a
+    launch records its rows (whether or not the caller wants them) and they are measured afterwards, which `record` of
+    the Launch says and `measure` never does.  fit = 0: launches of min(per, left) trajectories without rows, then the
+    row is taken from the chains where they lie."""
+    per = max(1, budget // cost)
+    fit = per // every
+    acts = []
+    if fit >= 1:
+        for r in range(0, rows, fit):
+            k = min(fit, rows - r)
+            acts.append(Launch(k * every, every, False, want_rows or stats, r, k))
+        return acts
+    for r in range(rows):
+        left = every
+        while left:
+            k = min(per, left)
+            acts.append(Launch(k))
+            left -= k
+        acts.append(Take(r, copy=want_rows))
+    return acts
