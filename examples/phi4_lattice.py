@@ -120,12 +120,13 @@ INTEGRATOR_N_MD = dict(leapfrog=10, omelyan=5, omf4=2)
 
 
 def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False, integrator='leapfrog', correlator=False,
-                     spectrum_path=None, fourier=None):
+                     spectrum_path=None, fourier=None, fourier_path=None):
     """<phi^2> of the trained flow + Metropolis next to hybrid Monte Carlo on the action itself (exact up to its own
     statistical error; the first quarter of every chain is dropped as thermalisation), then the observables of both.
     `cluster`: also model.hmc with a Swendsen-Wang sweep of the signs before every recorded step (cluster_every=1), so
     that tau_int(m) stands next to the one without sweeps.  `integrator`: model.hmc's integration scheme, at 10 force
-    evaluations per trajectory of length 1 whichever it is."""
+    evaluations per trajectory of length 1 whichever it is.  `fourier`: model.hmc once more with fa_mass_sq, by
+    `fourier_path` (None: the sampler's choice; 'fa', 'composed', or 'fa_tiled', the opt-in kernel for chains in HBM)."""
     n_md = INTEGRATOR_N_MD[integrator]
     hmc = dict(n_chains=n_chains, n_md=n_md, dt=1.0 / n_md, integrator=integrator)
     y = model.mcmc.sample(n_chains * rows, n_chains=n_chains)
@@ -139,7 +140,7 @@ def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False
     if fourier is not None:
         plain_tau = tau_ints(model, y, n_chains, rows // 4)
         model.hmc.start(n_chains=n_chains)
-        y = model.hmc.sample(n_chains * rows, fa_mass_sq=fourier, **hmc)
+        y = model.hmc.sample(n_chains * rows, fa_mass_sq=fourier, path=fourier_path, **hmc)
         print("<phi^2>  model.hmc, fa_mass_sq=%g   %.5f +- %.5f   (accept rate %.3f, rms dH %.3g)"
               % (fourier, *phi2(y, n_chains, rows // 4), model.hmc.history.accept_rate[-1], model.hmc.history.dh_rms[-1]))
         print("model.hmc, fa_mass_sq=%g   " % fourier + observables(model, y, n_chains, rows // 4))
@@ -204,6 +205,9 @@ def main():
     ap.add_argument("--fourier", type=float, default=None, metavar="M2",
                     help="with --hmc: model.hmc once more with the Fourier-accelerated kinetic term (fa_mass_sq=M2): acceptance, "
                          "<phi^2>, chi and tau_int(m), tau_int(phi^2) with and without acceleration")
+    ap.add_argument("--fourier-path", choices=("fa", "fa_tiled", "composed"), default=None,
+                    help="with --fourier: the path of the accelerated run; default: the sampler's choice (nf_phi4_hmc_fa where "
+                         "the chain fits one CU, else torch ops); fa_tiled is nf_phi4_hmc_fa_tiled, for lattices beyond one CU")
     ap.add_argument("--cluster", action="store_true",
                     help="with --hmc: model.hmc once more with cluster_every=1, tau_int(m) with and without cluster sweeps; "
                          "with --ladder: the ladder once more with exchanges and cluster_every=1")
@@ -234,7 +238,7 @@ def main():
         nf.backward_sanitychecker(model)
         if a.hmc:
             compare_with_hmc(model, cluster=a.cluster, improved=a.improved, integrator=a.integrator, correlator=a.correlator, fourier=a.fourier,
-                             spectrum_path=a.spectrum_path)
+                             spectrum_path=a.spectrum_path, fourier_path=a.fourier_path)
 
 
 if __name__ == "__main__":

@@ -968,6 +968,78 @@ int nf_phi4_hmc_fa(void *phi, double *action_out, const void *pi_in, void *pi_ou
                    int n_md, double dt, int n_traj, int force_accept, uint64_t seed, uint64_t offset, int dtype,
                    void *stream, const nf_hmc_scheme *scheme, double fa_mass_sq);
 
+/* ---- the same with the chains in HBM and many workgroups per chain (nf_hmc_fa_tiled.hip): the accelerated trajectory
+ * above, word for word -- the table, a(k) and a^(-1/2)(k) formed in double and cast, eta at (seed, offset + 2 t) as
+ * nf_normal_sample draws it and u at + 1 as nf_block_accept, H from pi and A pi at both ends, pi_in / pi_out are pi, the
+ * accept rule, a rejected chain not written at all -- for the lattices beyond nf_phi4_hmc_fa's LDS (32^3, 16^4, 32^4, 48^4,
+ * 64^3).  The energies follow nf_phi4_hmc_tiled: per-workgroup partials in double, added in a fixed order, no atomics.
+ *   The filter x <- T diag(d) T x runs over HBM.  The axes of lattice[4] are cut into g >= 1 groups of adjacent axes.  One
+ *     pass of a group loads panels into LDS -- the full extents of the group's axes times a run of the remaining sites,
+ *     contiguous along the sites behind the group (or, where the run takes all of those, a run of the index in front of
+ *     it: the panel is then one contiguous stretch) --, transforms them along the group's axes with the axis pass of
+ *     nf_spectral_core.h and writes them back.  A filter is 2 g - 1 passes: the groups from the fastest to the slowest,
+ *     diag(d) inside the slowest group's pass between its forward and its backward transform, the other groups back.  The
+ *     single axes are transformed in the order 3, 2, 1, 0 forward and 0, 1, 2, 3 back whatever the cut, and a line's
+ *     arithmetic depends on the line and its matrix alone: phi and pi out of a trajectory do not depend on the cut, bit for
+ *     bit (the energies' partials are the step kernel's, so dH does not either).
+ *   Drift and kick: phi' = phi + a_j dt v and pi' = pi - b_j dt F(phi') with v = A pi read from its own buffer -- the step of
+ *     nf_phi4_hmc_tiled (the same kernel template, tile plan, ring of four planes, halo rule and wide accesses) with the
+ *     velocity as a separate operand.
+ *   A trajectory is a fixed line of launches on `stream`: draw; the refresh filter (both skipped with pi_in); the H0 filter;
+ *     begin (the partials of sum pi (A pi) / 2 and S(phi), the first kick); per stage a filter and a step; the H1 filter;
+ *     the partials of the end; commit (decision, copy of the accepted chains, record row, pi_out) -- `launches` =
+ *     (n_md s + 3) (2 g - 1) + n_md s + 4 per trajectory, `filters` = n_md s + 3.  No allocation, no host synchronisation,
+ *     capturable into a HIP graph, bitwise reproducible; the plan does not depend on C, so a chain's result does not depend
+ *     on the chains it shares a call with; n_traj trajectories in one call equal n_traj calls of one; record /
+ *     record_every as in nf_phi4_hmc_tiled.  There is no measuring form and no ladder form.
+ * cut: -1 (the planner's choice) or a mask; bit mu (0 .. 2) set = a group boundary between axis mu and mu + 1 of
+ * lattice[4].  A mask that puts a boundary next to an axis of extent 1 is refused, and so is one with a group whose one
+ * line of sites and Hartley matrices exceed the 163840 B of LDS.  The planner sizes a panel for about 32 KiB, a run of 64
+ * bytes at least and at most 80 KiB of LDS per pass where the group allows (else up to 163840 B), and chooses for -1: the
+ * cuts whose every run reaches 64 bytes inside 80 KiB first, then the fewest groups, then the longest shortest contiguous
+ * stretch, then the smallest mask.  Cut 0 (one group, the whole chain in one panel) is legal where it fits.
+ * nf_phi4_hmc_fa_tiled_supported (pure host code): 1 iff dtype is NF_F32 / NF_F64, every extent is in 1 .. 64 (128^2 and
+ * 130^2 stay refused: the message names the axis), V < 2^31 and some cut fits -- every lattice nf_phi4_hmc_fa takes
+ * included -- else 0 with the reason in nf_last_error_string.
+ * nf_phi4_hmc_fa_tiled_plan (pure host code), for n_md steps of a scheme of `stages` stages: the cut used, `groups` = g,
+ * `passes` = 2 g - 1 per filter; per group i (the slowest first; entries from g on are 0) its axes first[i] .. last[i],
+ * run[i] remaining sites per panel (run_inner[i] of them along the sites behind the group), panels[i] per chain,
+ * panel_sites[i], lanes[i] of a workgroup, lds_bytes[i] (<= 163840) of which matrix_bytes[i] hold the matrices;
+ * `filters`, `launches` (per trajectory, as above) and `step`, the step kernel's tile plan (nf_phi4_hmc_tiled_plan's).
+ * nf_phi4_hmc_fa_tiled_workspace (pure host code): round256(C tiles 4 sizeof(double)) + 5 round256(C V sizeof(dtype)) bytes
+ * -- the partials and five fields (two phi, two pi, v), round256 rounding up to a multiple of 256 and tiles = step.tiles
+ * --, 0 for an unsupported case; it does not depend on the cut.  The caller owns the workspace; alignment as for
+ * nf_phi4_hmc_tiled (8 bytes; 16 for the wide accesses); it need not be initialised.
+ * nf_phi4_hmc_fa_tiled: nf_phi4_hmc_tiled_scheme's arguments (scheme NULL: leapfrog), fa_mass_sq and cut.
+ * NF_EINVAL, with the reason in the message: what nf_phi4_hmc_fa and nf_phi4_hmc_tiled refuse for the arguments they share
+ * (without nf_phi4_hmc_fa's work cap and lattice limits), a bad cut, or launches x n_traj > NF_HMC_TILED_MAX_LAUNCHES. */
+typedef struct nf_hmc_fa_tiled_plan {
+  int32_t cut;
+  int32_t groups;
+  int32_t passes;
+  int32_t reserved;
+  int32_t first[4];
+  int32_t last[4];
+  int32_t run[4];
+  int32_t run_inner[4];
+  int32_t panels[4];
+  int32_t lanes[4];
+  int64_t panel_sites[4];
+  int64_t lds_bytes[4];
+  int64_t matrix_bytes[4];
+  int64_t filters;
+  int64_t launches;
+  nf_hmc_tiled_plan step;
+} nf_hmc_fa_tiled_plan;
+int nf_phi4_hmc_fa_tiled_supported(const int32_t *lattice, int dtype);
+int nf_phi4_hmc_fa_tiled_plan(const int32_t *lattice, int dtype, int cut, int n_md, int stages, nf_hmc_fa_tiled_plan *out);
+size_t nf_phi4_hmc_fa_tiled_workspace(int64_t C, const int32_t *lattice, int dtype);
+int nf_phi4_hmc_fa_tiled(void *phi, double *action_out, const void *pi_in, void *pi_out, double *dh_out,
+                         uint8_t *accept_out, void *record, int record_every, int64_t C, const int32_t *lattice, double w0,
+                         double w2, double w4, int n_md, double dt, int n_traj, int force_accept, uint64_t seed,
+                         uint64_t offset, void *workspace, size_t workspace_bytes, int dtype, void *stream,
+                         const nf_hmc_scheme *scheme, double fa_mass_sq, int cut);
+
 /* ---- cluster updates of phi^4 chains (nf_cluster.hip; MI355X-side extension): one Swendsen-Wang sweep of the embedded
  * Ising signs (Brower-Tamayo: phi = s |phi|).  A sweep is never rejected, leaves sum phi^2 and sum phi^4 alone and
  * flips every cluster half of the time.  The sweep, stated once:

@@ -195,6 +195,14 @@ for _name in ("nf_phi4_hmc", "nf_phi4_hmc_measure", "nf_phi4_hmc_ladder", "nf_ph
     PROTOTYPES[_name + "_scheme"] = (_I, PROTOTYPES[_name][1] + [_P])
 del _name
 
+PROTOTYPES.update({
+    "nf_phi4_hmc_fa_tiled_supported": (_I, [C.POINTER(C.c_int32), _I]),
+    "nf_phi4_hmc_fa_tiled_plan": (_I, [C.POINTER(C.c_int32), _I, _I, _I, _I, _P]),
+    "nf_phi4_hmc_fa_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I]),
+    # nf_phi4_hmc_tiled_scheme's arguments, `double fa_mass_sq` and `int cut`
+    "nf_phi4_hmc_fa_tiled": (_I, PROTOTYPES["nf_phi4_hmc_tiled_scheme"][1] + [_D, _I]),
+})
+
 _lib = None
 _lock = threading.Lock()
 
@@ -2306,6 +2314,108 @@ def phi4_hmc_tiled(phi, w0, w2, w4, n_md, dt, n_traj=1, record_every=None, pi_in
     return _phi4_hmc_call("phi4_hmc_tiled", phi, w0, w2, w4, n_md, dt, n_traj=n_traj, record_every=record_every,
                           pi_in=pi_in, want_pi=want_pi, force_accept=force_accept, position=position, generator=generator,
                           workspace=workspace, scheme=scheme)
+
+
+# ========================================================================= Fourier-accelerated HMC, chains in HBM (nf_hmc_fa_tiled.hip)
+class HmcFaTiledPlan(C.Structure):
+    """nf_hmc_fa_tiled_plan (include/normflow_hip.h)."""
+    _fields_ = [("cut", C.c_int32), ("groups", C.c_int32), ("passes", C.c_int32), ("reserved", C.c_int32),
+                ("first", C.c_int32 * 4), ("last", C.c_int32 * 4), ("run", C.c_int32 * 4), ("run_inner", C.c_int32 * 4),
+                ("panels", C.c_int32 * 4), ("lanes", C.c_int32 * 4), ("panel_sites", C.c_int64 * 4),
+                ("lds_bytes", C.c_int64 * 4), ("matrix_bytes", C.c_int64 * 4), ("filters", C.c_int64),
+                ("launches", C.c_int64), ("step", HmcTiledPlan)]
+
+
+def _fa_cut(what, lat, cut):
+    """The library's `cut` for the lattice `lat` of 1 to 4 axes: -1 for None, else the mask of the boundaries between the
+    axes of `lat` (bit mu: between axis mu and mu + 1) moved onto the four-extent lattice."""
+    if cut is None:
+        return -1
+    cut = int(cut)
+    if not 0 <= cut < 1 << (len(lat) - 1):
+        raise NormflowHipError(f"{what}: cut must be None or a mask of the {len(lat) - 1} boundaries between the axes of "
+                               f"{tuple(lat)}, got {cut}")
+    return cut << (4 - len(lat))
+
+
+def hmc_fa_tiled_supported(lat, dtype):
+    """True if nf_phi4_hmc_fa_tiled takes chains on the lattice `lat` (1 to 4 extents) in `dtype`: the launcher's own
+    planner, pure host code; the reason of a refusal is in `last_error()`."""
+    return _planner_supported("nf_phi4_hmc_fa_tiled_supported", lat, dtype)
+
+
+def hmc_fa_tiled_plan(lat, dtype, cut=None, n_md=1, stages=1):
+    """What nf_phi4_hmc_fa_tiled will do on the lattice `lat` in `dtype` under `cut` (None: the planner's choice; else a
+    mask, bit mu = a group boundary between the axes mu and mu + 1 of `lat`) with n_md steps of a scheme of `stages`
+    stages: dict(cut (the mask used, in the axes of `lat`), groups (a list, the slowest first, of dict(axes, run,
+    run_inner, panels (per chain), panel_sites, lanes, lds_bytes, matrix_bytes)), passes (per filter: 2 g - 1), filters
+    and launches (per trajectory), step (`hmc_tiled_plan`'s dict of the step kernel)).  Pure host code."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"hmc_fa_tiled_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
+    code = NF_F32 if dtype == torch.float32 else NF_F64 if dtype == torch.float64 else NF_F16
+    out = HmcFaTiledPlan()
+    _check(load().nf_phi4_hmc_fa_tiled_plan(_lat4(lat), code, _fa_cut("hmc_fa_tiled_plan", lat, cut), int(n_md), int(stages),
+                                            C.byref(out)), "nf_phi4_hmc_fa_tiled_plan")
+    pad = 4 - len(lat)
+    groups = [dict(axes=tuple(range(max(out.first[i] - pad, 0), out.last[i] - pad + 1)), run=out.run[i],
+                   run_inner=out.run_inner[i], panels=out.panels[i], panel_sites=out.panel_sites[i], lanes=out.lanes[i],
+                   lds_bytes=out.lds_bytes[i], matrix_bytes=out.matrix_bytes[i]) for i in range(out.groups)]
+    st = out.step
+    step = dict(tile=tuple(st.tile)[pad:], ntiles=tuple(st.ntiles)[pad:], tiles=st.tiles,
+                march_axis=None if st.march_axis < 0 else st.march_axis - pad, ring_depth=st.ring_depth, lanes=st.lanes,
+                vec=st.vec, lds_bytes=st.lds_bytes, lds_budget=st.lds_budget)
+    return dict(cut=out.cut >> pad, groups=groups, passes=out.passes, filters=out.filters, launches=out.launches, step=step)
+
+
+def hmc_fa_tiled_workspace(Cn, lat, dtype):
+    """nf_phi4_hmc_fa_tiled_workspace: the bytes of the workspace of a call on Cn chains on `lat` in `dtype` (whatever the
+    cut); pure host code."""
+    code = NF_F32 if dtype == torch.float32 else NF_F64 if dtype == torch.float64 else NF_F16
+    return int(load().nf_phi4_hmc_fa_tiled_workspace(int(Cn), _lat4(tuple(lat)), code))
+
+
+def hmc_fa_tiled_budget(evals, passes=7):
+    """The trajectories that one call of nf_phi4_hmc_fa_tiled may hold under NF_HMC_TILED_MAX_LAUNCHES: a trajectory of
+    `evals` = n_md * s force evaluations is (evals + 3) * passes + evals + 4 launches, `passes` = 2 g - 1 of the plan (the
+    default is the most there can be: four groups)."""
+    evals, passes = int(evals), int(passes)
+    return HMC_TILED_MAX_LAUNCHES // ((evals + 3) * passes + evals + 4)
+
+
+def phi4_hmc_fa_tiled(phi, w0, w2, w4, n_md, dt, fa_mass_sq, n_traj=1, record_every=None, pi_in=None, want_pi=False,
+                      force_accept=False, position=None, generator=None, workspace=None, scheme=None, cut=None):
+    """nf_phi4_hmc_fa_tiled: `phi4_hmc_fa` for chains that live in HBM -- the same arguments, Philox positions and rule, the
+    dict of `phi4_hmc_tiled`.  `workspace`: a uint8 tensor of at least nf_phi4_hmc_fa_tiled_workspace bytes, else one from
+    torch's caching allocator per call.  `cut`: None (the planner's choice) or the mask of `hmc_fa_tiled_plan`; phi and pi
+    do not depend on it."""
+    what = "phi4_hmc_fa_tiled"
+    _require_device(phi, pi_in)
+    if not phi.is_contiguous() or (pi_in is not None and (not pi_in.is_contiguous() or pi_in.dtype != phi.dtype
+                                                            or pi_in.shape != phi.shape)):
+        raise NormflowHipError(f"{what} needs contiguous phi (C, *L) and pi_in of its shape and dtype")
+    Cn, lat, dev = phi.shape[0], tuple(phi.shape[1:]), phi.device
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"{what}: lattices of 1 to 4 axes, got {lat}")
+    n_traj = int(n_traj)
+    dh = torch.empty((max(n_traj, 0), Cn), dtype=torch.float64, device=dev)
+    accept = torch.empty((max(n_traj, 0), Cn), dtype=torch.uint8, device=dev)
+    action = torch.empty(Cn, dtype=torch.float64, device=dev)
+    rec = None
+    if record_every is not None:
+        rec = torch.empty((n_traj // int(record_every), Cn) + lat, dtype=phi.dtype, device=dev)
+    pi_out = torch.empty_like(phi) if want_pi else None
+    if workspace is None:
+        workspace = torch.empty(max(hmc_fa_tiled_workspace(Cn, lat, phi.dtype), 256), dtype=torch.uint8, device=dev)
+    if scheme is not None and scheme is not NULL_SCHEME:
+        scheme = hmc_scheme(scheme)
+    sc = None if scheme is None or scheme is NULL_SCHEME else C.byref(scheme)
+    seed, offset = position if position is not None else _philox_positions(dev, 2 * max(n_traj, 1), generator)
+    _check(load().nf_phi4_hmc_fa_tiled(_ptr(phi), _ptr(action), _ptr(pi_in), _ptr(pi_out), _ptr(dh), _ptr(accept), _ptr(rec),
+                                       1 if record_every is None else int(record_every), Cn, _lat4(lat), float(w0),
+                                       float(w2), float(w4), int(n_md), float(dt), n_traj, int(bool(force_accept)), seed,
+                                       offset, _ptr(workspace), workspace.numel(), _dtype_code(phi), _stream(), sc,
+                                       float(fa_mass_sq), _fa_cut(what, lat, cut)), "nf_phi4_hmc_fa_tiled")
+    return dict(action=action, dh=dh, accept=accept, record=rec, pi=pi_out)
 
 
 # ========================================================================= coupling ladders (nf_hmc.hip, nf_hmc_tiled.hip, nf_ladder.hip)

@@ -32,8 +32,12 @@ that every mode of the quadratic part of the action turns at nearly the same rat
   * fa:       nf_phi4_hmc_fa (nf_hmc_fa.hip), the chain and the Hartley transform resident in a CU -- ScalarPhi4Action on
               a HIP device, lattices nf_phi4_hmc_fa_supported takes;
   * composed: the same rule from torch ops, the filter through torch.fft.rfftn / irfftn with a(k) from the shared table
-              (`_hip.hmc_fa_table`) -- everywhere else: CPU tensors, lattices beyond one CU, any action with a `get_coef`.
-There is no tiled accelerated kernel.  Cluster sweeps fall between launches and do not see the kinetic term."""
+              (`_hip.hmc_fa_table`) -- everywhere else: CPU tensors, lattices beyond one CU, any action with a `get_coef`;
+  * fa_tiled: nf_phi4_hmc_fa_tiled (nf_hmc_fa_tiled.hip), the chains in HBM, the filter in 2 g - 1 passes over panels of
+              g groups of axes and the tiled step with the velocity as an operand -- ScalarPhi4Action on a HIP device,
+              lattices nf_phi4_hmc_fa_tiled_supported takes (every extent <= 64: 32^3, 16^4, 32^4, 48^4, 64^3).  OPT-IN:
+              only `path='fa_tiled'` runs it; path=None chooses between 'fa' and 'composed' as it always did.
+Cluster sweeps fall between launches and do not see the kinetic term."""
 import torch
 
 from .. import _hip
@@ -92,7 +96,7 @@ class HMCSampler:
         `integrator`: 'leapfrog', 'omelyan', 'omf4', a pair (a, b) of weights or an `_hip.HmcScheme`; anything but
         leapfrog is recorded in `last['integrator']` (the name, or the pair of weight tuples).
         `fa_mass_sq`: None, or M^2 > 0 of the Fourier-accelerated kinetic term (module docstring), recorded in
-        `last['fa_mass_sq']`; `path` is then None, 'fa' or 'composed'."""
+        `last['fa_mass_sq']`; `path` is then None, 'fa', 'composed' or (opt-in) 'fa_tiled'."""
         y, _ = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=True, want_stats=False,
                              cluster_every=cluster_every, integrator=integrator, **self._fa_kw(fa_mass_sq))
         return y, (-self._model.action(y)).to(y.dtype)
@@ -204,6 +208,9 @@ class HMCSampler:
         out = torch.empty((rows,) + tuple(phi.shape), dtype=phi.dtype, device=phi.device) if want_rows else None
         stats = _Stats(phi, rows) if want_stats else None
         ws = self._tiled_workspace(phi) if path == 'tiled' else None       # one workspace for all calls
+        if path == 'fa_tiled':
+            need = _hip.hmc_fa_tiled_workspace(phi.shape[0], tuple(phi.shape[1:]), phi.dtype)
+            ws = torch.empty(max(need, 256), dtype=torch.uint8, device=phi.device)
         sweep_ws = None
         if E and self._sweep_path(phi) == 'tiled':                # one workspace for all sweeps of the call
             need = _hip.cluster_tiled_workspace(phi.shape[0], tuple(phi.shape[1:]))
@@ -231,6 +238,9 @@ class HMCSampler:
                                             **({} if fa is None else dict(fa=fa)))
             elif path == 'fa':
                 S = self._run_fa(phi, self._coef(phi.shape[1:]), fa.mass_sq, k, every, n_md, dt, sink, dhs, accs, scheme)
+            elif path == 'fa_tiled':
+                S = self._run_fa_tiled(phi, self._coef(phi.shape[1:]), fa.mass_sq, k, every, n_md, dt, ws, sink, dhs, accs,
+                                       scheme)
             else:
                 S = self._run(path, phi, self._coef(phi.shape[1:]), k, every, n_md, dt, ws, sink, dhs, accs, scheme)
             r0 += k
@@ -239,6 +249,8 @@ class HMCSampler:
         self._finish(dhs, accs, scheme=scheme)
         if fa is not None:
             self.last['fa_mass_sq'] = fa.mass_sq
+        if path == 'fa_tiled':
+            self.last['path'] = path
         if E:
             self.last['cluster'] = (torch.stack(sweeps) if sweeps else
                                     torch.empty((0, phi.shape[0], 4), dtype=torch.int32, device=phi.device))
@@ -393,10 +405,11 @@ class HMCSampler:
         else:
             path = self._choose_fa(phi, path)
             fa = _Fourier(phi, self._fa_w0(phi), fa_mass_sq)
-        if path == 'fa':
+        if path in ('fa', 'fa_tiled'):
             kw = {} if scheme is None else dict(scheme=scheme)
-            r = _hip.phi4_hmc_fa(phi, *self._coef(phi.shape[1:]), n_md, dt, fa.mass_sq, n_traj=1, pi_in=pi, want_pi=True,
-                                 force_accept=force_accept, position=position, **kw)
+            kernel = _hip.phi4_hmc_fa if path == 'fa' else _hip.phi4_hmc_fa_tiled
+            r = kernel(phi, *self._coef(phi.shape[1:]), n_md, dt, fa.mass_sq, n_traj=1, pi_in=pi, want_pi=True,
+                       force_accept=force_accept, position=position, **kw)
             return dict(phi=phi, pi=r['pi'], dh=r['dh'][0], accept=r['accept'][0], action=r['action'])
         if path != 'composed':
             kernel = _hip.phi4_hmc if path == 'fused' else _hip.phi4_hmc_tiled
@@ -476,15 +489,33 @@ class HMCSampler:
                     else f"the chains are {phi.dtype} on {phi.ndim - 1} axes")
         return None
 
+    def _fa_tiled_refusal(self, phi):
+        """Why nf_phi4_hmc_fa_tiled does not take these chains, or None: the planner's reason where it is the planner's."""
+        if not isinstance(self._model.action, ScalarPhi4Action):
+            return f"the action is a {type(self._model.action).__name__}, not a ScalarPhi4Action"
+        if not phi.is_cuda:
+            return f"the chains are a {phi.device} tensor, not on a HIP device"
+        if not _hip.hmc_fa_tiled_supported(tuple(phi.shape[1:]), phi.dtype):
+            return (_hip.last_error() if phi.dtype in (torch.float32, torch.float64) and 1 <= phi.ndim - 1 <= 4
+                    else f"the chains are {phi.dtype} on {phi.ndim - 1} axes")
+        return None
+
     def _choose_fa(self, phi, path):
-        """'fa' or 'composed', with fa_mass_sq: the kernel where nf_phi4_hmc_fa_supported holds on device tensors, the
-        composed path everywhere else.  There is no tiled accelerated kernel: lattices beyond one CU stay composed."""
+        """'fa', 'fa_tiled' or 'composed', with fa_mass_sq: None is the kernel where nf_phi4_hmc_fa_supported holds on device
+        tensors and the composed path everywhere else; the accelerated kernel for chains in HBM (nf_phi4_hmc_fa_tiled, the
+        lattices beyond one CU) runs only where `path='fa_tiled'` asks for it."""
         if path in ('tiled', 'fused'):
-            raise ValueError(f"path={path!r} with fa_mass_sq: there is no {path} accelerated kernel (lattices beyond one CU "
-                             "run the composed path); path must be None, 'fa' or 'composed'")
-        if path not in (None, 'fa', 'composed'):
-            raise ValueError(f"path must be None, 'fa' or 'composed' with fa_mass_sq, got {path!r}")
+            raise ValueError(f"path={path!r} with fa_mass_sq: there is no {path} accelerated kernel under that name (lattices "
+                             "beyond one CU run the composed path, or nf_phi4_hmc_fa_tiled with path='fa_tiled'); path must "
+                             "be None, 'fa', 'fa_tiled' or 'composed'")
+        if path not in (None, 'fa', 'fa_tiled', 'composed'):
+            raise ValueError(f"path must be None, 'fa', 'fa_tiled' or 'composed' with fa_mass_sq, got {path!r}")
         if path == 'composed':
+            return path
+        if path == 'fa_tiled':
+            why = self._fa_tiled_refusal(phi)
+            if why is not None:
+                raise _hip.NormflowHipError(f"HMCSampler(path='fa_tiled'): nf_phi4_hmc_fa_tiled does not apply: {why}")
             return path
         why = self._fa_refusal(phi)
         if why is None:
@@ -545,6 +576,25 @@ class HMCSampler:
                 if sink.stats is not None:
                     for i in range(r['record'].shape[0]):
                         sink.put_stats(a.row0 + i, r['record'][i])
+        return r['action']
+
+    # ---- Fourier-accelerated kernel, chains in HBM
+    def _run_fa_tiled(self, phi, couplings, mass_sq, rows, every, n_md, dt, ws, sink, dhs, accs, scheme=None):
+        """`_run`'s tiled route for nf_phi4_hmc_fa_tiled: the launches that `schedule(tiled=True)` cuts under
+        `_hip.hmc_fa_tiled_budget`, one workspace, the statistics taken from the chains in place between the launches."""
+        evals = n_md * (1 if scheme is None else scheme.stages)
+        extra = {} if scheme is None else dict(scheme=scheme)
+        passes = _hip.hmc_fa_tiled_plan(tuple(phi.shape[1:]), phi.dtype)['passes']
+        budget = _hip.hmc_fa_tiled_budget(evals, passes)
+        for a in schedule(rows, every, evals, budget, tiled=True, ladder=False, stats=sink.stats is not None,
+                          want_rows=sink.out is not None, measure_cost=_hip.HMC_MEASURE_MD_STEPS):
+            if isinstance(a, Take):
+                sink.take(a.row, phi, a.copy)
+                continue
+            r = _hip.phi4_hmc_fa_tiled(phi, *couplings, n_md, dt, mass_sq, n_traj=a.n_traj, record_every=a.record_every,
+                                       workspace=ws, **extra)
+            dhs.append(r['dh']); accs.append(r['accept'])
+            sink.launch(a.row0, r)
         return r['action']
 
     # ---- composed
