@@ -487,7 +487,21 @@ int nf_conv_affine_split16(const void *in16, const void *wsplit, const void *bia
  *   32 with zeros), t = tap of the site pair (sites 2p-1 .. 2p+2); lane 16*g + n (column n = 8*shift + co) holds rows
  *   8*slice + 2*g + h (h = 0, 1) as values 4*h + t = W[co][r][t - shift] (zero outside 0..2), scaled by 2^10 and split as
  *   in NF_WLAYOUT_SPLIT16.  nf_conv_first_split16_supported: 8 output channels, 3^4 kernel, a fastest axis of 32 + 16 n
- *   sites, even other extents. */
+ *   sites, even other extents.
+ *   Frozen-parity flags, ORed into `act` (both entry points mask them off before they look at the activation): with
+ *   NF_FIRST_FROZEN_EVEN / NF_FIRST_FROZEN_ODD the caller states that `in` is non-zero only at the sites whose coordinate sum
+ *   x0 + x1 + x2 + x3 is even / odd (the frozen half of a checkerboard coupling).  On lattices with L3 % 32 == 0, L0 % 4 == 0
+ *   and L1 % 4 == 0 the parity-compact instance then runs: it LOADS those sites only (whatever stands at the others is never
+ *   read) and multiplies K = 27 rows x 2 live taps.  Every other supported lattice runs the dense kernel on `in` as it is.
+ *   A flagged call states the size of its blob with NF_FIRST_FRAGS(16): the 8 dense fragments above, then
+ *   [sigma (2)][K slice (2)][hi|lo][64 lanes][8]: sigma = (output row parity x0 + x1 + x2) ^ (frozen parity), K index =
+ *   2 r + t', lane 16*g + n holds rows 16*slice + 4*g + h (h = 0..3) as values 2*h + t' = W[co][r][t - shift] at the live
+ *   taps t = 1 - e + 2 t', e = sigma ^ (j0 + j1 + j2 + 1) & 1 (zero outside 0..2 and for r >= 27); scaled and split as the
+ *   dense ones.  A flagged call without it is refused (NF_EINVAL).  Without a flag nothing changes. */
+#define NF_FIRST_FROZEN_EVEN 0x100
+#define NF_FIRST_FROZEN_ODD 0x200
+#define NF_FIRST_FRAGS_MAX 0xff
+#define NF_FIRST_FRAGS(n) ((int)(n) << 16)
 int nf_conv_first_split16_supported(const int32_t *lattice, const int32_t *ksize, int cout, int act);
 int nf_conv_first_split16(const void *in, const void *wsplit, const void *bias, void *out16, int64_t B,
                           const int32_t *lattice, int act, void *stream);

@@ -987,14 +987,65 @@ def pack_conv_weight_split16_first(w):
     return out.contiguous()
 
 
-def conv_first_split16(x, weight, bias, act, weight_src=None):
+def _first_parity_taps():
+    """j3[sigma, shift, r, t'] = the kernel tap W[co][r][j3] that column 8*shift + co multiplies at live tap t' of kernel row r
+    (3 = none: a zero) -- include/normflow_hip.h, nf_conv_first_split16: live taps t = 1 - e + 2 t' of the pair's four,
+    e = sigma ^ (j0 + j1 + j2 + 1) & 1, j3 = t - shift."""
+    j3 = torch.full((2, 2, 32, 2), 3, dtype=torch.long, device='cpu')
+    for sigma in range(2):
+        for r in range(27):
+            e = sigma ^ ((r // 9 + (r // 3) % 3 + r % 3 + 1) & 1)
+            for shift in range(2):
+                for tp in range(2):
+                    j = 1 - e + 2 * tp - shift
+                    if 0 <= j <= 2:
+                        j3[sigma, shift, r, tp] = j
+    return j3
+
+
+_FIRST_PARITY_TAPS = []
+FIRST_FROZEN_FLAG = (0x100, 0x200)        # NF_FIRST_FROZEN_EVEN, NF_FIRST_FROZEN_ODD
+FIRST_PARITY_FRAGS = 16 << 16             # NF_FIRST_FRAGS(16): the blob of pack_conv_weight_split16_first_parity
+
+
+def pack_conv_weight_split16_first_parity(w):
+    """(8, 1, 3, 3, 3, 3) fp32 weights of a first ConvAct layer -> the blob a frozen-parity call of nf_conv_first_split16
+    takes (include/normflow_hip.h): the 8 dense fragments of `pack_conv_weight_split16_first`, then the parity fragments
+    [sigma (2)][K slice (2)][hi|lo][lane (64)][8]: K index = 2 r + t'; lane 16*g + n (column n = 8*shift + co) holds rows
+    16*slice + 4*g + h (h = 0..3), live taps t' = 0, 1, as value 2*h + t' = W[co][r][t - shift] with t = 1 - e + 2 t',
+    e = sigma ^ (j0 + j1 + j2 + 1) & 1 (zero outside 0..2 and for r >= 27), scaled by 2^10 and split."""
+    assert tuple(w.shape) == (8, 1, 3, 3, 3, 3)
+    if not _FIRST_PARITY_TAPS:
+        _FIRST_PARITY_TAPS.append(_first_parity_taps())
+    j3 = _FIRST_PARITY_TAPS[0].to(w.device)
+    wr = w.new_zeros(8, 32, 4, dtype=torch.float32)                      # co, row (padded), j3 (3 = the zero)
+    wr[:, :27, :3] = w.reshape(8, 27, 3).float() * SPLIT16_WEIGHT_SCALE
+    rows = torch.arange(32, device=w.device).view(1, 1, 32, 1).expand_as(j3)
+    w2 = wr[:, rows, j3].permute(1, 2, 0, 3, 4).reshape(2, 16, 32, 2)    # sigma, n = 8 shift + co, row, t'
+    hi = w2.half()
+    lo = (w2 - hi.float()).half()
+    out = torch.empty(2, 2, 2, 64, 8, dtype=torch.float16, device=w.device)
+    for k, part in enumerate((hi, lo)):
+        # part[sigma, n, r = 16 sl + 4 g + h, t'] -> [sigma, sl, g, n, h, t']
+        v = part.reshape(2, 16, 2, 4, 4, 2).permute(0, 2, 3, 1, 4, 5)
+        out[:, :, k] = v.reshape(2, 2, 64, 8)
+    return torch.cat((pack_conv_weight_split16_first(w).reshape(8, 64, 8), out.reshape(8, 64, 8))).contiguous()
+
+
+def conv_first_split16(x, weight, bias, act, weight_src=None, frozen_parity=None):
     """First ConvAct layer 1 -> 8 on the split-fp16 kernel (nf_conv_first_split16): x (B, 1, *L) fp32 -> the fp16 pair
-    tensor (B, V, 16); inference only."""
+    tensor (B, V, 16); inference only.  frozen_parity 0 / 1: the caller states that x is non-zero only at the sites whose
+    coordinate sum has that parity (the frozen half of a checkerboard coupling); the library then reads those sites only
+    where it has the parity-compact instance."""
     lib = load()
     B = x.shape[0]
     lat4 = _lat4(x.shape[2:])
     V = _sites(x.shape[2:])
-    wsp = _cached_pack(weight if weight_src is None else weight_src, 'first16', pack_conv_weight_split16_first)
+    if frozen_parity is None:
+        wsp = _cached_pack(weight if weight_src is None else weight_src, 'first16', pack_conv_weight_split16_first)
+    else:
+        wsp = _cached_pack(weight if weight_src is None else weight_src, 'first16p', pack_conv_weight_split16_first_parity)
+        act = int(act) | FIRST_FROZEN_FLAG[int(frozen_parity) & 1] | FIRST_PARITY_FRAGS
     bias = None if bias is None else bias.detach().float().contiguous()
     out = torch.empty((B, V, 16), dtype=torch.float16, device=x.device)
     for b0, b1 in _slabs(B, max(1, min(MAX_B, ((1 << 31) - 1) // V))):
@@ -1199,7 +1250,7 @@ def _conv_weight_map(shape, device, lat4, k4, cin, cout, compact, two_site, tran
                                               layout))
 
 
-def _conv_launch(x, weight, bias, act, compact, parity, weight_src=None, transposed=False):
+def _conv_launch(x, weight, bias, act, compact, parity, weight_src=None, transposed=False, frozen_parity=None):
     """One launch sequence of nf_conv_fwd for a (cout, cin, *k) weight tensor; packs the weights in
     the fragment layout the library will use (two-site column packing for cout <= 8).  transposed: the layer is the INPUT
     GRADIENT of the layer with these weights (flipped taps, channels exchanged)."""
@@ -1213,7 +1264,7 @@ def _conv_launch(x, weight, bias, act, compact, parity, weight_src=None, transpo
     if (split16 and cin == 1 and cout == 8 and d == 4 and x.dtype == torch.float32
             and _weights_fit_fp16(weight if weight_src is None else weight_src)     # (the caller's tensor: its verdict is cached)
             and lib.nf_conv_first_split16_supported(lat4, k4, cout, act)):
-        return conv_first_split16(x, weight, bias, act, weight_src)
+        return conv_first_split16(x, weight, bias, act, weight_src, frozen_parity)
     if split16 and not (lib.nf_conv_two_site(cout, 0, lat[-1], ksize[-1]) and cout == 8 and x.dtype == torch.float32):
         raise NormflowHipError("split-fp16 output needs an fp32 two-site layer with 8 output channels")
     two_site = bool(lib.nf_conv_two_site(cout, 0 if split16 else int(compact), lat[-1], ksize[-1]))
@@ -1594,14 +1645,17 @@ class FusedLastRqsFn(torch.autograd.Function):
         return gh, gw, gb, gx, (glogj if ctx.has_log0 else None), None, None, None
 
 
-def conv_layer(x, weight, bias, act=0, compact=False, parity=0):
-    """Circular 'same' conv + activation on the HIP kernel; differentiable."""
+def conv_layer(x, weight, bias, act=0, compact=False, parity=0, frozen_parity=None):
+    """Circular 'same' conv + activation on the HIP kernel; differentiable.  frozen_parity (0 / 1, inference with compact=2
+    only): x is zero off the sites of that coordinate-sum parity -- `conv_first_split16`; ignored by every other path, which
+    reads x as it is."""
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
         if act == 5:      # |.| hides the sign its derivative needs: keep the activation outside
             return torch.abs(ConvFn.apply(x, weight, bias, 0, compact, parity))
         return ConvFn.apply(x, weight, bias, act, compact, parity)
     x = x.contiguous()
-    return _conv_launch(x, weight.detach(), None if bias is None else bias.detach(), act, compact, parity, weight_src=weight)
+    return _conv_launch(x, weight.detach(), None if bias is None else bias.detach(), act, compact, parity, weight_src=weight,
+                        frozen_parity=frozen_parity if compact == 2 else None)
 
 
 def conv_affine_split16(h16, weight, bias, x_active, log0, parity, inverse, lattice, out=None):

@@ -307,6 +307,283 @@ __global__ __launch_bounds__(512, 2) void conv_c2_kernel(ConvArgs A) {
   }
 }
 
+// ---- the parity-compact instance.  The layer's input is the frozen half of a checkerboard: in a lattice row whose other three
+// coordinates sum to parity rho only the sites of parity e = phi ^ rho along the fastest axis are non-zero (phi = parity of
+// the frozen sites' coordinate sum).  Of the four taps (sites 2p - 1 .. 2p + 2) of a two-site column exactly two are frozen
+// sites, 2p - e and 2p - e + 2, so K = 27 kernel rows x 2 live taps = 54 -> 2 slices, 6 MFMAs per tile.  The kernel loads
+// frozen sites only: whatever stands at the other sites is never read.
+//
+// Shape: conv_c2_kernel's (persistent workgroups of 8 waves, 4 x 4 cross-section, 4-plane LDS ring, tiles w and w + 8 per
+// wave, epilogue from the accumulators), with these differences:
+//  * LDS holds, per halo row, 16 WINDOWS of 8 bytes (the hi and the lo image of a row side by side): window p = {hi(2p - e), hi(2p - e + 2), lo(2p - e), lo(2p - e + 2)},
+//    e the row's own frozen parity.  A lane reads the window of its pair, whatever e is: ONE ds_read_b64 per kernel row
+//    gives the hi and the lo half of a k-group's two taps, at an address that depends on neither e nor the tile.  Which taps
+//    the two values are (t = 1 - e + 2 t') is in the WEIGHTS: two fragment sets, sigma = (output row parity) ^ phi.
+//  * K index = 2 r + t'; slice sl, k-group g: kernel rows 16 sl + 4 g + h, h = 0..3.
+//  * The march is unrolled by the ring length, so ring slots are constants, and because L2 is even sigma alternates with the
+//    unrolled step: the lane's 8 window addresses per ring phase are computed once per kernel (tile offset folded in, the
+//    second tile is an immediate offset), the weight set is picked at compile time.  No address arithmetic per step.
+//  * Staging is one window per thread: two loads (frozen sites only), split, one ds_write_b64: 576 windows = one pass of the
+//    workgroup + one wave.  The parity of the plane being staged is a constant of the unrolled step too.
+// Banks (ds_read_b64: lanes 0-31 and 32-63 are serviced separately, bank = dword address mod 64): the 16 lanes of a
+// k-group read 16 consecutive windows = 32 consecutive dwords, so the two k-groups of a half-wave are conflict-free exactly
+// when their rows lie 32 (mod 64) dwords apart.  Kernel rows r and r + 4 (k-groups g and g + 1) differ by (j0, j1, j2) +=
+// (0, 1, 1), (1, -2, 1), (0, 2, -2) or (1, -1, -2).  Because slots 4 and 5 mirror 0 and 1 the slot difference is the j2
+// difference, never wrapped, and the four conditions on the pitches P (j1), R (j0), Q (plane), in dwords mod 64,
+//   P + Q = 32,  R - 2P + Q = 32,  2P - 2Q = 32,  R - P - 2Q = 32
+// have the solution P = 40, R = Q = 56: rows of 160 bytes (128 + 32 pad), 6 rows + 32 bytes per z0 group (248 dwords),
+// 6 groups + 160 bytes per plane (1528 dwords).  Padding rows read the address of the k-group beside them (a broadcast).
+namespace c3 {
+constexpr int ROWB = 160;                     // 16 windows x 8 bytes + 32 pad (P = 40 dwords)
+constexpr int H1 = 6, NROWS = 36;             // (4 + 2) x (4 + 2) halo rows of a plane
+constexpr int Z0B = H1 * ROWB + 32;           // a group of 6 rows with one z0 (R = 248 dwords)
+constexpr int PLANE = H1 * Z0B + 160;         // 6112 B (Q = 1528 dwords)
+constexpr int NPL = 4;                        // ring: planes z-1, z, z+1 being read + one being written
+constexpr int LDS_BYTES = (NPL + 2) * PLANE;  // 36672: slots 0 and 1 are MIRRORED at 4 and 5, so that ring phase k reads slots k .. k + 2 unwrapped
+constexpr int T1OFF = 2 * Z0B;                // tile w + 8 lies two rows of the cross-section (z0) beyond tile w
+constexpr int NFRAG_DENSE = 8, NFRAG = 16;    // fragments (64 lanes x 8 halfs) of the blob: dense, then [sigma][slice][hi|lo]
+static_assert((ROWB / 4) % 64 == 40 && (Z0B / 4) % 64 == 56 && (PLANE / 4) % 64 == 56, "the conflict-free pitches");
+}  // namespace c3
+
+template <int V>
+struct IntC { static constexpr int value = V; };
+
+__global__ __launch_bounds__(512, 2) void conv_c3_kernel(ConvArgs A) {
+  using namespace c3;
+  extern __shared__ __align__(16) unsigned char smem_c3[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = lane >> 4, p = lane & 15;
+  const int n0 = A.L[0] >> 2, n1 = A.L[1] >> 2, ncol = n0 * n1;
+  const int L2 = A.L[2], L3 = A.L[3];
+  const int RB = L3 * 32, HB = L3 * 16;                    // bytes of an output row of the pair tensor / of its hi block
+  const int seg_n = L3 >> 5;                               // full segments only
+  const int phi = A.parity;
+  const int total = int(A.nitems);                         // B * ncol * seg_n columns
+  const int nwg = gridDim.x;
+  if (int(blockIdx.x) >= total) return;
+  const int ncols_my = (total - int(blockIdx.x) + nwg - 1) / nwg;
+  auto decode = [&](int ci, int &b, int &i0, int &i1, int &hs) {
+    int gc = int(blockIdx.x) + ci * nwg;
+    hs = gc % seg_n;
+    gc /= seg_n;
+    b = gc / ncol;
+    const int c = gc - b * ncol;
+    i0 = c / n1;
+    i1 = c - i0 * n1;
+  };
+
+  // ---- my tiles: rows (z0, z1) = (wave >> 2, wave & 3) and (z0 + 2, z1) of the cross-section: the same row parity.  A column's
+  // origin is a multiple of 4 in both axes and L2 is even, so sigma of output plane z is sigma0 ^ (z & 1), and z = e (mod 2)
+  // for ring entry e (EPC is even): even steps of the unrolled march use the fragments of sigma0, odd steps the others.
+  const int wz0 = wave >> 2, wz1 = wave & 3;
+  const int sigma0 = (wz0 + wz1 + phi) & 1;
+  f16x8 wh[2][2], wl[2][2];                    // [step parity][slice]
+  {
+    const f16x8 *__restrict__ wsp = static_cast<const f16x8 *>(A.wfrag) + NFRAG_DENSE * 64 + lane;
+#pragma unroll
+    for (int sp = 0; sp < 2; ++sp)
+#pragma unroll
+      for (int sl = 0; sl < 2; ++sl) {
+        const int f = ((sigma0 ^ sp) * 2 + sl) * 2;
+        wh[sp][sl] = wsp[f * 64];
+        wl[sp][sl] = wsp[(f + 1) * 64];
+      }
+  }
+  float bv4[4], kc0[4];                        // bias of the four channels this lane ends up with: 4 (g & 1) + r
+#pragma unroll
+  for (int r = 0; r < 4; ++r) bv4[r] = A.bias ? static_cast<const float *>(A.bias)[4 * (g & 1) + r] : 0.f;
+  const bool is_tanh = A.act != kActSigmoid;
+  const float kcs = is_tanh ? 2.885390081777927f : -1.4426950408889634f;       // 2 log2(e) / -log2(e)
+  const float kal = is_tanh ? -2.0f : 1.0f, kga = is_tanh ? 1.0f : 0.0f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) kc0[r] = kcs * bv4[r];
+  const float kc1 = kcs * c2::kInvWScale;
+
+  // ---- window addresses of tile w in ring phase 0: [slice][h]: plane slot j2, halo row (z0 + j0, z1 + j1), window p; phase k
+  // = e & 3 reads k planes further on (slots 4, 5 mirror 0, 1): an immediate offset
+  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+  typedef __attribute__((address_space(3))) const u32x2 lds_win_t;
+  unsigned wadr[2][4];                         // LDS addresses
+#pragma unroll
+  for (int sl = 0; sl < 2; ++sl)
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      int r = 16 * sl + 4 * g + h;
+      r = r < 27 ? r : (r == 27 ? 26 : (r - 4 < 26 ? r - 4 : 26));     // padding rows (zero weights): the row the k-group beside reads
+      const int j0 = r / 9, j1 = (r / 3) % 3, j2 = r % 3;
+      wadr[sl][h] = unsigned(size_t((__attribute__((address_space(3))) unsigned char *)smem_c3)) +
+                    unsigned(j2 * PLANE + (wz0 + j0) * Z0B + (wz1 + j1) * ROWB + 8 * p);
+    }
+
+  // ---- staging: thread -> window wid = tid (and 512 + tid for wave 0) of the plane: halo row wid >> 4, window wid & 15.
+  // soff[q][plane parity][j]: byte offset in the sample of the window's two sites; row parity e = phi ^ (x0 + x1 + x2) & 1
+  const float *__restrict__ inb = static_cast<const float *>(A.in);
+  const bool second = wave == 0;               // windows 512 .. 575
+  unsigned soff[2][2][2];
+  float sv[2][2] = {{0.f, 0.f}, {0.f, 0.f}};   // loads in flight
+  auto open_stage_column = [&](int ci, const float *&base) {
+    int b, i0, i1, hs;
+    decode(ci, b, i0, i1, hs);
+    base = inb + int64_t(b) * A.V;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int wid = q * 512 + int(threadIdx.x);
+      const int row = wid >> 4, pw = wid & 15;
+      const int hz0 = row / H1, hz1 = row - hz0 * H1;       // (row < 36 for the windows that exist; others are never loaded)
+      int x0 = 4 * i0 + hz0 - 1, x1 = 4 * i1 + hz1 - 1;
+      x0 = x0 < 0 ? x0 + A.L[0] : (x0 >= A.L[0] ? x0 - A.L[0] : x0);
+      x1 = x1 < 0 ? x1 + A.L[1] : (x1 >= A.L[1] ? x1 - A.L[1] : x1);
+      const int rowbase = (x0 * A.L[1] + x1) * (L2 * L3);
+#pragma unroll
+      for (int pp = 0; pp < 2; ++pp) {
+        const int e = (phi + hz0 + hz1 + pp) & 1;           // (x0 + x1 = hz0 + hz1 mod 2: origins and extents are even)
+        int s0 = c2::SEG * hs + 2 * pw - e, s1 = s0 + 2;
+        s0 = s0 < 0 ? s0 + L3 : s0;
+        s1 = s1 >= L3 ? s1 - L3 : s1;
+        soff[q][pp][0] = unsigned(rowbase + s0) * 4u;       // < 2^31: checked by the launcher
+        soff[q][pp][1] = unsigned(rowbase + s1) * 4u;
+      }
+    }
+  };
+  unsigned sdst[2];                            // the window's byte offset in a plane
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int wid = q * 512 + int(threadIdx.x), row = wid >> 4;
+    sdst[q] = unsigned((row / H1) * Z0B + (row % H1) * ROWB + (wid & 15) * 8);
+  }
+  auto stage_issue = [&](const float *base, int x2, int pp) {      // plane x2 (parity pp) of the staging column -> registers
+    const int z = x2 < 0 ? x2 + L2 : (x2 >= L2 ? x2 - L2 : x2);
+    const unsigned char *pb = reinterpret_cast<const unsigned char *>(base + z * L3);
+    sv[0][0] = *reinterpret_cast<const float *>(pb + soff[0][pp][0]);
+    sv[0][1] = *reinterpret_cast<const float *>(pb + soff[0][pp][1]);
+    if (second) {
+      sv[1][0] = *reinterpret_cast<const float *>(pb + soff[1][pp][0]);
+      sv[1][1] = *reinterpret_cast<const float *>(pb + soff[1][pp][1]);
+    }
+  };
+  auto stage_commit = [&](int slot) {          // registers -> windows of ring plane `slot`
+    unsigned char *ph = smem_c3 + slot * PLANE;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (q == 0 || second) {
+        f16x4 w;
+        w[0] = static_cast<_Float16>(sv[q][0]);
+        w[1] = static_cast<_Float16>(sv[q][1]);
+        w[2] = static_cast<_Float16>(sv[q][0] - static_cast<float>(w[0]));
+        w[3] = static_cast<_Float16>(sv[q][1] - static_cast<float>(w[1]));
+        *reinterpret_cast<f16x4 *>(ph + sdst[q]) = w;
+        if (slot < 2) *reinterpret_cast<f16x4 *>(ph + NPL * PLANE + sdst[q]) = w;       // the mirror
+      }
+    }
+  };
+
+  // ---- epilogue addressing: lane (p, g) ends up with channels 4 (g & 1) .. + 3 of site 2 q + (g >> 1), q = 16 hs + p its pair
+  unsigned char *__restrict__ outb = static_cast<unsigned char *>(A.out);
+  const int64_t sampleB = A.V * 32;
+  unsigned char *orow[2] = {nullptr, nullptr};   // (wave-uniform) output row of my tiles at the plane being computed
+  unsigned lane_o = 0;
+  auto open_column = [&](int ci) {
+    int b, i0, i1, hs;
+    decode(ci, b, i0, i1, hs);
+    lane_o = unsigned(pair_row_offset(2 * (16 * hs + p) + (g >> 1), L3) + (g & 1) * 8);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+      orow[t] = outb + int64_t(b) * sampleB + int64_t(((4 * i0 + wz0 + 2 * t) * A.L[1] + 4 * i1 + wz1) * L2) * RB;
+  };
+
+  // ---- the march (conv_c2_kernel's: ring entry e = plane (e mod EPC) - 1 of my column e / EPC, slot e & 3; iteration e multiplies
+  // the output plane whose window is entries e .. e + 2 when they belong to one column, commits entry e + 3 and issues the
+  // loads of entry e + 4), unrolled by 4.  EPC is even: entry n is a plane of parity (n + 1) & 1.
+  const int EPC = L2 + 2;
+  const int nent = ncols_my * EPC;
+  int sci = 0, spl = -1;                       // staging cursor: column, plane
+  const float *sbase = nullptr;
+  auto stage_advance = [&]() {
+    if (++spl > L2) {
+      spl = -1;
+      if (++sci < ncols_my) open_stage_column(sci, sbase);
+    }
+  };
+  open_stage_column(0, sbase);
+  stage_issue(sbase, spl, 1); stage_commit(0); stage_advance();      // entries 0, 1, 2 (EPC >= 4: the same column)
+  stage_issue(sbase, spl, 0); stage_commit(1); stage_advance();
+  stage_issue(sbase, spl, 1); stage_commit(2); stage_advance();
+  bool stage_live = sci < ncols_my;            // entry 3 exists
+  if (stage_live) stage_issue(sbase, spl, 0);
+  lds_barrier();
+
+  int cci = 0, pl = -1;                        // the column and plane of entry e
+  open_column(0);
+  auto step = [&](auto kc) {
+    constexpr int k = decltype(kc)::value;     // e & 3
+    const bool compute = pl <= L2 - 2;         // window planes pl, pl+1, pl+2 inside the column: output plane z = pl + 1
+    f32x4 am[2], ac[2];
+    if (compute) {
+      am[0] = am[1] = ac[0] = ac[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+      __builtin_amdgcn_s_setprio(2);           // four waves share a SIMD: the one that multiplies issues first
+#pragma unroll
+      for (int sl = 0; sl < 2; ++sl) {         // (slice-major: the two tiles' windows of a kernel row come with one read)
+        union { f16x8 v; unsigned w[4]; } fh[2], fl[2];
+#pragma unroll
+        for (int h = 0; h < 4; ++h)
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            const u32x2 win = *(lds_win_t *)(wadr[sl][h] + unsigned(k * PLANE + t * T1OFF));
+            fh[t].w[h] = win.x;
+            fl[t].w[h] = win.y;
+          }
+        // weights as the A operand, site pairs as the B operand: D[m][pair] puts the four channels 4 (g & 1) .. + 3 of one
+        // site (2p + (g >> 1)) into each lane (conv_c2_kernel)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          am[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[k & 1][sl], fh[t].v, am[t], 0, 0, 0);
+          ac[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[k & 1][sl], fh[t].v, ac[t], 0, 0, 0);
+          ac[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[k & 1][sl], fl[t].v, ac[t], 0, 0, 0);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
+    // entry e + 3 (loaded an iteration ago) goes into the ring slot nobody reads; the loads of entry e + 4 are issued
+    if (stage_live) {
+      stage_commit((k + 3) & (NPL - 1));
+      stage_advance();
+      stage_live = sci < ncols_my;
+      if (stage_live) stage_issue(sbase, spl, (k + 1) & 1);
+    }
+    if (compute) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        f16x4 hi, lo;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float a = am[t][r] + ac[t][r];
+          const float v = act_affine_c(a, kc1, kc0[r], kal, kga);
+          const _Float16 h0 = static_cast<_Float16>(v);
+          hi[r] = h0;
+          lo[r] = static_cast<_Float16>(v - static_cast<float>(h0));
+        }
+        unsigned char *d = orow[t] + lane_o;
+        *reinterpret_cast<f16x4 *>(d) = hi;
+        *reinterpret_cast<f16x4 *>(d + HB) = lo;
+        orow[t] += RB;                         // the next plane of the column
+      }
+    }
+    lds_barrier();                             // entry e + 3 is complete; entry e's slot is free
+    if (++pl > L2) {                           // entry e + 1 opens the next column
+      pl = -1;
+      if (++cci < ncols_my) open_column(cci);
+    }
+  };
+  for (int e = 0; e < nent; e += 4) {          // nent is even
+    step(IntC<0>{});
+    step(IntC<1>{});
+    if (e + 2 >= nent) break;
+    step(IntC<2>{});
+    step(IntC<3>{});
+  }
+}
+
 }  // namespace nf
 
 using namespace nf;
@@ -315,6 +592,8 @@ using namespace nf;
 // an activation that keeps |out| <= 1.
 extern "C" int nf_conv_first_split16_supported(const int32_t *lattice, const int32_t *ksize, int cout, int act) {
   if (!nf::option(NF_OPT_SPLIT16) || !lattice || !ksize || cout != 8) return 0;
+  if ((act & NF_FIRST_FROZEN_EVEN) && (act & NF_FIRST_FROZEN_ODD)) return 0;
+  act &= ~(NF_FIRST_FROZEN_EVEN | NF_FIRST_FROZEN_ODD | NF_FIRST_FRAGS(NF_FIRST_FRAGS_MAX));
   if (act != kActTanh && act != kActSigmoid) return 0;
   for (int mu = 0; mu < 4; ++mu)
     if (ksize[mu] != 3) return 0;
@@ -328,7 +607,29 @@ extern "C" int nf_conv_first_split16(const void *in, const void *wsplit, const v
   const int32_t k3[4] = {3, 3, 3, 3};
   NF_REQUIRE(nf_conv_first_split16_supported(lattice, k3, 8, act), "nf_conv_first_split16: layer not supported (needs a fastest axis of 32 + 16 n sites, even other extents, tanh / sigmoid)");
   NF_REQUIRE(B >= 0 && B <= 65535, "nf_conv_first_split16: batch outside [0, 65535]");
+  // the frozen-parity flags: the caller states that only the sites of one coordinate-sum parity are non-zero
+  const bool frozen = (act & (NF_FIRST_FROZEN_EVEN | NF_FIRST_FROZEN_ODD)) != 0;
+  const int phi = (act & NF_FIRST_FROZEN_ODD) ? 1 : 0;
+  const int nfrag = (act >> 16) & NF_FIRST_FRAGS_MAX;
+  act &= 0xff;
+  NF_REQUIRE(!frozen || nfrag >= c3::NFRAG,
+             "nf_conv_first_split16: a frozen-parity flag needs the weight blob with the parity fragments (NF_FIRST_FRAGS(16))");
   if (B == 0) return NF_OK;
+  if (frozen && lattice[3] % 32 == 0 && lattice[0] % 4 == 0 && lattice[1] % 4 == 0) {
+    // the parity-compact instance: full segments, the 4 x 4 cross-section
+    ConvArgs A{};
+    A.in = in; A.wfrag = wsplit; A.bias = bias; A.out = out16;
+    set_lattice_k3(A, lattice);
+    A.cin = 1; A.cout = 8; A.act = act; A.parity = phi;
+    A.box[0] = A.box[1] = 4;
+    A.nitems = B * int64_t(lattice[0] / 4) * int64_t(lattice[1] / 4) * int64_t(lattice[3] / 32);
+    NF_REQUIRE(B * A.V < (int64_t(1) << 31), "nf_conv_first_split16: batch x volume >= 2^31 sites, split the batch");
+    NF_REQUIRE(A.V < (int64_t(1) << 29), "nf_conv_first_split16: volume >= 2^29 sites");
+    NF_REQUIRE(cu_count() > 0, "nf_conv_first_split16: no device properties");
+    const int64_t grid = persistent_grid(2, A.nitems, false);
+    hipLaunchKernelGGL(conv_c3_kernel, dim3(unsigned(grid)), dim3(512), c3::LDS_BYTES, stream, A);
+    return check_launch("conv split-fp16 first-layer kernel (frozen parity)");
+  }
   ConvArgs A{};
   A.in = in; A.wfrag = wsplit; A.bias = bias; A.out = out16;
   set_lattice_k3(A, lattice);

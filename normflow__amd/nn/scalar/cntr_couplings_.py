@@ -7,8 +7,9 @@ pair `(x, control)`; `CntrCoupling_` draws the control from a generator in `forw
 
 The control goes to the net exactly as it is given: it is not purified, so the net convolves its values on ALL sites,
 the active ones of the first atom included, and those values change the output, as in the reference.  The kernels
-behind an atom make no assumption about where their net's input vanishes (every first layer is a full convolution of
-its input), so the controlled atom takes the same paths as an ordinary one: the materialising path in fp64 / fp32,
+behind a controlled atom make no assumption about where their net's input vanishes (every first layer is a full
+convolution of its input: `frozen_input_is_masked = False` keeps the parity-compact first layer of the split-fp16 chain,
+which reads the frozen sites only, out of a controlled block), so the controlled atom takes the same paths as an ordinary one: the materialising path in fp64 / fp32,
 the pair-compact logits of `ConvAct.forward_active`, the one-launch small-lattice kernel, the split-fp16 chains, the
 logit-free training node and the per-site densities (tests/test_cntr_couplings.py holds each of them to the oracle
 with a control that is non-zero everywhere).
@@ -39,6 +40,8 @@ class DirectCntrCoupling_(Coupling_):
 
     parts_forward = _Absent()
     parts_backward = _Absent()
+    # net 0 reads the control, which is non-zero on every site: no first layer of this block may skip the active sites
+    frozen_input_is_masked = False
 
     def _as_control(self, control, like):
         """The control as the net takes it: on the field's device and in its dtype, otherwise untouched (not purified);

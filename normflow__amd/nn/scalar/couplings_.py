@@ -117,6 +117,10 @@ class Coupling_(Module_, ABC):
 
     # the block on the two parts of the field (`ModuleList_` chains consecutive blocks over one partition through these,
     # without the cat / split passes in between)
+    # An atom's x_frozen is the frozen half of the field: zero off the frozen partition.  A block whose nets read something
+    # else there (a control field: cntr_couplings_.py) says so, and its first layers read every site.
+    frozen_input_is_masked = True
+
     def parts_forward(self, parts, log0=0):
         for k, net in enumerate(self.nets):
             p = k % 2
@@ -170,6 +174,16 @@ class Coupling_(Module_, ABC):
         if not getattr(self.mask, 'pairable', False) or not hasattr(self.mask, 'checkerboard_parity'):
             return None
         return self.mask.checkerboard_parity(parity)
+
+    def _frozen_parity(self, parity):
+        """The coordinate-sum parity of the FROZEN sites of partition `parity` when the net's input is known to be zero off
+        them: x_frozen is the frozen half (`frozen_input_is_masked`: not a control field), the mask is a plain even-odd one
+        and `preprocess_fz` is the stock one (a subclass may put values on the active sites); else None.  Lets the first layer
+        of a split-fp16 chain read the frozen half only."""
+        a = self._pair_parity(parity)
+        if not self.frozen_input_is_masked or a is None or type(self).preprocess_fz is not Coupling_.preprocess_fz:
+            return None
+        return 1 - int(a)
 
     def _check_density(self):
         if self.propagate_density:
@@ -325,7 +339,8 @@ class AffineCoupling_(Coupling_):
         lattice = tuple(x_frozen.shape[1:])
         for b0, b1 in self._hidden_slabs(v, hidden):
             xf = x_frozen[b0:b1]
-            got = net.hidden_and_last(self.preprocess_fz(xf.float() if xf.dtype == torch.float16 else xf), last_kind='affine')
+            got = net.hidden_and_last(self.preprocess_fz(xf.float() if xf.dtype == torch.float16 else xf), last_kind='affine',
+                                      frozen_parity=self._frozen_parity(parity))
             if got is None:
                 return None
             h16, last, unit, split = got
@@ -420,7 +435,9 @@ class RQSplineCoupling_(Coupling_):
             planned = net._fuse_plan(xin) if hasattr(net, '_fuse_plan') else None
             if planned is not None and not any_kernel and not planned[4]:
                 return None                    # this knots_len is fused by the split-fp16 chain only, and the stack does not run it
-            got = net.hidden_and_last(xin, planned=planned) if planned is not None else net.hidden_and_last(xin)
+            fzp = self._frozen_parity(parity)
+            got = (net.hidden_and_last(xin, planned=planned, frozen_parity=fzp) if planned is not None
+                   else net.hidden_and_last(xin, frozen_parity=fzp))
             if got is None:
                 return None
             h, last, unit, split = got

@@ -204,10 +204,12 @@ class ConvAct(torch.nn.Sequential):
         chain = split and self._split16_chain(x, plan)
         return plan, x, unit, split, chain
 
-    def hidden_and_last(self, x, last_kind='rqs', planned=None):
+    def hidden_and_last(self, x, last_kind='rqs', planned=None, frozen_parity=None):
         """(hidden activations after all but the last conv, last conv module, |hidden| <= 1?, pair tensor?) when the stack
         maps onto the MFMA kernel and the last layer has no activation; else None.  Lets a coupling fuse the last layer
-        with its own kernel: last_kind = 'rqs' (nf_conv_rqs) or 'affine' (nf_conv_affine_split16: only the split-fp16 chain)."""
+        with its own kernel: last_kind = 'rqs' (nf_conv_rqs) or 'affine' (nf_conv_affine_split16: only the split-fp16 chain).
+        frozen_parity (0 / 1): the caller states that x is zero off the sites of that coordinate-sum parity; the first layer of
+        a split-fp16 chain then reads those sites only (`_hip.conv_first_split16`)."""
         got = planned if planned is not None else self._fuse_plan(x, last_kind)
         if got is None:
             return None
@@ -221,7 +223,8 @@ class ConvAct(torch.nn.Sequential):
                 x = _hip.conv_layer_split16(x, conv.weight, conv.bias, act, lat)
             else:
                 x = _hip.conv_layer(x, conv.weight, conv.bias, act,
-                                    compact=2 if ((chain and n == 0) or (split and last_hidden)) else False)
+                                    compact=2 if ((chain and n == 0) or (split and last_hidden)) else False,
+                                    frozen_parity=frozen_parity if (chain and n == 0) else None)
         return x, plan[-1][0], unit, split
 
     def small3d_plan(self):

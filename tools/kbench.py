@@ -24,6 +24,20 @@ if a.only == "k2":
 if a.only in ("g", "c"):
     oth = bench.time_hidden_layers(cpl, lattice, dev, a.reps, a.batch)
     print(f"[kbench {a.tag}] K5g {oth[1]['launch_ms']:.3f} ms  K5c {oth[0]['launch_ms']:.3f} ms", flush=True)
+    if a.only == "c":
+        # the parity-compact instance of K5c on the same slab: the frozen half of a checkerboard and the flag (the dense
+        # instance above is fed a dense random field, as in bench.py)
+        from normflow__amd import _hip
+        slab = oth[0]["slab_batch"]
+        c0 = [mod for mod in cpl.nets[0] if any(True for _ in mod.parameters())][0]
+        g = torch.Generator(device=dev).manual_seed(97)
+        x = torch.randn((slab, 1) + lattice, device=dev, dtype=torch.float32, generator=g)
+        phi = 1
+        xm = cpl.mask.purify(x.squeeze(1), 1 if cpl.mask.checkerboard_parity(1) == phi else 0).unsqueeze(1).contiguous()
+        w, b, tanh = c0.weight.detach(), c0.bias.detach(), _hip.ACT_CODES['tanh']
+        ms_d = bench._events_ms(lambda: _hip.conv_first_split16(xm, w, b, tanh), a.reps)
+        ms_c = bench._events_ms(lambda: _hip.conv_first_split16(xm, w, b, tanh, frozen_parity=phi), a.reps)
+        print(f"[kbench {a.tag}] K5c on the masked field: dense {ms_d:.3f} ms  parity-compact {ms_c:.3f} ms", flush=True)
     sys.exit(0)
 ft = bench.time_fused_last_layer(cpl, lattice, 16, dev, a.reps, a.batch)
 if a.only == "h":
