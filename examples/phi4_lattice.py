@@ -23,8 +23,10 @@ DistConvertor_), or a stack of RQ-spline couplings, assembled from the same name
                                                           run both ways: from the one sign assignment the sweeps left, and
                                                           averaged over all of them (the cluster-improved estimators)
     python examples/phi4_lattice.py --lat 8,8 --hmc --cluster --improved --correlator    that, and G(t) and m_eff(t) both ways
+    python examples/phi4_lattice.py --lat 8,8 --hmc --cluster --improved --modes         that, and G(p) off the axes and m_eff of G(t; p = (1, 0, ...))
 """
 import argparse
+import math
 import os
 import sys
 
@@ -33,7 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))) 
 import normflow__amd as nf          # the reference:  import normflow as nf
 from normflow__amd.action import ScalarPhi4Action
 from normflow__amd.lib import Ensemble, fmt_val_err
-from normflow__amd.lib.observables import ImprovedEnsemble
+from normflow__amd.lib.observables import ImprovedEnsemble, correlator_modes, measure_modes
 from normflow__amd.mask import EvenOddMask
 from normflow__amd.nn import (AffineCoupling_, ConvAct, DistConvertor_, FFTNet_, MeanFieldNet_, ModuleList_,
                               PSDBlock_, RQSplineCoupling_)
@@ -115,12 +117,41 @@ def correlators(m, n_chains, drop):
     return "\n".join(lines)
 
 
+def example_modes(lat):
+    """(off-axis momenta, the spatial momentum (1, 0, ...), the L momenta of its correlator along axis 0)."""
+    d = len(lat)
+    off = [n for n in ((1, 1) + (0,) * (d - 2), (1, 2) + (0,) * (d - 2), (2, -1) + (0,) * (d - 2), (2, 2) + (0,) * (d - 2),
+                       (1,) * d) if d >= 2]
+    spatial = ((1,) + (0,) * (d - 2)) if d >= 2 else ()
+    return list(dict.fromkeys(off)), spatial, correlator_modes(lat, 0, spatial)
+
+
+def off_axis(m, y, lat, n_chains, drop):
+    """G(p) = <|phi~(p)|^2> / V against phat^2 = sum_mu 4 sin^2(pi n_mu / L_mu) at a few off-axis momenta, and m_eff of the
+    time-slice correlator at the spatial momentum (1, 0, ...): cluster-improved (`m.improved`, measured with modes) next to
+    plain (`measure_modes` of the rows `y` with one cluster: the same kernel, the same fixed point)."""
+    off, spatial, _ = example_modes(lat)
+    ie = ImprovedEnsemble(m.improved, n_chains=n_chains, drop=drop)
+    pe = ImprovedEnsemble(measure_modes(y, m.improved.modes), n_chains=n_chains, drop=drop)
+    (ig, ige), (pg, pge) = ie.mode_propagator(), pe.mode_propagator()
+    lines = ["   n             phat^2    G(p)                    improved G(p)"]
+    for i, n in enumerate(off):
+        phat2 = sum(4 * math.sin(math.pi * k / L) ** 2 for k, L in zip(n, lat))
+        lines.append("   %-12s  %7.4f   %-23s %s" % (n, phat2, fmt_val_err(pg[i].item(), pge[i].item()), fmt_val_err(ig[i].item(), ige[i].item())))
+    (ims, imse), (pms, pmse) = ie.mode_effective_mass(0, spatial), pe.mode_effective_mass(0, spatial)
+    lines.append("   t   m_eff(t) of G(t; p = %s)   improved" % (spatial,))
+    for t in range(1, lat[0] // 2 + 1):
+        if t <= len(ims):
+            lines.append("  %2d   %-23s %s" % (t, fmt_val_err(pms[t - 1].item(), pmse[t - 1].item()), fmt_val_err(ims[t - 1].item(), imse[t - 1].item())))
+    return "\n".join(lines)
+
+
 # trajectories of length 1 at about the same cost in force evaluations: n_md of each integrator, dt = 1 / n_md
 INTEGRATOR_N_MD = dict(leapfrog=10, omelyan=5, omf4=2)
 
 
 def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False, integrator='leapfrog', correlator=False,
-                     spectrum_path=None, fourier=None, fourier_path=None):
+                     spectrum_path=None, fourier=None, fourier_path=None, modes=False):
     """<phi^2> of the trained flow + Metropolis next to hybrid Monte Carlo on the action itself (exact up to its own
     statistical error; the first quarter of every chain is dropped as thermalisation), then the observables of both.
     `cluster`: also model.hmc with a Swendsen-Wang sweep of the signs before every recorded step (cluster_every=1), so
@@ -153,12 +184,19 @@ def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False
               % (*phi2(y, n_chains, rows // 4), model.hmc.history.accept_rate[-1], big))
         print("model.hmc, cluster_every=1   " + observables(model, y, n_chains, rows // 4))
         if improved:
+            lat = tuple(model.prior.shape)
+            lst = (lambda off, spatial, along: off + along)(*example_modes(lat)) if modes and len(lat) >= 2 else None
             m = model.hmc.measure(n_chains * rows, cluster_every=1, improved=True, momenta='all' if correlator else None,
-                                  spectrum_path=spectrum_path if correlator else None, **hmc)
+                                  spectrum_path=spectrum_path if correlator else None, modes=lst, return_rows=lst is not None,
+                                  **hmc)
+            if lst is not None:
+                m, y = m
             print("model.hmc, cluster_every=1, the next %d steps both ways (sweeps and steps coincide: drop = 0)" % rows)
             print(both_ways(m, n_chains, 0))
             if correlator:
                 print(correlators(m, n_chains, 0))
+            if lst is not None:
+                print(off_axis(m, y, lat, n_chains, 0))
 
 
 def ladder_scan(lat, m_sq, lambd, kappas, replicas=32, steps=600, cluster=False):
@@ -216,6 +254,9 @@ def main():
     ap.add_argument("--correlator", action="store_true",
                     help="with --hmc --cluster --improved: the time-slice correlator G(t) and the effective mass along axis 0, "
                          "plain and cluster-improved (the sweeps' spectrum at all momenta)")
+    ap.add_argument("--modes", action="store_true",
+                    help="with --hmc --cluster --improved, two or more axes: G(p) against phat^2 at a few off-axis momenta and "
+                         "m_eff of G(t; p = (1, 0, ...)), cluster-improved next to plain (nf_cluster_modes)")
     ap.add_argument("--spectrum-path", choices=("hbm",), default=None,
                     help="with --correlator: take the sweeps' spectrum with nf_cluster_spectrum_tiled (the slots in HBM), the "
                          "kernel for lattices beyond one CU's LDS; default: the one-CU kernel where it applies, else torch ops")
@@ -238,7 +279,7 @@ def main():
         nf.backward_sanitychecker(model)
         if a.hmc:
             compare_with_hmc(model, cluster=a.cluster, improved=a.improved, integrator=a.integrator, correlator=a.correlator, fourier=a.fourier,
-                             spectrum_path=a.spectrum_path, fourier_path=a.fourier_path)
+                             spectrum_path=a.spectrum_path, fourier_path=a.fourier_path, modes=a.modes)
 
 
 if __name__ == "__main__":

@@ -1303,6 +1303,77 @@ int nf_cluster_spectrum_plan(const int32_t *lattice, int dtype, int kmax, nf_spe
 int nf_cluster_spectrum(const void *phi, const int32_t *labels, double *out, int32_t *status, int64_t C,
                         const int32_t *lattice, int kmax, const double *tw, int dtype, void *stream);
 
+/* ---- cluster modes (nf_cluster_modes.hip; MI355X-side extension): the "cluster-improved estimators" above at a LIST of
+ * momentum vectors, on or off the axes: the input of the improved propagator at general momenta and of the time-slice
+ * correlator at non-zero spatial momentum.  It extends that rule and changes nothing of it: the fixed point
+ * q(w) = llrint(w 2^32), the range test, the refusal (status 1, a NaN row, the label check before any indexed access), the
+ * int64 per-cluster sums by integer atomics only, phi cast to double and multiplied ONCE, and the order of a sum of
+ * squares over the V slots (lane l takes the slots l, l + lanes, ... with explicit fma, then the wave shuffle tree, then
+ * the waves in order) hold word for word.  What is new:
+ * Momenta.  A list of P >= 1 integer vectors n = (n_0 .. n_3), padded like the lattice, P <= 512.  The component of an
+ * axis of extent 1 must be 0.  Each component is reduced to 0 .. L_mu - 1, so negative components are legal.
+ * One table.  N = the lcm of the extents > 1; N = 1 (every extent is 1) is refused, and so is N > 65536.  twN is the
+ * caller's (N, 2) doubles; entry j is meant to be (cos, sin)(2 pi j / N), made on the host as math.cos(2.0 * math.pi * j /
+ * N): the formula of the table `tw` above for an axis of extent N.  The kernel uses whatever numbers it is given.
+ * Phase of a site.  j(x) = (sum_mu m_mu x_mu) mod N with m_mu = (n_mu mod L_mu) (N / L_mu), made on the host.  On the
+ * kernel's lattices m_mu < 2^16 and x_mu < 2^14, so the sum is below 2^32: unsigned 32-bit arithmetic cannot overflow.
+ * Per-cluster sums, all int64:
+ *   R_{C,n} = sum_{x in C} q(phi(x) twN[j(x)][0]),  I_{C,n} likewise with [1],  and A_C as above.
+ * Self-conjugate momenta.  A momentum with 2 n_mu = 0 (mod L_mu) on every axis -- the zero momentum and the Nyquist
+ * corners -- has its I LEFT OUT, as at the on-axis Nyquist point: the sine there is 0 or about 1e-16, q of it times any
+ * in-range phi is 0, and the column has the same bits as with it.
+ * The quantities, in order: A, then per momentum in list order R, I (R alone for a self-conjugate momentum):
+ *   Q = 1 + sum_n (2 - [n self-conjugate]).
+ * Outputs.
+ *   out     (C, 2 + P) double: sum_C a^2, sum_C a^4, then per momentum (sum_C r^2) + (sum_C i^2), formed after both sums
+ *           are complete (sum_C r^2 alone for a self-conjugate momentum).
+ *   status  (C) int32, as above; a refused chain's out row is all NaN.
+ * A row's bits depend on the chain, its labels, the lattice, the dtype and -- column by column -- the momentum of the
+ * column alone: not on C, not on the row's place in the batch, not on the other entries of the list or their order, not
+ * on the pass layout.  Consequences:
+ *   1. columns 0 and 1 are nf_cluster_moments' bits;
+ *   2. the zero momentum's column is column 0's bits: the table's entry 0 is exactly (1, 0);
+ *   3. for a momentum on axis mu alone, n = k e_mu, with N / L_mu a power of two, the column is nf_cluster_spectrum's
+ *      column (mu, k) bit for bit: entry j (N / L_mu) of the N-table then equals entry j of the L_mu-table (every lattice
+ *      of equal extents is such a case; (16, 16), (1, 2, 16), (24, 24, 24), (64, 128), (24, 48) were checked).  For other
+ *      ratios the entries may differ in the last bit ((5, 7, 3): 3 entries of the axis of 7; (48, 32): 11 of the axis of
+ *      32) and the columns agree within the rounding bound of the sums only;
+ *   4. the values are invariant under cluster flips bit for bit (q(-w) = -q(w)).
+ * With the signs averaged the column of n is sum_C |sum_{x in C} phi(x) e^{i p x}|^2, p_mu = 2 pi n_mu / L_mu; with ONE
+ * cluster (all labels equal) it is the plain |phi~(p)|^2 in the same fixed point.
+ *
+ * The quantity table.  desc is (Q, 8) int32, one row per quantity (nf_cluster_modes_core.h): m_0 .. m_3, the component
+ * (0 = R, 1 = I), the column, 1 for an R without an I, and the momentum's place in the list; row 0, the quantity A, is
+ * zero but for its last field, the row length 2 + P.  nf_cluster_modes_describe (pure host) makes it from the list, with
+ * Q and N; nf_cluster_modes_check (pure host) holds a HOST copy to the rule: NF_OK iff it is what _describe gives for some
+ * list of momenta.  The launcher itself takes desc and twN as DEVICE pointers owned by the caller and cannot read them
+ * without a synchronising copy, which a graph-capturable call may not make; so it checks Q, N and the lattice on the
+ * host, and the kernel holds every row to the part of the rule that guards memory (m_mu in 0 .. N - 1, the component in
+ * {0, 1}, the column in 2 .. 1 + P, an I right after its R) before it uses a field: with a table that fails, every chain
+ * gets status 1, out is left alone (the row length is the table's own word) and nothing is indexed.
+ *
+ * nf_cluster_modes: the lattices and the structure of nf_cluster_spectrum (one workgroup per chain, nf_phi4_cluster's
+ * lane map, phi and labels read once into registers, the checks before any indexed access, int64 slot arrays in dynamic
+ * LDS filled by 64-bit integer LDS adds, a lane's run of same-label sites as ONE atomic, passes that reuse the arrays, a
+ * 4 KiB reduction region, the carry of a sum r^2 whose sum i^2 falls into the next pass).  A quantity's row of desc is
+ * read with wave-uniform loads; a site's coordinates are taken once.  per_pass = min(Q, 16, (160 KiB - 4 KiB) / 8 V),
+ * passes = ceil(Q / per_pass), lds_bytes = 4096 + per_pass 8 V.  C is 1 .. 65535.  No allocation, no host
+ * synchronisation: graph-capturable.
+ * NF_EINVAL, all before any launch: whatever nf_cluster_moments refuses; NULL desc or twN; Q outside 2 .. 1025; N = 1,
+ * N > 65536 or N not the lattice's lcm.  _describe, _plan and _supported also refuse NULL modes, P outside 1 .. 512 and a
+ * non-zero component on an axis of extent 1; _check refuses every row that is not the rule's, with the row's number.
+ * nf_cluster_modes_plan / _supported: pure host, from the host list. */
+typedef struct nf_modes_plan {
+  int32_t sites_per_lane, lanes, N, columns, quantities, per_pass, passes;
+  int64_t lds_bytes;
+} nf_modes_plan;
+int nf_cluster_modes_supported(const int32_t *lattice, int dtype, const int32_t *modes, int P);
+int nf_cluster_modes_plan(const int32_t *lattice, int dtype, const int32_t *modes, int P, nf_modes_plan *out);
+int nf_cluster_modes_describe(const int32_t *lattice, const int32_t *modes, int P, int32_t *desc, int32_t *Q, int32_t *N);
+int nf_cluster_modes_check(const int32_t *lattice, const int32_t *desc, int Q, int N);
+int nf_cluster_modes(const void *phi, const int32_t *labels, double *out, int32_t *status, int64_t C,
+                     const int32_t *lattice, const int32_t *desc, int Q, const double *twN, int N, int dtype, void *stream);
+
 /* ---- the cluster spectrum with the chains, the labels and the int64 slots in HBM (nf_cluster_spectrum_tiled.hip): for
  * lattices beyond nf_cluster_spectrum's class (32^3, 16^4, 32^4, 48^4, ...).  The "cluster spectrum" rule above holds word
  * for word: the momenta K_mu from kmax; the quantities and their order (A, then per axis in order and per k ascending R,

@@ -123,6 +123,11 @@ PROTOTYPES = {
     "nf_cluster_spectrum_supported": (_I, [C.POINTER(C.c_int32), _I, _I]),
     "nf_cluster_spectrum_plan": (_I, [C.POINTER(C.c_int32), _I, _I, _P]),
     "nf_cluster_spectrum": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _I, _P, _I, _P]),
+    "nf_cluster_modes_supported": (_I, [C.POINTER(C.c_int32), _I, _P, _I]),
+    "nf_cluster_modes_plan": (_I, [C.POINTER(C.c_int32), _I, _P, _I, _P]),
+    "nf_cluster_modes_describe": (_I, [C.POINTER(C.c_int32), _P, _I, _P, _P, _P]),
+    "nf_cluster_modes_check": (_I, [C.POINTER(C.c_int32), _P, _I, _I]),
+    "nf_cluster_modes": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, _I, _I, _P]),
     "nf_cluster_moments_tiled_supported": (_I, [C.POINTER(C.c_int32), _I, _I64]),
     "nf_cluster_moments_tiled_plan": (_I, [C.POINTER(C.c_int32), _I, _I64, _I, _P]),
     "nf_cluster_moments_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I64, _I]),
@@ -2831,6 +2836,160 @@ def cluster_spectrum(phi, labels, momenta='all'):
     _check(load().nf_cluster_spectrum(_ptr(phi), _ptr(labels), _ptr(out), _ptr(status), Cn, _lat4(lat), kmax, _ptr(tw),
                                       _dtype_code(phi), _stream()), "nf_cluster_spectrum")
     return dict(out=out, status=status, momenta=K)
+
+
+# ========================================================================= cluster modes (nf_cluster_modes.hip)
+MODES_MAX = 512                         # momenta of one call
+MODES_MAX_N = 65536                     # the lcm of the extents
+
+
+class ModesPlan(C.Structure):
+    """nf_modes_plan (include/normflow_hip.h)."""
+    _fields_ = [("sites_per_lane", C.c_int32), ("lanes", C.c_int32), ("N", C.c_int32), ("columns", C.c_int32),
+                ("quantities", C.c_int32), ("per_pass", C.c_int32), ("passes", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
+def modes_list(lat, modes):
+    """`modes`, a sequence of P >= 1 integer vectors with one component per axis of `lat`, as a tuple of tuples of ints;
+    anything else is a NormflowHipError.  The components are left as given (`modes_reduced` reduces them)."""
+    lat = tuple(int(n) for n in lat)
+    try:
+        out = tuple(tuple(n for n in m) for m in modes)
+    except TypeError:
+        raise NormflowHipError(f"modes must be a sequence of integer vectors, one component per axis of {lat}, got {modes!r}")
+    if not out:
+        raise NormflowHipError(f"modes must hold at least one momentum, got {modes!r}")
+    for m in out:
+        if len(m) != len(lat) or any(isinstance(n, bool) or not isinstance(n, int) for n in m):
+            raise NormflowHipError(f"modes: every momentum has {len(lat)} integer components on the lattice {lat}, got {m!r}")
+        if any(abs(n) >= 2 ** 31 for n in m):
+            raise NormflowHipError(f"modes: components are 32-bit integers, got {m!r}")
+    return out
+
+
+def modes_reduced(lat, modes):
+    """The momenta with every component reduced to 0 .. L_mu - 1 (the rule's own reduction): a tuple of tuples."""
+    lat = tuple(int(n) for n in lat)
+    return tuple(tuple(n % L for n, L in zip(m, lat)) for m in modes_list(lat, modes))
+
+
+def modes_lcm(lat):
+    """N of the rule: the lcm of the extents (1 where every extent is 1)."""
+    return math.lcm(*[int(n) for n in lat])
+
+
+def _modes_array(lat, modes):
+    """(the (P, 4) int32 array of the padded momenta, P) for the library."""
+    lst = modes_list(lat, modes)
+    flat = [n for m in lst for n in (0,) * (4 - len(lat)) + m]
+    return _c_ints(flat), len(lst)
+
+
+def cluster_modes_supported(lat, dtype, modes):
+    """True if nf_cluster_modes takes chains on the lattice `lat` (1 to 4 extents) in `dtype` at the momenta `modes`: the
+    launcher's own planner, pure host code (the reason for a False is `last_error()`)."""
+    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
+        return False
+    arr, P = _modes_array(lat, modes)
+    return bool(load().nf_cluster_modes_supported(_lat4(lat), _dtype_code_of(dtype), arr, P))
+
+
+def cluster_modes_plan(lat, dtype, modes):
+    """What nf_cluster_modes will do on the lattice `lat` in `dtype` at `modes`: dict(sites_per_lane, lanes, N (the lcm of
+    the extents), columns (2 + P), quantities, per_pass, passes, lds_bytes).  Pure host code."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"cluster_modes_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
+    arr, P = _modes_array(lat, modes)
+    out = ModesPlan()
+    _check(load().nf_cluster_modes_plan(_lat4(lat), _dtype_code_of(dtype), arr, P, C.byref(out)), "nf_cluster_modes_plan")
+    return {name: getattr(out, name) for name, _ in ModesPlan._fields_}
+
+
+def cluster_modes_describe(lat, modes):
+    """nf_cluster_modes_describe: (desc (Q, 8) int32 on the host, N) of the momenta `modes` on `lat`; the rows are laid out
+    in normflow__amd/csrc/nf_cluster_modes_core.h.  Pure host code; the table is checked by nf_cluster_modes_check."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"cluster_modes_describe: lattices of 1 to 4 axes, got {tuple(lat)}")
+    arr, P = _modes_array(lat, modes)
+    desc = torch.zeros((1 + 2 * max(P, 1), 8), dtype=torch.int32, device='cpu')       # host code fills it: never the default device
+    Q, N = C.c_int32(0), C.c_int32(0)
+    _check(load().nf_cluster_modes_describe(_lat4(lat), arr, P, _ptr(desc), C.byref(Q), C.byref(N)),
+           "nf_cluster_modes_describe")
+    desc = desc[:Q.value].clone()
+    _check(load().nf_cluster_modes_check(_lat4(lat), _ptr(desc), Q.value, N.value), "nf_cluster_modes_check")
+    return desc, N.value
+
+
+_MODE_TWIDDLES = {}
+_MODE_DESCS = {}
+_MODE_CALLS = {}                        # (lattice, the list as given, device) -> (reduced, desc, N, twN) of `cluster_modes`
+
+
+def mode_twiddle_table(lat, device=None):
+    """The table twN (N, 2) float64 of nf_cluster_modes for the lattice `lat`, N = the lcm of its extents: row j =
+    (cos, sin)(2 pi j / N), computed once on the host (math.cos / math.sin of the double 2 pi j / N, `twiddle_table`'s
+    formula for an axis of extent N) and cached per (N, device), so that every path uses the same numbers bit for bit."""
+    N = modes_lcm(lat)
+    if not 2 <= N <= MODES_MAX_N:
+        raise NormflowHipError(f"mode_twiddle_table: N, the lcm of the extents of {tuple(lat)}, is {N}: it must be in 2 .. {MODES_MAX_N}")
+    key = (N, None if device is None else str(torch.device(device)))
+    if key not in _MODE_TWIDDLES:
+        if device is not None:
+            _MODE_TWIDDLES[key] = mode_twiddle_table(lat).to(device)
+        else:
+            rows = [(math.cos(2.0 * math.pi * j / N), math.sin(2.0 * math.pi * j / N)) for j in range(N)]
+            _MODE_TWIDDLES[key] = torch.tensor(rows, dtype=torch.float64, device='cpu')
+    return _MODE_TWIDDLES[key]
+
+
+def mode_descriptor(lat, modes, device=None):
+    """(desc (Q, 8) int32, N) of `cluster_modes_describe`, cached per (lattice, reduced momenta, device) like
+    `twiddle_table`; with a device the table lies there."""
+    lat = tuple(int(n) for n in lat)
+    key = (lat, modes_reduced(lat, modes), None if device is None else str(torch.device(device)))
+    if key not in _MODE_DESCS:
+        if device is not None:
+            desc, N = mode_descriptor(lat, modes)
+            _MODE_DESCS[key] = (desc.to(device), N)
+        else:
+            _MODE_DESCS[key] = cluster_modes_describe(lat, modes)
+    return _MODE_DESCS[key]
+
+
+def cluster_modes(phi, labels, modes):
+    """nf_cluster_modes: `cluster_moments` at the momentum vectors `modes` -- a sequence of P <= 512 integer vectors with one
+    component per lattice axis, on or off the axes, negative components allowed -- in ONE launch (C <= 65535).  Returns
+    dict(out (C, 2 + P) float64 = sum_C M_C^2, sum_C M_C^4, then per momentum in list order sum_C |M~_C(p)|^2 with
+    p_mu = 2 pi n_mu / L_mu; status (C) int32, 1 = refused (the out row is NaN); modes = the momenta reduced to
+    0 .. L_mu - 1).  The rule is stated in include/normflow_hip.h, "cluster modes".
+    Graph capture: the launch neither allocates nor synchronises, but the FIRST call for a (lattice, modes, device) copies
+    the twiddle table and the quantity table to the device.  Call this function once (or `mode_twiddle_table(lat,
+    device)` and `mode_descriptor(lat, modes, device)`) before capturing."""
+    _require_device(phi, labels)
+    lat = tuple(phi.shape[1:])
+    if not phi.is_contiguous() or not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"cluster_modes needs contiguous phi (C, *L) with 1 to 4 lattice axes, got {tuple(phi.shape)}")
+    if labels.shape != phi.shape or labels.dtype != torch.int32 or not labels.is_contiguous() or labels.device != phi.device:
+        raise NormflowHipError(f"cluster_modes: labels must be a contiguous int32 tensor {tuple(phi.shape)} on {phi.device}, "
+                               f"got {tuple(labels.shape)} {labels.dtype} on {labels.device}")
+    Cn, dev = phi.shape[0], phi.device
+    # a list seen before costs one dictionary look-up: its validation, reduction and table take tens of microseconds of
+    # Python, more than the kernel's run on a small lattice
+    try:
+        key = (lat, modes if isinstance(modes, tuple) else tuple(modes), dev)
+        hit = _MODE_CALLS.get(key)
+    except TypeError:                                         # momenta given as lists: not hashable, the slow way
+        key = hit = None
+    if hit is None:
+        hit = (modes_reduced(lat, modes),) + mode_descriptor(lat, modes, dev) + (mode_twiddle_table(lat, dev),)
+        if key is not None:
+            _MODE_CALLS[key] = hit
+    reduced, desc, N, tw = hit
+    out = torch.empty((Cn, 2 + len(reduced)), dtype=torch.float64, device=dev)
+    status = torch.empty((Cn,), dtype=torch.int32, device=dev)
+    _check(load().nf_cluster_modes(_ptr(phi), _ptr(labels), _ptr(out), _ptr(status), Cn, _lat4(lat), _ptr(desc),
+                                   desc.shape[0], _ptr(tw), N, _dtype_code(phi), _stream()), "nf_cluster_modes")
+    return dict(out=out, status=status, modes=reduced)
 
 
 # ========================================================================= the same, slots in HBM (nf_cluster_moments_tiled.hip)

@@ -15,7 +15,9 @@ and the on-axis momentum-space propagator |sum_t e^{ipt} S_mu(t)|^2 / V at p = 2
 p_min from the labels of a Swendsen-Wang sweep (`ImprovedMeasurement`, `ImprovedEnsemble`; nf_cluster_moments on the
 device).  With `momenta='all'` it also carries the cluster spectrum (nf_cluster_spectrum), from which the improved
 propagator at every on-axis momentum and the improved time-slice correlator follow; `spectrum_path='hbm'` takes it with
-nf_cluster_spectrum_tiled, the kernel for lattices beyond one CU's LDS.
+nf_cluster_spectrum_tiled, the kernel for lattices beyond one CU's LDS.  With `modes=[(n0, ...), ...]` it carries the
+same sums at a list of momentum vectors, on or off the axes (nf_cluster_modes): `mode_propagator`, `mode_correlator` at a
+spatial momentum, and through `measure_modes(cfgs, modes)` the plain |phi~(p)|^2 from the same kernel.
 
 `Ensemble` reads the rows as (steps, chains) -- row r = step r // C of chain r % C, the layout of model.mcmc,
 model.blocked_mcmc and model.hmc -- and gives every estimate as (value, error): leave-one-chain-out jackknife for
@@ -304,7 +306,7 @@ def route_improved(cfgs):
 
 
 @torch.no_grad()
-def measure_improved(cfgs, labels, path=None, momenta=None, spectrum_path=None, workspace=None):
+def measure_improved(cfgs, labels, path=None, momenta=None, spectrum_path=None, workspace=None, modes=None):
     """(N, *L) configurations and the (N, *L) int32 labels of their cluster decompositions (a Swendsen-Wang sweep's:
     `hmc.cluster(phi)['labels']`, with the field before or after the flip) -> `ImprovedMeasurement`: the averages over
     all 2^Nc assignments of the clusters' signs, in closed form from the clusters' sums M_C (include/normflow_hip.h,
@@ -322,7 +324,14 @@ def measure_improved(cfgs, labels, path=None, momenta=None, spectrum_path=None, 
     the slots in HBM, any lattice on the device (raises on CPU tensors); `out` is then that of path='hbm' bit for bit.
     `workspace`: a uint8 tensor for that kernel (`_hip.cluster_spectrum_tiled`), None: one per call; ValueError where it
     is given without spectrum_path.  Without
-    spectrum_path every call does what it did: path=None beyond one CU stays on the composed path."""
+    spectrum_path every call does what it did: path=None beyond one CU stays on the composed path.
+    modes=[(n0, ..), ...]: P <= 512 integer momentum vectors with one component per axis, on or off the axes, negative
+    components allowed (include/normflow_hip.h, "cluster modes"): the measurement also carries `.modes`, the vectors
+    reduced to 0 .. L_mu - 1, and `.mode_power` (N, P) = sum_C |M~_C(p)|^2 at p_mu = 2 pi n_mu / L_mu, from which
+    `mode_propagator` and `mode_correlator` follow.  It runs on its own: path=None / 'kernel' take nf_cluster_modes where
+    `improved_kernel_applies` (path=None elsewhere: composed), 'composed' is `mcmc.cluster.cluster_modes`, and 'hbm'
+    raises ValueError (there is no HBM form of the modes yet).  `momenta` keeps its meaning beside it; everything else
+    of the measurement, `out` included, is that of the call without `modes` bit for bit."""
     if path not in IMPROVED_PATHS:
         raise ValueError(f"path must be None, 'kernel', 'composed' or 'hbm', got {path!r}")
     if not 1 <= cfgs.ndim - 1 <= 4:
@@ -338,6 +347,29 @@ def measure_improved(cfgs, labels, path=None, momenta=None, spectrum_path=None, 
             raise ValueError("measure_improved: spectrum_path='hbm' is the path of the spectrum: it needs momenta")
         if path not in (None, 'hbm'):
             raise ValueError(f"measure_improved: spectrum_path='hbm' goes with path None or 'hbm', got path={path!r}")
+    if modes is not None:
+        if path == 'hbm':
+            raise ValueError("measure_improved: no modes on path 'hbm' (nf_cluster_modes has no HBM form): use "
+                             "path='composed' for lattices beyond one CU")
+        try:
+            _hip.modes_list(lat, modes)
+        except _hip.NormflowHipError as e:
+            raise ValueError(f"measure_improved: {e}") from None
+    im = _measure_improved(cfgs, labels, path, momenta, spectrum_path, workspace, lat)
+    if modes is not None:
+        if path is None:
+            path = 'kernel' if improved_kernel_applies(cfgs) else 'composed'
+        if path == 'kernel':
+            r = _hip.cluster_modes(cfgs.contiguous(), labels.contiguous(), modes)
+        else:
+            from ..mcmc.cluster import cluster_modes
+            r = cluster_modes(cfgs, labels, modes)
+        im.modes, im.mode_power = r['modes'], r['out'][:, 2:]
+    return im
+
+
+def _measure_improved(cfgs, labels, path, momenta, spectrum_path, workspace, lat):
+    """`measure_improved` without `modes`, its arguments checked."""
     if momenta is not None:
         if path == 'hbm' and spectrum_path is None:
             raise ValueError("measure_improved: no spectrum on path 'hbm' (nf_cluster_moments_tiled has no spectrum form): "
@@ -375,9 +407,11 @@ class ImprovedMeasurement:
         <(sum phi)^2> = sum M_C^2,   <(sum phi)^4> = 3 (sum M_C^2)^2 - 2 sum M_C^4,   <|phi~(p)|^2> = sum_C |M~_C(p)|^2,
     and all three are invariant under the flips: the field before or after the sweep gives the same bits.
     `spectrum` (None, or a list of d tensors (N, K_mu)): the last of the three at p = 2 pi k / L_mu, k = 1 .. K_mu, and
-    `momenta` the K_mu; `propagator` and `correlator` need the full spectrum, K_mu = L_mu // 2 (momenta='all')."""
+    `momenta` the K_mu; `propagator` and `correlator` need the full spectrum, K_mu = L_mu // 2 (momenta='all').
+    `modes` (None, or a tuple of P momentum vectors reduced to 0 .. L_mu - 1) and `mode_power` (N, P): the same sum at
+    p_mu = 2 pi n_mu / L_mu of every listed vector (`measure_improved(..., modes=...)`)."""
 
-    def __init__(self, out, status, lattice, spectrum=None, momenta=None):
+    def __init__(self, out, status, lattice, spectrum=None, momenta=None, modes=None, mode_power=None):
         self.out = out                        # (N, 2 + d): the three below side by side
         self.sum_m2, self.sum_m4c, self.prop1, self.status = out[:, 0], out[:, 1], out[:, 2:], status
         self.lattice = tuple(lattice)
@@ -388,6 +422,10 @@ class ImprovedMeasurement:
             if len(self.spectrum) != len(self.lattice) or momenta != tuple(int(t.shape[1]) for t in self.spectrum):
                 raise ValueError(f"spectrum: one (N, K_mu) tensor per axis of {self.lattice} with K = {momenta}")
         self.momenta = momenta if self.spectrum is not None else None
+        self.modes = None if modes is None else tuple(tuple(int(n) for n in m) for m in modes)
+        self.mode_power = mode_power if self.modes is not None else None
+        if self.modes is not None and (mode_power is None or tuple(mode_power.shape) != (out.shape[0], len(self.modes))):
+            raise ValueError(f"mode_power: one (N, P) tensor for the P = {len(self.modes)} momenta")
 
     @classmethod
     def from_spectrum(cls, row, status, lattice, momenta):
@@ -406,28 +444,34 @@ class ImprovedMeasurement:
     _axes = Measurement._axes
 
     @classmethod
-    def cat(cls, parts, lattice, device, momenta=None):
+    def cat(cls, parts, lattice, device, momenta=None, modes=None):
         """The rows of `parts` (ImprovedMeasurements of one lattice) one after the other; none: an empty one on `device`
-        (with the empty spectrum of `momenta`, the K_mu, where given)."""
+        (with the empty spectrum of `momenta`, the K_mu, and the empty mode_power of `modes`, where given)."""
         if not parts:
             spec = None if momenta is None else [torch.empty((0, K), dtype=torch.float64, device=device) for K in momenta]
+            power = None if modes is None else torch.empty((0, len(modes)), dtype=torch.float64, device=device)
             return cls(torch.empty((0, 2 + len(lattice)), dtype=torch.float64, device=device),
-                       torch.empty((0,), dtype=torch.int32, device=device), lattice, spec, momenta)
+                       torch.empty((0,), dtype=torch.int32, device=device), lattice, spec, momenta, modes, power)
         spec = None
         if parts[0].spectrum is not None:
             spec = [torch.cat([p.spectrum[mu] for p in parts]) for mu in range(len(lattice))]
-        return cls(torch.cat([p.out for p in parts]), torch.cat([p.status for p in parts]), lattice, spec, parts[0].momenta)
+        power = None if parts[0].modes is None else torch.cat([p.mode_power for p in parts])
+        return cls(torch.cat([p.out for p in parts]), torch.cat([p.status for p in parts]), lattice, spec, parts[0].momenta,
+                   parts[0].modes, power)
 
     def rows(self, col):
         """The same rows laid out by `col`: row i goes to row col[i] (the ladder's rung order)."""
         spec = None if self.spectrum is None else [torch.empty_like(t).index_copy_(0, col, t) for t in self.spectrum]
+        power = None if self.modes is None else torch.empty_like(self.mode_power).index_copy_(0, col, self.mode_power)
         return type(self)(torch.empty_like(self.out).index_copy_(0, col, self.out),
-                          torch.empty_like(self.status).index_copy_(0, col, self.status), self.lattice, spec, self.momenta)
+                          torch.empty_like(self.status).index_copy_(0, col, self.status), self.lattice, spec, self.momenta,
+                          self.modes, power)
 
     def pick(self, fn):
         """The measurement of the rows that `fn` picks from every (N, ...) tensor (the ladder's rows of one rung)."""
         spec = None if self.spectrum is None else [fn(t) for t in self.spectrum]
-        return type(self)(fn(self.out), fn(self.status), self.lattice, spec, self.momenta)
+        power = None if self.modes is None else fn(self.mode_power)
+        return type(self)(fn(self.out), fn(self.status), self.lattice, spec, self.momenta, self.modes, power)
 
     def m2(self):
         """<m^2>_signs = sum M_C^2 / V^2."""
@@ -478,6 +522,60 @@ class ImprovedMeasurement:
             cos = torch.cos(2.0 * math.pi * ((k[:, None] * k[None, :]) % L) / L)
             out = out + P @ cos / self.volume ** 2
         return out / len(axes)
+
+
+    def _modes(self, what):
+        if self.modes is None:
+            raise ValueError(f"{what} needs the modes: measure with modes=[(n0, ...), ...]")
+
+    def mode_propagator(self):
+        """(N, P) sum_C |M~_C(p)|^2 / V at the momenta of `modes`, in list order: the improved |phi~(p)|^2 / V."""
+        self._modes('mode_propagator')
+        return self.mode_power / self.volume
+
+    def mode_correlator(self, axis, spatial):
+        """(N, L) the improved time-slice correlator along `axis` at the spatial momentum `spatial` (the components of the
+        other axes, in their order): G(t; p) = (1 / V^2) sum_{k=0}^{L-1} P(k, p) cos(2 pi k t / L) in float64, in
+        `correlator`'s normalisation.  It needs all L momenta of `correlator_modes(lattice, axis, spatial)` among `modes`
+        and raises a ValueError that names the missing ones otherwise."""
+        self._modes('mode_correlator')
+        want = correlator_modes(self.lattice, axis, spatial)
+        have = {m: i for i, m in reversed(list(enumerate(self.modes)))}          # the first place of a repeated momentum
+        missing = [m for m in want if m not in have]
+        if missing:
+            raise ValueError(f"mode_correlator(axis={axis}, spatial={tuple(spatial)}) needs all {len(want)} momenta along "
+                             f"the axis; missing from modes: {missing}")
+        L = len(want)
+        P = torch.stack([self.mode_power[:, have[m]] for m in want], dim=1)
+        k = torch.arange(L, dtype=torch.float64, device=P.device)
+        cos = torch.cos(2.0 * math.pi * ((k[:, None] * k[None, :]) % L) / L)
+        return P @ cos / self.volume ** 2
+
+
+def correlator_modes(lattice, axis, spatial):
+    """The L momenta (k, p) that `mode_correlator(axis, spatial)` needs, k = 0 .. L - 1 along `axis` of `lattice` and
+    the components `spatial` (one per other axis, in their order) elsewhere, reduced to 0 .. L_mu - 1."""
+    lattice = tuple(int(n) for n in lattice)
+    axis = range(len(lattice))[axis]
+    spatial = tuple(spatial)
+    if len(spatial) != len(lattice) - 1 or any(isinstance(n, bool) or not isinstance(n, int) for n in spatial):
+        raise ValueError(f"spatial: {len(lattice) - 1} integer components, those of the axes of {lattice} other than {axis}, "
+                         f"got {spatial!r}")
+    return [tuple(n % L for n, L in zip(spatial[:axis] + (k,) + spatial[axis:], lattice)) for k in range(lattice[axis])]
+
+
+@torch.no_grad()
+def measure_modes(cfgs, modes, labels=None, path=None):
+    """`measure_improved(cfgs, labels, path=path, modes=modes)`: the `ImprovedMeasurement` with `.modes` and `.mode_power`.
+    labels=None is the decomposition into ONE cluster (all labels 0): with it `mode_power` is the plain |phi~(p)|^2 of
+    every row, in the estimators' fixed point and from the same kernel, at momenta that `Measurement.propagator` does not
+    reach.  path=None | 'kernel' | 'composed': None takes nf_cluster_modes where `improved_kernel_applies`, else the
+    composed path."""
+    if path not in (None, 'kernel', 'composed'):
+        raise ValueError(f"path must be None, 'kernel' or 'composed', got {path!r}")
+    if labels is None:
+        labels = torch.zeros(cfgs.shape, dtype=torch.int32, device=cfgs.device)
+    return measure_improved(cfgs, labels, path=path, modes=modes)
 
 
 class ImprovedEnsemble(Ensemble):
@@ -545,3 +643,19 @@ class ImprovedEnsemble(Ensemble):
         """`Ensemble.effective_mass`'s formula on the improved correlator."""
         self._spectral('an effective mass')
         return Ensemble.effective_mass(self, axis, connected, binsize)
+
+    def mode_propagator(self, binsize=1):
+        """<sum_C |M~_C(p)|^2> / V at the momenta of the measurement's `modes`, in list order."""
+        return self.estimate(self.series(self.m.mode_propagator()), binsize=binsize)
+
+    def mode_correlator(self, axis, spatial, binsize=1):
+        """<G(t; p)> improved, t = 0 .. L - 1 (`ImprovedMeasurement.mode_correlator`)."""
+        return self.estimate(self.series(self.m.mode_correlator(axis, spatial)), binsize=binsize)
+
+    def mode_effective_mass(self, axis, spatial, binsize=1):
+        """`Ensemble.effective_mass`'s formula on `mode_correlator(axis, spatial)`: the energy E(p) of the state at the
+        spatial momentum, arccosh((G(t - 1) + G(t + 1)) / (2 G(t))) at t = 1 .. L - 2; NaN where the argument is < 1."""
+        def mass(g):
+            arg = (g[..., :-2] + g[..., 2:]) / (2 * g[..., 1:-1])
+            return torch.where(arg >= 1, torch.acosh(arg.clamp(min=1)), torch.full_like(arg, float('nan')))
+        return self.estimate(self.series(self.m.mode_correlator(axis, spatial)), mass, binsize)

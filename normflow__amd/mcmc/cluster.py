@@ -2,7 +2,8 @@
 of include/normflow_hip.h (section "cluster updates") on any device.  `HMCSampler(cluster_every=E)` uses it for CPU
 tensors and for the device lattices that neither nf_phi4_cluster nor, by TILED_CLASSES, nf_phi4_cluster_tiled is routed
 to; on the device its `u` and `flip` come from nf_phi4_cluster_draws at the positions the kernels would use, so that it
-walks the kernels' chain.  `cluster_moments` is the composed path of the cluster-improved estimators (nf_cluster_moments)."""
+walks the kernels' chain.  `cluster_moments` is the composed path of the cluster-improved estimators (nf_cluster_moments),
+`cluster_spectrum` and `cluster_modes` those of nf_cluster_spectrum and nf_cluster_modes."""
 import torch
 
 PATHS = (None, 'kernel', 'tiled', 'composed')
@@ -167,3 +168,62 @@ def cluster_spectrum(phi, labels, momenta='all'):
     out = torch.stack(cols, dim=1)
     out = torch.where(bad.unsqueeze(1), torch.full_like(out, float('nan')), out)
     return dict(out=out, status=bad.to(torch.int32), momenta=K)
+
+
+def cluster_modes(phi, labels, modes):
+    """The rule of nf_cluster_modes (include/normflow_hip.h, "cluster modes") from torch ops, on any device and any
+    lattice of 1 to 4 axes with V < 2^31 and N = lcm of the extents in 2 .. 65536, fp32 / fp64: the dict of
+    `_hip.cluster_modes`, out (C, 2 + P) float64, status (C) int32, modes (the momenta reduced to 0 .. L_mu - 1).  q, the
+    int64 scatter_add_ and the `sum` in double are those of `cluster_moments`; the phase index
+    j(x) = (sum_mu m_mu x_mu) mod N, m_mu = (n_mu mod L_mu) (N / L_mu), is taken in int64 arithmetic on the table
+    `_hip.mode_twiddle_table`.  The integer sums are the kernel's bit for bit, the doubles agree within rounding.  The
+    sine quantity of a self-conjugate momentum (2 n_mu = 0 mod L_mu on every axis) is left out, as in the kernel.  Nothing
+    is read back from the device."""
+    from .. import _hip
+    C, lat = phi.shape[0], tuple(phi.shape[1:])
+    if not 1 <= len(lat) <= 4:
+        raise ValueError(f"cluster_modes: lattices of 1 to 4 axes, got {lat}")
+    if labels.shape != phi.shape:
+        raise ValueError(f"cluster_modes: labels {tuple(labels.shape)} do not match phi {tuple(phi.shape)}")
+    try:
+        reduced = _hip.modes_reduced(lat, modes)
+    except _hip.NormflowHipError as e:
+        raise ValueError(f"cluster_modes: {e}") from None
+    if len(reduced) > _hip.MODES_MAX:
+        raise ValueError(f"cluster_modes: at most {_hip.MODES_MAX} momenta in one call, got {len(reduced)}")
+    for m, given in zip(reduced, _hip.modes_list(lat, modes)):
+        if any(L == 1 and n != 0 for n, L in zip(given, lat)):
+            raise ValueError(f"cluster_modes: momentum {given}: a non-zero component on an axis of extent 1 of {lat}")
+    N = _hip.modes_lcm(lat)
+    if not 2 <= N <= _hip.MODES_MAX_N:
+        raise ValueError(f"cluster_modes: N, the lcm of the extents of {lat}, is {N}: it must be in 2 .. {_hip.MODES_MAX_N}")
+    V = 1
+    for n in lat:
+        V *= n
+    dev = phi.device
+    x = phi.double().reshape(C, V)
+    lab = labels.reshape(C, V).long()
+    bad = (~(x.abs() < _hip.cluster_moments_limit(V)) | (lab < 0) | (lab >= V)).any(dim=1)
+    x = torch.where(bad.unsqueeze(1), torch.zeros_like(x), x)
+    lab = torch.where(bad.unsqueeze(1), torch.zeros_like(lab), lab)
+    q = lambda w: torch.round(w * 2.0 ** 32).to(torch.int64)
+    slots = lambda w: torch.zeros((C, V), dtype=torch.int64, device=dev).scatter_add_(1, lab, q(w))
+    squares = lambda s: (s.double() * 2.0 ** -32).square().sum(dim=1)
+    a2 = (slots(x).double() * 2.0 ** -32).square()
+    cols = [a2.sum(dim=1), a2.square().sum(dim=1)]
+    tw = _hip.mode_twiddle_table(lat, dev)
+    site = torch.arange(V, dtype=torch.int64, device=dev)
+    coords, stride = [], V
+    for n in lat:
+        stride //= n
+        coords.append((site // stride) % n)
+    for m in reduced:
+        j = torch.zeros_like(site)
+        for n, L, xm in zip(m, lat, coords):
+            j = j + (n * (N // L)) * xm
+        t = tw[j % N]                                       # (V, 2)
+        col = squares(slots(x * t[:, 0]))
+        cols.append(col if all((2 * n) % L == 0 for n, L in zip(m, lat)) else col + squares(slots(x * t[:, 1])))
+    out = torch.stack(cols, dim=1)
+    out = torch.where(bad.unsqueeze(1), torch.full_like(out, float('nan')), out)
+    return dict(out=out, status=bad.to(torch.int32), modes=reduced)

@@ -47,8 +47,15 @@
       per_pass 4, 8, 16 and block_sites 2048, 4096, 8192, and the peak memory of one call; medians of at least 5
       alternating timings with [min, max].  `--shapes`, `--dtypes`, `--kappas` pick a part of the run.
 
+  --modes: instead of (a) .. (c), nf_cluster_modes on the chains and at the conditions of --spectrum (16^2 x 512 and
+      16^3 x 1024, fp32 and fp64, thermalised at kappa = 0.67 and 0.25): the bare call at the ON-AXIS momenta of
+      `momenta` 1, 2, 4 and all, given as a list, against nf_cluster_spectrum of the same build with the same Q (the
+      expectation: equal per quantity, within the larger of 10 % and the run's spread), and against the composed path
+      (`mcmc.cluster.cluster_modes`) on the device, which decides what `measure_modes(path=None)` takes; then the same at
+      a list of 16 generic off-axis momenta, against the composed path; medians of alternating timings with [min, max].
+
     python tools/cluster_bench.py [--reps 5] [--inner 20] [--steps 1500] [--skip-tau]
-                                  [--tiled | --improved | --improved-tiled | --spectrum | --spectrum-tiled]
+                                  [--tiled | --improved | --improved-tiled | --spectrum | --spectrum-tiled | --modes]
 Prints one JSON line per shape and dtype and one for (c)."""
 import argparse
 import json
@@ -345,6 +352,78 @@ def spectrum(lattice, C, dtype, kappa, reps, inner):
                 same_status=bool(torch.equal(k['status'], c['status'])))
         one = out['momenta']['1']
         out['momenta_1_within_margin_of_moments'] = bool(one['spectrum_over_moments'] <= 1 + one['margin'])
+    return out
+
+
+def modes(lattice, C, dtype, kappa, reps, inner):
+    """nf_cluster_modes at the on-axis momenta of `momenta` 1, 2, 4 and all, as a list, against nf_cluster_spectrum at the
+    same Q and against the composed path, and at 16 generic off-axis momenta against the composed path, timed alternately
+    on chains thermalised at `kappa` as in `spectrum`."""
+    from normflow__amd.mcmc.cluster import cluster_modes
+    prior = NormalPrior(loc=torch.zeros(lattice, dtype=dtype, device=DEV), scale=torch.ones(lattice, dtype=dtype, device=DEV))
+    model = nf.Model(net_=None, prior=prior, action=ScalarPhi4Action(**dict(COUPLINGS, kappa=kappa)))
+    s = model.hmc
+    torch.manual_seed(0)
+    s.start(n_chains=C)
+    d = len(lattice)
+    rnd = lambda t: [round(min(t), 4), round(max(t), 4)]
+    rel_spread = lambda t: (max(t) - min(t)) / statistics.median(t)
+    out = dict(lattice=list(lattice), chains=C, dtype=str(dtype).replace("torch.", ""), kappa=kappa, launches_per_timing=inner,
+               on_axis={}, off_axis={})
+    with torch.no_grad():
+        s.measure(30 * C, n_chains=C, n_md=N_MD, dt=DT, cluster_every=1)             # thermalise, sweeps included; no rows
+        phi = s._ref['sample'].clone()
+        w0 = float(model.action.get_coef(len(lattice))[0])
+        labels = _hip.phi4_cluster(phi.clone(), w0, position=(1, 0), want_labels=True)['labels']
+
+        def timed(lst, spectrum_momenta=None):
+            def kernel():
+                for _ in range(inner):
+                    _hip.cluster_modes(phi, labels, lst)
+
+            def spec():
+                for _ in range(inner):
+                    _hip.cluster_spectrum(phi, labels, spectrum_momenta)
+
+            composed = lambda: cluster_modes(phi, labels, lst)
+            fns = [kernel, composed] + ([spec] if spectrum_momenta is not None else [])
+            for _ in range(2):
+                for f in fns:
+                    f()
+            torch.cuda.synchronize()
+            k, c = _hip.cluster_modes(phi, labels, lst), composed()
+            rel = ((k['out'] - c['out']).abs() / c['out'].abs()).max().item()
+            tk, tc, ts = [], [], []
+            for _ in range(reps):
+                tk.append(_ms(kernel) / inner)
+                if spectrum_momenta is not None:
+                    ts.append(_ms(spec) / inner)
+                tc.append(_ms(composed))
+            mk, mc = statistics.median(tk), statistics.median(tc)
+            plan = _hip.cluster_modes_plan(lattice, dtype, lst)
+            margin = max([0.10, rel_spread(tk), rel_spread(tc)] + ([rel_spread(ts)] if ts else []))
+            row = dict(momenta_in_list=len(lst), quantities=plan['quantities'], passes=plan['passes'], modes_ms=round(mk, 4),
+                       modes_ms_spread=rnd(tk), us_per_quantity=round(1000 * mk / plan['quantities'], 2),
+                       composed_ms=round(mc, 3), composed_ms_spread=rnd(tc), composed_over_kernel=round(mc / mk, 1),
+                       margin=round(margin, 3), kernel_wins=bool(mc / mk > 1 + margin), max_rel_diff_of_the_doubles=rel,
+                       same_status=bool(torch.equal(k['status'], c['status'])))
+            if ts:
+                ms = statistics.median(ts)
+                sp = _hip.cluster_spectrum(phi, labels, spectrum_momenta)
+                row.update(spectrum_ms=round(ms, 4), spectrum_ms_spread=rnd(ts), modes_over_spectrum=round(mk / ms, 3),
+                           spectrum_quantities=_hip.cluster_spectrum_plan(lattice, dtype, spectrum_momenta)['quantities'],
+                           within_margin_of_spectrum=bool(mk / ms <= 1 + margin),
+                           same_bits_as_spectrum=bool(torch.equal(k['out'], sp['out'])))
+            return row
+
+        for momenta in (1, 2, 4, 'all'):
+            K = _hip.spectrum_momenta(lattice, momenta)
+            lst = [tuple(k if b == a else 0 for b in range(d)) for a in range(d) for k in range(1, K[a] + 1)]
+            out['on_axis'][str(momenta)] = timed(lst, momenta)
+        generic = [tuple((1 + i + 2 * a) % L for a, L in enumerate(lattice)) for i in range(16)]
+        out['off_axis']['16 generic'] = timed(generic)
+    out['all_within_margin_of_spectrum'] = all(r['within_margin_of_spectrum'] for r in out['on_axis'].values())
+    out['kernel_wins_everywhere'] = all(r['kernel_wins'] for part in (out['on_axis'], out['off_axis']) for r in part.values())
     return out
 
 
@@ -651,11 +730,18 @@ def main():
     ap.add_argument("--improved-tiled", action="store_true", help="nf_cluster_moments_tiled on the lattices beyond nf_cluster_moments")
     ap.add_argument("--spectrum", action="store_true", help="nf_cluster_spectrum and the improved correlator")
     ap.add_argument("--spectrum-tiled", action="store_true", help="nf_cluster_spectrum_tiled on the lattices beyond nf_cluster_spectrum")
+    ap.add_argument("--modes", action="store_true", help="nf_cluster_modes against nf_cluster_spectrum and the composed path")
     ap.add_argument("--shapes", default="", help="--improved-tiled, --spectrum-tiled: comma-separated indices into 16^3 x 1024 and "
                                                   "the four tiled shapes")
     ap.add_argument("--dtypes", default="float32,float64", help="--spectrum-tiled: the dtypes of the run")
     ap.add_argument("--kappas", default="0.67,0.25", help="--spectrum-tiled: the couplings of the run")
     a = ap.parse_args()
+    if a.modes:
+        for lattice, C in SHAPES:
+            for dtype in (torch.float32, torch.float64):
+                for kappa in (0.67, 0.25):
+                    print(json.dumps(modes(lattice, C, dtype, kappa, a.reps, a.inner)), flush=True)
+        return
     if a.spectrum_tiled:
         shapes = [((16, 16, 16), 1024, True)] + [(lat, C, False) for lat, C in TILED_SHAPES]
         picked = [int(i) for i in a.shapes.split(",") if i != ""] or range(len(shapes))
