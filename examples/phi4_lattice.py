@@ -151,7 +151,7 @@ INTEGRATOR_N_MD = dict(leapfrog=10, omelyan=5, omf4=2)
 
 
 def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False, integrator='leapfrog', correlator=False,
-                     spectrum_path=None, fourier=None, fourier_path=None, modes=False):
+                     spectrum_path=None, fourier=None, fourier_path=None, modes=False, modes_path=None):
     """<phi^2> of the trained flow + Metropolis next to hybrid Monte Carlo on the action itself (exact up to its own
     statistical error; the first quarter of every chain is dropped as thermalisation), then the observables of both.
     `cluster`: also model.hmc with a Swendsen-Wang sweep of the signs before every recorded step (cluster_every=1), so
@@ -188,7 +188,7 @@ def compare_with_hmc(model, n_chains=64, rows=128, cluster=False, improved=False
             lst = (lambda off, spatial, along: off + along)(*example_modes(lat)) if modes and len(lat) >= 2 else None
             m = model.hmc.measure(n_chains * rows, cluster_every=1, improved=True, momenta='all' if correlator else None,
                                   spectrum_path=spectrum_path if correlator else None, modes=lst, return_rows=lst is not None,
-                                  **hmc)
+                                  **({} if lst is None or modes_path is None else dict(modes_path=modes_path)), **hmc)
             if lst is not None:
                 m, y = m
             print("model.hmc, cluster_every=1, the next %d steps both ways (sweeps and steps coincide: drop = 0)" % rows)
@@ -260,6 +260,9 @@ def main():
     ap.add_argument("--spectrum-path", choices=("hbm",), default=None,
                     help="with --correlator: take the sweeps' spectrum with nf_cluster_spectrum_tiled (the slots in HBM), the "
                          "kernel for lattices beyond one CU's LDS; default: the one-CU kernel where it applies, else torch ops")
+    ap.add_argument("--modes-path", choices=("hbm",), default=None,
+                    help="with --modes: take the sweeps' modes with nf_cluster_modes_tiled (the slots in HBM), the kernel for "
+                         "lattices beyond one CU's LDS; default: the one-CU kernel where it applies, else torch ops")
     ap.add_argument("--ladder", action="store_true",
                     help="no fit: a ladder of 6 kappas from --kappa down to 0.4 of it in one HMC launch per step, chi, U4 and "
                          "tau_int(m) per rung without and with replica exchange")
@@ -279,7 +282,8 @@ def main():
         nf.backward_sanitychecker(model)
         if a.hmc:
             compare_with_hmc(model, cluster=a.cluster, improved=a.improved, integrator=a.integrator, correlator=a.correlator, fourier=a.fourier,
-                             spectrum_path=a.spectrum_path, fourier_path=a.fourier_path, modes=a.modes)
+                             spectrum_path=a.spectrum_path, fourier_path=a.fourier_path, modes=a.modes,
+                             modes_path=a.modes_path)
 
 
 if __name__ == "__main__":

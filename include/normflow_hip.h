@@ -1432,6 +1432,76 @@ int nf_cluster_spectrum_tiled(const void *phi, const int32_t *labels, double *ou
                               const int32_t *lattice, int kmax, const double *tw, int dtype, int64_t block_sites,
                               int per_pass, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- cluster modes with the chains, the labels and the int64 slots in HBM (nf_cluster_modes_tiled.hip): for lattices
+ * beyond nf_cluster_modes' class (32^3, 16^4, 32^4, 48^4, ...).  It changes nothing of "cluster modes" above, and these
+ * hold word for word: the momentum list (P <= 512, components reduced mod L_mu, 0 on axes of extent 1); the one table twN
+ * of N = lcm(L_mu) entries, N <= 65536; m_mu = (n_mu mod L_mu) N / L_mu and j(x) = (sum_mu m_mu x_mu) mod N; the fixed
+ * point q and the range test; the int64 sums A, R and I by integer atomics only; R alone for a self-conjugate momentum;
+ * the quantity table desc (Q, 8) of nf_cluster_modes_core.h with nf_cluster_modes_describe and nf_cluster_modes_check; the
+ * refusal (status 1 and a NaN row); out (C, 2 + P).  What is new, and only this:
+ * Lattices.  Any lattice of extents >= 1 with V < 2^31 whose N is 2 .. 65536, NF_F32 / NF_F64, C in 1 .. 65535.
+ * Phase arithmetic.  An extent may now reach 65536, so sum_mu m_mu x_mu can exceed 2^32 and "unsigned 32-bit arithmetic
+ * cannot overflow" no longer holds.  The phase is formed exactly (nf_cluster_modes_tiled_core.h): each product m_mu x_mu,
+ * below 2^32, is reduced mod N before the axes are added, and the sum of the four residues, below 4 N, is reduced once
+ * more.  64-bit arithmetic gives the same integer.  (The reductions use no division: with M = floor(2^32 / N) from the
+ * host, floor(t M / 2^32) is floor(t / N) or one less for every t < 2^32, and one conditional subtraction ends it.)
+ * Order of the sums of squares.  It is nf_cluster_moments_tiled's:
+ *   - a chain's slots are cut into BLOCKS, runs of block_sites consecutive slot indices (the last may be short);
+ *     block_sites = 0 is the default (4096), a value above V means V, blocks x 256 must stay below 2^32;
+ *   - within a block, lane l of 256 takes the slots first + l, first + l + 256, ... with the explicit fma forms above,
+ *     then the shuffle tree per wave, then the 4 waves in order: the block's partial;
+ *   - a last kernel adds the blocks' partials with one wave per (chain, sum): lane l takes the blocks l, l + 64, ... in
+ *     order, then the shuffle tree;
+ *   - a column is (sum r^2) + (sum i^2), formed after both sums are complete; sum r^2 alone for a self-conjugate momentum.
+ * Passes.  The Q quantities go in passes of per_pass CONSECUTIVE quantities that reuse the slot arrays; per_pass = 0 means
+ * min(Q, 16) and the legal values are 0 .. min(Q, 16).  A pass boundary may fall between the R and the I of one momentum.
+ * No carry is needed: every quantity's sum is kept in the partials until FINISH.
+ * Consequences:
+ *   1. a column's bits depend on the chain, its labels, the lattice, the dtype, block_sites and the column's own momentum
+ *      alone: not on the rest of the list or its order, not on per_pass, not on C, not on the row's place in the batch, not
+ *      on the workspace's former content, not on the schedule;
+ *   2. columns 0 and 1 are nf_cluster_moments_tiled's bits at the same block_sites, and status is its status;
+ *   3. the zero momentum's column is column 0's bits;
+ *   4. for n = k e_mu with N / L_mu a power of two, the column is nf_cluster_spectrum_tiled's column (mu, k) bit for bit
+ *      at the same block_sites;
+ *   5. where one block holds the chain and nf_cluster_modes runs 256 lanes (a (16, 16) lattice is such a case), the row is
+ *      nf_cluster_modes' bit for bit;
+ *   6. the values are invariant under cluster flips, bit for bit.
+ * Launches, in a line on `stream` after one memset of the flags: CHECK (the range and label test of every site, before
+ * anything is indexed by a label; it also holds every row of desc to cm_row_ok: with a failing table every chain gets
+ * status 1, out is left alone and nothing is indexed by a field of the table); per pass a memset of the pass's slot
+ * arrays, SCATTER (the pass's rows of desc by wave-uniform loads in front of the site loop; a site is read once per pass,
+ * its coordinates are taken once, the phase once per momentum of the pass -- the R and the I of one momentum share it, a
+ * pass that begins with an I forms it anew; a lane adds up its consecutive sites that share a label and sends the run
+ * through the claim-add-flush table of nf_cluster_moments_tiled, H = 512 entries with one int64 sum per quantity of the
+ * pass in dynamic LDS, 512 (4 + 8 per_pass) bytes) and SQUARES (the blocks' partials); FINISH (the partials in block
+ * order, the row or NaNs, status): 2 + 2 passes kernels and 1 + passes memsets.  No floating-point atomic, no allocation,
+ * no host synchronisation: the call can be captured into a HIP graph.
+ *   workspace   nf_cluster_modes_tiled_workspace bytes, 16-byte aligned, owned by the caller, need not be initialised:
+ *               4 C bytes of flags rounded up to 16, per_pass C V 8 bytes of slots, C (Q + 1) blocks doubles of partials
+ *               (a^2, a^4 and one sum per further quantity).
+ * desc and twN are DEVICE pointers, as in nf_cluster_modes.  nf_cluster_modes_tiled_plan (pure host, from the host list):
+ * blocks per chain, the block_sites in force, N, columns (2 + P), quantities, per_pass (in force), passes, table entries
+ * (H), kernel launches, and the LDS bytes of the scatter kernel.  _supported (pure host, per_pass = 0): 1 or 0 with the
+ * reason in nf_last_error_string.  _workspace (pure host, from Q): the bytes, 0 for a case the planner refuses or C outside
+ * 1 .. 65535.
+ * NF_EINVAL, all checked on the host before anything is launched, every message with the value that was refused: a NULL
+ * pointer, the dtype, an extent < 1, 2^31 sites or more, N = 1, N > 65536 or N not the lattice's lcm, Q outside 2 .. 1025,
+ * C outside 1 .. 65535, block_sites < 0 or so small that blocks x 256 reaches 2^32, per_pass outside 0 .. min(Q, 16), a
+ * NULL, short or misaligned workspace; _plan and _supported also refuse what nf_cluster_modes_describe refuses. */
+typedef struct nf_modes_tiled_plan {
+  int64_t blocks;
+  int32_t block_sites, N, columns, quantities, per_pass, passes, table_entries, launches;
+  int64_t lds_bytes;
+} nf_modes_tiled_plan;
+int nf_cluster_modes_tiled_supported(const int32_t *lattice, int dtype, const int32_t *modes, int P, int64_t block_sites);
+int nf_cluster_modes_tiled_plan(const int32_t *lattice, int dtype, const int32_t *modes, int P, int64_t block_sites,
+                                int per_pass, nf_modes_tiled_plan *out);
+size_t nf_cluster_modes_tiled_workspace(int64_t C, const int32_t *lattice, int Q, int64_t block_sites, int per_pass);
+int nf_cluster_modes_tiled(const void *phi, const int32_t *labels, double *out, int32_t *status, int64_t C,
+                           const int32_t *lattice, const int32_t *desc, int Q, const double *twN, int N, int dtype,
+                           int64_t block_sites, int per_pass, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- what the samplers' rows measure (nf_measure.hip; MI355X-side extension): every sufficient statistic of N
  * configurations in one pass.  cfgs (N, V) of dtype NF_F32 / NF_F64 on lattice[4] (leading extents 1 for d < 4);
  * out (N, n_out) DOUBLE, n_out = 7 + lattice[0] + lattice[1] + lattice[2] + lattice[3], per row

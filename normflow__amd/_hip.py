@@ -136,6 +136,10 @@ PROTOTYPES = {
     "nf_cluster_spectrum_tiled_plan": (_I, [C.POINTER(C.c_int32), _I, _I, _I64, _I, _P]),
     "nf_cluster_spectrum_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I, _I64, _I]),
     "nf_cluster_spectrum_tiled": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _I, _P, _I, _I64, _I, _P, _SZ, _P]),
+    "nf_cluster_modes_tiled_supported": (_I, [C.POINTER(C.c_int32), _I, _P, _I, _I64]),
+    "nf_cluster_modes_tiled_plan": (_I, [C.POINTER(C.c_int32), _I, _P, _I, _I64, _I, _P]),
+    "nf_cluster_modes_tiled_workspace": (_SZ, [_I64, C.POINTER(C.c_int32), _I, _I64, _I]),
+    "nf_cluster_modes_tiled": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, _I, _I, _I64, _I, _P, _SZ, _P]),
     "nf_phi4_cluster_ladder": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, C.c_uint64, C.c_uint64, _I, _P]),
     "nf_phi4_cluster_tiled_ladder": (_I, [_P, _P, _P, _I64, C.POINTER(C.c_int32), _P, _I, _P, C.c_uint64, C.c_uint64, _I,
                                           _I64, _P, _SZ, _P]),
@@ -3174,6 +3178,116 @@ def cluster_spectrum_tiled(phi, labels, momenta='all', block_sites=0, per_pass=N
                                             _dtype_code(phi), bs, pp, _ptr(workspace), workspace.numel(), _stream()),
            "nf_cluster_spectrum_tiled")
     return dict(out=out, status=status, momenta=K)
+
+
+# ========================================================================= the modes, slots in HBM (nf_cluster_modes_tiled.hip)
+MODES_TILED_MAX_PASS = 16               # quantities per pass: nf_cluster_modes' cap
+
+
+class ModesTiledPlan(C.Structure):
+    """nf_modes_tiled_plan (include/normflow_hip.h)."""
+    _fields_ = [("blocks", C.c_int64), ("block_sites", C.c_int32), ("N", C.c_int32), ("columns", C.c_int32),
+                ("quantities", C.c_int32), ("per_pass", C.c_int32), ("passes", C.c_int32), ("table_entries", C.c_int32),
+                ("launches", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
+def modes_quantities(lat, modes):
+    """Q of the rule: 1 + sum over the list of (2 - [the momentum is self-conjugate])."""
+    lat = tuple(int(n) for n in lat)
+    return 1 + sum(1 if all((2 * n) % L == 0 for n, L in zip(m, lat)) else 2 for m in modes_reduced(lat, modes))
+
+
+def cluster_modes_tiled_supported(lat, dtype, modes, block_sites=0):
+    """True if nf_cluster_modes_tiled takes chains on the lattice `lat` (1 to 4 extents) in `dtype` at the momenta `modes`
+    with blocks of `block_sites` sites (0: the default): the launcher's own planner, pure host code (the reason for a
+    False is `last_error()`)."""
+    if dtype not in (torch.float32, torch.float64) or not 1 <= len(lat) <= 4:
+        return False
+    arr, P = _modes_array(lat, modes)
+    return bool(load().nf_cluster_modes_tiled_supported(_lat4(lat), _dtype_code_of(dtype), arr, P, _block_sites(block_sites)))
+
+
+def cluster_modes_tiled_plan(lat, dtype, modes, block_sites=0, per_pass=0):
+    """What nf_cluster_modes_tiled will do on the lattice `lat` in `dtype` at `modes`: dict(blocks (per chain), block_sites
+    (in force), N (the lcm of the extents), columns (2 + P), quantities, per_pass (in force; 0 asks for min(Q, 16)), passes,
+    table_entries (H), launches (kernels: 2 + 2 passes), lds_bytes (of the scatter kernel)).  Pure host code."""
+    if not 1 <= len(lat) <= 4:
+        raise NormflowHipError(f"cluster_modes_tiled_plan: lattices of 1 to 4 axes, got {tuple(lat)}")
+    arr, P = _modes_array(lat, modes)
+    out = ModesTiledPlan()
+    _check(load().nf_cluster_modes_tiled_plan(_lat4(lat), _dtype_code_of(dtype), arr, P, _block_sites(block_sites),
+                                              int(per_pass or 0), C.byref(out)), "nf_cluster_modes_tiled_plan")
+    return {name: getattr(out, name) for name, _ in ModesTiledPlan._fields_}
+
+
+def cluster_modes_tiled_workspace(Cn, lat, modes, block_sites=0, per_pass=0):
+    """nf_cluster_modes_tiled_workspace: the bytes of the workspace of a call on Cn chains on `lat` at the momenta `modes`
+    (or, for an int, at that many quantities Q); pure host code."""
+    Q = int(modes) if isinstance(modes, int) else modes_quantities(lat, modes)
+    return int(load().nf_cluster_modes_tiled_workspace(int(Cn), _lat4(tuple(lat)), Q, _block_sites(block_sites),
+                                                       int(per_pass or 0)))
+
+
+def cluster_modes_tiled_per_pass(Cn, lat, modes, block_sites=0):
+    """The `per_pass` that `cluster_modes_tiled(per_pass=None)` takes: the largest value <= min(Q, 16) whose workspace
+    stays under `moments_max_workspace()`, and at least 1.  The workspace is linear in per_pass, so two planner calls
+    give it."""
+    lat = tuple(lat)
+    Q = int(modes) if isinstance(modes, int) else modes_quantities(lat, modes)
+    cap = min(MODES_TILED_MAX_PASS, Q)
+    one = cluster_modes_tiled_workspace(Cn, lat, Q, block_sites, 1)
+    if one == 0 or cap < 2:
+        return 1
+    step = cluster_modes_tiled_workspace(Cn, lat, Q, block_sites, 2) - one
+    if step <= 0:
+        return 1
+    return int(max(1, min(cap, 1 + (moments_max_workspace() - one) // step)))
+
+
+def cluster_modes_tiled(phi, labels, modes, block_sites=0, per_pass=None, workspace=None):
+    """nf_cluster_modes_tiled: `cluster_modes` for chains that live in HBM, any lattice of 1 to 4 axes with fewer than 2^31
+    sites whose lcm of extents is at most 65536; the same dict(out, status, modes).  status is `cluster_modes`' bit for bit,
+    out differs in the order of the sums of squares alone (blocks of `block_sites` slots, 0: the default;
+    include/normflow_hip.h): columns 0 and 1 are `cluster_moments_tiled`'s bits at the same `block_sites`.  The Q quantities
+    go in passes of `per_pass` <= 16 (None: `cluster_modes_tiled_per_pass`; it changes the footprint and the launches, never
+    a bit).  2 + 2 passes launches and 1 + passes memsets on the current stream.  The workspace comes from torch's caching
+    allocator per call (stream-aware and graph-pool safe), or is `workspace`: a uint8 tensor of at least
+    nf_cluster_modes_tiled_workspace bytes.  Graph capture: as `cluster_modes`, call this function once (or
+    `mode_twiddle_table(lat, device)` and `mode_descriptor(lat, modes, device)`) before capturing."""
+    _require_device(phi, labels)
+    lat = tuple(phi.shape[1:])
+    if not phi.is_contiguous() or not 1 <= len(lat) <= 4:
+        raise NormflowHipError("cluster_modes_tiled needs contiguous phi (C, *L) with 1 to 4 lattice axes, got "
+                               f"{tuple(phi.shape)}")
+    if labels.shape != phi.shape or labels.dtype != torch.int32 or not labels.is_contiguous() or labels.device != phi.device:
+        raise NormflowHipError(f"cluster_modes_tiled: labels must be a contiguous int32 tensor {tuple(phi.shape)} on "
+                               f"{phi.device}, got {tuple(labels.shape)} {labels.dtype} on {labels.device}")
+    Cn, dev, bs = phi.shape[0], phi.device, _block_sites(block_sites)
+    # the per-list cache of `cluster_modes`: a list seen before costs one dictionary look-up
+    try:
+        key = (lat, modes if isinstance(modes, tuple) else tuple(modes), dev)
+        hit = _MODE_CALLS.get(key)
+    except TypeError:                                         # momenta given as lists: not hashable, the slow way
+        key = hit = None
+    if hit is None:
+        hit = (modes_reduced(lat, modes),) + mode_descriptor(lat, modes, dev) + (mode_twiddle_table(lat, dev),)
+        if key is not None:
+            _MODE_CALLS[key] = hit
+    reduced, desc, N, tw = hit
+    Q = desc.shape[0]
+    pp = cluster_modes_tiled_per_pass(Cn, lat, Q, bs) if per_pass is None else int(per_pass)
+    if workspace is None:
+        need = load().nf_cluster_modes_tiled_workspace(Cn, _lat4(lat), Q, bs, pp)
+        workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+        raise NormflowHipError(f"cluster_modes_tiled: workspace must be a contiguous uint8 tensor on {dev}, got "
+                               f"{workspace.dtype} on {workspace.device}")
+    out = torch.empty((Cn, 2 + len(reduced)), dtype=torch.float64, device=dev)
+    status = torch.empty((Cn,), dtype=torch.int32, device=dev)
+    _check(load().nf_cluster_modes_tiled(_ptr(phi), _ptr(labels), _ptr(out), _ptr(status), Cn, _lat4(lat), _ptr(desc), Q,
+                                         _ptr(tw), N, _dtype_code(phi), bs, pp, _ptr(workspace), workspace.numel(),
+                                         _stream()), "nf_cluster_modes_tiled")
+    return dict(out=out, status=status, modes=reduced)
 
 
 # ========================================================================= observables of sampler rows (nf_measure.hip)

@@ -17,7 +17,8 @@ device).  With `momenta='all'` it also carries the cluster spectrum (nf_cluster_
 propagator at every on-axis momentum and the improved time-slice correlator follow; `spectrum_path='hbm'` takes it with
 nf_cluster_spectrum_tiled, the kernel for lattices beyond one CU's LDS.  With `modes=[(n0, ...), ...]` it carries the
 same sums at a list of momentum vectors, on or off the axes (nf_cluster_modes): `mode_propagator`, `mode_correlator` at a
-spatial momentum, and through `measure_modes(cfgs, modes)` the plain |phi~(p)|^2 from the same kernel.
+spatial momentum, and through `measure_modes(cfgs, modes)` the plain |phi~(p)|^2 from the same kernel;
+`modes_path='hbm'` takes them with nf_cluster_modes_tiled, the kernel for lattices beyond one CU's LDS.
 
 `Ensemble` reads the rows as (steps, chains) -- row r = step r // C of chain r % C, the layout of model.mcmc,
 model.blocked_mcmc and model.hmc -- and gives every estimate as (value, error): leave-one-chain-out jackknife for
@@ -288,6 +289,7 @@ class Ensemble:
 # ---------------------------------------------------------------- cluster-improved estimators
 IMPROVED_PATHS = (None, 'kernel', 'composed', 'hbm')
 SPECTRUM_PATHS = (None, 'hbm')             # of `measure_improved(spectrum_path=...)`: 'hbm' is nf_cluster_spectrum_tiled
+MODES_PATHS = (None, 'hbm')                # of `measure_improved(modes_path=...)`: 'hbm' is nf_cluster_modes_tiled
 
 
 def improved_kernel_applies(cfgs):
@@ -306,7 +308,8 @@ def route_improved(cfgs):
 
 
 @torch.no_grad()
-def measure_improved(cfgs, labels, path=None, momenta=None, spectrum_path=None, workspace=None, modes=None):
+def measure_improved(cfgs, labels, path=None, momenta=None, spectrum_path=None, workspace=None, modes=None, modes_path=None,
+                     modes_workspace=None):
     """(N, *L) configurations and the (N, *L) int32 labels of their cluster decompositions (a Swendsen-Wang sweep's:
     `hmc.cluster(phi)['labels']`, with the field before or after the flip) -> `ImprovedMeasurement`: the averages over
     all 2^Nc assignments of the clusters' signs, in closed form from the clusters' sums M_C (include/normflow_hip.h,
@@ -330,8 +333,14 @@ def measure_improved(cfgs, labels, path=None, momenta=None, spectrum_path=None, 
     reduced to 0 .. L_mu - 1, and `.mode_power` (N, P) = sum_C |M~_C(p)|^2 at p_mu = 2 pi n_mu / L_mu, from which
     `mode_propagator` and `mode_correlator` follow.  It runs on its own: path=None / 'kernel' take nf_cluster_modes where
     `improved_kernel_applies` (path=None elsewhere: composed), 'composed' is `mcmc.cluster.cluster_modes`, and 'hbm'
-    raises ValueError (there is no HBM form of the modes yet).  `momenta` keeps its meaning beside it; everything else
-    of the measurement, `out` included, is that of the call without `modes` bit for bit."""
+    raises ValueError unless `modes_path` is given: the tiled modes kernel is reached through that keyword, as the tiled
+    spectrum through `spectrum_path`.  `momenta` keeps its meaning beside it; everything else of the measurement, `out`
+    included, is that of the call without `modes` bit for bit.
+    modes_path='hbm' (opt-in; needs modes, and path None or 'hbm'; ValueError otherwise): `.modes` and `.mode_power` are
+    nf_cluster_modes_tiled's, the slots in HBM, any lattice on the device whose lcm of extents is at most 65536 (raises
+    NormflowHipError on CPU tensors).  `modes_workspace`: a uint8 tensor for that kernel (`_hip.cluster_modes_tiled`),
+    None: one per call; ValueError where it is given without modes_path.  Without modes_path every call does what it
+    did: path=None beyond one CU stays on the composed path."""
     if path not in IMPROVED_PATHS:
         raise ValueError(f"path must be None, 'kernel', 'composed' or 'hbm', got {path!r}")
     if not 1 <= cfgs.ndim - 1 <= 4:
@@ -347,16 +356,31 @@ def measure_improved(cfgs, labels, path=None, momenta=None, spectrum_path=None, 
             raise ValueError("measure_improved: spectrum_path='hbm' is the path of the spectrum: it needs momenta")
         if path not in (None, 'hbm'):
             raise ValueError(f"measure_improved: spectrum_path='hbm' goes with path None or 'hbm', got path={path!r}")
+    if modes_path not in MODES_PATHS:
+        raise ValueError(f"modes_path must be None or 'hbm', got {modes_path!r}")
+    if modes_workspace is not None and modes_path is None:
+        raise ValueError("measure_improved: modes_workspace is the workspace of modes_path='hbm' (nf_cluster_modes_tiled); "
+                         "no other path takes one")
+    if modes_path is not None:
+        if modes is None:
+            raise ValueError("measure_improved: modes_path='hbm' is the path of the modes: it needs modes")
+        if path not in (None, 'hbm'):
+            raise ValueError(f"measure_improved: modes_path='hbm' goes with path None or 'hbm', got path={path!r}")
     if modes is not None:
-        if path == 'hbm':
-            raise ValueError("measure_improved: no modes on path 'hbm' (nf_cluster_modes has no HBM form): use "
-                             "path='composed' for lattices beyond one CU")
+        if path == 'hbm' and modes_path is None:
+            raise ValueError("measure_improved: no modes on path 'hbm' (nf_cluster_moments_tiled has no modes form): use "
+                             "modes_path='hbm' (nf_cluster_modes_tiled), or path='composed', for lattices beyond one CU")
         try:
             _hip.modes_list(lat, modes)
         except _hip.NormflowHipError as e:
             raise ValueError(f"measure_improved: {e}") from None
+    if modes_path == 'hbm':
+        _hip._require_device(cfgs, labels)
     im = _measure_improved(cfgs, labels, path, momenta, spectrum_path, workspace, lat)
-    if modes is not None:
+    if modes_path == 'hbm':
+        r = _hip.cluster_modes_tiled(cfgs.contiguous(), labels.contiguous(), modes, workspace=modes_workspace)
+        im.modes, im.mode_power = r['modes'], r['out'][:, 2:]
+    elif modes is not None:
         if path is None:
             path = 'kernel' if improved_kernel_applies(cfgs) else 'composed'
         if path == 'kernel':
@@ -565,17 +589,21 @@ def correlator_modes(lattice, axis, spatial):
 
 
 @torch.no_grad()
-def measure_modes(cfgs, modes, labels=None, path=None):
+def measure_modes(cfgs, modes, labels=None, path=None, modes_path=None):
     """`measure_improved(cfgs, labels, path=path, modes=modes)`: the `ImprovedMeasurement` with `.modes` and `.mode_power`.
     labels=None is the decomposition into ONE cluster (all labels 0): with it `mode_power` is the plain |phi~(p)|^2 of
     every row, in the estimators' fixed point and from the same kernel, at momenta that `Measurement.propagator` does not
     reach.  path=None | 'kernel' | 'composed': None takes nf_cluster_modes where `improved_kernel_applies`, else the
-    composed path."""
-    if path not in (None, 'kernel', 'composed'):
-        raise ValueError(f"path must be None, 'kernel' or 'composed', got {path!r}")
+    composed path.  modes_path='hbm' (opt-in, with path None or 'hbm'): nf_cluster_modes_tiled, any lattice on the device."""
+    if modes_path not in MODES_PATHS:
+        raise ValueError(f"modes_path must be None or 'hbm', got {modes_path!r}")
+    if path not in ((None, 'kernel', 'composed') if modes_path is None else (None, 'hbm')):
+        raise ValueError(f"path must be None, 'kernel' or 'composed' (with modes_path='hbm': None or 'hbm'), got {path!r}")
     if labels is None:
         labels = torch.zeros(cfgs.shape, dtype=torch.int32, device=cfgs.device)
-    return measure_improved(cfgs, labels, path=path, modes=modes)
+    if modes_path is None:
+        return measure_improved(cfgs, labels, path=path, modes=modes)
+    return measure_improved(cfgs, labels, path=path, modes=modes, modes_path=modes_path)
 
 
 class ImprovedEnsemble(Ensemble):

@@ -103,7 +103,8 @@ class HMCSampler:
 
     @torch.no_grad()
     def measure(self, batch_size=1, n_chains=1, n_md=10, dt=0.1, n_skip=0, path=None, return_rows=False, cluster_every=0,
-                improved=False, integrator='leapfrog', momenta=None, spectrum_path=None, fa_mass_sq=None, modes=None):
+                improved=False, integrator='leapfrog', momenta=None, spectrum_path=None, fa_mass_sq=None, modes=None,
+                modes_path=None):
         """The `Measurement` of the rows that `sample(batch_size, ...)` would return from the same chain and generator
         state, WITHOUT storing them: every recorded state is measured where it is and only its 7 + sum L sums are kept.
         The rows are in the samplers' layout (`Ensemble(m, n_chains=C)` takes it as is), the action is attached when the
@@ -131,6 +132,9 @@ class HMCSampler:
         modes=[(n0, ...), ...] (with improved; ValueError without): `.improved` also carries `.modes` and `.mode_power`, the
         improved |phi~(p)|^2 at the listed momentum vectors, on or off the axes (`observables.measure_improved(...,
         modes=...)`, nf_cluster_modes); it changes nothing else of the call, bit for bit.
+        modes_path='hbm' (with modes; ValueError without; improved True or 'hbm'): `.modes` and `.mode_power` are
+        nf_cluster_modes_tiled's (`observables.measure_improved(..., modes_path='hbm')`), for the lattices beyond one CU's
+        LDS, with one workspace for all sweeps of the call and no further device-to-host read.
         fa_mass_sq (as in `sample_`): the accelerated kernel does not measure inside its launch; its launches record
         the rows and they are measured afterwards by the kernel `observables.route` names, the same bits."""
         ipath = self._improved_path(improved, cluster_every)
@@ -139,7 +143,8 @@ class HMCSampler:
         self._spectrum_path(spectrum_path, momenta, ipath)
         y, stats = self._advance(batch_size, n_chains, n_md, dt, n_skip, path, want_rows=return_rows, want_stats=True,
                                  cluster_every=cluster_every, improved=ipath, integrator=integrator, momenta=momenta,
-                                 spectrum_path=spectrum_path, **self._fa_kw(fa_mass_sq), **self._modes_kw(modes, ipath))
+                                 spectrum_path=spectrum_path, **self._fa_kw(fa_mass_sq),
+                                 **self._modes_kw(modes, ipath, modes_path))
         action = self._model.action
         m = stats.measurement(action if hasattr(action, 'get_coef') else None)
         if ipath is not False:
@@ -171,21 +176,44 @@ class HMCSampler:
             raise ValueError(f"spectrum_path='hbm' goes with improved=True or 'hbm', got improved={ipath!r}")
 
     @staticmethod
-    def _modes_kw(modes, ipath):
-        """The check of `measure(modes=...)`, before anything runs, and the keyword that hands the list on; none at all
-        for None, so that the calls are the ones they always were."""
+    def _modes_kw(modes, ipath, modes_path=None):
+        """The checks of `measure(modes=..., modes_path=...)`, before anything runs, and the keywords that hand them on;
+        none at all for None, so that the calls are the ones they always were."""
+        if modes_path is not None:
+            if modes_path != 'hbm':
+                raise ValueError(f"modes_path must be None or 'hbm', got {modes_path!r}")
+            if modes is None:
+                raise ValueError("modes_path='hbm' is the path of the modes of the improved estimators: it needs modes")
+            if ipath not in (None, 'hbm'):
+                raise ValueError(f"modes_path='hbm' goes with improved=True or 'hbm', got improved={ipath!r}")
         if modes is None:
             return {}
         if ipath is False:
             raise ValueError("modes asks for the improved estimators at a list of momenta: it needs improved=True (or a path)")
-        if ipath == 'hbm':
-            raise ValueError("modes: there is no HBM form of nf_cluster_modes; improved=True or 'composed' take lattices "
-                             "beyond one CU on the composed path")
+        if ipath == 'hbm' and modes_path is None:
+            raise ValueError("modes: improved='hbm' has no HBM form of the modes of its own; modes_path='hbm' is "
+                             "nf_cluster_modes_tiled, and improved=True or 'composed' take lattices beyond one CU on the "
+                             "composed path")
         try:                                     # a tuple of tuples: `_hip.cluster_modes` then knows the list by one look-up
             modes = tuple(tuple(m) for m in modes)
         except TypeError:
             pass                                 # not a list of vectors: `measure_improved` says so
-        return dict(modes=modes)
+        return dict(modes=modes) if modes_path is None else dict(modes=modes, modes_path=modes_path)
+
+    @staticmethod
+    def _modes_workspace(phi, modes, modes_path):
+        """One workspace of nf_cluster_modes_tiled for all sweeps of a call, and the keywords that hand it on."""
+        if modes_path is None:
+            return {}
+        if not phi.is_cuda:
+            raise _hip.NormflowHipError("modes_path='hbm' is nf_cluster_modes_tiled: it needs chains on the device")
+        Cn, lat = phi.shape[0], tuple(phi.shape[1:])
+        try:
+            need = _hip.cluster_modes_tiled_workspace(Cn, lat, modes, 0, _hip.cluster_modes_tiled_per_pass(Cn, lat, modes))
+        except _hip.NormflowHipError as e:
+            raise ValueError(f"modes: {e}") from None
+        return dict(modes_path=modes_path,
+                    modes_workspace=torch.empty(max(need, 256), dtype=torch.uint8, device=phi.device))
 
     @staticmethod
     def _spectrum_workspace(phi, momenta, spectrum_path):
@@ -209,7 +237,8 @@ class HMCSampler:
         return None if isinstance(integrator, str) and integrator == 'leapfrog' else _hip.hmc_scheme(integrator)
 
     def _advance(self, batch_size, n_chains, n_md, dt, n_skip, path, want_rows, want_stats, cluster_every=0,
-                 improved=False, integrator='leapfrog', momenta=None, spectrum_path=None, fa_mass_sq=None, modes=None):
+                 improved=False, integrator='leapfrog', momenta=None, spectrum_path=None, fa_mass_sq=None, modes=None,
+                 modes_path=None):
         """batch_size // n_chains recorded steps of the chains: (the rows (batch_size, *L) or None, the `_Stats` of the
         recorded states or None); the chains, `last` and `history` updated.  cluster_every = E >= 1: the recorded steps
         are run in spans that end before the next step s (counted across calls) with s % E == 0, with one cluster sweep
@@ -241,7 +270,7 @@ class HMCSampler:
             from ..lib.observables import ImprovedMeasurement, measure_improved
             spec = self._spectrum_workspace(phi, momenta, spectrum_path)      # one workspace for all sweeps of the call
             if modes is not None:
-                spec = dict(spec, modes=modes)
+                spec = dict(spec, modes=modes, **self._modes_workspace(phi, modes, modes_path))
                 modes = _hip.modes_reduced(tuple(phi.shape[1:]), modes)       # what an empty measurement carries
         dhs, accs, sweeps, parts, r0 = [], [], [], [], 0
         while r0 < rows:

@@ -151,19 +151,20 @@ class LadderHMCSampler(HMCSampler):
 
     @torch.no_grad()
     def measure(self, batch_size=1, return_rows=False, improved=False, momenta=None, spectrum_path=None, modes=None,
-                **kwargs):
+                modes_path=None, **kwargs):
         """The list of K `Measurement`s.  improved=True / 'kernel' / 'composed' / 'hbm' as in `HMCSampler.measure`: entry k then
         carries `.improved`, the `ImprovedMeasurement` of rung k's sweeps x R rows (the kernel does not know the
         couplings: a sweep's C rows are taken by chain and laid out rung-ordered, row (c // K) K + rung[c] with the rungs
         in force at that sweep, like `last['cluster']`).  momenta='all' or an int >= 1 as in `HMCSampler.measure`: the
         spectrum rides along, rung-ordered like the rest.  spectrum_path='hbm' and modes=[(n0, ...), ...] as in
-        `HMCSampler.measure`: `.modes` and `.mode_power` ride along in the same way."""
+        `HMCSampler.measure`: `.modes` and `.mode_power` ride along in the same way; modes_path='hbm' takes them from
+        nf_cluster_modes_tiled, as there."""
         ipath = self._improved_path(improved, kwargs.get('cluster_every', 0))
         if momenta is not None and ipath is False:
             raise ValueError("momenta asks for the spectrum of the improved estimators: it needs improved=True (or a path)")
         self._spectrum_path(spectrum_path, momenta, ipath)
         y, rung_stats = self._advance(batch_size, want_rows=return_rows, want_stats=True, improved=ipath, momenta=momenta,
-                                      spectrum_path=spectrum_path, **self._modes_kw(modes, ipath), **kwargs)
+                                      spectrum_path=spectrum_path, **self._modes_kw(modes, ipath, modes_path), **kwargs)
         stats = rung_stats.out
         from ..lib import observables as ob
         K = len(self._ladder)
@@ -236,7 +237,7 @@ class LadderHMCSampler(HMCSampler):
     # ---- which path: HMCSampler's `_choose`, on the proxy model (whose action is a phi^4 action)
     def _advance(self, batch_size, n_chains=None, n_md=10, dt=0.1, n_skip=0, exchange_every=1, path=None, want_rows=True,
                  want_stats=False, cluster_every=0, improved=False, integrator='leapfrog', momenta=None,
-                 spectrum_path=None, fa_mass_sq=None, modes=None):
+                 spectrum_path=None, fa_mass_sq=None, modes=None, modes_path=None):
         """batch_size // C recorded steps.  Returns (the rung-ordered rows or None, the `_RungStats` with the rung-ordered
         measure rows `out` (steps, C, n_out) or None)."""
         if fa_mass_sq is not None:
@@ -267,7 +268,7 @@ class LadderHMCSampler(HMCSampler):
             from ..lib.observables import ImprovedMeasurement, measure_improved
             spec = self._spectrum_workspace(phi, momenta, spectrum_path)      # one workspace for all sweeps of the call
             if modes is not None:
-                spec = dict(spec, modes=modes)
+                spec = dict(spec, modes=modes, **self._modes_workspace(phi, modes, modes_path))
                 modes = _hip.modes_reduced(lat, modes)   # what an empty measurement carries
         dhs, accs, swaps, parities, sweeps, parts = [], [], [], [], [], []
         r0 = 0
